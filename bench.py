@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the CtrlHair hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
-One "step" = one pass of the hot path over one batch already resident in HBM.  The default run (N = 1) answers, in ONE JSON
-line, every configuration of BASELINE.json that fits one GPU:
+One "step" = one pass of the hot path over one batch already resident in HBM.  A plain run measures the headline only: it
+sets up, runs W untimed warm-up steps, times K steps and prints ONE JSON line --
 
   top level   configs[1]: SEAN generator forward only, batch 16, synthetic 512x512 blocky label maps + tanh(N(0,1)) style
               codes + explicit N(0,1) noise planes, procedural (random, calibrated) weights of the real ngf=64 architecture,
               on the EXACT-f32 matrix-core path (v_mfma_f32_32x32x2_f32) -- the reference's arithmetic.  `value`, `dtype`,
-              `roofline`, the per-step percentiles and `cpu_baseline` all belong to this leg.
+              `ms_per_step` and the per-step percentiles belong to this leg.
+
+--full adds, in the same line, every configuration of BASELINE.json that fits one GPU and every figure that takes runs of
+its own (`roofline` + `sustained_peaks` from an instrumented pass, `host_enqueue_ms_per_step`, `cpu_baseline`):
+
   f32_class_f16x3        the same job with the conv products evaluated as a 3-term f16 split on the f16 matrix cores (f32
                          storage and accumulation, power-of-two operand scaling: ctrlhair_amd/csrc/sh16.h).  Narrower than
                          fp32 per product (2^-22), so it is NOT the fp32 number of record; tested to 1e-3 like the exact path.
@@ -18,8 +22,14 @@ line, every configuration of BASELINE.json that fits one GPU:
   pipeline               configs[2]: the whole edit at batch 8 (BiSeNet parse @512 -> label remap -> nearest 256 -> shape
                          encoders -> Zencoder @512 -> colour encoder / predictor / generator with slider deltas -> shape
                          decoder -> nearest x2 -> SEAN generator @512), f16x3 and exact-f32 legs, with per-stage times.
+  (side legs)            configs[3] / configs[4] per-GPU shapes, the Winograd / interior-reduction ablations, interactive_b1.
 
-With --gpus N > 1 the script starts N ranks itself when it was not launched by torch.distributed.run (it re-executes under
+--dump-outputs DIR writes what the timed path computed in its last timed step -- the images a caller receives ([B,3,S,S]
+float32; with N > 1 the gathered [N*B,3,S,S]) -- as DIR/images.npy.  Inputs and weights are functions of fixed seeds, so two
+builds run with the same arguments can be compared output for output.  Above 64 MB a fixed, seeded sample of whole images
+is kept and DIR/images_index.npy (float64) lists which.
+
+With --gpus N > 1 the script starts N ranks itself when it was not launched by torch.distributed.run (a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`), one process per GPU over RCCL:
 every rank runs its own batch (weak scaling; 32 per GPU with --gpus 8 = configs[3], B=256) and the output shards are
 all-gathered over xGMI inside the timed region (ctrlhair_amd.parallel.PipelinedGather: side stream, under the next step's
@@ -27,18 +37,19 @@ pass; --sync-gather serialises it).  `n_gpus` is the world size RCCL reports.
 
 Timing: W untimed warm-up steps, then K steps bracketed by barrier + torch.cuda.synchronize() on both sides (max over ranks)
 -> `value` / `ms_per_step`; an event is recorded on the launch stream at every step boundary (no synchronisation inside the
-region) -> `step_ms` median / p10 / p90.  Per-kernel figures come from a separate instrumented pass (hipEvents around every
-MFMA conv launch on the launch stream), never from the timed region.
+region) -> `step_ms` median / p10 / p90.  Per-kernel figures (--full) come from a separate instrumented pass (hipEvents around
+every MFMA conv launch on the launch stream), never from the timed region.
 
 Other flags: --workload generator|pipeline (only that workload), --path f32|f16x3|f16|bf16 (only that arithmetic as the top
 level; f16 / bf16 = single-term reduced-precision operands of configs[4], tolerance 5e-2), --labels blocky|face,
---only-headline (skip the extra blocks), --batch, --size, --no-cpu-baseline.
+--only-headline (with --full: skip the extra blocks), --batch, --size, --no-cpu-baseline.
 """
 import argparse
 import hashlib
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -52,6 +63,7 @@ CONTRACT_BYTES_PER_IMAGE = 5.805e9        # conv-layer accountin
 CONTRACT_WEIGHT_BYTES = 1.061e9           # ... + weights once per batch
 DENSE_REFERENCE_FLOP_PER_IMAGE = 2.5696e12    # the reference's dense graph at S=512
 PATH_OPTION = {'f32': 0, 'f16x3': 1, 'f16': 2, 'bf16': 3}
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together, .npy headers included
 
 DTYPE = {
     'f32': 'f32 (every product and sum an IEEE f32 operation on the f32 matrix cores, v_mfma_f32_16x16x4_f32 / 32x32x2_f32; 3x3 convs as '
@@ -333,9 +345,10 @@ def percentiles(ms):
             'p90': round(float(np.percentile(a, 90)), 3), 'n': int(a.size)}
 
 
-def run_leg(job, args, dist, dev, world, steps=None, warmup=None, profile=True):
-    """warm-up, then the timed region (barrier + synchronize on both sides, MAX over ranks), then a separate
-    instrumented pass for the per-kernel figures."""
+def run_leg(job, args, dist, dev, world, steps=None, warmup=None, profile=True, keep_output=False):
+    """warm-up, then the timed region (barrier + synchronize on both sides, MAX over ranks), then (profile) a separate
+    instrumented pass for the per-kernel figures.  keep_output: r['output'] = host copy of the last timed step's images
+    (the gathered ones with N > 1)."""
     import torch
     from ctrlhair_amd.parallel import PipelinedGather
     steps = args.steps if steps is None else steps
@@ -355,11 +368,11 @@ def run_leg(job, args, dist, dev, world, steps=None, warmup=None, profile=True):
     for _ in range(warmup):
         step()
     sync()
-    # host time to enqueue one step's launches, measured OUTSIDE the timed region on an EMPTY queue (synchronise, enqueue one step, stop the
-    # clock, synchronise): inside the region the HIP queue is full and step() blocks on it -- that figure (kept below as
+    # (--full) host time to enqueue one step's launches, measured OUTSIDE the timed region on an EMPTY queue (synchronise, enqueue one
+    # step, stop the clock, synchronise): inside the region the HIP queue is full and step() blocks on it -- that figure (kept below as
     # host_step_call_ms_in_region) is queue back-pressure, not enqueue cost (round 5 review)
     enq = []
-    for _ in range(min(5, max(steps, 0))):
+    for _ in range(min(5, max(steps, 0)) if args.full else 0):
         sync()
         h0 = time.perf_counter()
         step()
@@ -381,6 +394,7 @@ def run_leg(job, args, dist, dev, world, steps=None, warmup=None, profile=True):
         assert pg.check_slot(), 'all-gather result does not contain this rank\'s shard at its slot'
     out = pg.last_local()
     assert args.dbg or steps == 0 or bool(torch.isfinite(out).all())
+    kept = pg.finish().cpu() if keep_output else None       # before the instrumented pass below reuses the buffers
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -399,8 +413,32 @@ def run_leg(job, args, dist, dev, world, steps=None, warmup=None, profile=True):
         prof['all'] = job.handle.profile_read(-1)
         prof['steps'] = nprof
     value = world * job.images * steps / dt if steps else 0.0
-    return {'value': round(value, 3), 'ms_per_step': round(dt / max(steps, 1) * 1e3, 3), 'step_ms': percentiles(step_ms),
-            'host_enqueue_ms_per_step': percentiles(enq), 'host_step_call_ms_in_region': percentiles(call_ms), 'steps': steps, 'warmup': warmup}, prof
+    r = {'value': round(value, 3), 'ms_per_step': round(dt / max(steps, 1) * 1e3, 3), 'step_ms': percentiles(step_ms),
+         'host_enqueue_ms_per_step': percentiles(enq), 'host_step_call_ms_in_region': percentiles(call_ms), 'steps': steps, 'warmup': warmup}
+    if keep_output:
+        r['output'] = kept
+    return r, prof
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as <dirname>/<name>.npy in float32.  When all of them together exceed `budget` bytes, each
+    keeps a fixed, seeded sample of its leading-axis entries (whole images; rows of the last axis if one image alone is too
+    large), sorted, and <name>_index.npy (float64) lists the entries kept."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    header = 256                                            # bytes per .npy file beyond its data (128 in practice)
+    for name, a in arrays.items():
+        if total + header * len(arrays) > budget:
+            share = (budget - 2 * header * len(arrays)) * a.nbytes / total      # this array's part, its index file included
+            if a[0].nbytes + 8 > share:
+                a = a.reshape(-1, a.shape[-1])
+            k = max(1, int(share // (a[0].nbytes + 8)))
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))
+            a = a[idx]
+            np.save(os.path.join(dirname, name + '_index.npy'), idx.astype(np.float64))
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def roofline_block(path, prof, value, B, sustained):
@@ -510,7 +548,8 @@ def roofline_block(path, prof, value, B, sustained):
 
 
 def respawn_under_torchrun(n):
-    """--gpus N without a launcher: start N ranks ourselves (one per GPU) and let rank 0 print the JSON line."""
+    """--gpus N without a launcher: start N ranks ourselves (one per GPU, under a child launcher: this process has already
+    asked HIP for the device count, so it is not replaced) and let rank 0 print the JSON line."""
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have < n:
@@ -523,7 +562,7 @@ def respawn_under_torchrun(n):
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={n}', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(sys.executable, cmd, env)
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def main():
@@ -540,7 +579,11 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-b16', action='store_true', help='(default since round 6; kept for old command lines)')
     ap.add_argument('--no-cpu-b16', action='store_true', help='CPU baseline: skip the ONE real batch-16 forward of the dense graph (SURVEY.md 8(d): Config 2 at B=16; about a minute of host time)')
-    ap.add_argument('--only-headline', action='store_true', help='top-level leg only (no f16x3 / face-like / pipeline blocks)')
+    ap.add_argument('--full', action='store_true', help='also every side measurement: f16x3 / face-like / pipeline / side-leg blocks, roofline '
+                    '(instrumented pass), host enqueue time, interactive_b1 and cpu_baseline (a plain run times the headline leg only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the images of the last timed step of the headline leg as '
+                    'DIR/images.npy (float32; a fixed, seeded sample of whole images above 64 MB)')
+    ap.add_argument('--only-headline', action='store_true', help='with --full: top-level leg only (no f16x3 / face-like / pipeline blocks)')
     ap.add_argument('--no-strict-fp32', action='store_true', help=argparse.SUPPRESS)      # (older tools: implies --only-headline)
     ap.add_argument('--path', choices=tuple(PATH_OPTION), default='f32',
                     help='arithmetic of the top-level leg: f32 = exact-f32 MFMA (default, the reference\'s arithmetic); f16x3 = 3-term '
@@ -561,6 +604,8 @@ def main():
     args = ap.parse_args()
     if args.no_strict_fp32:
         args.only_headline = True
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error('--dump-outputs needs --steps >= 1 (it writes what the last timed step computed)')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         respawn_under_torchrun(args.gpus)
     # ONE per-GPU batch for every N of a scaling curve (N = 1 must be the workload of N = 8)
@@ -594,12 +639,14 @@ def main():
 
     S, ngf = args.size, args.ngf
     do_gen = args.workload in ('all', 'generator')
-    do_pipe = args.workload == 'pipeline' or (args.workload == 'all' and world == 1 and not args.only_headline)
-    extras = world == 1 and not args.only_headline
+    extras = world == 1 and args.full and not args.only_headline
+    do_pipe = args.workload == 'pipeline' or (args.workload == 'all' and extras)
+    keep = rank == 0 and args.dump_outputs is not None
     res = {}
     sustained = None
     sd = None
     all_weights = None
+    outputs = None                     # --dump-outputs: the headline leg's last timed step
 
     if do_gen:
         from ctrlhair_amd import procedural as P
@@ -609,14 +656,15 @@ def main():
         blocks = {}
         for path in legs:
             job = GeneratorJob(args, path, dev, rank, sd, labels=args.labels)
-            if sustained is None and rank == 0:
+            if sustained is None and rank == 0 and args.full:
                 try:
                     sustained = {'f32': round(job.handle.mfma_peak(0, 30), 1), 'f16': round(job.handle.mfma_peak(1, 30), 1),
                                  'unit': 'TFLOP/s', 'how': 'MFMA-only loop, 2 waves per SIMD, random operands, ~30 ms (ch_mfma_peak)'}
                 except Exception as e:         # never lose the run over the helper
                     sustained = {'error': str(e)}
-            r, prof = run_leg(job, args, dist, dev, world)
-            r['roofline'] = roofline_block(path, prof, r['value'] / world, gen_batch, sustained)
+            r, prof = run_leg(job, args, dist, dev, world, profile=args.full, keep_output=keep and path == args.path)
+            if prof is not None:
+                r['roofline'] = roofline_block(path, prof, r['value'] / world, gen_batch, sustained)
             r['dtype'] = DTYPE[path]
             if extras and args.labels == 'blocky':      # the same handle on face-like label maps (shorter run)
                 job.set_labels('face')
@@ -634,7 +682,7 @@ def main():
         # side legs of the exact-f32 number of record (shorter runs, same protocol): the per-GPU shape of configs[3] (32 images
         # per GPU), and at N = 1 the same job without the Winograd convs and without the SPADE-interior reduction (worst case)
         side = {}
-        if args.path == 'f32' and (extras or world == 8) and user_batch == 0:
+        if args.path == 'f32' and args.full and (extras or world == 8) and user_batch == 0:
             variants = [('configs3_b32_per_gpu', {'batch': 32}), ('configs4_bf16_b32_per_gpu', {'batch': 32, '_path': 'bf16'})]
             if extras:
                 variants += [('winograd_f2x2_only', {'wino': 1}), ('direct_convs_no_winograd', {'wino': 0}),
@@ -678,15 +726,16 @@ def main():
         res = {
             'metric': '512x512 edited images/sec (SEAN generator forward), whole job', 'value': head['value'], 'unit': 'images/s',
             'n_gpus': world, 'steps': head['steps'], 'warmup': head['warmup'], 'ms_per_step': head['ms_per_step'],
-            'step_ms': head['step_ms'], 'host_enqueue_ms_per_step': head['host_enqueue_ms_per_step'],
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPE[args.path],
+            'step_ms': head['step_ms'], 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPE[args.path],
             'data': f'synthetic ({args.labels} labels, tanh-normal codes, explicit noise planes; procedural calibrated weights, '
                     'no checkpoint ships with the reference)',
             'config': {'workload': f'SEAN generator forward only, batch {gen_batch}/GPU, {S}x{S}, ngf={ngf} (BASELINE.json {cfgn})',
                        'global_batch': world * gen_batch, 'conv_path': args.path, 'parallelism': par, 'labels': args.labels,
                        'spade_interior_reduction': bool(args.sparse), 'winograd': ({0: 'off', 1: 'F(2x2,3x3)', 2: 'ResBlock convs and the SPADE convs up to 64 pixels F(4x4,3x3), SPADE convs above F(2x2,3x3) over boundary quads'}[min(max(args.wino, 0), 2)] if args.path == 'f32' else 'n/a')},
-            'roofline': head['roofline'], 'sustained_peaks': sustained,
         }
+        if args.full:
+            res.update({'host_enqueue_ms_per_step': head['host_enqueue_ms_per_step'], 'roofline': head['roofline'], 'sustained_peaks': sustained})
+        outputs = head.pop('output', None)
         res.update(side)
         if 'f16x3' in blocks and args.path != 'f16x3':
             b = blocks['f16x3']
@@ -711,12 +760,12 @@ def main():
             plegs = ['f16x3', 'f32']
         else:           # --workload pipeline: the top level follows --path; the other f32-class arithmetic rides along as a block
             other = 'f16x3' if args.path == 'f32' else 'f32'
-            plegs = [args.path] + ([] if args.only_headline else [other])
+            plegs = [args.path] + ([other] if args.full and not args.only_headline else [])
         pb = {}
         for path in plegs:
             job = PipelineJob(args, path, dev, rank, weights, pipe_batch)
-            r, _ = run_leg(job, args, dist, dev, world, profile=False)
-            if rank == 0:
+            r, _ = run_leg(job, args, dist, dev, world, profile=False, keep_output=keep and args.workload == 'pipeline' and path == plegs[0])
+            if rank == 0 and args.full:
                 r['stages'] = job.stages(path)
             r['dtype'] = DTYPE[path]
             pb[path] = r
@@ -731,8 +780,10 @@ def main():
                    'n_gpus': world, 'steps': head['steps'], 'warmup': head['warmup'], 'ms_per_step': head['ms_per_step'],
                    'step_ms': head['step_ms'], 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
                    'dtype': DTYPE[plegs[0]], 'data': 'synthetic portraits; procedural calibrated weights',
-                   'config': {'workload': wl, 'global_batch': world * pipe_batch, 'conv_path': plegs[0]},
-                   'stages': head.get('stages')}
+                   'config': {'workload': wl, 'global_batch': world * pipe_batch, 'conv_path': plegs[0]}}
+            if args.full:
+                res['stages'] = head.get('stages')
+            outputs = head.pop('output', None)
             if len(plegs) > 1:
                 res['f32_class_f16x3' if plegs[1] == 'f16x3' else 'strict_fp32'] = pb[plegs[1]]
         else:
@@ -745,8 +796,10 @@ def main():
             res['interactive_b1'] = interactive_b1(ngf, S, sd, all_weights, dev)
         except Exception as e:          # never lose the line over a side block
             res['interactive_b1'] = {'error': f'{type(e).__name__}: {e}'}
-    if rank == 0 and do_gen and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and do_gen and args.full and not args.no_cpu_baseline and world == 1:
         res['cpu_baseline'] = cpu_baseline(ngf, S, sd, weights=all_weights, b16=not args.no_cpu_b16)
+    if keep:
+        dump_outputs(args.dump_outputs, {'images': outputs.numpy()})
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

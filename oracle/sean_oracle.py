@@ -15,8 +15,8 @@ is deliberately the *dense* algorithm of the reference (one-hot conv, broadcast 
 Pinning: the reference has no tests/golden vectors for this path, so this oracle is
 pinned against outputs of the imported reference modules themselves:
 tests/golden/make_golden.py (run in the build container where /root/reference exists) ->
-tests/golden/sean_*.npz, checked by tests/test_oracle_golden.py, plus a direct module-vs-oracle
-comparison in tests/test_oracle_vs_reference.py (skipped where /root/reference is absent).
+tests/golden/sean_*.npz, checked by tests/test_oracle_golden.py, plus the reference module's outputs on
+fresh inputs (tests/golden/oracle_vs_reference_fresh.npz, checked by tests/test_oracle_vs_reference.py).
 
 Each function cites the reference lines it follows.
 """

@@ -66,6 +66,25 @@ def case(name, ngf, S, B, ui, wseed=0, lseed=1234, cseed=2024, nseed=7, grid=16,
     print(name, 'std', img.std(), 'bytes', os.path.getsize(path))
 
 
+FRESH_CASES = [(2, False, 100), (1, True, 200)]      # (B, ui_mode, seed) of tests/test_oracle_vs_reference.py
+
+
+def fresh_cases():
+    """The reference generator on inputs no other fixture uses (ngf 16, 64 x 64, grid 4; labels / codes / noise from seed,
+    seed + 1, seed + 2): the whole images, for tests/test_oracle_vs_reference.py."""
+    ngf, S = 16, 64
+    sd = P.sean_state_dict(0, ngf)
+    out = {}
+    for B, ui, seed in FRESH_CASES:
+        lab = P.blocky_labels(B, S, seed=seed, grid=4)
+        img = R.run_generator(sd, lab, P.style_codes(B, seed=seed + 1), P.noise_planes(B, S, ngf, seed=seed + 2), ngf, ui_mode=ui)
+        key = f'{B}_{int(ui)}_{seed}'
+        out['labels_' + key], out['image_' + key] = lab, img
+    path = os.path.join(HERE, 'oracle_vs_reference_fresh.npz')
+    np.savez_compressed(path, **out)
+    print('fresh', sorted(out), 'bytes', os.path.getsize(path))
+
+
 def zenc_case(name, S, B, labels='blocky', lseed=1234, iseed=31, grid=16):
     sd = P.sean_state_dict(0, 16)     # Zencoder weights do not depend on ngf
     lab = P.blocky_labels(B, S, seed=lseed, grid=grid) if labels == 'blocky' else \
@@ -220,6 +239,9 @@ def main():
         return
     if 'b2' in sys.argv[1:]:
         case('ngf64_S512_B2', 64, 512, 2, False, lseed=41, cseed=42, nseed=43)
+        return
+    if 'fresh' in sys.argv[1:]:
+        fresh_cases()
         return
     if 'aux' in sys.argv[1:] or len(sys.argv) == 1:
         aux_cases()

@@ -2,8 +2,7 @@
 
 Build-container only: /root/reference does not exist on the GPU box, and nothing under
 ctrlhair_amd/, bench.py or the -m gpu tests imports this file.  It is used by
-make_golden.py (to generate committed fixtures) and by tests/test_oracle_vs_reference.py
-(skipped when the reference is absent).  Shims are the ones documented in SURVEY.md 8c /
+make_golden.py only, to generate the committed fixtures the tests read.  Shims are the ones documented in SURVEY.md 8c /
 Appendix A: stub modules for import-only dependencies, Tensor.cuda -> identity, no
 model-zoo download.  No reference source is copied; modules are imported where they lie.
 """

@@ -1,4 +1,5 @@
-"""bench.py contract checks: the multi-GPU launcher logic (CPU) and, on the GPU box, the RCCL code path with one rank."""
+"""bench.py contract checks: the multi-GPU launcher logic and the --dump-outputs sample (CPU); on the GPU box the plain line,
+the --full line and the RCCL code path with one rank."""
 import json
 import os
 import subprocess
@@ -27,10 +28,51 @@ def test_gpus_n_without_enough_devices_fails_loudly():
     assert f'only {have} GPU(s) visible' in (r.stderr + r.stdout)
 
 
+def test_dump_outputs_keeps_a_seeded_sample_under_the_budget(tmp_path):
+    """--dump-outputs: whole arrays when they fit; above the byte budget the same seeded sample of whole images on every call,
+    with the indices it kept."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = np.random.default_rng(5).standard_normal((40, 3, 16, 16)).astype(np.float64)
+    bench.dump_outputs(str(tmp_path / 'all'), {'images': a}, budget=1 << 20)
+    whole = np.load(tmp_path / 'all' / 'images.npy')
+    assert whole.dtype == np.float32 and np.array_equal(whole, a.astype(np.float32))
+    assert not (tmp_path / 'all' / 'images_index.npy').exists()
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), {'images': a}, budget=40_000)
+    s, idx = np.load(tmp_path / 's1' / 'images.npy'), np.load(tmp_path / 's1' / 'images_index.npy')
+    assert idx.dtype == np.float64 and 0 < len(idx) < len(a) and np.array_equal(s, whole[idx.astype(np.int64)])
+    assert np.array_equal(s, np.load(tmp_path / 's2' / 'images.npy'))
+    assert sum(f.stat().st_size for f in (tmp_path / 's1').iterdir()) <= 40_000
+
+
+@pytest.mark.gpu
+def test_plain_line_times_the_headline_only_and_dumps_its_images(tmp_path):
+    """A plain run: the headline leg only, exactly --steps timed steps, and --dump-outputs writes the images of the last timed
+    step -- the generator's output on the seeded benchmark inputs (oracle, 1e-3 like every parity test)."""
+    import numpy as np
+    B, S, ngf = 2, 128, 16
+    r = _run(['--steps', '3', '--warmup', '1', '--batch', str(B), '--size', str(S), '--ngf', str(ngf), '--dump-outputs', str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3 and line['step_ms']['n'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert line['unit'] == 'images/s' and line['higher_is_better'] is True and line['dtype'].startswith('f32 (every product')
+    for k in ('f32_class_f16x3', 'face_like_labels', 'pipeline', 'roofline', 'cpu_baseline', 'interactive_b1', 'host_enqueue_ms_per_step'):
+        assert k not in line, k
+    img = np.load(tmp_path / 'images.npy')
+    assert img.dtype == np.float32 and img.shape == (B, 3, S, S)
+    from ctrlhair_amd import procedural as P
+    from oracle import sean_oracle as O
+    ref = O.generator_forward(O.to_torch(P.sean_state_dict(0, ngf)), P.blocky_labels(B, S), P.style_codes(B),
+                              P.noise_planes(B, S, ngf), ngf).numpy()
+    assert float(np.abs(img - ref).max()) <= 1e-3
+
+
 @pytest.mark.gpu
 def test_force_dist_runs_the_rccl_path_on_one_gpu():
     """1-rank NCCL (= RCCL) process group: PipelinedGather's all_gather_into_tensor on a side stream, slot check, JSON line."""
-    r = _run(['--force-dist', '--only-headline', '--no-cpu-baseline', '--steps', '3', '--warmup', '1', '--batch', '2', '--size', '256'])
+    r = _run(['--full', '--force-dist', '--only-headline', '--no-cpu-baseline', '--steps', '3', '--warmup', '1', '--batch', '2', '--size', '256'])
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 1 and line['value'] > 0 and 'RCCL all-gather' in line['config']['parallelism']
@@ -41,8 +83,8 @@ def test_force_dist_runs_the_rccl_path_on_one_gpu():
 
 @pytest.mark.gpu
 def test_default_line_carries_every_block():
-    """The one driver-run line: exact-f32 top level + f16x3 block + face-like labels + Config 3 pipeline (small sizes here)."""
-    r = _run(['--no-cpu-baseline', '--steps', '3', '--warmup', '1', '--batch', '2', '--size', '256'])
+    """The --full line: exact-f32 top level + f16x3 block + face-like labels + Config 3 pipeline (small sizes here)."""
+    r = _run(['--full', '--no-cpu-baseline', '--steps', '3', '--warmup', '1', '--batch', '2', '--size', '256'])
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',

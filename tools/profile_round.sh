@@ -26,7 +26,7 @@ done
 cp $R/profiles/latest_traffic.json $OUT/latest_traffic.json
 cd /tmp && export TMPDIR=/tmp
 D=$R/gpurun_out/prof_${TAG}_pipe
-rocprofv3 --kernel-trace --stats -d $D/trace -o t -- python $R/bench.py --workload pipeline --path f16x3 --only-headline --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pipe_run.log 2>&1
+rocprofv3 --kernel-trace --stats -d $D/trace -o t -- python $R/bench.py --workload pipeline --path f16x3 --full --only-headline --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pipe_run.log 2>&1
 python $R/tools/rocprof_summary.py $D/trace/t_results.db > $OUT/${TAG}_pipeline_kernel_trace.md 2>> $OUT/pipe_run.log
 grep '^{' $OUT/pipe_run.log | tail -1 > $OUT/${TAG}_pipeline_bench_line.json
 rm -rf $D
@@ -38,7 +38,7 @@ cp $R/gpurun_out/${TAG}_aux_f32_kernel_trace.md $OUT/${TAG}_aux_f32_kernel_trace
 # exact-f32 pipeline trace too
 D=$R/gpurun_out/prof_${TAG}_pipe32
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $D/trace -o t -- python $R/bench.py --workload pipeline --path f32 --only-headline --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pipe32_run.log 2>&1 < /dev/null
+rocprofv3 --kernel-trace --stats -d $D/trace -o t -- python $R/bench.py --workload pipeline --path f32 --full --only-headline --steps 2 --warmup 1 --no-cpu-baseline > $OUT/pipe32_run.log 2>&1 < /dev/null
 python $R/tools/rocprof_summary.py $D/trace/t_results.db > $OUT/${TAG}_pipeline_f32_kernel_trace.md 2>> $OUT/pipe32_run.log < /dev/null
 grep '^{' $OUT/pipe32_run.log | tail -1 > $OUT/${TAG}_pipeline_f32_bench_line.json
 rm -rf $D
