@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <new>
 #include <string>
@@ -284,6 +286,45 @@ int ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target,
     hipError_t e = chk::poisson_blend(source, target, mask, out, H, W, with_gamma, max_iters, rel_tol, h->blend_ws, iters,
                                       static_cast<hipStream_t>(stream));
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_poisson_blend: ") + hipGetErrorString(e));
+}
+
+int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd,
+                        ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!src || !dst || B < 1 || B > 65535 || Hs < 1 || Ws < 1 || C < 1 || C > 4 || Hd < 1 || Hd > 65535 || Wd < 1)
+        return fail(h, CH_ERR_ARG, "ch_resize_linear_u8: bad argument");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::resize_linear_u8(src, dst, B, Hs, Ws, C, Hd, Wd, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_resize_linear_u8: ") + hipGetErrorString(e));
+}
+
+int ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, int label, int ksize, uint8_t* mask, int H, int W,
+                  ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!labels || !mask || B < 1 || B > 65535 || Hl < 1 || Wl < 1 || H < 1 || W < 1 || (H + 15) / 16 > 65535 || label < 0 || label > 255)
+        return fail(h, CH_ERR_ARG, "ch_hair_erode: bad argument");
+    if (ksize < 1 || ksize > 2 * chk::HAIR_ERODE_MAX_R + 1 || ksize % 2 == 0)
+        return fail(h, CH_ERR_ARG, "ch_hair_erode: ksize must be odd and in [1, 31]");
+    // cv2.getStructuringElement(MORPH_ELLIPSE, (ksize, ksize)): row dy spans dx = cvRound(c * sqrt((r^2 - dy^2) / r^2)), c = r
+    chk::HairErodeRows rows{};
+    const int r = ksize / 2;
+    rows.r = r;
+    const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
+    for (int dy = -r; dy <= r; ++dy)
+        rows.hw[dy + r] = (int)std::nearbyint(r * std::sqrt(((double)r * r - (double)dy * dy) * inv_r2));
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::hair_erode(labels, B, Hl, Wl, label, rows, mask, H, W, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_hair_erode: ") + hipGetErrorString(e));
+}
+
+int ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!img || !mask || !sums || B < 1 || B > 65535 || H < 1 || W < 1) return fail(h, CH_ERR_ARG, "ch_hair_color_stats: bad argument");
+    if ((int64_t)H * W > INT64_MAX / (255LL * 255 * 255 * 255))
+        return fail(h, CH_ERR_ARG, "ch_hair_color_stats: H * W too large for exact int64 sums of c^4");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::hair_color_stats(img, mask, B, H, W, sums, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_hair_color_stats: ") + hipGetErrorString(e));
 }
 
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {

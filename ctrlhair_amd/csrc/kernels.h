@@ -111,4 +111,16 @@ hipError_t poisson_blend(const uint8_t* src_hwc, const uint8_t* tgt_hwc, const u
                          int with_gamma, int max_iters, double rel_tol, void* ws, int* iters_out, hipStream_t s);
 hipError_t blend_mask(const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int H, int W, hipStream_t s);
 
+// color_stats.hip: hair colour statistics (script_get_rgb_hsv_label.py:52-63, script_get_color_var_label.py:52-90)
+constexpr int HAIR_ERODE_MAX_R = 15;          // ksize <= 31
+constexpr int HAIR_COLOR_NSTAT = 22;          // == CH_COLOR_STATS
+struct HairErodeRows {                        // MORPH_ELLIPSE element: half-width of row dy = -r..r at hw[dy + r]
+    int r;
+    int hw[2 * HAIR_ERODE_MAX_R + 1];
+};
+hipError_t resize_linear_u8(const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd, hipStream_t s);
+hipError_t hair_erode(const uint8_t* labels, int B, int Hl, int Wl, int label, const HairErodeRows& rows, uint8_t* mask, int H, int W,
+                      hipStream_t s);
+hipError_t hair_color_stats(const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums, hipStream_t s);
+
 }  // namespace chk

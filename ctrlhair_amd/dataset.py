@@ -9,9 +9,16 @@ On-disk formats are the reference's:
   label/<name>.png                      8-bit single-channel PNG, CelebAMask-HQ ids, 512x512 (script_get_mask.py:44-50)
   sean_code/<dataset>___<name>.pkl      pickle of float32 [19,512] (script_get_sean_code.py:56-62)
   sean_code_dict.pkl                    pickle of {'<dataset>___<name>': float32 [19,512]} (utils.py:14-21)
+  hair_info_all_dataset/rgb_stat/<dataset>___<name>.pkl        [moment1..4], float64 [3] each (script_get_rgb_hsv_label.py:58-67)
+  hair_info_all_dataset/color_var_stat/<dataset>___<name>.pkl  {'var_rgb', 'var_hsv', 'var_pca', 'var_pca_mean', 'var_pca_comp'},
+                                        only for images with > 5 hair pixels (script_get_color_var_label.py:58-90)
+  rgb_stat_dict.pkl, color_var_stat_dict.pkl   the merged dicts;  hsv_stat_dict_ordered.pkl   uint8 [N,3] table of the colour
+                                        sliders (script_get_rgb_hsv_label.py:70-90; load with hostutil.DistTranslation(root=<root>))
 
-    python -m ctrlhair_amd.dataset masks  <root> <dataset> [--batch 16]
-    python -m ctrlhair_amd.dataset codes  <root> <dataset> [--batch 16]
+    python -m ctrlhair_amd.dataset masks    <root> <dataset> [--batch 16]
+    python -m ctrlhair_amd.dataset codes    <root> <dataset> [--batch 16]
+    python -m ctrlhair_amd.dataset rgb      <root> <dataset> [--batch 16]     (no network weights: ctrlhair_amd.colorstats)
+    python -m ctrlhair_amd.dataset colorvar <root> <dataset> [--batch 16]
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -116,6 +123,68 @@ def encode_sean_codes(editor, img_dir: str, label_dir: str, code_dir: str, datas
     return out
 
 
+COLOR_JOBS = {'rgb': 'rgb_stat', 'colorvar': 'color_var_stat'}      # job -> hair_info_all_dataset/<dir>, <dir>_dict.pkl
+
+
+def hair_color_stats(stats, img_dir: str, label_dir: str, out_root: str, dataset: str, jobs: Sequence[str] = ('rgb',),
+                     batch: int = 16, rank: int = 0, world: int = 1) -> Dict[str, Dict[str, object]]:
+    """Hair colour labels of every (image, label) pair of this rank's shard (script_get_rgb_hsv_label.py:49-67,
+    script_get_color_var_label.py:48-90): eroded hair mask and exact sums on the device (`stats`: colorstats.HairColorStats),
+    statistics finished on the host, one pickle per image under `out_root/hair_info_all_dataset/<job dir>/`.  Returns
+    {job: {key: value}}; the colorvar job has no entry (and writes no file) for images with <= 5 hair pixels.
+    Images must be square: the reference resizes the label map to `hair_img.shape[:2]` as cv2's (w, h), which swaps the
+    axes of a non-square image."""
+    from . import colorstats as CS
+    unknown = [j for j in jobs if j not in COLOR_JOBS]
+    if unknown:
+        raise ValueError(f'unknown colour job(s) {unknown}; expected {sorted(COLOR_JOBS)}')
+    dirs = {j: os.path.join(out_root, 'hair_info_all_dataset', COLOR_JOBS[j]) for j in jobs}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    out = {j: {} for j in jobs}
+
+    def flush(group):
+        names, imgs, labs = zip(*group)
+        sums = stats.sums(np.stack(imgs), np.stack(labs))
+        for n, sm in zip(names, sums):
+            key = code_key(dataset, n)
+            for j in jobs:
+                v = CS.rgb_stat_from_sums(sm) if j == 'rgb' else CS.color_var_from_sums(sm)
+                if v is None:
+                    continue
+                with open(os.path.join(dirs[j], key + '.pkl'), 'wb') as f:
+                    pickle.dump(v, f)
+                out[j][key] = v
+
+    for names in batches(shard(list_images(img_dir), rank, world), batch):
+        group = []
+        for n in names:
+            img = read_rgb(os.path.join(img_dir, n))
+            if img.shape[0] != img.shape[1]:
+                raise ValueError(f'{n}: image is {img.shape[1]}x{img.shape[0]}; the colour statistics need square images '
+                                 f'(the reference\'s resize swaps (h, w) for cv2\'s dsize)')
+            lab = read_gray(os.path.join(label_dir, os.path.splitext(n)[0] + '.png'))
+            if group and (group[-1][1].shape != img.shape or group[-1][2].shape != lab.shape):
+                flush(group)             # one device batch per run of equal sizes
+                group = []
+            group.append((n, img, lab))
+        if group:
+            flush(group)
+    return out
+
+
+def merge_color_stats(out_root: str, jobs: Sequence[str]) -> None:
+    """Rank 0 after the barrier: merge the per-image pickles (dataset_scripts/utils.py:14-21) and, for the rgb job, build
+    hsv_stat_dict_ordered.pkl from the merged dict (script_get_rgb_hsv_label.py:70-90)."""
+    from .colorstats import hsv_table
+    for j in jobs:
+        d = COLOR_JOBS[j]
+        merged = merge_pickle_dir_to_dict(os.path.join(out_root, 'hair_info_all_dataset', d), os.path.join(out_root, d + '_dict.pkl'))
+        if j == 'rgb':
+            with open(os.path.join(out_root, 'hsv_stat_dict_ordered.pkl'), 'wb') as f:
+                pickle.dump(hsv_table(merged), f)
+
+
 def _dist_env():
     return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
 
@@ -123,7 +192,7 @@ def _dist_env():
 def main(argv=None):
     import argparse
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('job', choices=('masks', 'codes'))
+    ap.add_argument('job', choices=('masks', 'codes') + tuple(COLOR_JOBS))
     ap.add_argument('root')
     ap.add_argument('dataset')
     ap.add_argument('--batch', type=int, default=16)
@@ -140,8 +209,22 @@ def main(argv=None):
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         dist.init_process_group('gloo', rank=rank, world_size=world)      # only a barrier before the merge
     torch.cuda.set_device(local)
-    he = HairEditor(True, True, weights=args.weights, device=local, img_size=args.img_size, max_batch=args.batch)
     base = os.path.join(args.root, args.dataset)
+    if args.job in COLOR_JOBS:           # no network weights: the colour statistics need only the library
+        from . import lib
+        from .colorstats import HairColorStats
+        stats = HairColorStats(lib.Handle(local), torch.device('cuda', local))
+        res = hair_color_stats(stats, os.path.join(base, 'images_256'), os.path.join(base, 'label'), args.root, args.dataset,
+                               (args.job,), args.batch, rank, world)
+        if dist is not None:
+            dist.barrier()
+        if rank == 0:
+            merge_color_stats(args.root, (args.job,))
+        print(f'rank {rank}/{world}: {len(res[args.job])} files')
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    he = HairEditor(True, True, weights=args.weights, device=local, img_size=args.img_size, max_batch=args.batch)
     if args.job == 'masks':
         n = len(extract_masks(he, os.path.join(base, 'images_256'), os.path.join(base, 'label'), args.batch, rank, world))
     else:

@@ -64,6 +64,8 @@ class HipModels:
                                                                 f16x3=bool(f16x3))
         from .blending import PoissonBlender
         self.blender = PoissonBlender(h, dev)       # blending step after the generator (Backend(blending=True))
+        from .colorstats import HairColorStats
+        self.color_stats = HairColorStats(h, dev)   # hair colour statistics (get_hair_color, ctrlhair_amd.dataset rgb / colorvar)
 
 
 def is_released_checkpoint(weights) -> bool:
@@ -236,7 +238,18 @@ class HairEditor:
         return U.resize_nearest(parsing.astype('uint8'), (self.img_size, self.img_size))
 
     def get_hair_color(self, img):
-        """hair_editor.py:233-243 (needs cv2 for the 19x19 elliptical erosion)."""
+        """hair_editor.py:233-243: mean RGB (float64 [3]) of the hair pixels left by the 19x19 elliptical erosion at 1024 px.
+        With the HIP models (HipModels.color_stats) everything after the 512-px parse runs on the device (resize, erosion, exact
+        integer sums; ctrlhair_amd/colorstats.py); otherwise it needs cv2."""
+        cs = getattr(self.models, 'color_stats', None)
+        if cs is not None:
+            from PIL import Image
+            from .colorstats import ERODE_KSIZE, mean_from_sums
+            img = np.asarray(img).astype('uint8')
+            fp = self.face_parsing
+            lab, _ = fp.parse_tensor(fp.normalise(np.asarray(Image.fromarray(img).resize((512, 512), Image.BILINEAR))))
+            mask = cs.erode(lab, (1024, 1024), ERODE_KSIZE)          # nearest 512 -> 1024, label 13, erosion
+            return mean_from_sums(U.to_host(cs.mask_sums(cs.resize(img, (1024, 1024)), mask))[0])
         cv2 = U._cv2()
         if cv2 is None:
             raise RuntimeError('get_hair_color needs cv2 (elliptical erosion), which is not installed')

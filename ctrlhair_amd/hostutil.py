@@ -215,7 +215,7 @@ _MASK_LUT = {}
 
 class DistTranslation:
     """util/color_from_hsv_to_gaussian.py:16-33: HSV value <-> N(0,1) quantile through the dataset's sorted HSV table
-    (dataset_info_ctrlhair/hsv_stat_dict_ordered.pkl, not shipped).  `table` [N,3] (each column sorted) may be injected;
+    (dataset_info_ctrlhair/hsv_stat_dict_ordered.pkl, not shipped; `python -m ctrlhair_amd.dataset rgb` builds it).  `table` [N,3] (each column sorted) may be injected;
     otherwise the pickle is loaded if present, else a documented synthetic table (uniform quantiles of H in [0,179],
     S,V in [0,255]) is used so the API stays functional."""
 

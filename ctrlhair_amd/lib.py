@@ -37,6 +37,9 @@ SYMBOLS = {
     'ch_bisenet_parse': (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     'ch_blend_mask': (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     'ch_poisson_blend': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _D, C.POINTER(_I), _VP]),
+    'ch_resize_linear_u8': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
+    'ch_hair_erode': (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP, _I, _I, _VP]),
+    'ch_hair_color_stats': (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP]),
     'ch_sean_set_tap': (_I, [_VP, C.c_char_p, _VP]),
     'ch_sean_scale_report': (_I, [_VP, C.POINTER(C.c_float), _I]),
     'ch_sean_debug_read': (_I, [_VP, _VP, C.c_size_t]),

@@ -236,6 +236,28 @@ int  ch_blend_mask(ch_handle* h, const uint8_t* target_parsing, const uint8_t* f
 int  ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target, const uint8_t* mask, uint8_t* out, int H,
                       int W, int with_gamma, int max_iters, double rel_tol, int* iters, ch_stream_t stream);
 
+/* ---- Hair colour statistics (dataset labels, colour-slider table, HairEditor.get_hair_color) ------------------------------
+ * ch_resize_linear_u8 replaces cv2.resize(img, (Wd, Hd)) (INTER_LINEAR) of uint8 images (hair_editor.py:239): OpenCV's
+ *   fixed-point arithmetic (11-bit tap weights, >> 4, >> 16, + 2 >> 2), bit-exact.  src uint8 [B,Hs,Ws,C], dst uint8
+ *   [B,Hd,Wd,C] device pointers; 1 <= C <= 4, all sizes >= 1, Hd <= 65535.
+ * ch_hair_erode replaces script_get_rgb_hsv_label.py:52-56 / script_get_color_var_label.py:52-56 / hair_editor.py:238-241:
+ *   mask = cv2.erode((cv2.resize(labels, (W, H), INTER_NEAREST) == label), MORPH_ELLIPSE (ksize, ksize)), cv2's default
+ *   border (pixels outside the image never erode).  Nearest source row min((int)(y * ((double)Hl / H)), Hl - 1), columns
+ *   likewise.  labels uint8 [B,Hl,Wl], mask uint8 0/1 [B,H,W] device pointers; ksize odd, 1 <= ksize <= 31.
+ * ch_hair_color_stats replaces the statistics of script_get_rgb_hsv_label.py:58-63 and script_get_color_var_label.py:58-90
+ *   (moments, variances, PCA) by the exact integer sums they are finished from on the host (ctrlhair_amd/colorstats.py).
+ *   img uint8 [B,H,W,3] (RGB), mask uint8 [B,H,W] (non-zero = hair) device pointers; sums int64 [B,CH_COLOR_STATS] device
+ *   pointer, overwritten.  Per image: [0] pixel count, [1..3] sum c, [4..6] sum c^2, [7..9] sum c^3, [10..12] sum c^4 per
+ *   RGB channel, [13..15] sum c0*c1, c0*c2, c1*c2, [16..21] sum H, H^2, S, S^2, V, V^2 of cv2's 8-bit RGB2HSV (H in [0,180)).
+ *   H * W <= 2^63 / 255^4 (no overflow for any content).  Order-independent integer sums: run-to-run deterministic. */
+#define CH_COLOR_STATS 22
+int  ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd,
+                         ch_stream_t stream);
+int  ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, int label, int ksize, uint8_t* mask, int H, int W,
+                   ch_stream_t stream);
+int  ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums,
+                         ch_stream_t stream);
+
 /* Test hook: after the next ch_sean_generate calls, the activation produced at stage `name` ("fc", "<block>",
  * "<block>.ace_0" = tensor before leaky_relu, "<block>.conv_0", "<block>.shortcut") is also copied
  * (device-to-device, same stream) to `dev_ptr` (caller-sized: [B,C,r,r] floats).  dev_ptr NULL removes the tap. */
