@@ -260,22 +260,28 @@ int ch_bisenet_parse(ch_handle* h, const float* img, uint8_t* labels, float* log
     CH_CALL("ch_bisenet_parse", h->bisenet.parse(img, labels, logits, B, H, W, static_cast<hipStream_t>(stream)))
 }
 
-int ch_blend_mask(ch_handle* h, const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int H, int W,
-                  ch_stream_t stream) {
+int ch_blend_mask_batch(ch_handle* h, const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int B, int H, int W,
+                        ch_stream_t stream) {
     if (!h) return CH_ERR_ARG;
-    if (!target_parsing || !face_parsing || !out || H < 1 || W < 1) return fail(h, CH_ERR_ARG, "ch_blend_mask: bad argument");
+    if (!target_parsing || !face_parsing || !out || B < 1 || B > 65535 || H < 1 || W < 1)
+        return fail(h, CH_ERR_ARG, "ch_blend_mask: bad argument");
     DeviceGuard guard(h->device);
-    hipError_t e = chk::blend_mask(target_parsing, face_parsing, out, H, W, static_cast<hipStream_t>(stream));
+    hipError_t e = chk::blend_mask_batch(target_parsing, face_parsing, out, B, H, W, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_blend_mask: ") + hipGetErrorString(e));
 }
 
-int ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target, const uint8_t* mask, uint8_t* out, int H, int W,
-                     int with_gamma, int max_iters, double rel_tol, int* iters, ch_stream_t stream) {
+int ch_blend_mask(ch_handle* h, const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int H, int W,
+                  ch_stream_t stream) {
+    return ch_blend_mask_batch(h, target_parsing, face_parsing, out, 1, H, W, stream);
+}
+
+int ch_poisson_blend_batch(ch_handle* h, const uint8_t* source, const uint8_t* target, const uint8_t* mask, uint8_t* out, int B, int H,
+                           int W, int with_gamma, int max_iters, double rel_tol, int* iters, ch_stream_t stream) {
     if (!h) return CH_ERR_ARG;
-    if (!source || !target || !mask || !out || H < 3 || W < 3 || max_iters < 0 || !(rel_tol >= 0.0))
-        return fail(h, CH_ERR_ARG, "ch_poisson_blend: bad argument (images need H, W >= 3)");
+    if (!source || !target || !mask || !out || B < 1 || B > 65535 || H < 3 || W < 3 || max_iters < 0 || !(rel_tol >= 0.0))
+        return fail(h, CH_ERR_ARG, "ch_poisson_blend: bad argument (B >= 1; images need H, W >= 3)");
     DeviceGuard guard(h->device);
-    const size_t need = chk::poisson_workspace_bytes(H, W);
+    const size_t need = (size_t)B * chk::poisson_workspace_bytes(H, W);
     if (need > h->blend_ws_bytes) {
         if (h->blend_ws) (void)hipFree(h->blend_ws);
         h->blend_ws = nullptr;
@@ -283,9 +289,14 @@ int ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target,
         if (hipMalloc(&h->blend_ws, need) != hipSuccess) return fail(h, CH_ERR_HIP, "ch_poisson_blend: workspace allocation failed");
         h->blend_ws_bytes = need;
     }
-    hipError_t e = chk::poisson_blend(source, target, mask, out, H, W, with_gamma, max_iters, rel_tol, h->blend_ws, iters,
-                                      static_cast<hipStream_t>(stream));
+    hipError_t e = chk::poisson_blend_batch(source, target, mask, out, B, H, W, with_gamma, max_iters, rel_tol, h->blend_ws, iters,
+                                            static_cast<hipStream_t>(stream));
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_poisson_blend: ") + hipGetErrorString(e));
+}
+
+int ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target, const uint8_t* mask, uint8_t* out, int H, int W,
+                     int with_gamma, int max_iters, double rel_tol, int* iters, ch_stream_t stream) {
+    return ch_poisson_blend_batch(h, source, target, mask, out, 1, H, W, with_gamma, max_iters, rel_tol, iters, stream);
 }
 
 int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd,

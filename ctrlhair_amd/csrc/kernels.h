@@ -106,10 +106,12 @@ hipError_t lut_gemv_mfma(const float* x, const float* W, float* out, int N, int 
 hipError_t subspace_add(float* h, const float* z, int zld, const float* U, const float* L, const float* mu, int B, int D,
                         int Z, hipStream_t s);
 // poisson_kernels.hip: blending step after the generator (hair_editor.py:285-310, poisson_blending.py:29-87)
-size_t poisson_workspace_bytes(int H, int W);
-hipError_t poisson_blend(const uint8_t* src_hwc, const uint8_t* tgt_hwc, const uint8_t* mask, uint8_t* out_hwc, int H, int W,
-                         int with_gamma, int max_iters, double rel_tol, void* ws, int* iters_out, hipStream_t s);
-hipError_t blend_mask(const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int H, int W, hipStream_t s);
+// Batched over B images of one size ([B,H,W,3] / [B,H,W]); ws holds B * poisson_workspace_bytes(H, W) bytes, iters_out (host, optional)
+// B counts.  Image i is bit-identical to a B = 1 call on the same inputs.
+size_t poisson_workspace_bytes(int H, int W);      // per image
+hipError_t poisson_blend_batch(const uint8_t* src_hwc, const uint8_t* tgt_hwc, const uint8_t* mask, uint8_t* out_hwc, int B, int H, int W,
+                               int with_gamma, int max_iters, double rel_tol, void* ws, int* iters_out, hipStream_t s);
+hipError_t blend_mask_batch(const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int B, int H, int W, hipStream_t s);
 
 // color_stats.hip: hair colour statistics (script_get_rgb_hsv_label.py:52-63, script_get_color_var_label.py:52-90)
 constexpr int HAIR_ERODE_MAX_R = 15;          // ksize <= 31

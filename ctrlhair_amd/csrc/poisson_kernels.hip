@@ -11,10 +11,16 @@
 // ~1e-2 relative error, more than one uint8 level after the gamma power).  L2-resident streaming kernels, 2 launches per iteration
 // (Chronopoulos-Gear CG), scalars (alpha, beta, convergence) stay on the device.  Dot products are two-level and
 // deterministic: per-block partial sums, re-reduced in a fixed order by every block that needs the scalar (no atomics).
+//
+// Batched: every kernel runs on a grid of (blocks per image, B).  blockIdx.y selects the image; each image has its own
+// vectors, partials and PoissonCG state and keeps the block partition of a single-image solve, so image i of a batch is
+// bit-identical to the same image solved alone (iteration count included) and the single-image call is the B = 1 case.
+// At 256 px the solve is bound by its two launches per iteration, not by bandwidth: a batch shares them.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <stdint.h>
+#include <vector>
 
 #include "kernels.h"
 
@@ -40,12 +46,51 @@ __device__ __forceinline__ bool pb_unknown(const uint8_t* m, int y, int x, int H
     return m[y * W + x] != 0 || y == 0 || x == 0 || y == H - 1 || x == W - 1;
 }
 
+constexpr int PB_MAXBLK = 512;      // CG kernels: grid-stride over at most this many blocks per image
+
+struct PoissonCG {
+    double gamma[2][3], alpha[2][3], gamma0[3];
+    int done, iters;
+};
+
+// Workspace of a batch: PoissonCG[B] (contiguous, so the host reads every flag with one copy; B slots of PB_CG_SLOT bytes are
+// reserved), then per image `stride` bytes holding X, R, P, S, W (3 HW doubles each), partG, partD (3 PB_MAXBLK doubles each)
+// and the unknown map U (HW bytes).
+constexpr size_t PB_CG_SLOT = 256;
+static_assert(sizeof(PoissonCG) <= PB_CG_SLOT, "PoissonCG outgrew its slot");
+
+struct PoissonVec {
+    double *X, *R, *P, *S, *Wv, *partG, *partD;
+    uint8_t* U;
+};
+
+__host__ __device__ inline size_t pb_vec_stride(size_t HW) {
+    const size_t n = 5 * 3 * HW * sizeof(double) + 2 * 3 * PB_MAXBLK * sizeof(double) + HW;
+    return (n + 255) / 256 * 256;
+}
+
+__device__ __forceinline__ PoissonVec pb_vectors(char* vecs, int img, int HW) {
+    PoissonVec v;
+    v.X = reinterpret_cast<double*>(vecs + (size_t)img * pb_vec_stride((size_t)HW));
+    v.R = v.X + 3 * (size_t)HW;
+    v.P = v.R + 3 * (size_t)HW;
+    v.S = v.P + 3 * (size_t)HW;
+    v.Wv = v.S + 3 * (size_t)HW;
+    v.partG = v.Wv + 3 * (size_t)HW;
+    v.partD = v.partG + 3 * (size_t)PB_MAXBLK;
+    v.U = reinterpret_cast<uint8_t*>(v.partD + 3 * (size_t)PB_MAXBLK);
+    return v;
+}
+
+// The kernels below are thin: they pick the image of blockIdx.y and call a per-image body whose pointer PARAMETERS carry
+// __restrict__ (the qualifier is only honoured on parameters; without it the update kernel's loads of one channel wait for
+// the stores of the previous one: +5 % per solve, measured).
+
 // gamma transform, right-hand side, initial guess x0 = target, r0 = b - A x0, p = s = 0
-__global__ __launch_bounds__(256) void pb_setup_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ tgt,
-                                                       const uint8_t* __restrict__ mask, double* __restrict__ X,
-                                                       double* __restrict__ R, double* __restrict__ P,
-                                                       double* __restrict__ S, uint8_t* __restrict__ U, int H, int W,
-                                                       float inv_gamma) {
+__device__ __forceinline__ void pb_setup_image(const uint8_t* __restrict__ src, const uint8_t* __restrict__ tgt,
+                                               const uint8_t* __restrict__ mask, double* __restrict__ X, double* __restrict__ R,
+                                               double* __restrict__ P, double* __restrict__ S, uint8_t* __restrict__ U, int H, int W,
+                                               float inv_gamma) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     const int HW = H * W;
     if (k < HW) {
@@ -82,6 +127,15 @@ __global__ __launch_bounds__(256) void pb_setup_kernel(const uint8_t* __restrict
     }
 }
 
+__global__ __launch_bounds__(256) void pb_setup_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ tgt,
+                                                       const uint8_t* __restrict__ mask, char* __restrict__ vecs, int H, int W,
+                                                       float inv_gamma) {
+    const size_t HW = (size_t)H * W;
+    const PoissonVec pv = pb_vectors(vecs, blockIdx.y, H * W);
+    pb_setup_image(src + blockIdx.y * HW * 3, tgt + blockIdx.y * HW * 3, mask + blockIdx.y * HW, pv.X, pv.R, pv.P, pv.S, pv.U, H, W,
+                   inv_gamma);
+}
+
 // ---- CG in the Chronopoulos-Gear form: one matvec and ONE fused pair of dot products per iteration, hence two kernel
 // launches per iteration (the solver is launch-bound: the vectors of a 512x512 image live in L2):
 //      w = A r,  gamma = r.r,  delta = r.w                                        (pb_matvec_kernel)
@@ -89,14 +143,9 @@ __global__ __launch_bounds__(256) void pb_setup_kernel(const uint8_t* __restrict
 //      p = r + beta p;  s = w + beta s;  x += alpha p;  r -= alpha s              (pb_update_kernel)
 // Every block re-reduces the per-block partials in the same order, so all blocks agree bit for bit on the scalars and on
 // convergence (no flag race); the previous iteration's scalars sit in a ping-pong slot written by block 0.
-constexpr int PB_MAXBLK = 512;      // CG kernels: grid-stride over at most this many blocks (2 per CU)
-
-struct PoissonCG {
-    double gamma[2][3], alpha[2][3], gamma0[3];
-    int done, iters;
-};
-
-__global__ void pb_init_cg_kernel(PoissonCG* cg) {
+// Ragged convergence: every image stops on its own criterion; the blocks of a finished image return at the top of both kernels.
+__global__ void pb_init_cg_kernel(PoissonCG* cgs) {
+    PoissonCG* cg = cgs + blockIdx.x;
     for (int q = 0; q < 2; ++q)
         for (int c = 0; c < 3; ++c) cg->gamma[q][c] = cg->alpha[q][c] = 0.0;
     for (int c = 0; c < 3; ++c) cg->gamma0[c] = 0.0;
@@ -105,11 +154,10 @@ __global__ void pb_init_cg_kernel(PoissonCG* cg) {
 }
 
 // w = A r on the unknowns; partG[c][block] = partial r.r, partD[c][block] = partial r.w
-__global__ __launch_bounds__(256) void pb_matvec_kernel(const double* __restrict__ R, double* __restrict__ Wv,
-                                                        const uint8_t* __restrict__ U, const PoissonCG* cg,
-                                                        double* __restrict__ partG, double* __restrict__ partD, int H, int W) {
+__device__ __forceinline__ void pb_matvec_image(const double* __restrict__ R, double* __restrict__ Wv,
+                                                const uint8_t* __restrict__ U, const PoissonCG* cg,
+                                                double* __restrict__ partG, double* __restrict__ partD, int H, int W, double* sh) {
     if (cg->done) return;
-    __shared__ double sh[4];
     const int HW = H * W;
     double g[3] = {0.0, 0.0, 0.0}, d[3] = {0.0, 0.0, 0.0};
     // grid-stride: at most PB_MAXBLK blocks, so that the per-block partials every block re-reduces stay a few KiB
@@ -139,13 +187,17 @@ __global__ __launch_bounds__(256) void pb_matvec_kernel(const double* __restrict
     }
 }
 
-__global__ __launch_bounds__(256) void pb_update_kernel(double* __restrict__ X, double* __restrict__ R, double* __restrict__ P,
-                                                        double* __restrict__ S, const double* __restrict__ Wv,
-                                                        const uint8_t* __restrict__ U, PoissonCG* cg,
-                                                        const double* __restrict__ partG, const double* __restrict__ partD,
-                                                        int HW, int iter, double rel_tol2) {
-    if (cg->done) return;
+__global__ __launch_bounds__(256) void pb_matvec_kernel(char* __restrict__ vecs, const PoissonCG* cgs, int H, int W) {
     __shared__ double sh[4];
+    const PoissonVec pv = pb_vectors(vecs, blockIdx.y, H * W);
+    pb_matvec_image(pv.R, pv.Wv, pv.U, cgs + blockIdx.y, pv.partG, pv.partD, H, W, sh);
+}
+
+__device__ __forceinline__ void pb_update_image(double* __restrict__ X, double* __restrict__ R, double* __restrict__ P,
+                                                double* __restrict__ S, const double* __restrict__ Wv,
+                                                const uint8_t* __restrict__ U, PoissonCG* cg, const double* __restrict__ partG,
+                                                const double* __restrict__ partD, int HW, int iter, double rel_tol2, double* sh) {
+    if (cg->done) return;
     const int q = iter & 1;
     double alpha[3], beta[3], gam[3];
     bool live[3], any = false;
@@ -194,11 +246,22 @@ __global__ __launch_bounds__(256) void pb_update_kernel(double* __restrict__ X, 
     }
 }
 
+__global__ __launch_bounds__(256) void pb_update_kernel(char* __restrict__ vecs, PoissonCG* cgs, int HW, int iter,
+                                                        double rel_tol2) {
+    __shared__ double sh[4];
+    const PoissonVec pv = pb_vectors(vecs, blockIdx.y, HW);
+    pb_update_image(pv.X, pv.R, pv.P, pv.S, pv.Wv, pv.U, cgs + blockIdx.y, pv.partG, pv.partD, HW, iter, rel_tol2, sh);
+}
+
 // Residual check after the LAST allowed update (the update kernel only learns at the top of the following iteration that the
-// previous one met the tolerance): sums the partials of a final mat-vec and sets the flag.  One block.  nparts = blocks of
-// that mat-vec.  With no iteration done (max_iters = 0) there is no ||r0|| on file: only an exactly solved system counts.
-__global__ __launch_bounds__(256) void pb_final_check_kernel(PoissonCG* __restrict__ cg, const double* __restrict__ partG, int nparts,
+// previous one met the tolerance): sums the partials of a final mat-vec and sets the flag.  One block per image.  nparts =
+// blocks per image of that mat-vec.  With no iteration done (max_iters = 0) there is no ||r0|| on file: only an exactly solved
+// system counts.  An image that is already done ran no final mat-vec (its partials are those of its last iteration): skipped.
+__global__ __launch_bounds__(256) void pb_final_check_kernel(char* __restrict__ vecs, PoissonCG* __restrict__ cgs, int HW, int nparts,
                                                              double rel_tol2) {
+    PoissonCG* __restrict__ cg = cgs + blockIdx.y;
+    if (cg->done) return;
+    const double* __restrict__ partG = pb_vectors(vecs, blockIdx.y, HW).partG;
     __shared__ double sh[4];
     bool any = false;
 #pragma unroll
@@ -211,9 +274,11 @@ __global__ __launch_bounds__(256) void pb_final_check_kernel(PoissonCG* __restri
 }
 
 // out = clamp(x^gamma) truncated to uint8 (poisson_blending.py:81-86); NaN (negative base) -> 0
-__global__ void pb_finish_kernel(const double* __restrict__ X, uint8_t* __restrict__ out, int HW, float gamma) {
+__global__ void pb_finish_kernel(char* __restrict__ vecs, uint8_t* __restrict__ out_b, int HW, float gamma) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= HW) return;
+    const double* __restrict__ X = pb_vectors(vecs, blockIdx.y, HW).X;
+    uint8_t* __restrict__ out = out_b + (size_t)blockIdx.y * HW * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const double x = X[c * HW + k];
@@ -223,48 +288,43 @@ __global__ void pb_finish_kernel(const double* __restrict__ X, uint8_t* __restri
     }
 }
 
-size_t poisson_workspace_bytes(int H, int W) {
-    const size_t HW = (size_t)H * W;
-    return 5 * 3 * HW * sizeof(double) + 2 * 3 * PB_MAXBLK * sizeof(double) + HW + 512 + sizeof(PoissonCG);
-}
+size_t poisson_workspace_bytes(int H, int W) { return PB_CG_SLOT + pb_vec_stride((size_t)H * W); }
 
-hipError_t poisson_blend(const uint8_t* src, const uint8_t* tgt, const uint8_t* mask, uint8_t* out, int H, int W,
-                         int with_gamma, int max_iters, double rel_tol, void* ws, int* iters_out, hipStream_t s) {
+hipError_t poisson_blend_batch(const uint8_t* src, const uint8_t* tgt, const uint8_t* mask, uint8_t* out, int B, int H, int W,
+                               int with_gamma, int max_iters, double rel_tol, void* ws, int* iters_out, hipStream_t s) {
     const int HW = H * W;
-    double* X = static_cast<double*>(ws);
-    double *R = X + 3 * (size_t)HW, *P = R + 3 * (size_t)HW, *S = P + 3 * (size_t)HW, *Wv = S + 3 * (size_t)HW;
+    PoissonCG* cgs = static_cast<PoissonCG*>(ws);
+    char* vecs = static_cast<char*>(ws) + (size_t)B * PB_CG_SLOT;
     const int nb = (HW + 255) / 256, ncg = nb < PB_MAXBLK ? nb : PB_MAXBLK;
-    double *partG = Wv + 3 * (size_t)HW, *partD = partG + 3 * (size_t)PB_MAXBLK;
-    uint8_t* U = reinterpret_cast<uint8_t*>(partD + 3 * (size_t)PB_MAXBLK);
-    PoissonCG* cg = reinterpret_cast<PoissonCG*>(U + (((size_t)HW + 255) / 256) * 256);
     const float gamma = with_gamma ? 2.2f : 1.0f;
-    const dim3 g(nb), gc(ncg), b(256);
-    hipLaunchKernelGGL(pb_init_cg_kernel, dim3(1), dim3(1), 0, s, cg);
-    hipLaunchKernelGGL(pb_setup_kernel, g, b, 0, s, src, tgt, mask, X, R, P, S, U, H, W, 1.0f / gamma);
-    int done = 0;
+    const dim3 g(nb, B), gc(ncg, B), b(256);
+    std::vector<PoissonCG> host(B);
+    auto poll = [&]() -> hipError_t {      // every image's state in ONE copy
+        hipError_t e = hipMemcpyAsync(host.data(), cgs, (size_t)B * sizeof(PoissonCG), hipMemcpyDeviceToHost, s);
+        return e != hipSuccess ? e : hipStreamSynchronize(s);
+    };
+    hipLaunchKernelGGL(pb_init_cg_kernel, dim3(B), dim3(1), 0, s, cgs);
+    hipLaunchKernelGGL(pb_setup_kernel, g, b, 0, s, src, tgt, mask, vecs, H, W, 1.0f / gamma);
+    bool done = false;
     for (int it = 0; it < max_iters && !done; ++it) {
-        hipLaunchKernelGGL(pb_matvec_kernel, gc, b, 0, s, R, Wv, U, cg, partG, partD, H, W);
-        hipLaunchKernelGGL(pb_update_kernel, gc, b, 0, s, X, R, P, S, Wv, U, cg, partG, partD, HW, it, rel_tol * rel_tol);
-        if ((it & 63) == 63) {        // poll the device flag every 64 iterations (converged runs stop launching)
-            hipError_t e = hipMemcpyAsync(&done, &cg->done, sizeof(int), hipMemcpyDeviceToHost, s);
+        hipLaunchKernelGGL(pb_matvec_kernel, gc, b, 0, s, vecs, cgs, H, W);
+        hipLaunchKernelGGL(pb_update_kernel, gc, b, 0, s, vecs, cgs, HW, it, rel_tol * rel_tol);
+        if ((it & 63) == 63) {        // poll the device flags every 64 iterations (launching stops once every image is done)
+            const hipError_t e = poll();
             if (e != hipSuccess) return e;
-            e = hipStreamSynchronize(s);
-            if (e != hipSuccess) return e;
+            done = true;
+            for (int i = 0; i < B; ++i) done = done && host[i].done != 0;
         }
     }
     if (!done) {           // did the last allowed update reach the tolerance?  (mat-vec + reduction only, no update)
-        hipLaunchKernelGGL(pb_matvec_kernel, gc, b, 0, s, R, Wv, U, cg, partG, partD, H, W);
-        hipLaunchKernelGGL(pb_final_check_kernel, dim3(1), b, 0, s, cg, partG, ncg, rel_tol * rel_tol);
+        hipLaunchKernelGGL(pb_matvec_kernel, gc, b, 0, s, vecs, cgs, H, W);
+        hipLaunchKernelGGL(pb_final_check_kernel, dim3(1, B), b, 0, s, vecs, cgs, HW, ncg, rel_tol * rel_tol);
     }
-    hipLaunchKernelGGL(pb_finish_kernel, g, b, 0, s, X, out, HW, gamma);
-    if (iters_out) {       // iteration count; negated (INT_MIN for zero iterations) when rel_tol was not reached
-        int dn = 0, its = 0;
-        hipError_t e = hipMemcpyAsync(&dn, &cg->done, sizeof(int), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(&its, &cg->iters, sizeof(int), hipMemcpyDeviceToHost, s);
+    hipLaunchKernelGGL(pb_finish_kernel, g, b, 0, s, vecs, out, HW, gamma);
+    if (iters_out) {       // iteration counts; negated (INT_MIN for zero iterations) when rel_tol was not reached
+        const hipError_t e = poll();
         if (e != hipSuccess) return e;
-        e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return e;
-        *iters_out = dn ? its : (its > 0 ? -its : INT_MIN);
+        for (int i = 0; i < B; ++i) iters_out[i] = host[i].done ? host[i].iters : (host[i].iters > 0 ? -host[i].iters : INT_MIN);
     }
     return hipGetLastError();
 }
@@ -275,10 +335,14 @@ hipError_t poisson_blend(const uint8_t* src, const uint8_t* tgt, const uint8_t* 
 __constant__ int c_hw13[13] = {0, 3, 4, 5, 6, 6, 6, 6, 6, 5, 4, 3, 0};
 __constant__ int c_hw5[5] = {0, 2, 2, 2, 0};
 
-__global__ void blend_mask_kernel(const uint8_t* __restrict__ tp, const uint8_t* __restrict__ fp, uint8_t* __restrict__ out,
+__global__ void blend_mask_kernel(const uint8_t* __restrict__ tp_b, const uint8_t* __restrict__ fp_b, uint8_t* __restrict__ out_b,
                                   int H, int W) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= H * W) return;
+    const size_t img = (size_t)blockIdx.y * H * W;
+    const uint8_t* __restrict__ tp = tp_b + img;
+    const uint8_t* __restrict__ fp = fp_b + img;
+    uint8_t* __restrict__ out = out_b + img;
     const int y = k / W, x = k % W;
     const bool bg = tp[k] == 0;
     const int r = bg ? 2 : 6;
@@ -297,8 +361,9 @@ __global__ void blend_mask_kernel(const uint8_t* __restrict__ tp, const uint8_t*
     out[k] = v;
 }
 
-hipError_t blend_mask(const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int H, int W, hipStream_t s) {
-    hipLaunchKernelGGL(blend_mask_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, target_parsing, face_parsing, out, H, W);
+hipError_t blend_mask_batch(const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int B, int H, int W,
+                            hipStream_t s) {
+    hipLaunchKernelGGL(blend_mask_kernel, dim3((H * W + 255) / 256, B), dim3(256), 0, s, target_parsing, face_parsing, out, H, W);
     return hipGetLastError();
 }
 

@@ -320,6 +320,55 @@ class HairEditor:
         res_mask_dilated = d13 * (1 - bg_mask) + d5 * bg_mask
         return blender(face_img, res_img, 1 - res_mask_dilated, with_gamma=True), res_mask_dilated
 
+    def postprocess_blending_batch(self, face_img, res_imgs, face_parsing, target_parsings, blender=None):
+        """postprocess_blending for N generated images of one portrait, on the HIP blender (PoissonBlender) only: ONE mask
+        call, ONE batched Poisson solve and ONE download instead of N of each.  face_img: the portrait, uint8 [H,W,3] or a
+        [3,H,W] / [1,3,H,W] tensor in [-1,1]; res_imgs [N,3,S,S] in [-1,1]; face_parsing one label map [h,w]; target_parsings
+        [N,h,w] (nearest-resized to S like postprocess_blending's).  Returns (uint8 images [N,S,S,3] numpy, res_mask_dilated
+        uint8 [N,S,S] on the device).  Image i equals postprocess_blending(face_img, res_imgs[i], face_parsing,
+        target_parsings[i])[0] bit for bit."""
+        from .blending import PoissonBlender
+        if blender is None:
+            blender = getattr(self.models, 'blender', None)
+        if not isinstance(blender, PoissonBlender):
+            raise RuntimeError('postprocess_blending_batch needs the HIP models (HipModels.blender); loop over '
+                               'postprocess_blending for an injected blender')
+        dev = blender.device
+
+        def to_u8(x):                # [-1,1] float -> uint8 with the arithmetic of postprocess_blending, clamped before the cast
+            return (x * 127.5 + 127.5).clamp(0, 255).to(torch.uint8)
+
+        res = torch.as_tensor(res_imgs).to(dev)
+        if res.dtype != torch.uint8:
+            res = to_u8(res.float())
+        if res.shape[-1] > 3:                                  # tensor order [N,3,S,S] -> cv2 order
+            res = res.permute(0, 2, 3, 1)
+        res = res.contiguous()
+        S = tuple(res.shape[1:3])
+        face = face_img if isinstance(face_img, torch.Tensor) else np.asarray(face_img)
+        if face.ndim == 4:
+            face = face[0]
+        if face.shape[2] > 3:                                  # tensor order, [-1,1]
+            face = to_u8(torch.as_tensor(face).to(dev).float()).permute(1, 2, 0)
+        face = U.to_host(face).astype('uint8') if isinstance(face, torch.Tensor) else face.astype('uint8')
+        if face.shape[:2] != S:
+            face = U.resize_bilinear(face, S)
+
+        def at_image_size(m):        # [..., h, w] label maps on the device, nearest-resized (cv2 INTER_NEAREST) to the images' size
+            m = (m if isinstance(m, torch.Tensor) else torch.as_tensor(np.asarray(m))).to(dev).to(torch.uint8)
+            h, w = m.shape[-2:]
+            if (h, w) == S:
+                return m
+            ys = torch.as_tensor(np.minimum((np.arange(S[0]) * (h / S[0])).astype(np.int64), h - 1), device=dev)
+            xs = torch.as_tensor(np.minimum((np.arange(S[1]) * (w / S[1])).astype(np.int64), w - 1), device=dev)
+            return m.index_select(-2, ys).index_select(-1, xs)
+        tp = target_parsings if isinstance(target_parsings, torch.Tensor) else torch.as_tensor(np.asarray(target_parsings))
+        tp = at_image_size(tp.reshape(res.shape[0], *tp.shape[-2:]))
+        fp = at_image_size(face_parsing)
+        res_mask_dilated = blender.blend_mask(tp, fp.reshape(fp.shape[-2], fp.shape[-1]))
+        out = blender.blend_batch(face, res, 1 - res_mask_dilated, with_gamma=True)
+        return U.to_host(out), res_mask_dilated
+
     def crop_face(self, img_rgb, save_path=None):
         """hair_editor.py:312-329: dlib landmark alignment -- CPU pre-processing, out of scope."""
         raise NotImplementedError('crop_face needs dlib landmark models (external_code/crop.py); crop offline')

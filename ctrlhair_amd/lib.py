@@ -37,6 +37,8 @@ SYMBOLS = {
     'ch_bisenet_parse': (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     'ch_blend_mask': (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     'ch_poisson_blend': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _D, C.POINTER(_I), _VP]),
+    'ch_blend_mask_batch': (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    'ch_poisson_blend_batch': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _D, C.POINTER(_I), _VP]),
     'ch_resize_linear_u8': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP]),
     'ch_hair_erode': (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP, _I, _I, _VP]),
     'ch_hair_color_stats': (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP]),

@@ -237,6 +237,24 @@ class EditPipeline:
             stages.update(lat, labels=labels, mask=mask, image=image)
         return image
 
+    def edit_blended(self, img: torch.Tensor, sliders: Optional[dict] = None, noise: Optional[torch.Tensor] = None, seed: int = 1,
+                     labels: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                     stages: Optional[dict] = None) -> torch.Tensor:
+        """edit(), then the reference's default post-processing (Backend(blending=True), hair_editor.py:285-310): every edited
+        portrait is Poisson-blended back into its input, the whole batch in one solve (PoissonBlender.blend_batch).  The
+        composition of Backend.output(): source = `img` as uint8, target = the generated image as uint8, face parsing = the
+        parsed labels, target parsing = the decoded mask nearest-upsampled to S.  Returns uint8 [B,S,S,3] on the device; the
+        only host synchronisation is the solver's convergence poll.  `stages` also receives 'blend_mask'."""
+        st = {} if stages is None else stages
+        image = self.edit(img, sliders=sliders, noise=noise, seed=seed, labels=labels, mask=mask, stages=st)
+        to_u8 = lambda x: (x * 127.5 + 127.5).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+        r = img.shape[-1] // 256
+        target_parsing = st['mask'] if r == 1 else st['mask'].repeat_interleave(r, 1).repeat_interleave(r, 2).contiguous()
+        blender = self.models.blender
+        keep = blender.blend_mask(target_parsing, st['labels'])
+        st['blend_mask'] = keep
+        return blender.blend_batch(to_u8(img), to_u8(image), 1 - keep, with_gamma=True)
+
     STAGES = ('parse', 'shape_encode', 'zencoder', 'colour', 'shape_decode', 'generator')
 
     def stage_times(self, img: torch.Tensor, reps: int = 3, before=None) -> Dict[str, float]:

@@ -186,7 +186,8 @@ class Backend(HairEditor):
         """Batched output(): renders a list of LatentRepresentation with ONE shape-decoder, ONE colour-generator and ONE SEAN
         generator call (the reference offers only batch-1 output() and loops over it: shape_branch/validation_in_train.py:
         114-121, color_texture_branch/solver.py:270-299, README "Editing with Batch").  Image i equals what
-        `output(latents[i])` returns for the same noise; cur_latent / cur_mask are left untouched.  Returns (list of uint8
+        `output(latents[i])` returns for the same noise; cur_latent / cur_mask are left untouched.  With blending on, the N
+        images are Poisson-blended into the input photo by ONE batched solve (HairEditor.postprocess_blending_batch).  Returns (list of uint8
         RGB images, uint8 label maps [N,256,256])."""
         latents = list(latents)
         n = len(latents)
@@ -208,8 +209,14 @@ class Backend(HairEditor):
         if noise is None and self.noise is not None:                                 # pinned planes: same draw for every image
             noise = self.noise.expand(n, -1).contiguous() if self.noise.shape[0] == 1 else self.noise
         imgs = self.gen_imgs(codes, lab, noise=noise)
-        out = [self.postprocess_blending(self.input_img, imgs[i], self.input_mask, masks_np[i], blending=self.blending,
-                                         blender=self.blender)[0] for i in range(n)]
+        from ..blending import PoissonBlender
+        blender = self.blender if self.blender is not None else getattr(getattr(self, 'models', None), 'blender', None)
+        if self.blending and isinstance(blender, PoissonBlender):
+            # one mask call, one batched Poisson solve, one download (bit-identical to the per-image loop below)
+            out = list(self.postprocess_blending_batch(self.input_img, imgs, self.input_mask, masks, blender=blender)[0])
+        else:                                    # no blending, or an injected callable blender
+            out = [self.postprocess_blending(self.input_img, imgs[i], self.input_mask, masks_np[i], blending=self.blending,
+                                             blender=self.blender)[0] for i in range(n)]
         return out, masks_np
 
     def sweep(self, att_name, idx, values, noise=None):

@@ -230,11 +230,23 @@ int  ch_bisenet_parse(ch_handle* h, const float* img, uint8_t* labels, float* lo
  *   iterations) when the solve stopped at max_iters without reaching rel_tol -- checked once more after the last update
  *   (the reference uses a direct solve: an unconverged image is not its output).  Output agrees with the
  *   reference to +-1 grey level (the floor() after the gamma power amplifies last-bit differences of pow() and of the
- *   solve wherever the result sits on an integer boundary, e.g. every kept target pixel).  Run-to-run deterministic. */
+ *   solve wherever the result sits on an integer boundary, e.g. every kept target pixel).  Run-to-run deterministic.
+ * ch_blend_mask_batch / ch_poisson_blend_batch: the same two steps for B images of one size in one call (what
+ *   Backend.outputs() and EditPipeline.edit_blended() blend): target_parsing, face_parsing, mask, out of ch_blend_mask uint8
+ *   [B,H,W]; source, target, out uint8 [B,H,W,3]; *iters a host array of B counts (optional), each with the sign convention
+ *   above.  Every CG iteration is ONE pair of launches for all B images; each image keeps its own state and stops on its own
+ *   criterion, so image i is bit-identical to the single-image call on the same inputs, iteration count included (the
+ *   single-image calls are the B = 1 case).  1 <= B <= 65535.  The handle's blend workspace grows to B times the
+ *   single-image one (~15 f64 planes per image: 31.7 MB per 512x512 image, 0.5 GB for B = 16 at 512x512) and is kept until
+ *   ch_destroy; split larger batches on the caller's side (PoissonBlender.max_workspace_bytes). */
 int  ch_blend_mask(ch_handle* h, const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int H, int W,
                    ch_stream_t stream);
 int  ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target, const uint8_t* mask, uint8_t* out, int H,
                       int W, int with_gamma, int max_iters, double rel_tol, int* iters, ch_stream_t stream);
+int  ch_blend_mask_batch(ch_handle* h, const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int B, int H,
+                         int W, ch_stream_t stream);
+int  ch_poisson_blend_batch(ch_handle* h, const uint8_t* source, const uint8_t* target, const uint8_t* mask, uint8_t* out, int B,
+                            int H, int W, int with_gamma, int max_iters, double rel_tol, int* iters, ch_stream_t stream);
 
 /* ---- Hair colour statistics (dataset labels, colour-slider table, HairEditor.get_hair_color) ------------------------------
  * ch_resize_linear_u8 replaces cv2.resize(img, (Wd, Hd)) (INTER_LINEAR) of uint8 images (hair_editor.py:239): OpenCV's
