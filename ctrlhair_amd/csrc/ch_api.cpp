@@ -299,6 +299,31 @@ int ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target,
     return ch_poisson_blend_batch(h, source, target, mask, out, 1, H, W, with_gamma, max_iters, rel_tol, iters, stream);
 }
 
+size_t ch_mask_warp_workspace_bytes(int B) { return chk::mask_warp_workspace_bytes(B); }
+
+int ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
+                       const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out, float* uv_out,
+                       float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!hair_labels || !face_labels || !V || !F || !desc || !labels_out || !workspace || B < 1 || B > 65535 || (!U_in && (!b || !bc)))
+        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch: bad argument");
+    if (workspace_bytes < chk::mask_warp_workspace_bytes(B))
+        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch: workspace smaller than ch_mask_warp_workspace_bytes(B)");
+    for (int i = 0; i < B; ++i) {
+        const int32_t* d = desc + 6 * i;
+        if (d[0] < 0 || d[2] < 0 || d[4] < 0 || d[5] < 0)
+            return fail(h, CH_ERR_ARG, "ch_mask_warp_batch: negative offset or count in desc[" + std::to_string(i) + "]");
+        if (d[1] < 3 || d[1] > chk::WARP_MAX_V || d[3] < 1 || d[3] > chk::WARP_MAX_F)
+            return fail(h, CH_ERR_ARG, "ch_mask_warp_batch: mesh " + std::to_string(i) + " has " + std::to_string(d[1]) + " vertices / " +
+                                           std::to_string(d[3]) + " triangles; supported: 3.." + std::to_string(chk::WARP_MAX_V) +
+                                           " vertices, 1.." + std::to_string(chk::WARP_MAX_F) + " triangles");
+    }
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::mask_warp_batch(hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, uv_out, U_out, workspace, B,
+                                        CH_WARP_OUTER_ITERS, CH_WARP_MAX_CG, CH_WARP_REL_TOL, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_mask_warp_batch: ") + hipGetErrorString(e));
+}
+
 int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd,
                         ch_stream_t stream) {
     if (!h) return CH_ERR_ARG;

@@ -125,4 +125,18 @@ hipError_t hair_erode(const uint8_t* labels, int B, int Hl, int Wl, int label, c
                       hipStream_t s);
 hipError_t hair_color_stats(const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums, hipStream_t s);
 
+// mask_warp.hip: hair-shape transfer warp (wrap_codes/mask_adaptor.py:87-143): batched ARAP solve of packed 2-D triangle meshes, then
+// UV render + mask sampling + compose into uint8 [B,512,512] label maps.  desc_host: B x {v_off, n_v, f_off, n_f, b_off, n_b} (host).
+constexpr int WARP_MAX_V = 2048;              // vertices / triangles of one pair's mesh (LDS budget of arap_solve_kernel)
+constexpr int WARP_MAX_F = 4096;
+constexpr int WARP_DESC_PAIRS = 16;           // descriptors reach the workspace as kernel arguments, this many pairs per store launch
+struct WarpDesc {
+    int n, pair0;
+    int d[WARP_DESC_PAIRS][6];
+};
+size_t mask_warp_workspace_bytes(int B);
+hipError_t mask_warp_batch(const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int* F, const int* bidx,
+                           const float* bc, const int* desc_host, const float* U_in, uint8_t* labels_out, float* uv_out, float* U_out,
+                           void* ws, int B, int outer_iters, int max_cg, float rel_tol, hipStream_t s);
+
 }  // namespace chk

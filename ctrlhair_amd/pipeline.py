@@ -91,6 +91,7 @@ class EditPipeline:
         self.median = torch.from_numpy(med.astype(np.float32)).to(self.device)
         self.side = torch.cuda.Stream(self.device)      # edit(): the shape branch runs here, underneath the Zencoder
         self.overlap = True
+        self.warper = None             # warping.MaskWarper of transfer_shape, built on first use (shares the models' handle)
         self.split_encode = False      # edit(): BiSeNet underneath the Zencoder's convs (ch_sean_encode_features / _regions);
                                        # measured: no further gain once the shape branch runs aside (tools/edit_modes.py)
         self.mean = torch.tensor(_MEAN, device=self.device).view(1, 3, 1, 1)
@@ -100,11 +101,12 @@ class EditPipeline:
         self.models.generator.handle.close()
 
     # ---- stages (each returns device tensors; citations: module docstring) -----------------------------------------------
-    def parse(self, img: torch.Tensor) -> torch.Tensor:
+    def parse(self, img: torch.Tensor, full: bool = False) -> torch.Tensor:
         """img [B,3,S,S] in [-1,1] -> CelebAMask-HQ label map uint8 [B,S,S].  As the reference does for every img_size
         (my_parsing_util.py:34-35, hair_editor.py:331-335): the parser always sees a 512x512 bilinear resize of the portrait
         (8-bit, like the PIL image it resizes), and the label map is nearest-resized back to S (cv2 INTER_NEAREST:
-        src = floor(dst * 512 / S)); ToTensor + Normalize, net, argmax, remap in between."""
+        src = floor(dst * 512 / S)); ToTensor + Normalize, net, argmax, remap in between.  full: the 512x512 label map itself
+        (what the mask warp of transfer_shape works on)."""
         S = img.shape[-1]
         x01 = img * 0.5 + 0.5
         if S != 512:
@@ -115,7 +117,7 @@ class EditPipeline:
                 u8 = torch.round(u8).clamp(0, 255)
             x01 = u8 / 255.0
         lab = self.models.face_parsing.parse_tensor((x01 - self.mean) / self.std)[0]
-        if S != 512:
+        if S != 512 and not full:
             idx = (torch.arange(S, device=lab.device) * 512) // S
             lab = lab[:, idx][:, :, idx].contiguous()
         return lab
@@ -254,6 +256,37 @@ class EditPipeline:
         keep = blender.blend_mask(target_parsing, st['labels'])
         st['blend_mask'] = keep
         return blender.blend_batch(to_u8(img), to_u8(image), 1 - keep, with_gamma=True)
+
+    def transfer_shape(self, img: torch.Tensor, donor_img: torch.Tensor, lm, donor_lm, sliders: Optional[dict] = None,
+                       noise: Optional[torch.Tensor] = None, seed: int = 1, stages: Optional[dict] = None,
+                       labels512: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Backend.transfer_latent_representation('shape') + output() for B pairs: the hair SHAPE of donor_img[i] on img[i].
+        img, donor_img: cuda float32 [B,3,S,S] in [-1,1]; lm, donor_lm: their 81-point landmarks, float [B,81,2] in [0,1]
+        (host).  Both batches are parsed at 512, the donors' hair masks are warped onto the faces by ONE ch_mask_warp_batch
+        call (warping.MaskWarper.warp_batch), the result goes nearest -> 256 into the shape encoder, and the image is rendered
+        with that hair code, the input's own face code and appearance.  The masks never leave the device (meshing the landmarks
+        is host work).  sliders: as edit(), applied after the transfer.  labels512: a caller-supplied parsing, uint8 [2B,512,512]
+        (the B faces, then the B donors), instead of parsing here (like edit(labels=...); the tests use it to step over argmax
+        ties between batch sizes).  `stages` also receives 'warp_target' uint8 [B,512,512] and 'labels512'."""
+        sliders = {} if sliders is None else sliders
+        B, S = img.shape[0], img.shape[-1]
+        if self.warper is None:
+            from .warping import MaskWarper
+            self.warper = MaskWarper(self.models.generator.handle, self.device)
+        lab512 = self.parse(torch.cat([img, donor_img]), full=True) if labels512 is None else labels512
+        warped = self.warper.warp_batch(lab512[B:], lab512[:B], donor_lm, lm)
+        labels = lab512[:B]
+        if S != 512:                                   # parse(): cv2 INTER_NEAREST, src = floor(dst * 512 / S), for every S
+            idx = (torch.arange(S, device=lab512.device) * 512) // S
+            labels = labels[:, idx][:, :, idx].contiguous()
+        lat = self.analyse(img, labels)
+        # Backend: preprocess_mask (nearest -> img_size) then nearest -> 256: floor(dst * 2) both times
+        lat['shape'] = self.models.mask_generator.encode_labels(warped[:, ::2, ::2].contiguous())[0]
+        lat = self.apply_sliders(lat, sliders)
+        image, mask = self.render(lat, noise=noise, seed=seed)
+        if stages is not None:
+            stages.update(lat, labels=labels, mask=mask, image=image, warp_target=warped, labels512=lab512)
+        return image
 
     STAGES = ('parse', 'shape_encode', 'zencoder', 'colour', 'shape_decode', 'generator')
 

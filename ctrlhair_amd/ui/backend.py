@@ -1,7 +1,9 @@
 """Mirror of /root/reference/ui/backend.py::Backend (the editing API CtrlHair scripts call) on the MI355X library.
 Every public method of ui/backend.py:67-462 is present with the same name, argument order and return types; line
-references are given per method.  Shape transfer by photo (`transfer_latent_representation('shape')`) needs the
-reference's ARAP warping tool chain (wrap_codes/, dlib) and accepts an injected `warper` instead.
+references are given per method.  Shape transfer by photo (`transfer_latent_representation('shape')`) warps the target's hair mask
+onto the input face with the built-in GPU warper (ctrlhair_amd/warping.py) once 81-point landmarks are known (`set_landmarks`, or
+a `landmarker` callable; landmark detection itself is not part of this project); an injected `warper` (the reference's
+wrap_codes.mask_adaptor.wrap_by_imgs) still takes precedence.
 """
 import contextlib
 import os
@@ -34,9 +36,10 @@ class LatentRepresentation:                       # ui/backend.py:31-37
 
 class Backend(HairEditor):
     def __init__(self, maximum_value_fe, blending=True, temp_path=os.path.join(TEMP_FOLDER, 'demo_output'), *,
-                 hsv_table=None, warper=None, blender=None, **editor_kwargs):
+                 hsv_table=None, warper=None, blender=None, landmarker=None, **editor_kwargs):
         """ui/backend.py:45-65.  Keyword-only extras: hsv_table (DistTranslation data), warper (shape-transfer warp
-        function), blender (Poisson blender), and HairEditor's weights/device/img_size/models."""
+        function with wrap_by_imgs' signature; without it the built-in MaskWarper is used), landmarker (callable img_rgb ->
+        float [81,2] landmarks in pixels of that image, for the built-in warper), blender (Poisson blender), and HairEditor's weights/device/img_size/models."""
         super().__init__(True, True, **editor_kwargs)
         self.target_img = None
         self.input_img = None
@@ -53,6 +56,10 @@ class Backend(HairEditor):
         self.dist_translation = U.DistTranslation(hsv_table)
         self.warper = warper
         self.blender = blender
+        self.landmarker = landmarker
+        self.input_landmarks = None      # [81,2] in [0,1]: set_landmarks(), or the landmarker's answer at transfer time
+        self.target_landmarks = None
+        self.mask_warper = None          # built on first use
         self.noise = None          # optional pinned noise planes for repeatable output() (tests / A-B comparisons)
 
     def _side_stream(self):
@@ -149,12 +156,14 @@ class Backend(HairEditor):
         parsed = self.parse_img(img_rgb)
         (self.input_img, self.cur_mask, self.cur_latent, self.input_mask, self.input_sean_code,
          self.input_hair_feature) = parsed
+        self.input_landmarks = None                  # landmarks belong to the photo they were given for
         return self.input_img, mask_to_rgb(self.cur_mask, draw_type=1)
 
     def set_target_img(self, img_rgb):            # :137-145
         parsed = self.parse_img(img_rgb)
         self.target_img, self.target_latent, self.target_mask, self.target_hair_feature = (parsed[0], parsed[2], parsed[3],
                                                                                           parsed[5])
+        self.target_landmarks = None
         return self.target_img, mask_to_rgb(self.target_mask, draw_type=1)
 
     # ---- render (ui/backend.py:147-175) ----------------------------------------------------------------------
@@ -287,11 +296,17 @@ class Backend(HairEditor):
     # ---- transfer (ui/backend.py:266-302) ---------------------------------------------------------------------
     def transfer_latent_representation(self, flag, refresh=True):
         if flag == 'shape':
-            if self.warper is None:
-                raise RuntimeError("transfer_latent_representation('shape') warps the target hair mask with the reference's "
-                                   "ARAP tool chain (wrap_codes.mask_adaptor.wrap_by_imgs: dlib + my_arap binaries); pass "
-                                   "Backend(..., warper=wrap_by_imgs) to enable it")
-            wt, _ = self.warper(self.target_img, self.input_img, wrap_temp_folder=self.temp_path, need_crop=False)
+            if self.warper is not None:
+                wt, _ = self.warper(self.target_img, self.input_img, wrap_temp_folder=self.temp_path, need_crop=False)
+            else:
+                lms = self._shape_transfer_landmarks()
+                if lms is None:
+                    raise RuntimeError("transfer_latent_representation('shape') warps the target hair mask onto the input face and "
+                                       "needs 81-point landmarks of both images for the built-in GPU warper: call "
+                                       "Backend.set_landmarks(input_lm, target_lm) or pass Backend(..., landmarker=fn); or pass "
+                                       "Backend(..., warper=wrap_by_imgs) to use the reference's ARAP tool chain "
+                                       "(wrap_codes.mask_adaptor.wrap_by_imgs: dlib + my_arap binaries)")
+                wt = self._builtin_warp(*lms)
             wt = self.preprocess_mask(wt)
             self.warp_target = wt[0, 0]
             w256 = U.resize_nearest(wt[0, 0], (256, 256))
@@ -306,6 +321,42 @@ class Backend(HairEditor):
             self.refresh_cur_mask()
         if flag == 'texture':                            # texture and curliness travel together (:300-302)
             self.transfer_latent_representation('curliness')
+
+    def set_landmarks(self, input_lm, target_lm):
+        """81-point landmarks (the dlib model the reference uses, external_code/landmarks_util.py) of the input and the target
+        image for the built-in shape transfer: float [81,2] (x, y) in [0,1] image coordinates, what hair_mask_transfer_wrap takes.
+        Call it after set_input_img / set_target_img: loading another photo forgets that photo's landmarks (the landmarker, if
+        any, is then asked again)."""
+        self.input_landmarks = np.asarray(input_lm, np.float64).reshape(81, 2)
+        self.target_landmarks = np.asarray(target_lm, np.float64).reshape(81, 2)
+
+    def _shape_transfer_landmarks(self):
+        """(target = hair donor, input = face) landmarks in [0,1], or None when they cannot be had."""
+        if self.input_landmarks is not None and self.target_landmarks is not None:
+            return self.target_landmarks, self.input_landmarks
+        if self.landmarker is None:
+            return None
+        out = []
+        for img in (self.target_img, self.input_img):          # mask_adaptor.py:202-205: pixels / image width
+            out.append(np.asarray(self.landmarker(img), np.float64).reshape(81, 2) / np.asarray(img).shape[1])
+        return out[0], out[1]
+
+    def _parse512(self, img_rgb):
+        """FaceParsing.parsing_img + swap_parsing_label_to_celeba_mask as wrap_by_imgs runs them (mask_adaptor.py:207-212):
+        uint8 [512,512] CelebAMask ids on the device."""
+        from PIL import Image
+        fp = self.face_parsing
+        pil = img_rgb if isinstance(img_rgb, Image.Image) else Image.fromarray(np.asarray(img_rgb).astype('uint8'))
+        return fp.parse_tensor(fp.normalise(np.asarray(pil.resize((512, 512), Image.BILINEAR))))[0][0]
+
+    def _builtin_warp(self, hair_lm, face_lm):
+        """wrap_by_imgs(target_img, input_img, need_crop=False)[0] on the GPU: result_parsing [512,512]."""
+        if self.mask_warper is None:
+            from ..warping import MaskWarper
+            self.mask_warper = MaskWarper(self.face_parsing.handle, self.device)
+        labels = self.mask_warper.warp_batch(self._parse512(self.target_img)[None], self._parse512(self.input_img)[None],
+                                             hair_lm[None], face_lm[None])
+        return U.to_host(labels[0]).astype('int')
 
     def refresh_cur_mask(self, target_latent=None):      # :304-315
         lat = self.cur_latent if target_latent is None else target_latent

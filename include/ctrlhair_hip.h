@@ -270,6 +270,37 @@ int  ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, i
 int  ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums,
                          ch_stream_t stream);
 
+/* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
+ * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image
+ * edge extended 10 px, mask_adaptor.py:119-131), the pair's triangle mesh is deformed as rigidly as possible (libigl's per-element
+ * ARAP energy for 2-D triangles, cotangent weights, CH_WARP_OUTER_ITERS local/global iterations from U = V as my_arap.cpp:181-187;
+ * the global step is a Jacobi-preconditioned conjugate-gradient solve, warm-started, run until ||r|| <= CH_WARP_REL_TOL * ||rhs|| or
+ * CH_WARP_MAX_CG iterations), the deformed mesh is drawn with per-vertex colour V / 671 (mesh_core.cpp render_colors_core: float32
+ * barycentrics in its operation order, first covering triangle in face order wins, uncovered = -1), the canvas edge is fixed
+ * (triangle_wrap_hair.py:77-85), the padded mask is sampled as cv2.remap(INTER_LINEAR, constant border 0) does and truncated to
+ * uint8, the border is cropped and naive_transfer composes: warped hair -> 13, the face's own hair -> 255, else face_labels.
+ *   hair_labels, face_labels, labels_out: uint8 [B,512,512] (CelebAMask-HQ ids).
+ *   Packed meshes: V float [sum n_v, 2] rest positions on the canvas (x, y); F int32 [sum n_f, 3] vertex indices LOCAL to the
+ *   pair; b int32 [sum n_b] constrained vertices (local), bc float [sum n_b, 2] their targets.  desc: HOST array int32 [B,6] =
+ *   {v_off, n_v, f_off, n_f, b_off, n_b} per pair (offsets in vertices / triangles / constraints); 3 <= n_v <= CH_WARP_MAX_V,
+ *   1 <= n_f <= CH_WARP_MAX_F, checked here.  A mesh whose device-side indices are out of range is rendered undeformed.
+ *   U_in (optional) float [sum n_v, 2]: deformed positions given by the caller -- the ARAP solve is skipped (b, bc may be null).
+ *   uv_out (optional) float [B,672,672,2]: the UV image after the edge fix.  U_out (optional) float [sum n_v, 2].
+ *   workspace: caller-owned device buffer of ch_mask_warp_workspace_bytes(B) bytes (256-byte aligned), contents undefined.
+ *   The descriptors are copied to its head as kernel arguments (desc may be freed on return); the ARAP solve and the render are
+ *   each ONE launch for all B pairs (one workgroup per pair / per 16x16 tile and pair).
+ * Everything is enqueued on `stream`; no synchronisation, no allocation.  No atomics on floating-point data and fixed reduction
+ * trees: pair i of a batch is bit-identical to a B = 1 call on the same inputs. */
+#define CH_WARP_MAX_V 2048
+#define CH_WARP_MAX_F 4096
+#define CH_WARP_OUTER_ITERS 100
+#define CH_WARP_MAX_CG 200
+#define CH_WARP_REL_TOL 1e-6f
+size_t ch_mask_warp_workspace_bytes(int B);
+int  ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
+                        const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out,
+                        float* uv_out, float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream);
+
 /* Test hook: after the next ch_sean_generate calls, the activation produced at stage `name` ("fc", "<block>",
  * "<block>.ace_0" = tensor before leaky_relu, "<block>.conv_0", "<block>.shortcut") is also copied
  * (device-to-device, same stream) to `dev_ptr` (caller-sized: [B,C,r,r] floats).  dev_ptr NULL removes the tap. */
