@@ -24,6 +24,7 @@ struct ch_handle {
     chk::BiSeNetModel bisenet;
     void* blend_ws = nullptr;        // Poisson CG workspace, grown on demand
     size_t blend_ws_bytes = 0;
+    chk::AlignCache align_cache;     // host Lanczos tables of the face alignment, built on first use
 };
 
 namespace {
@@ -43,6 +44,46 @@ struct DeviceGuard {
         if (switched) (void)hipSetDevice(prev);
     }
 };
+}  // namespace
+
+// ---- face alignment (face_align.hip) ---------------------------------------------------------------------------------------------
+namespace {
+constexpr int ALIGN_MAX_DIM = 32768;         // photo sides; keeps every byte offset and pixel count far inside int / size_t
+bool align_dims_ok(int H, int W) { return H >= 1 && W >= 1 && H <= ALIGN_MAX_DIM && W <= ALIGN_MAX_DIM; }
+bool pads_ok(const int32_t* p, int radius) {
+    return p && p[0] >= 1 && p[1] >= 1 && p[2] >= 1 && p[3] >= 1 && p[0] <= ALIGN_MAX_DIM && p[1] <= ALIGN_MAX_DIM && p[2] <= ALIGN_MAX_DIM &&
+           p[3] <= ALIGN_MAX_DIM && radius >= 0 && radius <= ALIGN_MAX_DIM;
+}
+// plan doubles -> AlignPlan; empty string when consistent with an H x W photo
+std::string parse_plan(const double* d, int H, int W, chk::AlignPlan& p) {
+    for (int i = 0; i < CH_ALIGN_PLAN_LEN; ++i)
+        if (!std::isfinite(d[i])) return "plan[" + std::to_string(i) + "] is not finite";
+    for (int i = 0; i < 12; ++i)
+        if (d[i] != std::floor(d[i]) || std::fabs(d[i]) > 1e9) return "plan[" + std::to_string(i) + "] is not an integer";
+    if (d[20] != std::floor(d[20]) || d[21] != std::floor(d[21]) || std::fabs(d[20]) > 1e9 || std::fabs(d[21]) > 1e9)
+        return "transform_size / output_size is not an integer";
+    p.shrink = (int)d[0], p.rw = (int)d[1], p.rh = (int)d[2];
+    p.cx0 = (int)d[3], p.cy0 = (int)d[4], p.cx1 = (int)d[5], p.cy1 = (int)d[6];
+    p.do_pad = d[7] != 0.0, p.pl = (int)d[8], p.pt = (int)d[9], p.pr = (int)d[10], p.pb = (int)d[11];
+    for (int i = 0; i < 8; ++i) p.q[i] = d[12 + i];
+    p.T = (int)d[20], p.S = (int)d[21];
+    if (p.shrink < 0) return "negative shrink";
+    if (p.shrink > 1) {
+        if (!align_dims_ok(p.rh, p.rw)) return "resized size out of range";
+        if (p.rw != (int)std::nearbyint((double)W / p.shrink) || p.rh != (int)std::nearbyint((double)H / p.shrink))
+            return "resized size is not the photo's divided by the shrink factor (rounded half to even)";
+    } else if (p.rw != W || p.rh != H) {
+        return "resized size differs from the photo's without a shrink";
+    }
+    if (p.cx0 < 0 || p.cy0 < 0 || p.cx1 > p.rw || p.cy1 > p.rh || p.cx0 >= p.cx1 || p.cy0 >= p.cy1) return "crop box outside the (resized) photo";
+    if (p.do_pad) {
+        const int32_t pads[4] = {p.pl, p.pt, p.pr, p.pb};
+        if (!pads_ok(pads, 0)) return "pad widths must be in [1, 32768]";
+        if ((p.cy1 - p.cy0) + p.pt + p.pb > ALIGN_MAX_DIM || (p.cx1 - p.cx0) + p.pl + p.pr > ALIGN_MAX_DIM) return "padded size out of range";
+    }
+    if (p.S < 1 || p.T < p.S || p.T > CH_ALIGN_MAX_TRANSFORM) return "need 1 <= output_size <= transform_size <= " + std::to_string(CH_ALIGN_MAX_TRANSFORM);
+    return "";
+}
 }  // namespace
 
 extern "C" {
@@ -322,6 +363,84 @@ int ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t* 
     hipError_t e = chk::mask_warp_batch(hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, uv_out, U_out, workspace, B,
                                         CH_WARP_OUTER_ITERS, CH_WARP_MAX_CG, CH_WARP_REL_TOL, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_mask_warp_batch: ") + hipGetErrorString(e));
+}
+
+size_t ch_resample_lanczos_workspace_bytes(int Hs, int Ws, int C, int Hd, int Wd) {
+    if (!align_dims_ok(Hs, Ws) || !align_dims_ok(Hd, Wd) || C < 1 || C > 4) return 0;
+    return chk::lanczos_workspace_bytes(Hs, Ws, C, Hd, Wd);
+}
+
+int ch_resample_lanczos_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst, int Hd, int Wd, void* workspace,
+                           size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!src || !dst || !workspace || !align_dims_ok(Hs, Ws) || !align_dims_ok(Hd, Wd) || C < 1 || C > 4)
+        return fail(h, CH_ERR_ARG, "ch_resample_lanczos_u8: bad argument");
+    if (workspace_bytes < chk::lanczos_workspace_bytes(Hs, Ws, C, Hd, Wd))
+        return fail(h, CH_ERR_ARG, "ch_resample_lanczos_u8: workspace smaller than ch_resample_lanczos_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::lanczos_resample_u8(h->align_cache, src, (long long)Ws * C, Hs, Ws, C, dst, Hd, Wd, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_resample_lanczos_u8: ") + hipGetErrorString(e));
+}
+
+size_t ch_quad_warp_workspace_bytes(int T, int S) {
+    if (S < 1 || T < S || T > CH_ALIGN_MAX_TRANSFORM) return 0;
+    return chk::quad_warp_workspace_bytes(T, S);
+}
+
+int ch_quad_warp_resample_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, const double* coef, int T, int S, uint8_t* dst, void* workspace,
+                             size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!src || !dst || !coef || !align_dims_ok(Hs, Ws) || S < 1 || T < S || T > CH_ALIGN_MAX_TRANSFORM || (!workspace && S != T))
+        return fail(h, CH_ERR_ARG, "ch_quad_warp_resample_u8: bad argument");
+    for (int i = 0; i < 8; ++i)
+        if (!std::isfinite(coef[i])) return fail(h, CH_ERR_ARG, "ch_quad_warp_resample_u8: quad coefficient is not finite");
+    if (workspace_bytes < chk::quad_warp_workspace_bytes(T, S))
+        return fail(h, CH_ERR_ARG, "ch_quad_warp_resample_u8: workspace smaller than ch_quad_warp_workspace_bytes(T, S)");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::quad_warp_resample_u8(h->align_cache, src, (long long)Ws * 3, Hs, Ws, coef, T, S, dst, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_quad_warp_resample_u8: ") + hipGetErrorString(e));
+}
+
+size_t ch_align_pad_workspace_bytes(int Hs, int Ws, const int32_t* pads, int radius) {
+    if (!align_dims_ok(Hs, Ws) || !pads_ok(pads, radius)) return 0;
+    const int Hp = Hs + pads[1] + pads[3], Wp = Ws + pads[0] + pads[2];
+    if (!align_dims_ok(Hp, Wp)) return 0;
+    return chk::align_pad_workspace_bytes(Hp, Wp, radius);
+}
+
+int ch_align_pad_feather_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, const int32_t* pads, const double* gauss_w, int radius,
+                            uint8_t* dst, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!src || !dst || !gauss_w || !workspace || !align_dims_ok(Hs, Ws) || !pads_ok(pads, radius))
+        return fail(h, CH_ERR_ARG, "ch_align_pad_feather_u8: bad argument (pads must be >= 1)");
+    const size_t need = ch_align_pad_workspace_bytes(Hs, Ws, pads, radius);
+    if (need == 0) return fail(h, CH_ERR_ARG, "ch_align_pad_feather_u8: padded size out of range");
+    if (workspace_bytes < need) return fail(h, CH_ERR_ARG, "ch_align_pad_feather_u8: workspace smaller than ch_align_pad_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::align_pad_feather_u8(src, (long long)Ws * 3, Hs, Ws, pads, gauss_w, radius, dst, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_align_pad_feather_u8: ") + hipGetErrorString(e));
+}
+
+size_t ch_face_align_workspace_bytes(int H, int W, const double* plan, int radius) {
+    chk::AlignPlan p;
+    if (!plan || !align_dims_ok(H, W) || radius < 0 || radius > ALIGN_MAX_DIM || !parse_plan(plan, H, W, p).empty()) return 0;
+    return chk::face_align_workspace_bytes(H, W, p, radius) + 256;
+}
+
+int ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* plan, const double* gauss_w, int radius, uint8_t* dst,
+                  void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!src || !dst || !plan || !workspace || !align_dims_ok(H, W) || radius < 0 || radius > ALIGN_MAX_DIM)
+        return fail(h, CH_ERR_ARG, "ch_face_align: bad argument");
+    chk::AlignPlan p;
+    const std::string why = parse_plan(plan, H, W, p);
+    if (!why.empty()) return fail(h, CH_ERR_ARG, "ch_face_align: " + why);
+    if (p.do_pad && !gauss_w) return fail(h, CH_ERR_ARG, "ch_face_align: the plan pads but gauss_w is null");
+    if (workspace_bytes < chk::face_align_workspace_bytes(H, W, p, radius) + 256)
+        return fail(h, CH_ERR_ARG, "ch_face_align: workspace smaller than ch_face_align_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::face_align(h->align_cache, src, H, W, p, gauss_w, radius, dst, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_align: ") + hipGetErrorString(e));
 }
 
 int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd,

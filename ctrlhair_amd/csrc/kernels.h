@@ -3,6 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <utility>
+#include <vector>
+
 namespace chk {
 hipError_t label_downsample(const uint8_t* in, uint8_t* out, int B, int S, int r, hipStream_t s);
 // need (optional, [B][H][W]): pixels with need == 0 are not written (ace_sparse.h: nothing reads them)
@@ -138,5 +142,36 @@ size_t mask_warp_workspace_bytes(int B);
 hipError_t mask_warp_batch(const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int* F, const int* bidx,
                            const float* bc, const int* desc_host, const float* U_in, uint8_t* labels_out, float* uv_out, float* U_out,
                            void* ws, int B, int outer_iters, int max_cg, float rel_tol, hipStream_t s);
+
+
+// face_align.hip: FFHQ face alignment of one photo (external_code/crop.py:20-107): Pillow's 8-bit Lanczos resample, its QUAD / BILINEAR
+// transform fused into the horizontal Lanczos pass, and the reflect-pad / Gaussian-feather / median branch of the reference, all exact.
+struct LanczosTable {                          // Pillow's precompute_coeffs + normalize_coeffs_8bpc for one (in, out) size pair
+    int in_size = 0, out_size = 0, ksize = 0;
+    std::vector<int32_t> data;                 // bounds [out][2] (first tap, tap count) | kk [out][ksize] | the same transposed [ksize][out]
+};
+struct AlignCache {                            // host tables, built on first use and kept (the handle owns one)
+    std::map<std::pair<int, int>, LanczosTable> tables;
+};
+struct AlignPlan {                             // ctrlhair_amd/alignment.py align_plan, see CH_ALIGN_PLAN_LEN in ctrlhair_hip.h
+    int shrink, rw, rh;                        // shrink > 1: Lanczos-resize the photo to rw x rh first
+    int cx0, cy0, cx1, cy1;                    // crop box in the (resized) photo
+    int do_pad, pl, pt, pr, pb;                // padding branch and its widths (left, top, right, bottom)
+    double q[8];                               // Pillow's bilinear-quad coefficients
+    int T, S;                                  // transform_size, output_size
+};
+// ws sizes in bytes; every launcher enqueues on s without synchronising (host tables are copied with hipMemcpyAsync from pageable memory)
+size_t lanczos_workspace_bytes(int Hs, int Ws, int C, int Hd, int Wd);
+hipError_t lanczos_resample_u8(AlignCache& cache, const uint8_t* src, long long stride, int Hs, int Ws, int C, uint8_t* dst, int Hd, int Wd,
+                               void* ws, hipStream_t s);
+size_t quad_warp_workspace_bytes(int T, int S);
+hipError_t quad_warp_resample_u8(AlignCache& cache, const uint8_t* src, long long stride, int Hs, int Ws, const double* coef, int T, int S,
+                                 uint8_t* dst, void* ws, hipStream_t s);
+size_t align_pad_workspace_bytes(int Hp, int Wp, int radius);
+hipError_t align_pad_feather_u8(const uint8_t* src, long long stride, int Hs, int Ws, const int* pads, const double* gauss_w, int radius,
+                                uint8_t* dst, void* ws, hipStream_t s);
+size_t face_align_workspace_bytes(int H, int W, const AlignPlan& p, int radius);
+hipError_t face_align(AlignCache& cache, const uint8_t* src, int H, int W, const AlignPlan& p, const double* gauss_w, int radius, uint8_t* dst,
+                      void* ws, hipStream_t s);
 
 }  // namespace chk

@@ -9,6 +9,7 @@ On-disk formats are the reference's:
   label/<name>.png                      8-bit single-channel PNG, CelebAMask-HQ ids, 512x512 (script_get_mask.py:44-50)
   sean_code/<dataset>___<name>.pkl      pickle of float32 [19,512] (script_get_sean_code.py:56-62)
   sean_code_dict.pkl                    pickle of {'<dataset>___<name>': float32 [19,512]} (utils.py:14-21)
+  images_256/<name>                     the aligned portrait under the source photo's file name (script_crop.py:31-54)
   hair_info_all_dataset/rgb_stat/<dataset>___<name>.pkl        [moment1..4], float64 [3] each (script_get_rgb_hsv_label.py:58-67)
   hair_info_all_dataset/color_var_stat/<dataset>___<name>.pkl  {'var_rgb', 'var_hsv', 'var_pca', 'var_pca_mean', 'var_pca_comp'},
                                         only for images with > 5 hair pixels (script_get_color_var_label.py:58-90)
@@ -19,6 +20,9 @@ On-disk formats are the reference's:
     python -m ctrlhair_amd.dataset codes    <root> <dataset> [--batch 16]
     python -m ctrlhair_amd.dataset rgb      <root> <dataset> [--batch 16]     (no network weights: ctrlhair_amd.colorstats)
     python -m ctrlhair_amd.dataset colorvar <root> <dataset> [--batch 16]
+    python -m ctrlhair_amd.dataset crop <src_dir> <root> <dataset> --landmarks <file> [--size 256]
+                                          (dataset_scripts/script_crop.py: FFHQ-align every photo of <src_dir> into
+                                           <root>/<dataset>/images_256/<name>; no network weights: ctrlhair_amd.alignment)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -185,12 +189,59 @@ def merge_color_stats(out_root: str, jobs: Sequence[str]) -> None:
                 pickle.dump(hsv_table(merged), f)
 
 
+def load_landmarks(path: str) -> Dict[str, np.ndarray]:
+    """Landmarks of the crop job: image name -> float [68,2] (or [81,2]) PIXELS of the source photo.  `.npz` (one array per name) or
+    a pickled dict, the container dataset_scripts/script_landmark_detection.py writes (landmark68.pkl; its values there are
+    divided by the image height -- multiply them back before using them here).  A name may be the file name, the file name without
+    its extension, or '<dataset>___<name without extension>' (the key layout of landmark68.pkl)."""
+    if path.lower().endswith('.npz'):
+        with np.load(path) as z:
+            return {k: np.asarray(z[k], np.float64) for k in z.files}
+    with open(path, 'rb') as f:
+        d = pickle.load(f)
+    if not isinstance(d, dict):
+        raise ValueError(f'{path}: expected a dict of name -> [68,2] landmarks')
+    return {str(k): np.asarray(v, np.float64) for k, v in d.items()}
+
+
+def find_landmarks(landmarks: Dict[str, np.ndarray], dataset: str, file_name: str):
+    for key in (file_name, os.path.splitext(file_name)[0], code_key(dataset, file_name)):
+        if key in landmarks:
+            return landmarks[key]
+    return None
+
+
+def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = 256, rank: int = 0,
+               world: int = 1):
+    """dataset_scripts/script_crop.py:36-54 for this rank's shard of `src_dir`: align every photo that has landmarks
+    (`aligner`: alignment.FaceAligner) and write it to `out_dir/<name>`.  Returns (done, skipped): the file names written and the
+    ones without a landmark entry, which are reported and left out."""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    done, skipped = [], []
+    for n in shard(list_images(src_dir), rank, world):
+        lm = find_landmarks(landmarks, dataset, n)
+        if lm is None:
+            print(f'crop: no landmarks for {n}, skipped')
+            skipped.append(n)
+            continue
+        crop, _ = aligner.align(read_rgb(os.path.join(src_dir, n)), lm[:68], size)
+        crop = crop.cpu().numpy() if hasattr(crop, 'cpu') else np.asarray(crop)
+        Image.fromarray(crop).save(os.path.join(out_dir, n))
+        done.append(n)
+    return done, skipped
+
+
 def _dist_env():
     return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
 
 
 def main(argv=None):
     import argparse
+    import sys
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if argv and argv[0] == 'crop':
+        return _main_crop(argv[1:])
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('job', choices=('masks', 'codes') + tuple(COLOR_JOBS))
     ap.add_argument('root')
@@ -238,6 +289,26 @@ def main(argv=None):
     print(f'rank {rank}/{world}: {n} files')
     if dist is not None:
         dist.destroy_process_group()
+
+
+def _main_crop(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog='ctrlhair_amd.dataset crop', description='FFHQ-align a directory of photos from 68 landmarks')
+    ap.add_argument('src_dir')
+    ap.add_argument('root')
+    ap.add_argument('dataset')
+    ap.add_argument('--landmarks', required=True, help='.npz or pickled dict: image name -> [68,2] pixel landmarks')
+    ap.add_argument('--size', type=int, default=256)
+    args = ap.parse_args(argv)
+    import torch
+    from . import lib
+    from .alignment import FaceAligner
+    rank, world, local = _dist_env()
+    torch.cuda.set_device(local)
+    aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
+    done, skipped = crop_faces(aligner, args.src_dir, os.path.join(args.root, args.dataset, 'images_256'), args.dataset,
+                               load_landmarks(args.landmarks), args.size, rank, world)
+    print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} without landmarks')
 
 
 if __name__ == '__main__':

@@ -66,6 +66,8 @@ class HipModels:
         self.blender = PoissonBlender(h, dev)       # blending step after the generator (Backend(blending=True))
         from .colorstats import HairColorStats
         self.color_stats = HairColorStats(h, dev)   # hair colour statistics (get_hair_color, ctrlhair_amd.dataset rgb / colorvar)
+        from .alignment import FaceAligner
+        self.aligner = FaceAligner(h, dev)          # FFHQ alignment from 68 landmarks (crop_face, ctrlhair_amd.dataset crop)
 
 
 def is_released_checkpoint(weights) -> bool:
@@ -369,6 +371,26 @@ class HairEditor:
         out = blender.blend_batch(face, res, 1 - res_mask_dilated, with_gamma=True)
         return U.to_host(out), res_mask_dilated
 
-    def crop_face(self, img_rgb, save_path=None):
-        """hair_editor.py:312-329: dlib landmark alignment -- CPU pre-processing, out of scope."""
-        raise NotImplementedError('crop_face needs dlib landmark models (external_code/crop.py); crop offline')
+    def crop_face(self, img_rgb, save_path=None, landmarks=None):
+        """hair_editor.py:312-329: align the face of a photo to the FFHQ frame the editing system works in -> RGB uint8
+        [img_size,img_size,3] (written to save_path when given).  The reference finds the 68 landmarks with dlib; here they are an
+        input: `landmarks` [68,2] or [81,2] pixels (the first 68 count), or the answer of `self.landmarker` (Backend(...,
+        landmarker=fn)) when there is one.  The alignment itself (external_code/crop.py:20-107) runs on the device
+        (HipModels.aligner, ctrlhair_amd/alignment.py)."""
+        if landmarks is None and getattr(self, 'landmarker', None) is not None:
+            landmarks = self.landmarker(img_rgb)
+        if landmarks is None:
+            raise NotImplementedError('crop_face needs dlib landmark models (external_code/crop.py); crop offline')
+        aligner = getattr(self.models, 'aligner', None)
+        if aligner is None:
+            raise RuntimeError('crop_face with landmarks needs the HIP models (HipModels.aligner, ctrlhair_amd.alignment.FaceAligner: '
+                               'the library and a GPU); there is no CPU path')
+        lm = np.asarray(landmarks, np.float64)
+        if lm.ndim != 2 or lm.shape[0] not in (68, 81) or lm.shape[1] != 2:
+            raise ValueError(f'landmarks must be [68,2] or [81,2] pixel coordinates, got {lm.shape}')
+        crop, _ = aligner.align(np.ascontiguousarray(np.asarray(img_rgb)[..., :3].astype('uint8')), lm[:68], self.img_size)
+        img = U.to_host(crop)
+        if save_path is not None:
+            from PIL import Image
+            Image.fromarray(img).save(save_path)
+        return img

@@ -44,6 +44,14 @@ SYMBOLS = {
     'ch_hair_color_stats': (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP]),
     'ch_mask_warp_workspace_bytes': (C.c_size_t, [_I]),
     'ch_mask_warp_batch': (_I, [_VP] * 13 + [C.c_size_t, _I, _VP]),
+    'ch_resample_lanczos_workspace_bytes': (C.c_size_t, [_I] * 5),
+    'ch_resample_lanczos_u8': (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I, _VP, C.c_size_t, _VP]),
+    'ch_quad_warp_workspace_bytes': (C.c_size_t, [_I, _I]),
+    'ch_quad_warp_resample_u8': (_I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, C.c_size_t, _VP]),
+    'ch_align_pad_workspace_bytes': (C.c_size_t, [_I, _I, _VP, _I]),
+    'ch_align_pad_feather_u8': (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, C.c_size_t, _VP]),
+    'ch_face_align_workspace_bytes': (C.c_size_t, [_I, _I, _VP, _I]),
+    'ch_face_align': (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, C.c_size_t, _VP]),
     'ch_sean_set_tap': (_I, [_VP, C.c_char_p, _VP]),
     'ch_sean_scale_report': (_I, [_VP, C.POINTER(C.c_float), _I]),
     'ch_sean_debug_read': (_I, [_VP, _VP, C.c_size_t]),

@@ -301,6 +301,43 @@ int  ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t*
                         const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out,
                         float* uv_out, float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream);
 
+/* ---- Face alignment: external_code/crop.py:20-107 (recreate_aligned_images) for one photo -------------------------------------
+ * The geometry (oriented quad, shrink factor, crop box, pad widths, blur, Pillow's quad coefficients) is a host plan
+ * (ctrlhair_amd/alignment.py align_plan); the pixel work is here, bit-exact against Pillow 8-bit / numpy / scipy:
+ * ch_resample_lanczos_u8 replaces Image.resize((Wd, Hd), LANCZOS) of an 8-bit image: src uint8 [Hs,Ws,C], dst uint8 [Hd,Wd,C]
+ *   device pointers, 1 <= C <= 4.  Coefficient tables are built on the host (libm sin, double), normalised and rounded to 22
+ *   fractional bits; horizontal pass into a uint8 intermediate, then the vertical pass; a pass whose size does not change is skipped.
+ * ch_quad_warp_resample_u8 replaces Image.transform((T, T), QUAD, quad, BILINEAR) followed by resize((S, S), LANCZOS) of an RGB
+ *   image: coef = the 8 bilinear-quad coefficients Pillow derives from the corners (host doubles); src uint8 [Hs,Ws,3], dst uint8
+ *   [S,S,3].  One workgroup evaluates one row of the T x T grid in float64 into LDS and filters it horizontally at once: only the
+ *   [T,S,3] intermediate is written.  S == T writes the transform itself.  S <= T <= CH_ALIGN_MAX_TRANSFORM.
+ * ch_align_pad_feather_u8 replaces crop.py:83-92: np.pad(reflect) to float32, scipy gaussian_filter with the caller's kernel
+ *   (gauss_w: HOST doubles [2 * radius + 1], symmetric; reflect borders, axis 0 then 1, double accumulation in correlate1d's order,
+ *   float32 between passes), the feather mask and both blends as numpy evaluates them, np.median by an exact radix select,
+ *   rint / clip / uint8.  pads: HOST int32 {left, top, right, bottom}, all >= 1; src uint8 [Hs,Ws,3], dst uint8
+ *   [Hs+top+bottom, Ws+left+right, 3].
+ * ch_face_align runs a whole plan on one stream: optional Lanczos shrink, crop (an offset and a stride), optional padding branch,
+ *   quad warp + reduction.  src uint8 [H,W,3], dst uint8 [S,S,3].  plan: HOST doubles [CH_ALIGN_PLAN_LEN] =
+ *   {shrink, resized W, resized H (= W / shrink, H / shrink rounded half to even when shrink > 1, else W, H), crop x0, y0, x1, y1, pad flag, pad left, top, right, bottom, quad coefficients a0..a7,
+ *    transform_size, output_size, 0, 0}; gauss_w / radius as above (ignored without the pad flag).
+ * workspace: caller-owned device buffer (256-byte aligned) of at least the matching ..._workspace_bytes query, contents
+ *   undefined.  Everything is enqueued on `stream`: no device synchronisation, no allocation; host arrays may be freed on return.
+ *   All results are integer arithmetic or single IEEE operations in a fixed order: run-to-run deterministic. */
+#define CH_ALIGN_PLAN_LEN 24
+#define CH_ALIGN_MAX_TRANSFORM 16384
+size_t ch_resample_lanczos_workspace_bytes(int Hs, int Ws, int C, int Hd, int Wd);
+int  ch_resample_lanczos_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, int C, uint8_t* dst, int Hd, int Wd, void* workspace,
+                            size_t workspace_bytes, ch_stream_t stream);
+size_t ch_quad_warp_workspace_bytes(int T, int S);
+int  ch_quad_warp_resample_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, const double* coef, int T, int S, uint8_t* dst,
+                              void* workspace, size_t workspace_bytes, ch_stream_t stream);
+size_t ch_align_pad_workspace_bytes(int Hs, int Ws, const int32_t* pads, int radius);
+int  ch_align_pad_feather_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, const int32_t* pads, const double* gauss_w, int radius,
+                             uint8_t* dst, void* workspace, size_t workspace_bytes, ch_stream_t stream);
+size_t ch_face_align_workspace_bytes(int H, int W, const double* plan, int radius);
+int  ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* plan, const double* gauss_w, int radius,
+                   uint8_t* dst, void* workspace, size_t workspace_bytes, ch_stream_t stream);
+
 /* Test hook: after the next ch_sean_generate calls, the activation produced at stage `name` ("fc", "<block>",
  * "<block>.ace_0" = tensor before leaky_relu, "<block>.conv_0", "<block>.shortcut") is also copied
  * (device-to-device, same stream) to `dev_ptr` (caller-sized: [B,C,r,r] floats).  dev_ptr NULL removes the tap. */
