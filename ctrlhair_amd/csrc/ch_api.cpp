@@ -443,6 +443,36 @@ int ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* 
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_align: ") + hipGetErrorString(e));
 }
 
+// ---- median style codes (style_medoid.hip) ---------------------------------------------------------------------------------------
+namespace {
+bool medoid_args_ok(const int64_t* off, int R, int dim, int n_split) {
+    if (!off || R < 1 || R > CH_MEDOID_MAX_SEGMENTS || dim < 4 || dim > CH_MEDOID_MAX_DIM || dim % 4 != 0 || n_split < 0 || off[0] != 0)
+        return false;
+    for (int r = 0; r < R; ++r)
+        if (off[r + 1] < off[r] || off[r + 1] - off[r] > CH_MEDOID_MAX_ROWS) return false;
+    return true;
+}
+}  // namespace
+
+size_t ch_style_medoid_workspace_bytes(const int64_t* seg_offsets, int R, int dim, int n_split) {
+    if (!medoid_args_ok(seg_offsets, R, dim, n_split)) return 0;
+    return chk::style_medoid_workspace_bytes(seg_offsets, R, n_split);
+}
+
+int ch_style_medoid(ch_handle* h, const float* codes, const int64_t* seg_offsets, int R, int dim, int n_split, int32_t* index, double* sums,
+                    float* mean, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!medoid_args_ok(seg_offsets, R, dim, n_split))
+        return fail(h, CH_ERR_ARG, "ch_style_medoid: bad argument (dim a multiple of 4, seg_offsets ascending from 0, n_split >= 0)");
+    if (!index || !mean || !workspace || (!codes && seg_offsets[R] > 0) || (reinterpret_cast<uintptr_t>(codes) & 15))
+        return fail(h, CH_ERR_ARG, "ch_style_medoid: null output or workspace, or codes not 16-byte aligned");
+    if (workspace_bytes < chk::style_medoid_workspace_bytes(seg_offsets, R, n_split))
+        return fail(h, CH_ERR_ARG, "ch_style_medoid: workspace smaller than ch_style_medoid_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::style_medoid(codes, seg_offsets, R, dim, n_split, index, sums, mean, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_style_medoid: ") + hipGetErrorString(e));
+}
+
 int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd,
                         ch_stream_t stream) {
     if (!h) return CH_ERR_ARG;

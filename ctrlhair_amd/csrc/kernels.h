@@ -174,4 +174,10 @@ size_t face_align_workspace_bytes(int H, int W, const AlignPlan& p, int radius);
 hipError_t face_align(AlignCache& cache, const uint8_t* src, int H, int W, const AlignPlan& p, const double* gauss_w, int radius, uint8_t* dst,
                       void* ws, hipStream_t s);
 
+// style_medoid.hip: per-segment medoid (first minimum of the float64 row sums of float32 difference-form distances) and float64 mean
+// of compacted style codes (sean_codes/get_mean_code.py); seg_offsets is a host array [R + 1].  See ch_style_medoid in ctrlhair_hip.h.
+size_t style_medoid_workspace_bytes(const int64_t* seg_offsets, int R, int n_split);
+hipError_t style_medoid(const float* codes, const int64_t* seg_offsets, int R, int dim, int n_split, int* index, double* sums, float* mean,
+                        void* ws, hipStream_t s);
+
 }  // namespace chk

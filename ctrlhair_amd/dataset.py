@@ -23,6 +23,11 @@ On-disk formats are the reference's:
     python -m ctrlhair_amd.dataset crop <src_dir> <root> <dataset> --landmarks <file> [--size 256]
                                           (dataset_scripts/script_crop.py: FFHQ-align every photo of <src_dir> into
                                            <root>/<dataset>/images_256/<name>; no network weights: ctrlhair_amd.alignment)
+    python -m ctrlhair_amd.dataset median <root> [--out FILE] [--tree DIR]
+                                          (sean_codes/get_mean_code.py: the per-region medoid of <root>/sean_code_dict.pkl, written as
+                                           <root>/mean_style_code.npz for HairEditor(mean_style_code=...); no network weights:
+                                           ctrlhair_amd.stylestats.  Single process: all 19 regions are one kernel call that takes
+                                           well under a second at tens of thousands of images, so there is nothing to shard)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -242,6 +247,8 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == 'crop':
         return _main_crop(argv[1:])
+    if argv and argv[0] == 'median':
+        return _main_median(argv[1:])
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('job', choices=('masks', 'codes') + tuple(COLOR_JOBS))
     ap.add_argument('root')
@@ -309,6 +316,41 @@ def _main_crop(argv):
     done, skipped = crop_faces(aligner, args.src_dir, os.path.join(args.root, args.dataset, 'images_256'), args.dataset,
                                load_landmarks(args.landmarks), args.size, rank, world)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} without landmarks')
+
+
+def median_codes(medoid, root: str, out: str = None, tree: str = None) -> dict:
+    """sean_codes/get_mean_code.py over <root>/sean_code_dict.pkl (what the codes job merges): per region the medoid and the mean of
+    the codes of the images that have the region (`medoid`: stylestats.StyleMedoid).  Writes `out` (default
+    <root>/mean_style_code.npz, the packaged file's format) and, with `tree`, the reference's <tree>/mean_style_code/{mean,median}/<i>/
+    ACE.npy layout; prints count and chosen key per region.  Single process: no rank sharding at this cost."""
+    from . import stylestats as SS
+    with open(os.path.join(root, 'sean_code_dict.pkl'), 'rb') as f:
+        codes = pickle.load(f)
+    if not isinstance(codes, dict) or not codes:
+        raise ValueError(f'{root}/sean_code_dict.pkl: expected a non-empty dict of key -> [19,512] style codes')
+    res = medoid.median_style_codes(codes)
+    SS.save_mean_style_code(out if out is not None else os.path.join(root, 'mean_style_code.npz'), res)
+    if tree is not None:
+        SS.write_reference_tree(tree, res)
+    for j in range(SS.N_REGIONS):
+        chosen = res['keys'][res['index'][j]] if res['index'][j] >= 0 else '(no image has it: packaged row kept)'
+        print(f'region {j:2d}: {int(res["count"][j]):6d} codes  median = {chosen}')
+    return res
+
+
+def _main_median(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog='ctrlhair_amd.dataset median', description='Per-region median (medoid) and mean style codes')
+    ap.add_argument('root')
+    ap.add_argument('--out', default=None, help='.npz to write (default <root>/mean_style_code.npz)')
+    ap.add_argument('--tree', default=None, help="also write the reference's mean_style_code/{mean,median}/<i>/ACE.npy tree here")
+    args = ap.parse_args(argv)
+    import torch
+    from . import lib
+    from .stylestats import StyleMedoid
+    _, _, local = _dist_env()
+    torch.cuda.set_device(local)
+    return median_codes(StyleMedoid(lib.Handle(local), torch.device('cuda', local)), args.root, args.out, args.tree)
 
 
 if __name__ == '__main__':

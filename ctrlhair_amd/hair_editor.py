@@ -68,6 +68,8 @@ class HipModels:
         self.color_stats = HairColorStats(h, dev)   # hair colour statistics (get_hair_color, ctrlhair_amd.dataset rgb / colorvar)
         from .alignment import FaceAligner
         self.aligner = FaceAligner(h, dev)          # FFHQ alignment from 68 landmarks (crop_face, ctrlhair_amd.dataset crop)
+        from .stylestats import StyleMedoid
+        self.style_medoid = StyleMedoid(h, dev)     # per-region medoid of style codes (ctrlhair_amd.dataset median)
 
 
 def is_released_checkpoint(weights) -> bool:
@@ -83,8 +85,11 @@ class HairEditor:
 
     def __init__(self, load_feature_model=True, load_mask_model=True, *, weights='procedural', device: int = 0,
                  img_size: int = 256, models=None, texture_dirs=None, shape_dirs=None, max_batch: int = 1, f16x3=None,
-                 cap_threads: bool = None):
-        """f16x3: None = by the weights: True (split-operand f16 MFMA, f32-class, ~3x faster) for procedural weights, on which
+                 cap_threads: bool = None, mean_style_code: Optional[str] = None):
+        """mean_style_code: path of an .npz with the per-region fallback codes ('mean', 'median': float32 [19,512]), as
+        `python -m ctrlhair_amd.dataset median` writes it from a dataset's own style codes (ctrlhair_amd/stylestats.py); None = the
+        packaged copy of the reference's rows.  A file with other keys or shapes raises ValueError.
+        f16x3: None = by the weights: True (split-operand f16 MFMA, f32-class, ~3x faster) for procedural weights, on which
         every parity test runs; False (exact-f32 MFMA, the reference's arithmetic) for a released checkpoint tree
         (weights='reference' or a directory) -- the split-operand path is tested on heavy-tailed synthetic weights
         (tests/test_hip_robust_weights.py) but has never seen the real checkpoints, which cannot be fetched here.  Pass
@@ -98,6 +103,10 @@ class HairEditor:
             cap_threads = os.environ.get('CTRLHAIR_NO_THREAD_CAP', '') in ('', '0')
         if cap_threads:
             U.cap_threads_to_cpu_quota()
+        self.mean_style_code = mean_style_code
+        if mean_style_code is not None:
+            from .stylestats import load_mean_style_code
+            load_mean_style_code(mean_style_code)             # a malformed file fails here, before any model is built
         if models is None:
             if weights == 'procedural':
                 weights = procedural_weights()
@@ -152,7 +161,12 @@ class HairEditor:
     def load_average_feature(self):
         """hair_editor.py:130-147: {str(i): {'ACE': tensor[512]}} of the per-category median style codes."""
         if self._median is None:
-            self._median = torch.from_numpy(np.load(os.path.join(_DATA, 'mean_style_code.npz'))['median']).to(self.device)
+            if self.mean_style_code is None:
+                med = np.load(os.path.join(_DATA, 'mean_style_code.npz'))['median']
+            else:
+                from .stylestats import load_mean_style_code
+                med = load_mean_style_code(self.mean_style_code)['median']
+            self._median = torch.from_numpy(med).to(self.device)
         return {str(i): {'ACE': self._median[i]} for i in range(19)}
 
     # ---- networks --------------------------------------------------------------------------------------------

@@ -69,8 +69,10 @@ def hsv_to_rgb_u8(hsv: torch.Tensor) -> torch.Tensor:
 
 class EditPipeline:
     def __init__(self, weights: Optional[Dict[str, dict]] = None, device: int = 0, img_size: int = 512, max_batch: int = 8,
-                 f16x3=None, models=None, texture_dirs=None, shape_dirs=None, hsv_table=None, options=None):
-        """f16x3: None = by the weights, like HairEditor: 0 (exact f32) for a released checkpoint (a dict made by
+                 f16x3=None, models=None, texture_dirs=None, shape_dirs=None, hsv_table=None, options=None,
+                 mean_style_code: Optional[str] = None):
+        """mean_style_code: path of an .npz with the per-region fallback codes, like HairEditor's; None = the packaged file.
+        f16x3: None = by the weights, like HairEditor: 0 (exact f32) for a released checkpoint (a dict made by
         checkpoints.reference_checkpoints), 1 (split-operand f16 MFMA, f32-class) for procedural / untagged weights."""
         from .hair_editor import HipModels, is_released_checkpoint, procedural_weights
         if f16x3 is None:
@@ -87,7 +89,11 @@ class EditPipeline:
         self.shape_dirs = torch.as_tensor(np.asarray(sdirs)).float().to(self.device)
         self.dist_translation = U.DistTranslation(hsv_table)
         import os
-        med = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'mean_style_code.npz'))['median']
+        if mean_style_code is None:
+            med = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'mean_style_code.npz'))['median']
+        else:
+            from .stylestats import load_mean_style_code
+            med = load_mean_style_code(mean_style_code)['median']
         self.median = torch.from_numpy(med.astype(np.float32)).to(self.device)
         self.side = torch.cuda.Stream(self.device)      # edit(): the shape branch runs here, underneath the Zencoder
         self.overlap = True

@@ -39,7 +39,8 @@ class Backend(HairEditor):
                  hsv_table=None, warper=None, blender=None, landmarker=None, **editor_kwargs):
         """ui/backend.py:45-65.  Keyword-only extras: hsv_table (DistTranslation data), warper (shape-transfer warp
         function with wrap_by_imgs' signature; without it the built-in MaskWarper is used), landmarker (callable img_rgb ->
-        float [81,2] landmarks in pixels of that image, for the built-in warper), blender (Poisson blender), and HairEditor's weights/device/img_size/models."""
+        float [81,2] landmarks in pixels of that image, for the built-in warper), blender (Poisson blender), and HairEditor's weights/device/img_size/models.
+        HairEditor's mean_style_code (an .npz of a dataset's own fallback codes) passes through with them."""
         super().__init__(True, True, **editor_kwargs)
         self.target_img = None
         self.input_img = None

@@ -338,6 +338,32 @@ size_t ch_face_align_workspace_bytes(int H, int W, const double* plan, int radiu
 int  ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* plan, const double* gauss_w, int radius,
                    uint8_t* dst, void* workspace, size_t workspace_bytes, ch_stream_t stream);
 
+/* ---- Median style codes: sean_codes/get_mean_code.py for R segments (the 19 regions) in one call -----------------------------
+ * For each segment the medoid is the row whose summed Euclidean distance to the segment's rows is smallest.  The reference builds
+ * the n x n matrix from the Gram identity in float32; here the matrix is never stored and the arithmetic is fixed as follows:
+ *   d_ij^2 = sum_k (x_ik - x_jk)^2 in float32, the difference formed before squaring (fused multiply-add allowed, summed in
+ *            ascending k; no Gram identity anywhere), d_ij = sqrtf(d_ij^2), so d_ii = 0 exactly;
+ *   S_i    = sum_j d_ij in float64;  index = the FIRST i attaining min S_i (numpy argmin);
+ *   mean   = float64 column sums / n, rounded once to float32.
+ * codes: device float [total, dim], the rows of segment r are seg_offsets[r] .. seg_offsets[r+1]-1 (16-byte aligned; dim a multiple
+ *   of 4, 4 <= dim <= CH_MEDOID_MAX_DIM).  seg_offsets: HOST int64 [R+1], ascending from 0; 1 <= R <= CH_MEDOID_MAX_SEGMENTS; a
+ *   segment has at most CH_MEDOID_MAX_ROWS rows.
+ * n_split: each 128-row tile walks its 128-column tiles in ascending order; the column range is cut into n_split contiguous parts
+ *   (clamped to the number of tiles) run by different workgroups, whose float64 partial sums are added in ascending order.
+ *   0 = auto, a function of the segment's row count alone.
+ * index: device int32 [R], row within the segment, -1 for an empty segment.  sums (optional): device double [total].
+ * mean: device float [R, dim], zeros for an empty segment.
+ * workspace: caller-owned device buffer (256-byte aligned) of ch_style_medoid_workspace_bytes(seg_offsets, R, dim, n_split) bytes
+ *   (0 = bad argument), contents undefined.  Everything is enqueued on `stream`: no synchronisation, no allocation; seg_offsets
+ *   may be freed on return.  No floating-point atomics and fixed reduction trees: two runs are bit-identical, and a segment's
+ *   sums have the same bits whether it is run alone or among others (same n_split). */
+#define CH_MEDOID_MAX_DIM 65536
+#define CH_MEDOID_MAX_SEGMENTS 65535
+#define CH_MEDOID_MAX_ROWS (1 << 30)
+size_t ch_style_medoid_workspace_bytes(const int64_t* seg_offsets, int R, int dim, int n_split);
+int  ch_style_medoid(ch_handle* h, const float* codes, const int64_t* seg_offsets, int R, int dim, int n_split, int32_t* index,
+                     double* sums, float* mean, void* workspace, size_t workspace_bytes, ch_stream_t stream);
+
 /* Test hook: after the next ch_sean_generate calls, the activation produced at stage `name` ("fc", "<block>",
  * "<block>.ace_0" = tensor before leaky_relu, "<block>.conv_0", "<block>.shortcut") is also copied
  * (device-to-device, same stream) to `dev_ptr` (caller-sized: [B,C,r,r] floats).  dev_ptr NULL removes the tap. */
