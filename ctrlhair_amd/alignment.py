@@ -17,6 +17,8 @@ import numpy as np
 from . import lib as _lib
 
 PLAN_LEN = 24                   # CH_ALIGN_PLAN_LEN
+UNALIGN_PLAN_LEN = 16           # CH_UNALIGN_PLAN_LEN
+UNALIGN_MAX_SCALE = 16          # CH_UNALIGN_MAX_SCALE
 MAX_TRANSFORM = 16384           # CH_ALIGN_MAX_TRANSFORM
 GAUSS_TRUNCATE = 4.0            # scipy.ndimage.gaussian_filter's default
 
@@ -40,11 +42,11 @@ def quad_coefficients(quad_corners, size):
                      nwy, (ney - nwy) * inv_w, (swy - nwy) * inv_h, (sey - swy - ney + nwy) * inv_w * inv_h], np.float64)
 
 
-def perspective_matrix(src4, dst4):
+def perspective_matrix(src4, dst4, exact=False):
     """The 3x3 homography that maps four source points onto four target points (what cv2.getPerspectiveTransform solves), by
-    numpy's solve of the 8x8 system; both inputs pass through float32 like cv2's arguments."""
-    s = np.asarray(src4, np.float32).astype(np.float64).reshape(4, 2)
-    d = np.asarray(dst4, np.float32).astype(np.float64).reshape(4, 2)
+    numpy's solve of the 8x8 system; both inputs pass through float32 like cv2's arguments (exact=True: they stay float64)."""
+    s = (np.asarray(src4, np.float64) if exact else np.asarray(src4, np.float32).astype(np.float64)).reshape(4, 2)
+    d = (np.asarray(dst4, np.float64) if exact else np.asarray(dst4, np.float32).astype(np.float64)).reshape(4, 2)
     A, b = np.zeros((8, 8)), np.zeros(8)
     for i in range(4):
         x, y, u, v = s[i, 0], s[i, 1], d[i, 0], d[i, 1]
@@ -147,6 +149,50 @@ def pack_plan(plan):
     v[8:12] = plan['pad']
     v[12:20] = plan['coef']
     v[20], v[21] = plan['transform_size'], plan['output_size']
+    return v
+
+
+def unalign_plan(plan, height, width):
+    """The way back from an alignment: geometry that pastes an edited S x S crop of `plan` (align_plan's dict) into the height x width
+    photo it was aligned from.  Coordinates are continuous with pixel i covering [i, i + 1).  A crop point (x, y) lies at
+    NW + (x / S)(NE - NW) + (y / S)(SW - NW) of the frame the transform read (corners = quad + 0.5), the frame is the resized photo
+    shifted by crop[:2] - pad[:2], and the Lanczos shrink maps edge to edge: photo = resized * (width / resized_w, height / resized_h).
+    Returns a dict: A float64 [2,3] (photo pixel centre (X + 0.5, Y + 0.5, 1) -> (x, y)), Ainv [2,3] (the inverse), bbox (x0, y0, x1, y1)
+    of the quad in the photo, clipped to it, scale (crop pixels per photo pixel), output_size."""
+    height, width, S = int(height), int(width), int(plan['output_size'])
+    corners = np.asarray(plan['quad'], np.float64) + 0.5
+    Hm = perspective_matrix([[0, 0], [0, S], [S, S], [S, 0]], corners, exact=True)           # crop -> frame
+    if np.abs(Hm[2] - [0.0, 0.0, 1.0]).max() > 1e-9:
+        raise ValueError('the quad of the plan is not a parallelogram: the crop-to-photo map is not affine')
+    rw, rh = plan['resized']
+    if plan['shrink'] <= 1 and (rw, rh) != (width, height):
+        raise ValueError(f'the plan was made for a {rw} x {rh} photo, not {width} x {height}')
+    if plan['shrink'] > 1 and (rw, rh) != (int(np.rint(float(width) / plan['shrink'])), int(np.rint(float(height) / plan['shrink']))):
+        raise ValueError(f'the plan (shrink {plan["shrink"]}, resized {rw} x {rh}) was not made for a {width} x {height} photo')
+    shift = np.asarray(plan['crop'][:2], np.float64) - np.asarray(plan['pad'][:2], np.float64)
+    zoom = np.array([width / rw, height / rh])
+    Ainv = np.empty((2, 3))
+    Ainv[:, :2] = Hm[:2, :2] * zoom[:, None]
+    Ainv[:, 2] = (Hm[:2, 2] + shift) * zoom
+    L = np.linalg.inv(Ainv[:, :2])
+    A = np.concatenate([L, -(L @ Ainv[:, 2])[:, None]], axis=1)
+    scale = float(max(np.hypot(*A[:, 0]), np.hypot(*A[:, 1])))
+    if scale > UNALIGN_MAX_SCALE:
+        raise ValueError(f'the crop has {scale:.1f} pixels per photo pixel; paste-back supports at most {UNALIGN_MAX_SCALE}')
+    q = (Ainv[:, :2] @ np.array([[0, 0, S, S], [0, S, S, 0]], np.float64) + Ainv[:, 2:3]).T          # the quad in the photo
+    bbox = (max(int(np.floor(q[:, 0].min())), 0), max(int(np.floor(q[:, 1].min())), 0),
+            min(int(np.ceil(q[:, 0].max())), width), min(int(np.ceil(q[:, 1].max())), height))
+    if bbox[2] <= bbox[0] or bbox[3] <= bbox[1]:
+        raise ValueError('the face lies outside the photo: nothing to paste')
+    return {'A': A, 'Ainv': Ainv, 'bbox': bbox, 'scale': scale, 'output_size': S}
+
+
+def pack_unalign(plan_u):
+    """unalign_plan's dict as ch_face_unalign takes it: float64 [CH_UNALIGN_PLAN_LEN] (include/ctrlhair_hip.h)."""
+    v = np.zeros(UNALIGN_PLAN_LEN, np.float64)
+    v[0:6] = np.asarray(plan_u['A'], np.float64).reshape(6)
+    v[6:10] = plan_u['bbox']
+    v[10], v[11] = plan_u['scale'], plan_u['output_size']
     return v
 
 
@@ -259,11 +305,49 @@ class FaceAligner:
         self.handle.call('ch_face_align', x.data_ptr(), H, W, pp, gp, radius, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
         return out
 
-    def align(self, img_rgb_u8, lm_68, output_size, transform_size=4096, enable_padding=True):
+    def align(self, img_rgb_u8, lm_68, output_size, transform_size=4096, enable_padding=True, return_plan=False):
         """recreate_aligned_images(img, lm_68, output_size): img uint8 [H,W,3] RGB (numpy is uploaded), lm_68 [68,2] pixels ->
-        (aligned uint8 [S,S,3] device tensor, int32 [68,2] landmarks in it)."""
+        (aligned uint8 [S,S,3] device tensor, int32 [68,2] landmarks in it); return_plan=True -> (aligned, align_plan's dict), what
+        paste_back needs to put an edit of the crop back into the photo."""
         shape = tuple(img_rgb_u8.shape)
         if len(shape) != 3 or shape[2] != 3:
             raise ValueError(f'expected an RGB image [H,W,3], got {shape}')
         plan = align_plan(lm_68, shape[0], shape[1], output_size, transform_size, enable_padding)
+        if return_plan:
+            return self.run_plan(img_rgb_u8, plan), plan
         return self.run_plan(img_rgb_u8, plan), plan['landmarks']
+
+    def paste_back(self, photo, edits, plan, weight=None, feather=None):
+        """The way back: composite edited crops into the photo they were aligned from, ONE ch_face_unalign call for all of them.
+        photo uint8 [H,W,3]; edits uint8 [S,S,3] or [N,S,S,3] (numpy is uploaded); plan: align_plan's dict (align(...,
+        return_plan=True)) or unalign_plan's; weight: optional uint8 [S,S] map, 255 = the edit, 0 = the photo; feather: width in crop
+        pixels of the ramp at the crop's border (default S / 16, <= 0 = hard edge).  -> uint8 [N,H,W,3] device tensor."""
+        import torch
+        x = self._u8(photo, 3)
+        H, W = int(x.shape[0]), int(x.shape[1])
+        pu = plan if 'A' in plan else unalign_plan(plan, H, W)
+        S = int(pu['output_size'])
+        e = edits if isinstance(edits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(edits, dtype=np.uint8)))
+        if e.dtype != torch.uint8:
+            raise TypeError(f'expected uint8 edits, got {e.dtype}')
+        if e.dim() == 3:
+            e = e[None]
+        if e.dim() != 4 or tuple(e.shape[1:]) != (S, S, 3) or e.shape[0] < 1:
+            raise ValueError(f'expected edits [N,{S},{S},3] (the plan\'s output_size is {S}), got {tuple(e.shape)}')
+        e = e.to(self.device).contiguous()
+        wp = None
+        if weight is not None:
+            w = weight if isinstance(weight, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(weight, dtype=np.uint8)))
+            if w.dtype != torch.uint8 or tuple(w.shape) != (S, S):
+                raise ValueError(f'expected a uint8 weight map [{S},{S}], got {w.dtype} {tuple(w.shape)}')
+            w = w.to(self.device).contiguous()
+            wp = w.data_ptr()
+        bx = pu['bbox']
+        if pu['scale'] > UNALIGN_MAX_SCALE or bx[0] < 0 or bx[1] < 0 or bx[2] > W or bx[3] > H or bx[2] <= bx[0] or bx[3] <= bx[1]:
+            raise ValueError(f'the plan (bbox {tuple(bx)}, scale {pu["scale"]:.2f}) does not fit a {W} x {H} photo')
+        N = int(e.shape[0])
+        pv, pp = self._f64(pack_unalign(pu))
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=self.device)
+        self.handle.call('ch_face_unalign', x.data_ptr(), H, W, e.data_ptr(), N, wp, pp, float(S / 16.0 if feather is None else feather),
+                         out.data_ptr(), self._stream())
+        return out

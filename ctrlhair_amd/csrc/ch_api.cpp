@@ -443,6 +443,33 @@ int ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* 
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_align: ") + hipGetErrorString(e));
 }
 
+// ---- paste-back (face_unalign.hip) -------------------------------------------------------------------------------------------------
+int ch_face_unalign(ch_handle* h, const uint8_t* photo, int H, int W, const uint8_t* edits, int N, const uint8_t* weight, const double* plan,
+                    double feather_px, uint8_t* out, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!photo || !edits || !plan || !out || !align_dims_ok(H, W) || N < 1 || N > 65535 || !std::isfinite(feather_px))
+        return fail(h, CH_ERR_ARG, "ch_face_unalign: bad argument (null pointer, photo side outside [1, 32768], N outside [1, 65535])");
+    for (int i = 0; i < CH_UNALIGN_PLAN_LEN; ++i)
+        if (!std::isfinite(plan[i])) return fail(h, CH_ERR_ARG, "ch_face_unalign: plan[" + std::to_string(i) + "] is not finite");
+    for (int i = 6; i < 12; ++i)
+        if (i != 10 && (plan[i] != std::floor(plan[i]) || std::fabs(plan[i]) > 1e9))
+            return fail(h, CH_ERR_ARG, "ch_face_unalign: plan[" + std::to_string(i) + "] is not an integer");
+    chk::UnalignPlan p;
+    for (int i = 0; i < 6; ++i) p.A[i] = plan[i];
+    p.x0 = (int)plan[6], p.y0 = (int)plan[7], p.x1 = (int)plan[8], p.y1 = (int)plan[9];
+    p.scale = plan[10], p.S = (int)plan[11];
+    if (p.x0 < 0 || p.y0 < 0 || p.x1 > W || p.y1 > H || p.x0 >= p.x1 || p.y0 >= p.y1)
+        return fail(h, CH_ERR_ARG, "ch_face_unalign: bbox empty or outside the photo");
+    if (!(p.scale > 0.0) || p.scale > CH_UNALIGN_MAX_SCALE)
+        return fail(h, CH_ERR_ARG, "ch_face_unalign: scale outside (0, " + std::to_string(CH_UNALIGN_MAX_SCALE) + "]");
+    if (p.S < 1 || p.S > CH_ALIGN_MAX_TRANSFORM) return fail(h, CH_ERR_ARG, "ch_face_unalign: output_size outside [1, " + std::to_string(CH_ALIGN_MAX_TRANSFORM) + "]");
+    const size_t bytes = (size_t)H * W * 3;
+    if (out < photo + bytes && photo < out + bytes * (size_t)N) return fail(h, CH_ERR_ARG, "ch_face_unalign: out overlaps photo");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::face_unalign(photo, edits, weight, p, H, W, N, feather_px, out, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_unalign: ") + hipGetErrorString(e));
+}
+
 // ---- median style codes (style_medoid.hip) ---------------------------------------------------------------------------------------
 namespace {
 bool medoid_args_ok(const int64_t* off, int R, int dim, int n_split) {

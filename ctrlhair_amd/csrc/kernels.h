@@ -174,6 +174,17 @@ size_t face_align_workspace_bytes(int H, int W, const AlignPlan& p, int radius);
 hipError_t face_align(AlignCache& cache, const uint8_t* src, int H, int W, const AlignPlan& p, const double* gauss_w, int radius, uint8_t* dst,
                       void* ws, hipStream_t s);
 
+// face_unalign.hip: paste N edited crops back into the photo (the inverse map of an alignment plan: ctrlhair_amd/alignment.py
+// unalign_plan): rotated scale-adaptive Lanczos-3 resample fused with a feathered composite.  See ch_face_unalign in ctrlhair_hip.h.
+struct UnalignPlan {
+    double A[6];                               // photo pixel centre -> crop coordinates, row-major [2][3]
+    int x0, y0, x1, y1;                        // the quad's bounding box, clipped to the photo
+    double scale;                              // crop pixels per photo pixel
+    int S;                                     // the crop's side
+};
+hipError_t face_unalign(const uint8_t* photo, const uint8_t* edits, const uint8_t* weight, const UnalignPlan& p, int H, int W, int N,
+                        double feather_px, uint8_t* out, hipStream_t s);
+
 // style_medoid.hip: per-segment medoid (first minimum of the float64 row sums of float32 difference-form distances) and float64 mean
 // of compacted style codes (sean_codes/get_mean_code.py); seg_offsets is a host array [R + 1].  See ch_style_medoid in ctrlhair_hip.h.
 size_t style_medoid_workspace_bytes(const int64_t* seg_offsets, int R, int n_split);

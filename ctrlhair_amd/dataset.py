@@ -23,6 +23,9 @@ On-disk formats are the reference's:
     python -m ctrlhair_amd.dataset crop <src_dir> <root> <dataset> --landmarks <file> [--size 256]
                                           (dataset_scripts/script_crop.py: FFHQ-align every photo of <src_dir> into
                                            <root>/<dataset>/images_256/<name>; no network weights: ctrlhair_amd.alignment)
+    python -m ctrlhair_amd.dataset uncrop <photos> <edits> <out> --landmarks <file> [--size S]
+                                          (the inverse of crop: paste the edited crop <edits>/<name> back into <photos>/<name> with the
+                                           same landmarks and write the photo-sized result to <out>/<name>; ctrlhair_amd.alignment)
     python -m ctrlhair_amd.dataset median <root> [--out FILE] [--tree DIR]
                                           (sean_codes/get_mean_code.py: the per-region medoid of <root>/sean_code_dict.pkl, written as
                                            <root>/mean_style_code.npz for HairEditor(mean_style_code=...); no network weights:
@@ -237,6 +240,32 @@ def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dic
     return done, skipped
 
 
+def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = None,
+                 rank: int = 0, world: int = 1):
+    """The inverse of crop_faces for this rank's shard of `photo_dir`: paste the edited crop `edit_dir/<name>` back into the photo
+    `photo_dir/<name>` it was aligned from (same landmarks, same file names) and write the photo-sized result to `out_dir/<name>`.
+    size: the crops' side (default: each edit's own).  Returns (done, skipped); a photo without landmarks or without an edit is
+    reported and left out."""
+    from PIL import Image
+    from .alignment import align_plan
+    os.makedirs(out_dir, exist_ok=True)
+    done, skipped = [], []
+    for n in shard(list_images(photo_dir), rank, world):
+        lm = find_landmarks(landmarks, dataset, n)
+        if lm is None or not os.path.exists(os.path.join(edit_dir, n)):
+            print(f'uncrop: no {"landmarks" if lm is None else "edit"} for {n}, skipped')
+            skipped.append(n)
+            continue
+        photo, edit = read_rgb(os.path.join(photo_dir, n)), read_rgb(os.path.join(edit_dir, n))
+        S = int(edit.shape[0]) if size is None else int(size)
+        if edit.shape[:2] != (S, S):
+            raise ValueError(f'{os.path.join(edit_dir, n)}: expected a {S} x {S} crop, got {edit.shape[1]} x {edit.shape[0]}')
+        out = aligner.paste_back(photo, edit, align_plan(lm[:68], photo.shape[0], photo.shape[1], S))[0]
+        Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n))
+        done.append(n)
+    return done, skipped
+
+
 def _dist_env():
     return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
 
@@ -247,6 +276,8 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == 'crop':
         return _main_crop(argv[1:])
+    if argv and argv[0] == 'uncrop':
+        return _main_uncrop(argv[1:])
     if argv and argv[0] == 'median':
         return _main_median(argv[1:])
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
@@ -316,6 +347,27 @@ def _main_crop(argv):
     done, skipped = crop_faces(aligner, args.src_dir, os.path.join(args.root, args.dataset, 'images_256'), args.dataset,
                                load_landmarks(args.landmarks), args.size, rank, world)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} without landmarks')
+
+
+def _main_uncrop(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog='ctrlhair_amd.dataset uncrop', description='Paste edited FFHQ-aligned crops back into their photos')
+    ap.add_argument('photos', help='directory of the original photos')
+    ap.add_argument('edits', help='directory of the edited crops, one per photo, same file names')
+    ap.add_argument('out', help='directory for the photo-sized results')
+    ap.add_argument('--landmarks', required=True, help='.npz or pickled dict: image name -> [68,2] pixel landmarks (the crop job\'s file)')
+    ap.add_argument('--size', type=int, default=None, help="the crops' side (default: each edit's own)")
+    ap.add_argument('--dataset', default='', help="dataset name of '<dataset>___<name>' landmark keys")
+    args = ap.parse_args(argv)
+    import torch
+    from . import lib
+    from .alignment import FaceAligner
+    rank, world, local = _dist_env()
+    torch.cuda.set_device(local)
+    aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
+    done, skipped = uncrop_faces(aligner, args.photos, args.edits, args.out, args.dataset, load_landmarks(args.landmarks), args.size,
+                                 rank, world)
+    print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
 
 
 def median_codes(medoid, root: str, out: str = None, tree: str = None) -> dict:

@@ -402,9 +402,35 @@ class HairEditor:
         lm = np.asarray(landmarks, np.float64)
         if lm.ndim != 2 or lm.shape[0] not in (68, 81) or lm.shape[1] != 2:
             raise ValueError(f'landmarks must be [68,2] or [81,2] pixel coordinates, got {lm.shape}')
-        crop, _ = aligner.align(np.ascontiguousarray(np.asarray(img_rgb)[..., :3].astype('uint8')), lm[:68], self.img_size)
+        photo = np.ascontiguousarray(np.asarray(img_rgb)[..., :3].astype('uint8'))
+        crop, _ = aligner.align(photo, lm[:68], self.img_size)
+        from .alignment import align_plan
+        # what paste_back needs to put an edit back into this photo (the plan is host arithmetic on the landmarks alone)
+        self.last_alignment = {'photo': photo, 'plan': align_plan(lm[:68], photo.shape[0], photo.shape[1], self.img_size)}
         img = U.to_host(crop)
         if save_path is not None:
             from PIL import Image
             Image.fromarray(img).save(save_path)
         return img
+
+    def paste_back(self, edited, photo=None, plan=None, weight=None, feather=None):
+        """The way back from crop_face: composite edited crops (uint8 [S,S,3] or [N,S,S,3], numpy or device tensors) into the photo
+        they were aligned from, on the device (FaceAligner.paste_back, one ch_face_unalign call) -> uint8 [N,H,W,3] device tensor.
+        photo / plan default to those of the last crop_face call (`self.last_alignment`); weight: optional uint8 [S,S] map (255 =
+        the edit, 0 = the photo) on top of the feathered border."""
+        last = getattr(self, 'last_alignment', None)
+        if photo is None or plan is None:
+            if last is None:
+                raise RuntimeError('paste_back needs the photo and the plan of an alignment: call crop_face(photo, landmarks=...) '
+                                   'first, or pass photo= and plan= (FaceAligner.align(..., return_plan=True))')
+            photo = last['photo'] if photo is None else photo
+            plan = last['plan'] if plan is None else plan
+        size = tuple(edited.shape[-3:-1]) if len(edited.shape) in (3, 4) else None
+        S = int(plan['output_size'])
+        if size != (S, S) or edited.shape[-1] != 3:
+            raise ValueError(f'edited images must be [{S},{S},3] or [N,{S},{S},3] (the plan\'s output_size is {S}), got {tuple(edited.shape)}')
+        aligner = getattr(getattr(self, 'models', None), 'aligner', None)
+        if aligner is None:
+            raise RuntimeError('paste_back needs the HIP models (HipModels.aligner, ctrlhair_amd.alignment.FaceAligner: the library '
+                               'and a GPU); there is no CPU path')
+        return aligner.paste_back(photo, edited, plan, weight=weight, feather=feather)

@@ -338,6 +338,25 @@ size_t ch_face_align_workspace_bytes(int H, int W, const double* plan, int radiu
 int  ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* plan, const double* gauss_w, int radius,
                    uint8_t* dst, void* workspace, size_t workspace_bytes, ch_stream_t stream);
 
+/* ---- Paste-back: N edited crops of one alignment composited into the photo they came from ------------------------------------
+ * The inverse geometry is a host plan (ctrlhair_amd/alignment.py unalign_plan / pack_unalign).  plan: HOST doubles
+ *   [CH_UNALIGN_PLAN_LEN] = {A00, A01, A02, A10, A11, A12, bbox x0, y0, x1, y1, scale, output_size S, 0, 0, 0, 0}: A maps the photo
+ *   pixel centre (X + 0.5, Y + 0.5, 1) to crop coordinates (x, y) (pixel i covers [i, i + 1)), evaluated in float64 as
+ *   (A00 (X + 0.5) + A01 (Y + 0.5)) + A02 without fused multiply-adds; bbox = the quad's bounding box inside the photo, not empty;
+ *   scale = s, crop pixels per photo pixel, 0 < s <= CH_UNALIGN_MAX_SCALE.
+ * photo uint8 [H,W,3], edits uint8 [N,S,S,3], weight uint8 [S,S] or NULL, out uint8 [N,H,W,3] (must not overlap photo): device.
+ * Inside bbox, per edit: alpha = clamp(min(x, S - x, y, S - y) / feather_px, 0, 1) (feather_px <= 0: 1 inside the quad, 0 outside),
+ *   times weight / 255 sampled bilinearly at (x, y) (centres at i + 0.5, edges clamped) when weight is given; e = the edit resampled
+ *   with Lanczos-3 at filter scale fs = max(1, s): taps |i + 0.5 - x| < 3 fs and likewise in y, weight L((i + 0.5 - x) / fs)
+ *   L((j + 0.5 - y) / fs), taps outside [0, S) dropped and the rest renormalised; out = clamp(floor(alpha e + (1 - alpha) p + 0.5),
+ *   0, 255) in float32.  alpha == 0 and everything outside bbox: the photo's bytes.
+ * Two launches on `stream` (copy outside bbox, resample + composite inside) for all N; no workspace, no synchronisation, no
+ *   atomics: image n of a batch is bit-identical to an N = 1 call. */
+#define CH_UNALIGN_PLAN_LEN 16
+#define CH_UNALIGN_MAX_SCALE 16
+int  ch_face_unalign(ch_handle* h, const uint8_t* photo, int H, int W, const uint8_t* edits, int N, const uint8_t* weight,
+                     const double* plan, double feather_px, uint8_t* out, ch_stream_t stream);
+
 /* ---- Median style codes: sean_codes/get_mean_code.py for R segments (the 19 regions) in one call -----------------------------
  * For each segment the medoid is the row whose summed Euclidean distance to the segment's rows is smallest.  The reference builds
  * the n x n matrix from the Gram identity in float32; here the matrix is never stored and the arithmetic is fixed as follows:
