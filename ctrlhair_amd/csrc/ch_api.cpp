@@ -365,6 +365,40 @@ int ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t* 
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_mask_warp_batch: ") + hipGetErrorString(e));
 }
 
+int ch_mask_warp_batch_dev(ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
+                           const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out, float* uv_out,
+                           float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!hair_labels || !face_labels || !V || !F || !desc || !labels_out || !workspace || B < 1 || B > 65535 || (!U_in && (!b || !bc)))
+        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch_dev: bad argument");
+    if (workspace_bytes < chk::mask_warp_workspace_bytes(B))
+        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch_dev: workspace smaller than ch_mask_warp_workspace_bytes(B)");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::mask_warp_batch_dev(hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, uv_out, U_out, workspace, B,
+                                            CH_WARP_OUTER_ITERS, CH_WARP_MAX_CG, CH_WARP_REL_TOL, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_mask_warp_batch_dev: ") + hipGetErrorString(e));
+}
+
+size_t ch_delaunay_workspace_bytes(int B) { return chk::delaunay_workspace_bytes(B); }
+
+int ch_delaunay_batch(ch_handle* h, const float* V, const int32_t* v_desc, int32_t* F, int32_t* n_f, int32_t* status, void* workspace,
+                      size_t workspace_bytes, int B, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!V || !v_desc || !F || !n_f || !status || !workspace || B < 1 || B > 65535)
+        return fail(h, CH_ERR_ARG, "ch_delaunay_batch: bad argument");
+    if (workspace_bytes < chk::delaunay_workspace_bytes(B))
+        return fail(h, CH_ERR_ARG, "ch_delaunay_batch: workspace smaller than ch_delaunay_workspace_bytes(B)");
+    for (int i = 0; i < B; ++i)
+        if (v_desc[2 * i] < 0) return fail(h, CH_ERR_ARG, "ch_delaunay_batch: negative offset in v_desc[" + std::to_string(i) + "]");
+    static_assert(CH_DELAUNAY_OK == chk::DELAUNAY_OK && CH_DELAUNAY_BAD_COUNT == chk::DELAUNAY_BAD_COUNT &&
+                      CH_DELAUNAY_OFF_GRID == chk::DELAUNAY_OFF_GRID && CH_DELAUNAY_DUPLICATE == chk::DELAUNAY_DUPLICATE &&
+                      CH_DELAUNAY_COLLINEAR == chk::DELAUNAY_COLLINEAR && CH_DELAUNAY_INTERNAL == chk::DELAUNAY_INTERNAL,
+                  "status codes of the header and of delaunay.hip");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::delaunay_batch(V, v_desc, F, n_f, status, workspace, B, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_delaunay_batch: ") + hipGetErrorString(e));
+}
+
 size_t ch_resample_lanczos_workspace_bytes(int Hs, int Ws, int C, int Hd, int Wd) {
     if (!align_dims_ok(Hs, Ws) || !align_dims_ok(Hd, Wd) || C < 1 || C > 4) return 0;
     return chk::lanczos_workspace_bytes(Hs, Ws, C, Hd, Wd);

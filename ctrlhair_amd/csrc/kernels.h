@@ -142,7 +142,29 @@ size_t mask_warp_workspace_bytes(int B);
 hipError_t mask_warp_batch(const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int* F, const int* bidx,
                            const float* bc, const int* desc_host, const float* U_in, uint8_t* labels_out, float* uv_out, float* U_out,
                            void* ws, int B, int outer_iters, int max_cg, float rel_tol, hipStream_t s);
+// the same with the descriptors in device memory (desc_dev int [B,6]): they are copied to the workspace by a kernel that validates
+// them (counts within the caps, n_f >= 1, offsets >= 0); a pair that fails is drawn with the identity map
+hipError_t mask_warp_batch_dev(const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int* F, const int* bidx,
+                               const float* bc, const int* desc_dev, const float* U_in, uint8_t* labels_out, float* uv_out, float* U_out,
+                               void* ws, int B, int outer_iters, int max_cg, float rel_tol, hipStream_t s);
 
+// delaunay.hip: exact Delaunay triangulation of B planar point sets on the 2^-20 grid of [0, 1024), one workgroup per set.
+// v_desc_host: B x {v_off, n_v} (host).  F int [B, WARP_MAX_F, 3], n_f int [B], status int [B] (device).
+constexpr int DELAUNAY_DESC_SETS = 64;        // descriptors reach the workspace as kernel arguments, this many sets per store launch
+struct DelaunayDesc {
+    int n, set0;
+    int d[DELAUNAY_DESC_SETS][2];
+};
+enum DelaunayStatus {                         // == CH_DELAUNAY_* in ctrlhair_hip.h
+    DELAUNAY_OK = 0,
+    DELAUNAY_BAD_COUNT = 1,
+    DELAUNAY_OFF_GRID = 2,
+    DELAUNAY_DUPLICATE = 3,
+    DELAUNAY_COLLINEAR = 4,
+    DELAUNAY_INTERNAL = 5,
+};
+size_t delaunay_workspace_bytes(int B);
+hipError_t delaunay_batch(const float* V, const int* v_desc_host, int* F, int* n_f, int* status, void* ws, int B, hipStream_t s);
 
 // face_align.hip: FFHQ face alignment of one photo (external_code/crop.py:20-107): Pillow's 8-bit Lanczos resample, its QUAD / BILINEAR
 // transform fused into the horizontal Lanczos pass, and the reflect-pad / Gaussian-feather / median branch of the reference, all exact.

@@ -38,6 +38,19 @@ __global__ void warp_store_desc_kernel(WarpDesc desc, int* __restrict__ dst) {
     if (i < desc.n * 6) dst[desc.pair0 * 6 + i] = desc.d[i / 6][i % 6];
 }
 
+// ch_mask_warp_batch_dev: the descriptors are in device memory.  Copied to the same place, and validated on the way (the host
+// entry point does this before it launches): a pair whose counts or offsets are out of range gets the all-zero descriptor, for
+// which the solver does nothing and the renderer draws the identity map.
+__global__ void warp_copy_desc_kernel(const int* __restrict__ src, int B, int* __restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    int d[6];
+    for (int k = 0; k < 6; ++k) d[k] = src[6 * i + k];
+    const bool ok = d[0] >= 0 && d[2] >= 0 && d[4] >= 0 && d[1] >= 3 && d[1] <= WARP_MAX_V && d[3] >= 1 && d[3] <= WARP_MAX_F &&
+                    d[5] >= 0 && d[5] <= WARP_MAX_V;
+    for (int k = 0; k < 6; ++k) dst[6 * i + k] = ok ? d[k] : 0;
+}
+
 // Sum of two doubles per thread over the workgroup, the same value in every thread: butterfly-free fixed tree (shuffle down
 // inside each wave, then the 16 wave sums added in wave order), so the result does not depend on timing.  `buf` alternates
 // between calls so that one barrier per reduction is enough.
@@ -463,6 +476,10 @@ __global__ __launch_bounds__(TILE* TILE) void uv_render_sample_kernel(const uint
     // triangle_wrap_hair.py:77-85 ("fix edge"), assignments in the reference's order; lin = float32(np.linspace(0, 1, 672))
     const float cedge = (float)(1.0 - 1.0 / CANVAS);
     auto lin = [](int i) { return i == CANVAS - 1 ? 1.f : (float)((double)i * (1.0 / (CANVAS - 1))); };
+    if (nF == 0) {                             // a descriptor that warp_copy_desc_kernel refused: the identity map (colour = position / 671)
+        cu = lin(x);
+        cv = lin(y);
+    }
     if (y == 0 || y == CANVAS - 1) cu = lin(x);
     if (y == 0) cv = 0.f;
     if (y == CANVAS - 1) cv = cedge;
@@ -498,6 +515,32 @@ __global__ __launch_bounds__(TILE* TILE) void uv_render_sample_kernel(const uint
 
 size_t mask_warp_workspace_bytes(int B) { return B > 0 ? ws_head(B) + (size_t)B * WS_PAIR : 0; }
 
+// the launches behind both entry points, once the descriptors are at the head of the workspace
+static hipError_t warp_launch(const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int* F, const int* bidx,
+                              const float* bc, const float* U_in, uint8_t* labels_out, float* uv_out, float* U_out, char* w, int B,
+                              int outer_iters, int max_cg, float rel_tol, hipStream_t s) {
+    if (U_in)
+        warp_load_u_kernel<<<dim3(4, B), 256, 0, s>>>(U_in, B, w, U_out);
+    else
+        arap_solve_kernel<<<B, AT, 0, s>>>(V, F, bidx, bc, B, w, U_out, outer_iters, max_cg, rel_tol);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // without a UV output only the tiles of the cropped 512 x 512 window are rendered (80 = 5 tiles)
+    const int tile0 = uv_out ? 0 : BG / TILE, nt = uv_out ? TILES : IMG / TILE;
+    uv_render_sample_kernel<<<dim3(nt, nt, B), TILE * TILE, 0, s>>>(hair_labels, face_labels, V, F, B, w, labels_out, uv_out, tile0);
+    return hipGetLastError();
+}
+
+hipError_t mask_warp_batch_dev(const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int* F, const int* bidx,
+                               const float* bc, const int* desc_dev, const float* U_in, uint8_t* labels_out, float* uv_out, float* U_out,
+                               void* ws, int B, int outer_iters, int max_cg, float rel_tol, hipStream_t s) {
+    char* w = static_cast<char*>(ws);
+    warp_copy_desc_kernel<<<(B + 255) / 256, 256, 0, s>>>(desc_dev, B, reinterpret_cast<int*>(w));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return warp_launch(hair_labels, face_labels, V, F, bidx, bc, U_in, labels_out, uv_out, U_out, w, B, outer_iters, max_cg, rel_tol, s);
+}
+
 hipError_t mask_warp_batch(const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int* F, const int* bidx,
                            const float* bc, const int* desc_host, const float* U_in, uint8_t* labels_out, float* uv_out, float* U_out,
                            void* ws, int B, int outer_iters, int max_cg, float rel_tol, hipStream_t s) {
@@ -512,16 +555,7 @@ hipError_t mask_warp_batch(const uint8_t* hair_labels, const uint8_t* face_label
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (U_in)
-        warp_load_u_kernel<<<dim3(4, B), 256, 0, s>>>(U_in, B, w, U_out);
-    else
-        arap_solve_kernel<<<B, AT, 0, s>>>(V, F, bidx, bc, B, w, U_out, outer_iters, max_cg, rel_tol);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    // without a UV output only the tiles of the cropped 512 x 512 window are rendered (80 = 5 tiles)
-    const int tile0 = uv_out ? 0 : BG / TILE, nt = uv_out ? TILES : IMG / TILE;
-    uv_render_sample_kernel<<<dim3(nt, nt, B), TILE * TILE, 0, s>>>(hair_labels, face_labels, V, F, B, w, labels_out, uv_out, tile0);
-    return hipGetLastError();
+    return warp_launch(hair_labels, face_labels, V, F, bidx, bc, U_in, labels_out, uv_out, U_out, w, B, outer_iters, max_cg, rel_tol, s);
 }
 
 }  // namespace chk

@@ -31,6 +31,13 @@ On-disk formats are the reference's:
                                            <root>/mean_style_code.npz for HairEditor(mean_style_code=...); no network weights:
                                            ctrlhair_amd.stylestats.  Single process: all 19 regions are one kernel call that takes
                                            well under a second at tens of thousands of images, so there is nothing to shard)
+    python -m ctrlhair_amd.dataset warp-pool <root> <pool_dir> --landmarks <file> (--pairs N [--seed S] | --pairs-file FILE)
+                                          [--datasets A B ...] [--batch 16] [--only-hair]
+                                          (shape_branch/adaptor_generation.py AdaptorPoolGeneration: warp the hair mask of
+                                           <root>/<hair dataset>/label/<hair name>.png onto <root>/<face dataset>/label/<face name>.png
+                                           for many hair / face pairs and write <pool_dir>/<hair_dir>___<hair_num>___<face_dir>___
+                                           <face_num>___<rank:02d>.png; landmarks: name -> [81,2] in [0,1]; meshing and warp are
+                                           batched on the GPU: warping.MaskWarper.warp_batch(mesher='device'))
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -266,6 +273,112 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
     return done, skipped
 
 
+def pool_candidates(root: str, datasets: Sequence[str] = None) -> List[tuple]:
+    """(dataset, label file name) of every label PNG under <root>/<dataset>/label, sorted; datasets: default every
+    sub-directory of root that has a label folder."""
+    if datasets is None:
+        datasets = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d, 'label')))
+    return [(d, n) for d in datasets for n in list_images(os.path.join(root, d, 'label'))]
+
+
+def random_pairs(candidates: Sequence[tuple], n: int, seed: int) -> List[tuple]:
+    """n (hair, face) pairs drawn with replacement from the candidates, a function of (candidates, n, seed) alone -- every rank
+    draws the same list and takes its shard (the reference seeds each thread with the time)."""
+    rng = np.random.default_rng(seed)
+    idx = rng.integers(0, len(candidates), size=(n, 2)) if len(candidates) else np.zeros((0, 2), np.int64)
+    return [(candidates[int(i)], candidates[int(j)]) for i, j in idx]
+
+
+def read_pairs_file(path: str) -> List[tuple]:
+    """Lines `hair_dataset hair_name face_dataset face_name` (blank lines and lines starting with # are skipped)."""
+    pairs = []
+    with open(path) as f:
+        for k, line in enumerate(f, 1):
+            w = line.split()
+            if not w or w[0].startswith('#'):
+                continue
+            if len(w) != 4:
+                raise ValueError(f'{path}:{k}: expected `hair_dataset hair_name face_dataset face_name`, got {line.strip()!r}')
+            pairs.append(((w[0], w[1]), (w[2], w[3])))
+    return pairs
+
+
+def pool_name(hair: tuple, face: tuple, rank: int) -> str:
+    """adaptor_generation.py:33-36: the numbers are the last five characters of the file names without their extension."""
+    num = lambda n: os.path.splitext(n)[0][-5:]
+    return '%s___%s___%s___%s___%02d.png' % (hair[0], num(hair[1]), face[0], num(face[1]), rank)
+
+
+def warp_pool(warper, root: str, pool_dir: str, landmarks: Dict[str, np.ndarray], pairs: Sequence[tuple], batch: int = 16,
+              rank: int = 0, world: int = 1, only_hair: bool = False):
+    """The adaptor warp pool (adaptor_generation.py:31-52) for this rank's shard of `pairs` = [((hair_dataset, hair_name),
+    (face_dataset, face_name)), ...]: the hair of <root>/<hair_dataset>/label/<hair_name> warped onto the face parsing, `batch`
+    pairs per warper.warp_batch(mesher='device') call (`warper`: warping.MaskWarper; landmarks: name -> [81,2] in [0,1], looked up
+    like the crop job's).  Writes <pool_dir>/<pool_name>: the label map, or (label == 13) * 255 with only_hair.
+    Returns (done, skipped): the files written, and the 'dataset/name' entries without landmarks (reported, their pairs left
+    out) plus the pairs whose points the device mesher refused."""
+    os.makedirs(pool_dir, exist_ok=True)
+    done, skipped, ready = [], [], []
+    for hair, face in shard(list(pairs), rank, world):
+        lms = [find_landmarks(landmarks, d, n) for d, n in (hair, face)]
+        for (d, n), lm in zip((hair, face), lms):
+            if lm is None and f'{d}/{n}' not in skipped:
+                print(f'warp-pool: no landmarks for {d}/{n}, skipped')
+                skipped.append(f'{d}/{n}')
+        if lms[0] is not None and lms[1] is not None:
+            ready.append((hair, face, np.asarray(lms[0], np.float64)[:81], np.asarray(lms[1], np.float64)[:81]))
+    label = lambda e: read_gray(os.path.join(root, e[0], 'label', e[1]))
+    for group in batches(ready, batch):
+        out = warper.warp_batch(np.stack([label(g[0]) for g in group]), np.stack([label(g[1]) for g in group]),
+                                np.stack([g[2] for g in group]), np.stack([g[3] for g in group]), mesher='device')
+        out = out.cpu().numpy() if hasattr(out, 'cpu') else np.asarray(out)
+        status = getattr(warper, 'last_mesh_status', None)
+        status = np.zeros(len(group), np.int64) if status is None else np.asarray(status.cpu() if hasattr(status, 'cpu') else status)
+        for g, lab, st in zip(group, out, status):
+            name = pool_name(g[0], g[1], rank)
+            if int(st) != 0:
+                print(f'warp-pool: the mesher refused {name} (status {int(st)}), skipped')
+                skipped.append(name)
+                continue
+            write_label_png(os.path.join(pool_dir, name), (lab == 13) * 255 if only_hair else lab)
+            done.append(name)
+    return done, skipped
+
+
+def _main_warp_pool(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog='ctrlhair_amd.dataset warp-pool', description='Warp hair masks onto faces for many hair / face pairs')
+    ap.add_argument('root', help='directory with <dataset>/label/<name>.png, as the masks job writes them')
+    ap.add_argument('pool_dir', help='directory for the warped label maps')
+    ap.add_argument('--landmarks', required=True, help='.npz or pickled dict: image name -> [81,2] landmarks in [0,1]')
+    ap.add_argument('--pairs', type=int, default=None, help='number of random hair / face pairs (with --seed)')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--pairs-file', default=None, help='lines `hair_dataset hair_name face_dataset face_name`')
+    ap.add_argument('--datasets', nargs='*', default=None, help='datasets to draw from (default: every one under root)')
+    ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--only-hair', action='store_true', help='write (label == 13) * 255 instead of the label map')
+    args = ap.parse_args(argv)
+    if (args.pairs is None) == (args.pairs_file is None):
+        ap.error('give either --pairs N or --pairs-file FILE')
+    import torch
+    from . import lib
+    from .warping import MaskWarper
+    rank, world, local = _dist_env()
+    torch.cuda.set_device(local)
+    landmarks = load_landmarks(args.landmarks)
+    if args.pairs_file is not None:
+        pairs = read_pairs_file(args.pairs_file)
+    else:
+        cands = pool_candidates(args.root, args.datasets)
+        have = [c for c in cands if find_landmarks(landmarks, c[0], c[1]) is not None]
+        for d, n in sorted(set(cands) - set(have)):
+            print(f'warp-pool: no landmarks for {d}/{n}, not drawn')
+        pairs = random_pairs(have, args.pairs, args.seed)
+    warper = MaskWarper(lib.Handle(local), torch.device('cuda', local))
+    done, skipped = warp_pool(warper, args.root, args.pool_dir, landmarks, pairs, args.batch, rank, world, args.only_hair)
+    print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
+
+
 def _dist_env():
     return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
 
@@ -278,6 +391,8 @@ def main(argv=None):
         return _main_crop(argv[1:])
     if argv and argv[0] == 'uncrop':
         return _main_uncrop(argv[1:])
+    if argv and argv[0] == 'warp-pool':
+        return _main_warp_pool(argv[1:])
     if argv and argv[0] == 'median':
         return _main_median(argv[1:])
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])

@@ -44,6 +44,9 @@ SYMBOLS = {
     'ch_hair_color_stats': (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP]),
     'ch_mask_warp_workspace_bytes': (C.c_size_t, [_I]),
     'ch_mask_warp_batch': (_I, [_VP] * 13 + [C.c_size_t, _I, _VP]),
+    'ch_mask_warp_batch_dev': (_I, [_VP] * 13 + [C.c_size_t, _I, _VP]),
+    'ch_delaunay_workspace_bytes': (C.c_size_t, [_I]),
+    'ch_delaunay_batch': (_I, [_VP] * 7 + [C.c_size_t, _I, _VP]),
     'ch_resample_lanczos_workspace_bytes': (C.c_size_t, [_I] * 5),
     'ch_resample_lanczos_u8': (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I, _VP, C.c_size_t, _VP]),
     'ch_quad_warp_workspace_bytes': (C.c_size_t, [_I, _I]),

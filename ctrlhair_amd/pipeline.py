@@ -70,8 +70,10 @@ def hsv_to_rgb_u8(hsv: torch.Tensor) -> torch.Tensor:
 class EditPipeline:
     def __init__(self, weights: Optional[Dict[str, dict]] = None, device: int = 0, img_size: int = 512, max_batch: int = 8,
                  f16x3=None, models=None, texture_dirs=None, shape_dirs=None, hsv_table=None, options=None,
-                 mean_style_code: Optional[str] = None):
-        """mean_style_code: path of an .npz with the per-region fallback codes, like HairEditor's; None = the packaged file.
+                 mean_style_code: Optional[str] = None, mesher: str = 'host'):
+        """mesher: who triangulates the landmarks of transfer_shape: 'host' (scipy / Qhull, one pair at a time) or 'device'
+        (ch_delaunay_batch, all pairs in one launch; warping.MaskWarper.warp_batch).
+        mean_style_code: path of an .npz with the per-region fallback codes, like HairEditor's; None = the packaged file.
         f16x3: None = by the weights, like HairEditor: 0 (exact f32) for a released checkpoint (a dict made by
         checkpoints.reference_checkpoints), 1 (split-operand f16 MFMA, f32-class) for procedural / untagged weights."""
         from .hair_editor import HipModels, is_released_checkpoint, procedural_weights
@@ -98,6 +100,9 @@ class EditPipeline:
         self.side = torch.cuda.Stream(self.device)      # edit(): the shape branch runs here, underneath the Zencoder
         self.overlap = True
         self.warper = None             # warping.MaskWarper of transfer_shape, built on first use (shares the models' handle)
+        if mesher not in ('host', 'device'):
+            raise ValueError(f"mesher must be 'host' or 'device', got {mesher!r}")
+        self.mesher = mesher
         self.split_encode = False      # edit(): BiSeNet underneath the Zencoder's convs (ch_sean_encode_features / _regions);
                                        # measured: no further gain once the shape branch runs aside (tools/edit_modes.py)
         self.mean = torch.tensor(_MEAN, device=self.device).view(1, 3, 1, 1)
@@ -265,7 +270,7 @@ class EditPipeline:
 
     def transfer_shape(self, img: torch.Tensor, donor_img: torch.Tensor, lm, donor_lm, sliders: Optional[dict] = None,
                        noise: Optional[torch.Tensor] = None, seed: int = 1, stages: Optional[dict] = None,
-                       labels512: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       labels512: Optional[torch.Tensor] = None, mesher: Optional[str] = None) -> torch.Tensor:
         """Backend.transfer_latent_representation('shape') + output() for B pairs: the hair SHAPE of donor_img[i] on img[i].
         img, donor_img: cuda float32 [B,3,S,S] in [-1,1]; lm, donor_lm: their 81-point landmarks, float [B,81,2] in [0,1]
         (host).  Both batches are parsed at 512, the donors' hair masks are warped onto the faces by ONE ch_mask_warp_batch
@@ -280,7 +285,7 @@ class EditPipeline:
             from .warping import MaskWarper
             self.warper = MaskWarper(self.models.generator.handle, self.device)
         lab512 = self.parse(torch.cat([img, donor_img]), full=True) if labels512 is None else labels512
-        warped = self.warper.warp_batch(lab512[B:], lab512[:B], donor_lm, lm)
+        warped = self.warper.warp_batch(lab512[B:], lab512[:B], donor_lm, lm, mesher=self.mesher if mesher is None else mesher)
         labels = lab512[:B]
         if S != 512:                                   # parse(): cv2 INTER_NEAREST, src = floor(dst * 512 / S), for every S
             idx = (torch.arange(S, device=lab512.device) * 512) // S

@@ -36,10 +36,11 @@ class LatentRepresentation:                       # ui/backend.py:31-37
 
 class Backend(HairEditor):
     def __init__(self, maximum_value_fe, blending=True, temp_path=os.path.join(TEMP_FOLDER, 'demo_output'), *,
-                 hsv_table=None, warper=None, blender=None, landmarker=None, **editor_kwargs):
+                 hsv_table=None, warper=None, blender=None, landmarker=None, mesher='host', **editor_kwargs):
         """ui/backend.py:45-65.  Keyword-only extras: hsv_table (DistTranslation data), warper (shape-transfer warp
         function with wrap_by_imgs' signature; without it the built-in MaskWarper is used), landmarker (callable img_rgb ->
-        float [81,2] landmarks in pixels of that image, for the built-in warper), blender (Poisson blender), and HairEditor's weights/device/img_size/models.
+        float [81,2] landmarks in pixels of that image, for the built-in warper), mesher ('host' or 'device': who triangulates the
+        landmarks for the built-in warper, warping.MaskWarper.warp_batch), blender (Poisson blender), and HairEditor's weights/device/img_size/models.
         HairEditor's mean_style_code (an .npz of a dataset's own fallback codes) passes through with them."""
         super().__init__(True, True, **editor_kwargs)
         self.target_img = None
@@ -61,6 +62,9 @@ class Backend(HairEditor):
         self.input_landmarks = None      # [81,2] in [0,1]: set_landmarks(), or the landmarker's answer at transfer time
         self.target_landmarks = None
         self.mask_warper = None          # built on first use
+        if mesher not in ('host', 'device'):
+            raise ValueError(f"mesher must be 'host' or 'device', got {mesher!r}")
+        self.mesher = mesher
         self.noise = None          # optional pinned noise planes for repeatable output() (tests / A-B comparisons)
 
     def _side_stream(self):
@@ -393,7 +397,9 @@ class Backend(HairEditor):
             from ..warping import MaskWarper
             self.mask_warper = MaskWarper(self.face_parsing.handle, self.device)
         labels = self.mask_warper.warp_batch(self._parse512(self.target_img)[None], self._parse512(self.input_img)[None],
-                                             hair_lm[None], face_lm[None])
+                                             hair_lm[None], face_lm[None], mesher=self.mesher)
+        if self.mesher == 'device' and int(self.mask_warper.last_mesh_status[0]) != 0:
+            raise RuntimeError(f'device meshing failed with status {int(self.mask_warper.last_mesh_status[0])} (ch_delaunay_batch)')
         return U.to_host(labels[0]).astype('int')
 
     def refresh_cur_mask(self, target_latent=None):      # :304-315

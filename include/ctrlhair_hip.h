@@ -300,6 +300,43 @@ size_t ch_mask_warp_workspace_bytes(int B);
 int  ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
                         const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out,
                         float* uv_out, float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream);
+/* ch_mask_warp_batch_dev: the same call with desc in DEVICE memory (int32 [B,6]), so a mesh made on the device (ch_delaunay_batch)
+ * never visits the host.  The descriptors are validated by the kernel that copies them to the workspace: offsets >= 0,
+ * 3 <= n_v <= CH_WARP_MAX_V, 1 <= n_f <= CH_WARP_MAX_F, 0 <= n_b <= CH_WARP_MAX_V.  A pair that fails is rendered undeformed (the
+ * identity map: UV = pixel / 671 before the edge fix), its U_out rows are not written; the other pairs are not affected.  With
+ * equal descriptors the results are those of ch_mask_warp_batch, byte for byte. */
+int  ch_mask_warp_batch_dev(ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
+                            const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out,
+                            float* uv_out, float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream);
+
+/* ---- Meshing for the warp: exact Delaunay triangulation of B planar point sets in one launch ---------------------------------
+ * V float [sum n_v, 2] device, packed; v_desc: HOST int32 [B,2] = {v_off, n_v} per set (copied as kernel arguments, may be freed on
+ * return).  F int32 [B, CH_WARP_MAX_F, 3], n_f int32 [B], status int32 [B]: device.  One workgroup per set, points in LDS, one lane
+ * per point: nearest neighbour, then a walk around the point that finds each triangle's apex by a scan of the set.
+ * Exactness domain: every coordinate is a float32 in [0, 1024) that is a multiple of 2^-20 (what warping.build_points_batch makes),
+ *   i.e. a 30-bit integer on that grid.  Orientation fits int64 and the incircle determinant 124 bits; both are evaluated in
+ *   float64 first and again in integers (__int128) whenever the float64 value is within its error bound, so the result is exactly
+ *   a Delaunay triangulation of the convex hull: no point strictly inside any circumcircle, every triangle of positive area (no
+ *   zero-area triangles along collinear hull points), 2 n - 2 - h triangles for h points on the hull boundary.
+ * Ties: k >= 4 points on one empty circle are fanned from the smallest index among them -- a rule of the co-circular set alone, so
+ *   the result is a manifold triangulation.
+ * Canonical form: rows counter-clockwise in (x, y), smallest index first, in lexicographic order, no duplicates, indices local.
+ * status[i]: CH_DELAUNAY_OK, or BAD_COUNT (n_v outside 3..CH_WARP_MAX_V), OFF_GRID (a coordinate outside the domain, NaN included),
+ *   DUPLICATE (two equal points), COLLINEAR (all points on one line), INTERNAL (inconsistency, never seen); then n_f[i] = 0 and
+ *   F's rows of the set are not written.  Nothing outside the set's own slots is ever written.
+ * workspace: ch_delaunay_workspace_bytes(B) bytes, 256-byte aligned: the descriptors, then per set two uint64 counters (incircle
+ *   tests evaluated, and how many of them went to the integer evaluation) at offset ((8 B + 255) / 256) * 256.
+ * Enqueued on `stream`, no synchronisation, no allocation, no waiting between workgroups, no floating-point atomics: set i of a
+ * batch is bit-identical to a B = 1 call. */
+#define CH_DELAUNAY_OK 0
+#define CH_DELAUNAY_BAD_COUNT 1
+#define CH_DELAUNAY_OFF_GRID 2
+#define CH_DELAUNAY_DUPLICATE 3
+#define CH_DELAUNAY_COLLINEAR 4
+#define CH_DELAUNAY_INTERNAL 5
+size_t ch_delaunay_workspace_bytes(int B);
+int  ch_delaunay_batch(ch_handle* h, const float* V, const int32_t* v_desc, int32_t* F, int32_t* n_f, int32_t* status,
+                       void* workspace, size_t workspace_bytes, int B, ch_stream_t stream);
 
 /* ---- Face alignment: external_code/crop.py:20-107 (recreate_aligned_images) for one photo -------------------------------------
  * The geometry (oriented quad, shrink factor, crop box, pad widths, blur, Pillow's quad coefficients) is a host plan
