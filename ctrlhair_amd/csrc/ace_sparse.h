@@ -132,7 +132,10 @@ struct AceInteriorParams {
     const float* p6;            //   P6[(b, j)][6][2][C] of this call, or null (unstyled ACE)
     int variant;                // exact-f32 kernel: 0 = one pixel per thread (default), 1 = four pixels per thread (16-byte
                                 // accesses), 2 = one pixel per thread writing whole 32-byte sectors (A/B measurements)
+    int groups;                 // exact-f32 tile4 kernel: channel groups of 32 served by one block (option "sean.int_groups"): 0 = chosen by the
+                                // launcher (ace_interior_groups), n >= 1 = at most n; the kernel receives the number in use
 };
+int ace_interior_groups(const AceInteriorParams& q);      // groups per block the tile4 launch of q uses (a divisor of ceil(C / 32))
 hipError_t ace_interior_f32(const AceInteriorParams& q, hipStream_t s);
 // f16x3 path (tile-skip mode): the pixels of the tiles of 32 x 16 WITHOUT a boundary pixel (q.cnt[tile] == 0); x in the C4
 // layout, out in the SH16 layout, scale protocol of sh16.h (q.pass 0: write at out_scale and record the maximum in q.out_amax;

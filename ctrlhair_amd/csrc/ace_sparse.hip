@@ -465,17 +465,23 @@ __global__ __launch_bounds__(256) void ace_interior_f32_tile_kernel(const AceInt
 typedef float nt_f32x4 __attribute__((ext_vector_type(4)));      // (a 16-byte store the compiler keeps whole)
 // Four pixels of a row per thread, blocks of 128 x 8 pixels (W >= 128): 16-byte stores, 8- / 16-byte x loads, the four noise
 // values of a thread share their 32-byte sectors with the seven other rows of the block.
+// A block serves q.groups consecutive channel groups of its tile: what depends on the pixels only -- marks, noise, ownership, line fill,
+// the slots of the straight-edge codes -- is set up once per block (per round), the table rows and the channel loop run per group.
+// Table rows are interleaved {1 + gamma_c, beta_c} pairs (one 8-byte read per pixel and channel; the 1 + gamma is the same f32 addition the
+// channel loop used to do, moved to the table build), {bn_a, nv, bn_d} one 16-byte entry per channel (one broadcast read).
 __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const AceInteriorParams q) {      // (8 blocks per CU: <= 64 VGPR; it is a streaming kernel)
 #ifndef ACE_T4_ES_BITS
 #define ACE_T4_ES_BITS 6      // 64 slots.  32 (14 KB of LDS instead of 22: eight blocks per CU at 64 VGPRs) was measured: 5.6 vs 4.2 ms per step on the
 #endif                        // benchmark labels -- a 128 x 8 block of the 128-pixel level holds up to ~60 codes, so it takes a second round; 16: 9.1 ms
-    constexpr int RS = 2 * IN_CG + 1, ES = 1 << ACE_T4_ES_BITS;      // ES: slots of the block's table of straight-edge rows
-    __shared__ float gt[19 * RS];
-    __shared__ float et[ES * RS];
+    // RS: row pitch in floats.  8-byte reads bank on (address / 4) % 64 per half wave: with 2 * IN_CG + 2 the rows r and r + 1 sit one bank
+    // pair apart, so up to 32 different rows read by one half wave at the same channel do not collide.
+    constexpr int RS = 2 * IN_CG + 2, ES = 1 << ACE_T4_ES_BITS;      // ES: slots of the block's table of straight-edge rows
+    __shared__ __attribute__((aligned(16))) float gt[19 * RS];
+    __shared__ __attribute__((aligned(16))) float et[ES * RS];
+    __shared__ __attribute__((aligned(16))) float4 pp[IN_CG];      // {bn_a, nv, bn_d, -}
     __shared__ int ekey[ES], olist[ES], nocc;
-    __shared__ float pa[IN_CG], pd[IN_CG], pn[IN_CG];
     const int HW = q.H * q.W, tpr = (q.W + 127) >> 7, tpc = (q.H + 7) >> 3;
-    const int b = blockIdx.x / (tpr * tpc), r = blockIdx.x - b * (tpr * tpc), tyi = r / tpr, c0 = blockIdx.y * IN_CG;
+    const int b = blockIdx.x / (tpr * tpc), r = blockIdx.x - b * (tpr * tpc), tyi = r / tpr;
     const int x = (r - tyi * tpr) * 128 + (threadIdx.x & 31) * 4, y = tyi * 8 + (threadIdx.x >> 5);
     const bool inimg = x < q.W && y < q.H;                   // W % 4 == 0: the four pixels are inside together
     const int pix = y * q.W + x;
@@ -492,6 +498,7 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
         i2 = i3 = q1;
     }
     const bool m0 = i0 || e0, m1 = i1 || e1, m2 = i2 || e2, m3 = i3 || e3;      // pixels this pass owns
+    const unsigned im = (i0 ? 1u : 0u) | (i1 ? 2u : 0u) | (i2 ? 4u : 0u) | (i3 ? 8u : 0u);      // (the interior ones)
     const int nmine = __syncthreads_count(m0) + __syncthreads_count(m1) + __syncthreads_count(m2) + __syncthreads_count(m3);
     if (nmine == 0) return;                                  // no pixel of this pass in this block
     // What is written.  A partially written 128-byte line costs more than a whole one (masked stores: 538 vs 423 us at 77 % interior
@@ -513,30 +520,19 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
         const float* np = q.noise + (long long)b * q.noise_bstride + (long long)x * q.H + y;      // plane layout [W][H]
         nz0 = np[0]; nz1 = np[q.H]; nz2 = np[2 * q.H]; nz3 = np[3 * q.H];
     }
-    for (int i = threadIdx.x; i < 19 * 2 * IN_CG; i += 256) {
-        const int jj = i / (2 * IN_CG), rr = i % (2 * IN_CG), gb = rr / IN_CG, c = c0 + rr % IN_CG;
-        gt[jj * RS + rr] = c < q.C ? q.gtab[(((long long)b * 19 + jj) * 2 + gb) * q.C + c] : 0.f;
-    }
-    if (threadIdx.x < IN_CG) {
-        const int c = c0 + threadIdx.x;
-        pa[threadIdx.x] = c < q.C ? q.bn_a[c] : 0.f;
-        pd[threadIdx.x] = c < q.C ? q.bn_d[c] : 0.f;
-        pn[threadIdx.x] = c < q.C ? q.nv[c] : 0.f;
-    }
     const int xW = q.W >> q.x_up, xHW = xW * (q.H >> q.x_up);
-    const float* __restrict__ xp = q.x + ((long long)b * q.C + c0) * xHW + (y >> q.x_up) * xW + (x >> q.x_up);
-    float* __restrict__ op = reinterpret_cast<float*>(q.out) + ((long long)b * q.C + c0) * HW + pix;
-    const int cmax = q.C - c0 < IN_CG ? q.C - c0 : IN_CG;
+    const int ngrp = (q.C + IN_CG - 1) / IN_CG, G = q.groups > 0 ? q.groups : 1;
+    const int gfirst = blockIdx.y * G, glast = gfirst + G < ngrp ? gfirst + G : ngrp;      // this block's channel groups
     const float slope = q.act == ACT_NONE ? 1.f : (q.act == ACT_LRELU ? 0.2f : 0.f);
     // Straight-edge pixels: the block's distinct codes go into a 64-slot table (open addressing on the code, LDS compare-and-swap); the
-    // rows -- E[code] + the three style sums -- are built once per block, cooperatively, and read like the interior rows.  Codes that
-    // find no slot (more than 64 distinct ones in 128 x 8 pixels: not seen on any label map of the tests) wait for another ROUND of the
-    // same code with a fresh table; a later round stores its pixels one by one.  pend: the edge pixels without a row yet.
-    unsigned short kk[4] = {0, 0, 0, 0};
-    bool pend[4] = {e0, e1, e2, e3};
-    if (e0 || e1 || e2 || e3) {
-        const ushort4 k4 = *reinterpret_cast<const ushort4*>(q.e16 + (long long)b * HW + pix);
-        kk[0] = k4.x; kk[1] = k4.y; kk[2] = k4.z; kk[3] = k4.w;
+    // rows -- E[code] + the three style sums -- are built once per block and channel group, cooperatively, and read like the interior
+    // rows.  Codes that find no slot (more than 64 distinct ones in 128 x 8 pixels) wait for another ROUND of the same code with a fresh
+    // table; a later round stores its pixels one by one.  The slots of a round hold for every channel group of that round.
+    // pend: the edge pixels without a row yet.
+    unsigned k01 = 0, k23 = 0, pend = (e0 ? 1u : 0u) | (e1 ? 2u : 0u) | (e2 ? 4u : 0u) | (e3 ? 8u : 0u);      // codes of the four pixels (16 bits each)
+    if (pend) {
+        const uint2 k4 = *reinterpret_cast<const uint2*>(q.e16 + (long long)b * HW + pix);
+        k01 = k4.x; k23 = k4.y;
     }
     for (bool first = true;; first = false) {
         int slot[4] = {-1, -1, -1, -1};
@@ -545,14 +541,14 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
             __syncthreads();
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                if (!pend[s]) continue;
-                const int code = kk[s];
+                if (!(pend >> s & 1u)) continue;
+                const int code = (int)(((s & 2) ? k23 : k01) >> ((s & 1) * 16) & 0xFFFFu);
                 unsigned h = ((unsigned)code * 2654435761u) >> (32 - ACE_T4_ES_BITS);
                 for (int probe = 0; probe < ES; ++probe) {
                     const int old = atomicCAS(&ekey[h], -1, code);
                     if (old == -1 || old == code) {
                         slot[s] = (int)h;
-                        pend[s] = false;
+                        pend &= ~(1u << s);
                         break;
                     }
                     h = (h + 1) & (ES - 1);
@@ -565,34 +561,61 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
                 if (occ) olist[__popcll(om & ((1ull << threadIdx.x) - 1ull))] = threadIdx.x;
                 if (threadIdx.x == 0) nocc = __popcll(om);
             }
-            __syncthreads();
-            const int ne = nocc * 2 * IN_CG;
-            for (int i = threadIdx.x; i < ne; i += 256) {
-                const int sl = olist[i / (2 * IN_CG)], rr = i % (2 * IN_CG), gb = rr / IN_CG, c = c0 + rr % IN_CG;
-                const int code = ekey[sl];
-                float v = 0.f;
+        }
+        // this round's pixels: the first round takes the interior pixels, the edge pixels that found a slot and (fill) the line's others
+        const unsigned wm = (slot[0] >= 0 ? 1u : 0u) | (slot[1] >= 0 ? 2u : 0u) | (slot[2] >= 0 ? 4u : 0u) | (slot[3] >= 0 ? 8u : 0u) | (first ? im : 0u);
+        const bool work = first ? any : wm != 0;
+        // a pixel's row of {1 + gamma, beta} pairs: the (sample, label) row of an interior pixel, the block-table row of a straight-edge pixel
+        const float *g0 = slot[0] >= 0 ? et + slot[0] * RS : gt + ((im & 1u) ? j4.x : 0) * RS, *g1 = slot[1] >= 0 ? et + slot[1] * RS : gt + ((im & 2u) ? j4.y : 0) * RS,
+                    *g2 = slot[2] >= 0 ? et + slot[2] * RS : gt + ((im & 4u) ? j4.z : 0) * RS, *g3 = slot[3] >= 0 ? et + slot[3] * RS : gt + ((im & 8u) ? j4.w : 0) * RS;
+        for (int gi = gfirst; gi < glast; ++gi) {
+            const int c0 = gi * IN_CG;
+            __syncthreads();                                 // (olist / nocc are written; the previous group's table reads are over)
+            // one thread = one channel of one row, gamma and beta together.  (tid is opaque to the compiler here: the addresses of the table
+            // build are otherwise hoisted out of the group loop and held in registers through the channel loop)
+            int tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));
+            for (int i = tid; i < 19 * IN_CG; i += 256) {
+                const int jj = i / IN_CG, cl = i % IN_CG, c = c0 + cl;
+                float2 v = make_float2(0.f, 0.f);
                 if (c < q.C) {
-                    v = q.etab[((long long)code * 2 + gb) * q.C + c];
-                    if (q.p6) {
-                        const int sn = (code & 3) + 1, Bl = (code >> 2) % 19, A = ((code >> 2) / 19) % 19, o = (code >> 2) / 361;
+                    const float* gp = q.gtab + ((long long)b * 19 + jj) * 2 * q.C + c;
+                    v = make_float2(gp[0], gp[q.C]);
+                }
+                *reinterpret_cast<float2*>(gt + jj * RS + 2 * cl) = make_float2(1.f + v.x, v.y);
+            }
+            if (tid < IN_CG) {
+                const int c = c0 + tid;
+                pp[tid] = c < q.C ? make_float4(q.bn_a[c], q.nv[c], q.bn_d[c], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            if (edges) {
+                const int ne = nocc * IN_CG;
+                for (int i = tid; i < ne; i += 256) {
+                    const int sl = olist[i / IN_CG], cl = i % IN_CG, c = c0 + cl;
+                    const int code = ekey[sl];
+                    float2 v = make_float2(0.f, 0.f);
+                    if (c < q.C) {
+                        const float* ep = q.etab + (long long)code * 2 * q.C + c;
+                        v = make_float2(ep[0], ep[q.C]);
+                        if (q.p6) {
+                            const int sn = (code & 3) + 1, Bl = (code >> 2) % 19, A = ((code >> 2) / 19) % 19, o = (code >> 2) / 361;
 #pragma unroll
-                        for (int t = 0; t < 3; ++t) {
-                            const int l = (1 + t < sn) ? A : Bl;        // line label 1 + t of A^s B^(5-s)
-                            v += q.p6[((((long long)b * 19 + l) * 6 + o * 3 + t) * 2 + gb) * q.C + c];
+                            for (int t = 0; t < 3; ++t) {
+                                const int l = (1 + t < sn) ? A : Bl;        // line label 1 + t of A^s B^(5-s)
+                                const float* pq = q.p6 + (((long long)b * 19 + l) * 6 + o * 3 + t) * 2 * q.C + c;
+                                v.x += pq[0];
+                                v.y += pq[q.C];
+                            }
                         }
                     }
+                    *reinterpret_cast<float2*>(et + sl * RS + 2 * cl) = make_float2(1.f + v.x, v.y);
                 }
-                et[sl * RS + rr] = v;
             }
-        }
-        __syncthreads();
-        // this round's pixels: the first round takes the interior pixels, the edge pixels that found a slot and (fill) the line's others
-        const bool w0 = first ? (i0 || slot[0] >= 0) : slot[0] >= 0, w1 = first ? (i1 || slot[1] >= 0) : slot[1] >= 0,
-                   w2 = first ? (i2 || slot[2] >= 0) : slot[2] >= 0, w3 = first ? (i3 || slot[3] >= 0) : slot[3] >= 0;
-        if (first ? any : (w0 || w1 || w2 || w3)) {
-            // a pixel's gamma | beta row: the (sample, label) row of an interior pixel, the block-table row of a straight-edge pixel
-            const float *g0 = slot[0] >= 0 ? et + slot[0] * RS : gt + (i0 ? j4.x : 0) * RS, *g1 = slot[1] >= 0 ? et + slot[1] * RS : gt + (i1 ? j4.y : 0) * RS,
-                        *g2 = slot[2] >= 0 ? et + slot[2] * RS : gt + (i2 ? j4.z : 0) * RS, *g3 = slot[3] >= 0 ? et + slot[3] * RS : gt + (i3 ? j4.w : 0) * RS;
+            __syncthreads();
+            if (!work) continue;
+            const float* __restrict__ xp = q.x + ((long long)b * q.C + c0) * xHW + (y >> q.x_up) * xW + (x >> q.x_up);
+            float* __restrict__ op = reinterpret_cast<float*>(q.out) + ((long long)b * q.C + c0) * HW + pix;
+            const int cmax = q.C - c0 < IN_CG ? q.C - c0 : IN_CG;
             // x of channel c (optionally loaded ACE_T4_AHEAD iterations before its use: measured slower, see the macro)
             auto loadx = [&](int c) {
                 float4 xv;
@@ -605,12 +628,17 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
                 return xv;
             };
             auto channel = [&](int c, const float4 xv) {
-                const float a = pa[c], n = pn[c], d = pd[c];
+                const float4 p = pp[c];
+                const float a = p.x, n = p.y, d = p.z;
+                const float2 r0 = *reinterpret_cast<const float2*>(g0 + 2 * c), r1 = *reinterpret_cast<const float2*>(g1 + 2 * c),
+                             r2 = *reinterpret_cast<const float2*>(g2 + 2 * c), r3 = *reinterpret_cast<const float2*>(g3 + 2 * c);
                 float4 o;
-                o.x = (a * xv.x + n * nz0 + d) * (1.f + g0[c]) + g0[IN_CG + c];
-                o.y = (a * xv.y + n * nz1 + d) * (1.f + g1[c]) + g1[IN_CG + c];
-                o.z = (a * xv.z + n * nz2 + d) * (1.f + g2[c]) + g2[IN_CG + c];
-                o.w = (a * xv.w + n * nz3 + d) * (1.f + g3[c]) + g3[IN_CG + c];
+                // (a x + n nz + d) (1 + gamma) + beta with the two fused multiply-adds written out -- fma(a, x, n nz) + d, then fma(., 1 + gamma, beta):
+                // what the compiler made of the plain expression up to now, pinned so that the images do not follow its choice
+                o.x = __builtin_fmaf(__builtin_fmaf(a, xv.x, n * nz0) + d, r0.x, r0.y);
+                o.y = __builtin_fmaf(__builtin_fmaf(a, xv.y, n * nz1) + d, r1.x, r1.y);
+                o.z = __builtin_fmaf(__builtin_fmaf(a, xv.z, n * nz2) + d, r2.x, r2.y);
+                o.w = __builtin_fmaf(__builtin_fmaf(a, xv.w, n * nz3) + d, r3.x, r3.y);
                 o.x = fmaxf(o.x, slope * o.x); o.y = fmaxf(o.y, slope * o.y);
                 o.z = fmaxf(o.z, slope * o.z); o.w = fmaxf(o.w, slope * o.w);
                 return o;
@@ -632,7 +660,7 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
                 xq[QN - 1] = loadx(c + QN < cmax ? c + QN : cmax - 1);
                 return xv;
             };
-            if (first && (fill || (w0 && w1 && w2 && w3))) {
+            if (first && (fill || wm == 15u)) {
 #pragma unroll ACE_T4_UNROLL
                 for (int c = 0; c < cmax; ++c) {
                     const float4 o = channel(c, next_x(c));
@@ -643,27 +671,55 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
                 for (int c = 0; c < cmax; ++c) {
                     const float4 o = channel(c, next_x(c));
                     float* oc = op + (long long)c * HW;
-                    if (w0) oc[0] = o.x;
-                    if (w1) oc[1] = o.y;
-                    if (w2) oc[2] = o.z;
-                    if (w3) oc[3] = o.w;
+                    if (wm & 1u) oc[0] = o.x;
+                    if (wm & 2u) oc[1] = o.y;
+                    if (wm & 4u) oc[2] = o.z;
+                    if (wm & 8u) oc[3] = o.w;
                 }
             }
         }
         if (!edges) break;
-        if (!__syncthreads_or(pend[0] || pend[1] || pend[2] || pend[3])) break;      // (block-uniform; also orders this round's table reads before the next clear)
+        if (!__syncthreads_or(pend != 0)) break;      // (block-uniform; also orders this round's table reads before the next clear)
     }
 }
 
-
+// Channel groups per block of the tile4 kernel (q.groups: 0 = this rule, n >= 1 = at most n; always a divisor of the group count).
+// The set-up of a block does not depend on the channel group, so more groups per block repeat it less often, but the grid has to keep
+// every CU supplied: the largest divisor that leaves at least SIXTEEN blocks per CU.  Seven blocks are resident per CU, so eight per CU
+// are 1.14 rounds and the second round runs on an almost empty machine: measured at the nine launch shapes of B = 16, 512^2
+// (profiles/r07_interior_groups_bench.txt), 128 pixels, C = 512: 422 us with one group per block, 475 with two (2048 blocks); 256 pixels,
+// C = 256: 399 / 382 / 415 us with 1 / 2 / 4; 512 pixels, C = 128: 667 / 654 / 645 us.  What the loop saves is 2-3 % of a launch.
+static int interior_num_cus() {
+    static int ncus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!ncus[dev]) {
+        int n = 0;
+        ncus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
+    }
+    return ncus[dev];
+}
+int ace_interior_groups(const AceInteriorParams& q) {
+    const int ngrp = (q.C + IN_CG - 1) / IN_CG;
+    const long long tiles = (long long)q.B * ((q.W + 127) / 128) * ((q.H + 7) / 8), need = 16LL * interior_num_cus();
+    int G = 1;
+    for (int d = 2; d <= ngrp; ++d) {
+        if (ngrp % d) continue;
+        if (q.groups > 0 ? d <= q.groups : tiles * (ngrp / d) >= need) G = d;
+    }
+    return G;
+}
 
 hipError_t ace_interior_f32(const AceInteriorParams& q, hipStream_t s) {
     if (q.act > ACT_RELU) return hipErrorInvalidValue;
     if (q.W % 4 != 0) return hipErrorInvalidValue;
     const int HW = q.H * q.W;
     if (q.impl == 2 && q.W >= 128) {
-        dim3 gridt((unsigned)(q.B * ((q.W + 127) / 128) * ((q.H + 7) / 8)), (unsigned)((q.C + IN_CG - 1) / IN_CG));
-        hipLaunchKernelGGL(ace_interior_f32_tile4_kernel, gridt, dim3(256), 0, s, q);
+        AceInteriorParams qq = q;
+        qq.groups = ace_interior_groups(q);
+        const int ngrp = (q.C + IN_CG - 1) / IN_CG;
+        dim3 gridt((unsigned)(q.B * ((q.W + 127) / 128) * ((q.H + 7) / 8)), (unsigned)((ngrp + qq.groups - 1) / qq.groups));
+        hipLaunchKernelGGL(ace_interior_f32_tile4_kernel, gridt, dim3(256), 0, s, qq);
         return hipGetLastError();
     }
     if (q.impl == 0 || q.impl == 2) {

@@ -678,6 +678,10 @@ int ch_set_option(ch_handle* h, const char* key, int value) {
         h->sean.edge = value != 0;
         return CH_OK;
     }
+    if (std::strcmp(key, "sean.int_groups") == 0) {   // channel groups per block of the four-pixel interior pass: 0 = chosen per launch (default), n >= 1 = at most n
+        h->sean.int_groups = value < 0 ? 0 : value;
+        return CH_OK;
+    }
     if (std::strcmp(key, "sean.batch_invariant") == 0) {      // exact-f32 path: 1 = kernel choices independent of the batch size of a call (default 0)
         h->sean.batch_inv = value != 0;
         return CH_OK;

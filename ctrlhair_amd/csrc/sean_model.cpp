@@ -1373,6 +1373,7 @@ struct Runner {
                 // four pixels per thread (16-byte stores) from 128 pixels of width: 530 -> 420 us on the up-sampled 512^2 launches
                 // (tools/interior_bench.hip); level in the 100 ms step of round 3, measurable in this one
                 ip.impl = r >= 128 ? 2 : 0;
+                ip.groups = m.int_groups;       // (tile4 kernel: channel groups per block, 0 = the launcher's rule; ace_sparse.hip)
                 if (wp.edges) {         // straight-edge pixels: table row of the code + three column / row sums of the style LUT (built below)
                     if (!a.edge_tab || r < 128) check(hipErrorInvalidValue, "straight-edge marks on a level whose ACE has no table");
                     ip.e16 = wp.S->e16;

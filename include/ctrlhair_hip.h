@@ -102,6 +102,11 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  * "sean.patch" (default 1; before ch_finalize): when a level is left with few boundary quads (at most 32 chunks of 64 per sample) their
  *   hidden-activation patches are written pre-gathered, in the conv kernel's stage layout, instead of being fetched piecewise from the
  *   planes (csrc/conv_wino.h WinoAceParams::patch); decided per level and call on the device; bit-identical.  0 = planes only.
+ * "sean.int_groups" (default 0; any time; exact-f32 Winograd path, levels of 128 pixels and more): a block of the four-pixel interior pass
+ *   (csrc/ace_sparse.hip, ace_interior_f32_tile4_kernel) sets up its 128 x 8 pixels once -- marks, noise, ownership, the slots of its
+ *   straight-edge codes -- and then serves several groups of 32 channels.  0 = per launch, the largest divisor of the group count that
+ *   leaves at least sixteen blocks per compute unit in the grid; n >= 1 = at most n groups per block (1 = one group per block, the
+ *   decomposition before the group loop).  Bit-identical for every value.
  * "sean.batch_invariant" (default 0; any time; exact-f32 path): by default several choices follow the number of tasks of a call, i.e. its
  *   batch size -- F(4x4,3x3) vs F(2x2,3x3) (wino4_pays), split-K of launches with few tasks, sample-pair tiles of the 16-pixel level, the
  *   GEMV / tiny-level routes of interactive batches -- so the same sample rendered alone and inside a batch differs by the rounding of two

@@ -1,10 +1,14 @@
 // tools/interior_bench.hip -- stand-alone timing of the f16x3 interior pass (ace_interior_sh16_kernel) against a byte-for-byte
 // copy kernel of the same access pattern.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ctrlhair_amd/csrc
 //   tools/interior_bench.hip -o tools/interior_bench.bin ; run on the GPU box.
+// `interior_bench.bin groups`: the four-pixel exact-f32 kernel (ace_interior_f32_tile4_kernel) at the nine launch shapes of the headline
+//   leg (B = 16, 512^2) with straight-edge marks on blocky labels, for 1, 2, 4, 8 channel groups per block and the launcher's rule.
 #include "../ctrlhair_amd/csrc/ace_sparse.hip"
 #include <cstdio>
 #include <vector>
 #include <cstdlib>
+#include <algorithm>
+#include <string>
 
 using namespace chk;
 
@@ -32,7 +36,87 @@ __global__ __launch_bounds__(256) void copy_like_kernel(const float4* __restrict
     }
 }
 
+// The nine tile4 launches of a headline step (B = 16, 512^2): ace_0 / ace_s read the up-sampled x of the level below, ace_1 reads full size.
+// Labels: a 16 x 16 grid of random labels per sample (as the benchmark's blocky labels), classified by ace_classify with straight-edge marks.
+static int run_groups() {
+    struct Cfg { const char* name; int C, H, up, styled; };
+    const Cfg cfgs[] = {{"128px ace_0", 512, 128, 1, 1}, {"128px ace_s", 512, 128, 1, 1}, {"128px ace_1", 256, 128, 0, 1},
+                        {"256px ace_0", 256, 256, 1, 1}, {"256px ace_s", 256, 256, 1, 1}, {"256px ace_1", 128, 256, 0, 1},
+                        {"512px ace_0", 128, 512, 1, 0}, {"512px ace_s", 128, 512, 1, 0}, {"512px ace_1", 64, 512, 0, 0}};
+    const int B = 16;
+    double tot[5] = {0, 0, 0, 0, 0};
+    const int gsel[5] = {1, 2, 4, 8, 0};
+    for (const Cfg& c : cfgs) {
+        const int C = c.C, H = c.H, W = c.H, HW = H * W, xh = H >> c.up, cell = H / 16;
+        std::vector<uint8_t> lab((size_t)B * HW);
+        unsigned rng = 12345u + (unsigned)H;
+        for (int b = 0; b < B; ++b) {
+            uint8_t g[256];
+            for (auto& v : g) { rng = rng * 1664525u + 1013904223u; v = (uint8_t)((rng >> 16) % 19); }
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x) lab[((size_t)b * H + y) * W + x] = g[(y / cell) * 16 + x / cell];
+        }
+        const int ntiles = B * ((W + 31) / 32) * ((H + 7) / 8);
+        uint8_t *d_lab, *d_u5, *d_need; uint16_t *d_list, *d_e16; int* d_cnt;
+        float *d_x, *d_gtab, *d_par, *d_noise, *d_etab, *d_p6, *d_out;
+        const size_t nx = (size_t)B * C * xh * xh, nout = (size_t)B * C * HW;
+        CK(hipMalloc(&d_lab, lab.size())); CK(hipMemcpy(d_lab, lab.data(), lab.size(), hipMemcpyHostToDevice));
+        CK(hipMalloc(&d_u5, lab.size())); CK(hipMalloc(&d_need, lab.size()));
+        CK(hipMalloc(&d_e16, lab.size() * 2)); CK(hipMemset(d_e16, 0, lab.size() * 2));
+        CK(hipMalloc(&d_list, (size_t)ntiles * 256 * 2)); CK(hipMalloc(&d_cnt, (size_t)ntiles * 4));
+        CK(ace_classify(d_lab, d_u5, d_need, d_list, d_cnt, B, H, W, 8, 0, d_e16));
+        std::vector<uint8_t> u5(lab.size());
+        CK(hipMemcpy(u5.data(), d_u5, u5.size(), hipMemcpyDeviceToHost));
+        size_t nint = 0, nedge = 0;
+        for (uint8_t v : u5) { nint += v < 19; nedge += v == ACE_EDGE; }
+        auto fill = [&](float** d, size_t n, float lo, float hi) {
+            std::vector<float> h(n);
+            for (auto& v : h) v = lo + (hi - lo) * (float)rand() / RAND_MAX;
+            CK(hipMalloc(d, n * 4)); CK(hipMemcpy(*d, h.data(), n * 4, hipMemcpyHostToDevice));
+        };
+        fill(&d_x, nx, -2.f, 2.f); fill(&d_gtab, (size_t)B * 19 * 2 * C, -0.5f, 0.5f); fill(&d_par, 3 * (size_t)C, 0.5f, 1.5f);
+        fill(&d_noise, (size_t)B * HW, -0.5f, 0.5f); fill(&d_etab, (size_t)ACE_EDGE_CODES * 2 * C, -0.5f, 0.5f);
+        fill(&d_p6, (size_t)B * 19 * 6 * 2 * C, -0.1f, 0.1f);
+        CK(hipMalloc(&d_out, nout * 4));
+        AceInteriorParams q{};
+        q.x = d_x; q.out = d_out; q.u5 = d_u5; q.gtab = d_gtab; q.bn_a = d_par; q.bn_d = d_par + C; q.nv = d_par + 2 * C;
+        q.noise = d_noise; q.noise_bstride = HW; q.B = B; q.C = C; q.H = H; q.W = W; q.x_up = c.up; q.act = 1;
+        q.impl = 2; q.fill_min = 0; q.e16 = d_e16; q.etab = d_etab; q.p6 = c.styled ? d_p6 : nullptr;
+        std::vector<uint32_t> ref(nout), got(nout);
+        hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+        printf("%s C=%3d H=%3d up=%d interior=%.3f straight-edge=%.3f |", c.name, C, H, c.up, (double)nint / u5.size(), (double)nedge / u5.size());
+        for (int k = 0; k < 5; ++k) {
+            q.groups = gsel[k];
+            const int G = ace_interior_groups(q);
+            CK(hipMemset(d_out, 0, nout * 4));
+            CK(ace_interior_f32(q, 0));
+            CK(hipMemcpy((k ? got : ref).data(), d_out, nout * 4, hipMemcpyDeviceToHost));
+            size_t bad = 0;
+            if (k) for (size_t i = 0; i < nout; ++i) bad += got[i] != ref[i];
+            float t[9];
+            for (int it = 0; it < 9; ++it) {
+                CK(hipEventRecord(e0, 0));
+                CK(ace_interior_f32(q, 0));
+                CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+                CK(hipEventElapsedTime(&t[it], e0, e1));
+            }
+            std::sort(t + 1, t + 9);                       // (the first run warms up) median of eight
+            const float med = 0.5f * (t[4] + t[5]);
+            tot[k] += med;
+            printf(" groups=%d -> G=%d %7.1f us (min %.1f) diff=%zu |", gsel[k], G, med * 1e3, t[1] * 1e3, bad);
+        }
+        printf("\n");
+        hipFree(d_lab); hipFree(d_u5); hipFree(d_need); hipFree(d_e16); hipFree(d_list); hipFree(d_cnt); hipFree(d_x); hipFree(d_gtab);
+        hipFree(d_par); hipFree(d_noise); hipFree(d_etab); hipFree(d_p6); hipFree(d_out);
+    }
+    printf("sum of the nine launches:");
+    for (int k = 0; k < 5; ++k) printf(" groups=%d %.3f ms |", gsel[k], tot[k]);
+    printf("\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "groups") return run_groups();
     struct Cfg { int B, C, H, up; };
     const Cfg cfgs[] = {{16, 64, 512, 1}, {16, 64, 512, 0}, {16, 128, 256, 1}, {16, 128, 256, 0}, {16, 256, 128, 1}};
     for (int stripes = 0; stripes < 3; ++stripes)
