@@ -691,6 +691,11 @@ int ch_set_option(ch_handle* h, const char* key, int value) {
         h->sean.wino4v = value != 0;
         return CH_OK;
     }
+    if (std::strcmp(key, "sean.wino4_split") == 0) {  // plain F(4x4,3x3) convs on the position-split kernel (conv_wino4_split.h): 0 = never, 1 = wherever supported, < 0 = per shape (default)
+        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino4_split) must precede ch_finalize");
+        h->sean.wino4_split = value < 0 ? -1 : (value != 0);
+        return CH_OK;
+    }
     if (std::strcmp(key, "sean.wino4_ace") == 0) {    // largest level (pixels) whose SPADE convs run as F(4x4,3x3) over every tile; 0 = none
         if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino4_ace) must precede ch_finalize");
         h->sean.wino4_ace_max_r = value < 0 ? 0 : value;

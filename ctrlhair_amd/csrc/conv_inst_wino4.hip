@@ -1,5 +1,6 @@
 // conv_inst_wino4.hip -- instantiation + launcher of the Winograd F(4x4,3x3) exact-f32 MFMA kernel (conv_wino4.h)
 #include "conv_wino4v.h"
+#include "conv_wino4_split.h"
 
 namespace chk {
 
@@ -15,12 +16,23 @@ hipError_t conv_wino4_plain(Wino4Params p, hipStream_t s) {
         if (e != hipSuccess) return e;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_plain_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
         if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_plain_split_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_plain_split_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
+        if (e != hipSuccess) return e;
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
         done[dev] = true;
     }
     const int grid = p.ntasks < cus[dev] ? p.ntasks : cus[dev];
+    // positions, not rows, split between the two waves of a tile group (conv_wino4_split.h): bit-identical results
+    if (p.wpk_split && (p.split > 0 || (p.split < 0 && wino4_split_pays(p)))) {
+        if (p.nks & 1) return hipErrorInvalidValue;
+        if (p.reflect) hipLaunchKernelGGL(wino4_plain_split_kernel<1>, dim3(grid), dim3(512), wino4::LDS_BYTES, s, p);
+        else hipLaunchKernelGGL(wino4_plain_split_kernel<0>, dim3(grid), dim3(512), wino4::LDS_BYTES, s, p);
+        return hipGetLastError();
+    }
     if (p.reflect) hipLaunchKernelGGL(wino4_plain_kernel<1>, dim3(grid), dim3(512), wino4::LDS_BYTES, s, p);
     else hipLaunchKernelGGL(wino4_plain_kernel<0>, dim3(grid), dim3(512), wino4::LDS_BYTES, s, p);
     return hipGetLastError();

@@ -57,12 +57,20 @@ struct Wino4Params {
     const float* v;         // conv_wino4v.h only: the pre-transformed input (wino4v_pack) -- `in` is then unused
     // set by the launcher
     int nrt, ntx, nty, ntiles, ntasks, nks, rb, tbk;
+    // conv_wino4_split.h: the pack_wino4_A(..., split = true) image or null, and option "sean.wino4_split" for this launch
+    const float* wpk_split;
+    int split;              // 0 = wino4_plain_kernel, 1 = wino4_plain_split_kernel when wpk_split is set, < 0 = wino4_split_pays decides
 };
 
+// fragment order of the split image (conv_wino4_split.h): wave half jh = j / 3 owns fragments 36 jh .. 36 jh + 35 (nine contiguous units);
+// inside, position q = 3 i + j % 3 of row half m is fragment 2 q + m (a unit = two positions x two row halves = one group of four MFMAs)
+constexpr int wino4_split_frag(int m, int i, int j) { return (j / 3) * 36 + 2 * (3 * i + j % 3) + m; }
+
 // image of (row tile rt, k-step s): [idx 0..17][lane][4 floats]; float e of idx holds fragment a = 4 idx + e = 36 m + xi (the nine
-// reads of a row half are contiguous):  U[xi][row = 32 rt + 16 m + (lane & 15)][ci = 4 s + (lane >> 4)],  U = G g G^T  (xi = 6 i + j)
+// reads of a row half are contiguous):  U[xi][row = 32 rt + 16 m + (lane & 15)][ci = 4 s + (lane >> 4)],  U = G g G^T  (xi = 6 i + j);
+// split = true: the same values with a = wino4_split_frag(m, i, j)
 template <class F>
-std::vector<float> pack_wino4_A(int rows, int Cin, F get) {
+std::vector<float> pack_wino4_A(int rows, int Cin, F get, bool split = false) {
     static const double G[6][3] = {{0.25, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
                                    {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     const int nrt = (rows + 31) / 32, nks = Cin / 4;
@@ -82,7 +90,7 @@ std::vector<float> pack_wino4_A(int rows, int Cin, F get) {
                     for (int i = 0; i < 6; ++i)
                         for (int j = 0; j < 6; ++j) {
                             const double u = t[i][0] * G[j][0] + t[i][1] * G[j][1] + t[i][2] * G[j][2];
-                            const int a = m * 36 + i * 6 + j;
+                            const int a = split ? wino4_split_frag(m, i, j) : m * 36 + i * 6 + j;
                             img[((a >> 2) * 64 + lane) * 4 + (a & 3)] = (float)u;
                         }
                 }
@@ -110,6 +118,15 @@ __device__ __forceinline__ void wino4_out1d(float m0, float m1, float m2, float 
     y2 = __builtin_fmaf(4.f, s2, s1);
     y3 = __builtin_fmaf(8.f, d2, d1) + m5;
 }
+
+// Where the input transform's arithmetic really runs.  The k-step below writes each row / column transform behind the MFMAs of a group,
+// but its results are first used in the NEXT k-step, and hipcc sinks the whole transform past issue_tail's branches to the top of that
+// k-step, in front of its barrier: a k-step executes as [vector block] barrier [36 MFMAs with the LDS reads and DMAs between them].
+// wino4_pin (an empty asm on a result: no instruction) keeps a transform in the group that computes it, i.e. the order as written;
+// -DCH_W4_PIN applies it in wino4_plain_kernel and wino4_plain_split_kernel.  Measured SLOWER: 14.02 vs 13.45 ms over the twelve
+// ResBlock convs for wino4_plain_kernel, 12.97 vs 12.27 ms for the split kernel (profiles/r08_wino4_split_bench.txt) -- vector
+// instructions between the MFMAs of a wave cost matrix-pipe time, one block of them in front of the barrier costs less.  Not defined.
+__device__ __forceinline__ void wino4_pin(float& a) { asm volatile("" : "+v"(a)); }
 
 // The two halo columns of a patch row (q[0]: dword 3 of a 16-byte unit, q[5]: dword 0 of the unit after next).  As 4-byte reads every
 // lane's address is = 3 (= 0) mod 4 and the 32 lanes of a ds_read_b32 group fall on 8 of its 32 banks (4-way conflict: 53 % of the
@@ -373,6 +390,15 @@ __global__ __launch_bounds__(512, 1) void wino4_plain_kernel(const Wino4Params p
                     wino4_in1d(vx[j], vx[6 + j], vx[12 + j], vx[18 + j], vx[24 + j], vx[30 + j], vx[j], vx[6 + j], vx[12 + j], vx[18 + j], vx[24 + j],
                                vx[30 + j]);
             }
+#ifdef CH_W4_PIN
+            if constexpr (g < 6) {
+#pragma unroll
+                for (int j = 0; j < 6; ++j) wino4_pin(vx[6 * g + j]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { wino4_pin(vx[6 * i + 2 * (g - 6)]); wino4_pin(vx[6 * i + 2 * (g - 6) + 1]); }
+            }
+#endif
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (g >= 2 && g < 6) issue_piece(WInt<g - 2>{});
             __builtin_amdgcn_sched_barrier(0);
@@ -702,6 +728,11 @@ inline void wino4_fill_launch(Wino4Params& p) {
     p.rb = p.nrt >= 4 ? 4 : p.nrt;
     p.tbk = 32 / p.rb;
 }
+// Which launches take wino4_plain_split_kernel when the option leaves it to the library: those with at least 32 k-steps per task
+// (Cin >= 128).  Its five extra barriers and 96 KB of LDS traffic per task are paid once, the halved transform in every k-step: measured
+// -5 ... -13 % per launch from 32 k-steps up, +2 % at 16 (up_3.conv_1, 64 -> 64 at 512 x 512), +3 ... 5 % on launches of a few
+// microseconds with 4 ... 16 k-steps (tools/wino4_bench.hip split, profiles/r08_wino4_split_bench.txt)
+inline bool wino4_split_pays(const Wino4Params& p) { return p.Cin >= 128; }
 hipError_t conv_wino4_plain(Wino4Params p, hipStream_t s);      // conv_inst_wino4.hip
 inline bool wino4_ace_supported(int H, int W, int C) { return H % wino4::TS == 0 && W % wino4::TS == 0 && C % 2 == 0; }
 hipError_t conv_wino4_ace(Wino4AceParams p, hipStream_t s);

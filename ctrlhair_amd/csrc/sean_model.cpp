@@ -131,7 +131,10 @@ std::string SeanModel::build(const TensorStore& ts, int mb, int ms) {
             } else {
                 cw.wpk = B.upload(pack_A(r.cout, r.cin, r.ks, r.ks == 3 ? CK_KS3 : CK_KS1, getw));
                 if (wino && r.ks == 3 && r.cin % 8 == 0) cw.wino = B.upload(pack_wino_A(r.cout, r.cin, getw));
-                if (wino >= 2 && r.ks == 3 && r.cin % 8 == 0 && r.cin >= 16) cw.wino4 = B.upload(pack_wino4_A(r.cout, r.cin, getw));
+                if (wino >= 2 && r.ks == 3 && r.cin % 8 == 0 && r.cin >= 16) {
+                    cw.wino4 = B.upload(pack_wino4_A(r.cout, r.cin, getw));
+                    if (wino4_split > 0 || (wino4_split < 0 && r.cout < 512)) cw.wino4s = B.upload(pack_wino4_A(r.cout, r.cin, getw, true));
+                }
                 if (wino && r.ks == 1 && r.cin % 16 == 0) cw.pw = B.upload(pack_pw_A(r.cout, r.cin, [&](int row, int ci) { return getw(row, ci, 0); }));
             }
             cw.Cout = r.cout;
@@ -444,13 +447,15 @@ std::string SeanModel::build(const TensorStore& ts, int mb, int ms) {
             z10 = make_conv(B, w, B.vec("Zencoder.model.10.bias", 256), 256, 128, 3, 1, 1, false);      // (its Winograd form is z10_wino: four phase convs)
         }
         plain("Zencoder.model.14", 512, 256, 1, z14);
-        z14_wino = z10_wino = z14_wino4 = nullptr;
+        z14_wino = z10_wino = z14_wino4 = z14_wino4s = nullptr;
         if (!use_sh16 && wino) {   // exact-f32 path: the 256 -> 512 conv (91 % of the Zencoder FLOPs) as Winograd F(2x2,3x3), reflection-padded
             auto w14 = B.vec("Zencoder.model.14.weight", (size_t)512 * 256 * 9);
             const float* wp = w14.data();
             z14_wino = B.upload(pack_wino_A(512, 256, [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; }));
             // "sean.wino" = 2: the same conv as F(4x4,3x3) (conv_wino4.h, reflection instantiation) where the half-resolution grid is a multiple of 32
             if (wino >= 2) z14_wino4 = B.upload(pack_wino4_A(512, 256, [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; }));
+            if (wino >= 2 && wino4_split > 0)      // (512 GEMM rows: the V route by default; the split kernel only on request)
+                z14_wino4s = B.upload(pack_wino4_A(512, 256, [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; }, true));
             // ConvTranspose2d(128, 256, k3, s2, p1, op1) (architecture.py:167-170) as four phase convs of the INPUT grid:
             //   out[2y+py][2x+px] = sum over dy, dx in {0, 1} of x[y+dy][x+dx] * Wt[ci][co][py+1-2dy][px+1-2dx]   (taps outside 0..2 absent)
             // each a 3x3 kernel with non-zero taps at offsets 0 / +1 only; as Winograd F(2x2,3x3) that is 4 products per output pixel,
@@ -1639,6 +1644,8 @@ struct Runner {
             q.bias = w.bias;
             q.res = res;
             q.res_up = res_up;
+            q.wpk_split = w.wino4s;
+            q.split = m.wino4_split;
             next_flops_exec = 2.0 * w.Cout * w.Cin * 36.0 * npix / 16.0;
             // many GEMM rows on a small level: the input transform once, in its own pass, instead of in every row tile (conv_wino4v.h)
             const bool vroute = m.wino4v && wino4v_pays(w.Cout, r) && m.wino4v_fits(B, r, w.Cin / 4);
@@ -1994,6 +2001,8 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
                 q.bias = z14.bias;
                 q.act = ACT_TANH;
                 q.reflect = 1;
+                q.wpk_split = z14_wino4s;
+                q.split = wino4_split;
                 if (wino4v && wino4v_fits(B, h2, 64)) {          // 512 GEMM rows: the (reflected) input transform in its own pass
                     Wino4vPackParams vp{};
                     vp.in = hs;

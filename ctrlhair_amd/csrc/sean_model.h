@@ -19,6 +19,7 @@ struct ConvW {
     float* wscale = nullptr;                    // f16x3 path: per-row 2^-k undoing the weight scaling (sh16.h)
     float* wino = nullptr;                      // exact-f32 path, 3x3: Winograd F(2x2,3x3) image U = G g G^T (conv_wino.h)
     float* wino4 = nullptr;                     // exact-f32 path, 3x3, sean.wino = 2: Winograd F(4x4,3x3) image (conv_wino4.h)
+    float* wino4s = nullptr;                    // ... and the same values in the split kernel's fragment order (conv_wino4_split.h), see SeanModel::wino4_split
     float* pw = nullptr;                        // exact-f32 path, 1x1: pack_pw_A image (conv_pw.h)
     int Cout = 0, Cin = 0, KS = 0;
 };
@@ -87,6 +88,7 @@ struct SeanModel {
     float* z10_pw[4] = {};                             // option "sean.convt_gemm": the same ConvTranspose as four phase GEMMs over shifted views (conv_pw.h; phase = 2 py + px)
     int convt_gemm = 1;
     float* z14_wino = nullptr;                         // exact-f32 path: z14 as Winograd A images (conv_wino.h, reflection padding)
+    float* z14_wino4s = nullptr;                       // (the F(4x4,3x3) image in the split kernel's fragment order, conv_wino4_split.h)
     float* z14_wino4 = nullptr;                        // ... and as F(4x4,3x3) images (conv_wino4.h), sean.wino = 2
     float *z14_ws = nullptr, *z10_ws = nullptr;        // their per-row inverse weight scales
     float *z10_d2s = nullptr, *z10_d2s_ws = nullptr;   // the ConvTranspose in its 2x2-tap depth-to-space form (rows = phase * 256 + co)
@@ -176,6 +178,9 @@ struct SeanModel {
                                                //   batch: sample i alone == sample i in any batch, bit for bit (exact-f32 path)
     int wino4v = 1;                            // option "sean.wino4v": 1 = F(4x4,3x3) layers with >= 512 GEMM rows at <= 64 pixels (and the Zencoder's 256 -> 512
                                                //   conv) take their input pre-transformed by one extra pass (conv_wino4v.h; bit-identical results)
+    int wino4_split = -1;                      // option "sean.wino4_split": the plain F(4x4,3x3) convs that do not take the V route on wino4_plain_split_kernel
+                                               //   (conv_wino4_split.h; bit-identical results): 0 = never, 1 = every one, -1 = where wino4_split_pays says so.
+                                               //   Second weight images: -1: layers below 512 GEMM rows (the others take the V route), 1: every F(4x4,3x3) layer
     float* vbuf = nullptr;                     // the pre-transformed input V of the layer being run (conv_wino4v.h)
     size_t vbuf_bytes = 0;
     bool wino4v_fits(int Bn, int r, int nks) const;      // sean_model.cpp

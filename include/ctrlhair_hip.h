@@ -118,6 +118,12 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   256 -> 512 conv read their input pre-transformed (V = B^T d B, written once by an extra bandwidth-bound pass, csrc/conv_wino4v.h)
  *   instead of transforming it again in every row tile; same arithmetic in the same order: bit-identical results.  Costs a workspace
  *   of 9 bytes per input element of the largest such layer (604 MB at max_batch 16, 512 x 512).  0 = transform inside the conv kernel.
+ * "sean.wino4_split" (default -1; before ch_finalize; with "sean.wino" = 2): the plain F(4x4,3x3) convs that transform their input inside
+ *   the kernel (everything the V route of "sean.wino4v" does not take) on wino4_plain_split_kernel (csrc/conv_wino4_split.h): the two waves
+ *   that share a group of tiles split the 36 Winograd positions instead of the 32 GEMM rows, so each does half of the input transform, and
+ *   they exchange partial output transforms once per task; same operations on the same values in the same order: bit-identical results.
+ *   0 = never, 1 = wherever the shape allows, -1 = per layer shape where it measured faster (wino4_split_pays, csrc/conv_wino4.h).  Costs a
+ *   second weight image per such layer: 37 MB at ngf = 64 with -1 (the layers below 512 GEMM rows), 470 MB with 1 (every layer).
  * "sean.overlap" (default 0; before ch_finalize): number of CUs given to CU-masked side streams on which the interior passes and
  *   label-table kernels run beside the convs (with dynamic task claiming in the Winograd kernels).  Bit-identical results; measured
  *   SLOWER than the serial order at every setting on MI355X: kept as an option, not used.

@@ -1,6 +1,9 @@
 // tools/wino4_bench.hip -- stand-alone check + timing of the Winograd F(4x4,3x3) exact-f32 MFMA conv (conv_wino4.h) against a naive
 // direct convolution on the GPU (double accumulation), over the ResBlock conv shapes of the ngf = 64 generator at 512^2, B = 16.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/wino4_bench.hip -o tools/wino4_bench.bin ; run on the GPU box.
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize tools/wino4_bench.hip -o tools/wino4_bench.bin ; run on the GPU box.
+// `wino4_bench.bin split [quick]`: wino4_plain_kernel against wino4_plain_split_kernel (conv_wino4_split.h) on the same shapes -- outputs
+// compared word for word, timings alternated -- per layer and summed over the twelve ResBlock convs of a step.  -DCH_W4_PIN builds both
+// kernels with the input transform pinned into the MFMA groups (wino4_pin, conv_wino4.h: the ablation of DESIGN.md section 7).
 #include "../ctrlhair_amd/csrc/conv_inst_wino4.hip"
 #ifdef W4S_EXPERIMENT      // the shared-transform variant (tools/wino4s_experiment.h): measured, not adopted
 #include "wino4s_experiment.h"
@@ -52,10 +55,11 @@ __global__ void ref_conv_kernel(const float* in, const float* w, const float* bi
     }
 }
 struct Shape { int B, Cin, Cout, H, res; const char* name; };   // res: 0 none, 1 same size, 2 upsampled, 3 = reflection padding + tanh
+static int run_split(const Shape* all, int nshapes, bool quick);
 
 int main(int argc, char** argv) {
-    const bool quick = argc > 1 && !strcmp(argv[1], "quick");
-    const Shape all[] = {
+    const bool quick = argc > 1 && !strcmp(argv[argc - 1], "quick");
+    static const Shape all[] = {
         {2, 16, 16, 32, 0, "tiny"}, {3, 32, 48, 64, 1, "tiny res, ragged rows"}, {1, 24, 32, 32, 2, "tiny res_up"}, {2, 64, 64, 96, 1, "96^2 res"},
         {3, 16, 40, 64, 3, "tiny reflect + tanh"}, {8, 256, 512, 256, 3, "Zencoder 256->512 reflect + tanh"},
         {16, 1024, 1024, 32, 0, "G_middle conv_0"}, {16, 1024, 1024, 32, 1, "G_middle conv_1 (+x)"},
@@ -64,6 +68,7 @@ int main(int argc, char** argv) {
         {16, 256, 128, 256, 0, "up_2 conv_0"}, {16, 128, 128, 256, 1, "up_2 conv_1 (+xs)"},
         {16, 128, 64, 512, 0, "up_3 conv_0"}, {16, 64, 64, 512, 1, "up_3 conv_1 (+xs)"},
     };
+    if (argc > 1 && !strcmp(argv[1], "split")) return run_split(all, (int)(sizeof(all) / sizeof(all[0])), quick);
     double tot_ms = 0, tot_fl = 0, tot_ms_s = 0;
     for (const Shape& c : all) {
         if (quick && c.B * (long long)c.H * c.H * c.Cout > (1 << 22)) continue;
@@ -210,4 +215,87 @@ int main(int argc, char** argv) {
     }
     if (!quick) printf("sum over the ResBlock convs of one step from 32^2 up (G_middle x2): %.2f ms, dense-equivalent %.1f TF/s; shared transform: %.2f ms\n", tot_ms, tot_fl / tot_ms * 1e-9, tot_ms_s);
     return 0;
+}
+
+// wino4_plain_kernel (p.split = 0) against wino4_plain_split_kernel (p.split = 1): same inputs, outputs compared word for word; timed in
+// three alternating rounds of five launches each, the fastest round of each kernel reported
+static int run_split(const Shape* all, int nshapes, bool quick) {
+    double tot_old = 0, tot_new = 0;
+    int bad = 0;
+    for (int si = 0; si < nshapes; ++si) {
+        const Shape& c = all[si];
+        if (quick && c.B * (long long)c.H * c.H * c.Cout > (1 << 22)) continue;
+        const int B = c.B, Cin = c.Cin, Cout = c.Cout, H = c.H, W = c.H;
+        if (!wino4_supported(H, W, Cin)) continue;
+        const size_t nin = (size_t)B * Cin * H * W, nout = (size_t)B * Cout * H * W;
+        const int rh = c.res == 2 ? H / 2 : H;
+        const size_t nres = (c.res == 1 || c.res == 2) ? (size_t)B * Cout * rh * rh : 0;
+        unsigned seed = 12345u + Cin * 7 + Cout;
+        std::vector<float> hin(nin), hw((size_t)Cout * Cin * 9), hb(Cout), hres(nres);
+        const float ws = 1.f / sqrtf((float)Cin * 9.f);
+        for (auto& v : hin) v = frand(seed);
+        for (auto& v : hw) v = frand(seed) * ws;
+        for (auto& v : hb) v = frand(seed) * 0.1f;
+        for (auto& v : hres) v = frand(seed);
+        const float* wp = hw.data();
+        auto getw = [&](int row, int ci, int t) { return wp[((size_t)row * Cin + ci) * 9 + t]; };
+        std::vector<float> pk = pack_wino4_A(Cout, Cin, getw), pks = pack_wino4_A(Cout, Cin, getw, true);
+        float *d_in, *d_b, *d_pk, *d_pks, *d_out[2], *d_res = nullptr;
+        CK(hipMalloc(&d_in, nin * 4 + 256)); CK(hipMalloc(&d_b, Cout * 4));
+        CK(hipMalloc(&d_pk, pk.size() * 4)); CK(hipMalloc(&d_pks, pks.size() * 4));
+        CK(hipMemcpy(d_in, hin.data(), nin * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(d_b, hb.data(), Cout * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(d_pk, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(d_pks, pks.data(), pks.size() * 4, hipMemcpyHostToDevice));
+        if (nres) { CK(hipMalloc(&d_res, nres * 4)); CK(hipMemcpy(d_res, hres.data(), nres * 4, hipMemcpyHostToDevice)); }
+        Wino4Params p[2];
+        for (int k = 0; k < 2; ++k) {
+            CK(hipMalloc(&d_out[k], nout * 4));
+            CK(hipMemset(d_out[k], 0xFF, nout * 4));
+            p[k] = Wino4Params{};
+            p[k].in = d_in; p[k].wpk = d_pk; p[k].wpk_split = d_pks; p[k].split = k; p[k].out = d_out[k];
+            p[k].B = B; p[k].Cin = Cin; p[k].Cout = Cout; p[k].H = H; p[k].W = W;
+            p[k].bias = d_b; p[k].res = d_res; p[k].res_up = c.res == 2 ? 1 : 0;
+            p[k].reflect = c.res == 3; p[k].act = c.res == 3 ? ACT_TANH : ACT_NONE;
+            CK(conv_wino4_plain(p[k], 0));
+        }
+        CK(hipDeviceSynchronize());
+        std::vector<float> h0(nout), h1(nout);
+        CK(hipMemcpy(h0.data(), d_out[0], nout * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(h1.data(), d_out[1], nout * 4, hipMemcpyDeviceToHost));
+        size_t ndiff = 0, nnan = 0;
+        double maxd = 0;
+        for (size_t i = 0; i < nout; ++i) {
+            if (memcmp(&h0[i], &h1[i], 4)) { ++ndiff; const double d = fabs((double)h0[i] - h1[i]); if (!(d <= maxd)) maxd = d; }
+            if (!(h0[i] == h0[i])) ++nnan;
+        }
+        if (ndiff || nnan) ++bad;
+        float best[2] = {0, 0};
+        if (!quick) {
+            hipEvent_t e0, e1;
+            CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+            const int it = 5;
+            for (int round = 0; round < 3; ++round)
+                for (int k = 0; k < 2; ++k) {
+                    CK(hipEventRecord(e0, 0));
+                    for (int i = 0; i < it; ++i) CK(conv_wino4_plain(p[k], 0));
+                    CK(hipEventRecord(e1, 0));
+                    CK(hipEventSynchronize(e1));
+                    float ms = 0;
+                    CK(hipEventElapsedTime(&ms, e0, e1));
+                    ms /= it;
+                    if (round == 0 || ms < best[k]) best[k] = ms;
+                }
+            if (B == 16) { const int mul = strstr(c.name, "G_middle") ? 2 : 1; tot_old += best[0] * mul; tot_new += best[1] * mul; }
+        }
+        const double exec = 2.0 * B * (H / 4) * (W / 4) * (double)Cout * Cin * 36.0;
+        printf("%-32s B%2d %4d->%4d %3d^2  %s (%zu words differ, max %.3e; %zu NaN)  old %7.3f ms %6.1f TF/s   split %7.3f ms %6.1f TF/s   %+5.1f %%\n", c.name, B,
+               Cin, Cout, H, ndiff ? "DIFF " : "BITEQ", ndiff, maxd, nnan, best[0], best[0] > 0 ? exec / best[0] * 1e-9 : 0.0, best[1],
+               best[1] > 0 ? exec / best[1] * 1e-9 : 0.0, best[0] > 0 ? 100.0 * (best[1] - best[0]) / best[0] : 0.0);
+        fflush(stdout);
+        (void)hipFree(d_in); (void)hipFree(d_b); (void)hipFree(d_pk); (void)hipFree(d_pks); (void)hipFree(d_out[0]); (void)hipFree(d_out[1]);
+        if (d_res) (void)hipFree(d_res);
+    }
+    if (!quick) printf("sum over the ResBlock convs of one step from 32^2 up (G_middle x2): old %.2f ms, split %.2f ms\n", tot_old, tot_new);
+    return bad ? 1 : 0;
 }
