@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -188,73 +189,6 @@ size_t ch_sean_noise_floats(const ch_handle* h, int S) {
     return h->sean.noise_floats(S);
 }
 
-int ch_sean_generate(ch_handle* h, const uint8_t* labels, const float* codes, const float* noise, uint64_t seed,
-                     float* out, int B, int S, ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!h->sean_ready) return fail(h, CH_ERR_STATE, "ch_sean_generate: SEAN weights not finalized");
-    if (!labels || !codes || !out) return fail(h, CH_ERR_ARG, "ch_sean_generate: null pointer");
-    DeviceGuard guard(h->device);
-    try {
-        std::string e = h->sean.generate(labels, codes, noise, seed, out, B, S, static_cast<hipStream_t>(stream));
-        if (!e.empty()) return fail(h, CH_ERR_HIP, "ch_sean_generate: " + e);
-    } catch (const std::exception& e) {
-        return fail(h, CH_ERR_HIP, std::string("ch_sean_generate: ") + e.what());
-    }
-    return CH_OK;
-}
-
-int ch_sean_draw_noise(ch_handle* h, uint64_t seed, float* noise, int B, int S, ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!h->sean_ready) return fail(h, CH_ERR_STATE, "ch_sean_draw_noise: SEAN weights not finalized");
-    if (!noise || B < 1) return fail(h, CH_ERR_ARG, "ch_sean_draw_noise: bad argument");
-    DeviceGuard guard(h->device);
-    std::string e = h->sean.draw_noise(seed, noise, B, S, static_cast<hipStream_t>(stream));
-    if (!e.empty()) return fail(h, CH_ERR_HIP, "ch_sean_draw_noise: " + e);
-    return CH_OK;
-}
-
-int ch_sean_encode(ch_handle* h, const float* img, const uint8_t* labels, float* codes, int B, int S,
-                   ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!h->sean_ready) return fail(h, CH_ERR_STATE, "ch_sean_encode: SEAN weights not finalized");
-    if (!img || !labels || !codes || B < 1) return fail(h, CH_ERR_ARG, "ch_sean_encode: bad argument");
-    DeviceGuard guard(h->device);
-    try {
-        std::string e = h->sean.encode(img, labels, codes, B, S, static_cast<hipStream_t>(stream));
-        if (!e.empty()) return fail(h, CH_ERR_HIP, "ch_sean_encode: " + e);
-    } catch (const std::exception& e) {
-        return fail(h, CH_ERR_HIP, std::string("ch_sean_encode: ") + e.what());
-    }
-    return CH_OK;
-}
-
-int ch_sean_encode_features(ch_handle* h, const float* img, int B, int S, ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!h->sean_ready) return fail(h, CH_ERR_STATE, "ch_sean_encode_features: SEAN weights not finalized");
-    if (!img || B < 1) return fail(h, CH_ERR_ARG, "ch_sean_encode_features: bad argument");
-    DeviceGuard guard(h->device);
-    try {
-        std::string e = h->sean.encode(img, nullptr, nullptr, B, S, static_cast<hipStream_t>(stream), 1);
-        if (!e.empty()) return fail(h, CH_ERR_HIP, "ch_sean_encode_features: " + e);
-    } catch (const std::exception& e) {
-        return fail(h, CH_ERR_HIP, std::string("ch_sean_encode_features: ") + e.what());
-    }
-    return CH_OK;
-}
-int ch_sean_encode_regions(ch_handle* h, const uint8_t* labels, float* codes, int B, int S, ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!h->sean_ready) return fail(h, CH_ERR_STATE, "ch_sean_encode_regions: SEAN weights not finalized");
-    if (!labels || !codes || B < 1) return fail(h, CH_ERR_ARG, "ch_sean_encode_regions: bad argument");
-    DeviceGuard guard(h->device);
-    try {
-        std::string e = h->sean.encode(nullptr, labels, codes, B, S, static_cast<hipStream_t>(stream), 2);
-        if (!e.empty()) return fail(h, CH_ERR_HIP, "ch_sean_encode_regions: " + e);
-    } catch (const std::exception& e) {
-        return fail(h, CH_ERR_HIP, std::string("ch_sean_encode_regions: ") + e.what());
-    }
-    return CH_OK;
-}
-
 #define CH_CALL(name, expr)                                                             \
     if (!h) return CH_ERR_ARG;                                                          \
     DeviceGuard guard(h->device);                                                       \
@@ -266,6 +200,36 @@ int ch_sean_encode_regions(ch_handle* h, const uint8_t* labels, float* codes, in
         return fail(h, CH_ERR_HIP, std::string(name) + ": " + ex.what());               \
     }                                                                                   \
     return CH_OK;
+
+// what every ch_sean_* call checks before it runs: CH_OK, or the status to return (with the handle's message set)
+static int sean_precheck(ch_handle* h, const char* name, bool args_ok, const char* what = "bad argument") {
+    if (!h) return CH_ERR_ARG;
+    if (!h->sean_ready) return fail(h, CH_ERR_STATE, std::string(name) + ": SEAN weights not finalized");
+    return args_ok ? CH_OK : fail(h, CH_ERR_ARG, std::string(name) + ": " + what);
+}
+
+int ch_sean_generate(ch_handle* h, const uint8_t* labels, const float* codes, const float* noise, uint64_t seed,
+                     float* out, int B, int S, ch_stream_t stream) {
+    if (int rc = sean_precheck(h, "ch_sean_generate", labels && codes && out, "null pointer")) return rc;
+    CH_CALL("ch_sean_generate", h->sean.generate(labels, codes, noise, seed, out, B, S, static_cast<hipStream_t>(stream)))
+}
+int ch_sean_draw_noise(ch_handle* h, uint64_t seed, float* noise, int B, int S, ch_stream_t stream) {
+    if (int rc = sean_precheck(h, "ch_sean_draw_noise", noise && B >= 1)) return rc;
+    CH_CALL("ch_sean_draw_noise", h->sean.draw_noise(seed, noise, B, S, static_cast<hipStream_t>(stream)))
+}
+int ch_sean_encode(ch_handle* h, const float* img, const uint8_t* labels, float* codes, int B, int S,
+                   ch_stream_t stream) {
+    if (int rc = sean_precheck(h, "ch_sean_encode", img && labels && codes && B >= 1)) return rc;
+    CH_CALL("ch_sean_encode", h->sean.encode(img, labels, codes, B, S, static_cast<hipStream_t>(stream)))
+}
+int ch_sean_encode_features(ch_handle* h, const float* img, int B, int S, ch_stream_t stream) {
+    if (int rc = sean_precheck(h, "ch_sean_encode_features", img && B >= 1)) return rc;
+    CH_CALL("ch_sean_encode_features", h->sean.encode(img, nullptr, nullptr, B, S, static_cast<hipStream_t>(stream), 1))
+}
+int ch_sean_encode_regions(ch_handle* h, const uint8_t* labels, float* codes, int B, int S, ch_stream_t stream) {
+    if (int rc = sean_precheck(h, "ch_sean_encode_regions", labels && codes && B >= 1)) return rc;
+    CH_CALL("ch_sean_encode_regions", h->sean.encode(nullptr, labels, codes, B, S, static_cast<hipStream_t>(stream), 2))
+}
 
 int ch_color_generate(ch_handle* h, const float* noise, const float* cond, float* code, int B, ch_stream_t stream) {
     if (h && (!noise || !cond || !code || B < 1)) return fail(h, CH_ERR_ARG, "ch_color_generate: bad argument");
@@ -606,149 +570,91 @@ int ch_sean_debug_read(ch_handle* h, void* host_out, size_t bytes) {
     return CH_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// ch_set_option: one row per key.  `frozen_by`: the model whose ch_finalize freezes the key (NEVER: live at any time).  The value
+// goes through `map` (BOOL: value != 0; CLAMP: into [lo, hi]; RAW) into `set`; a `guard`, where a key has one, may refuse it first.
+enum OptFreeze { NEVER, BY_SEAN, BY_SHAPE, BY_BISENET };
+enum OptMap { BOOL, CLAMP, RAW };
+struct OptRow {
+    const char* key;
+    OptFreeze frozen_by;
+    OptMap map;
+    int lo, hi;                          // CLAMP only
+    void (*set)(ch_handle*, int);
+    int (*guard)(ch_handle*, int);       // CH_OK, or the status to return
+};
+constexpr int MAXI = 0x7fffffff;
+#define OPT_FIELD(field) [](ch_handle* h, int v) { h->field = v; }, nullptr
+#define SEAN_FIELD(field) OPT_FIELD(sean.opt.field)
+
+int guard_sparse(ch_handle* h, int value) {
+    // after ch_finalize the reduction can be switched OFF (and back on); a handle finalised without it has no classification
+    // buffers, and turning it on would silently do nothing
+    if (h->sean_ready && value != 0 && !h->sean.gtab)
+        return fail(h, CH_ERR_STATE, "ch_set_option(sean.sparse = 1): the handle was finalised with sean.sparse = 0 (no buffers); set it before ch_finalize");
+    return CH_OK;
+}
+int guard_dbg(ch_handle* h, int value) {
+#ifndef CH_ABLATE
+    if (value & CH_ABLATE_DBG_MASK)
+        return fail(h, CH_ERR_ARG, "ch_set_option(sean.dbg): timing-ablation / superseded-kernel bits need a library built with -DCH_ABLATE "
+                                   "(make -C ctrlhair_amd/csrc ABLATE=1)");
+#endif
+    return CH_OK;
+}
+
+const OptRow OPTION_TABLE[] = {
+    // 0 exact f32 | 1 f16x3 split operands (f32-class) | 2 single-term f16 operands | 3 single-term bf16 operands
+    {"sean.f16x3", BY_SEAN, RAW, 0, 0, [](ch_handle* h, int v) { h->sean.opt.use_sh16 = v != 0; h->sean.opt.terms = v == 2 ? 1 : (v == 3 ? 2 : 3); }, nullptr},
+    {"shape.f16x3", BY_SHAPE, BOOL, 0, 0, OPT_FIELD(shape.use_sh16)},
+    {"shape.overlap", BY_SHAPE, BOOL, 0, 0, OPT_FIELD(shape.overlap)},       // 1 = the hair encoder / decoder on a side stream beside the face one (default), 0 = one after the other
+    {"shape.enc_lut", BY_SHAPE, BOOL, 0, 0, OPT_FIELD(shape.enc_l0_lut)},    // exact-f32 shape encoders: 1 = layer 0 as a label table (default), 0 = through the conv kernel
+    {"bisenet.f16x3", BY_BISENET, BOOL, 0, 0, OPT_FIELD(bisenet.use_sh16)},
+    // exact-f32 kernels of the shape VAE / BiSeNet: 3x3 stride-1 convs as Winograd F(2x2,3x3) (default 1)
+    {"aux.wino", NEVER, BOOL, 0, 0, [](ch_handle* h, int v) { h->shape.wino = h->bisenet.wino = v; }, nullptr},
+    // run-ahead mode up to `value` images of 512x512 per chunk (0 = off)
+    {"sean.ahead", BY_SEAN, RAW, 0, 0, [](ch_handle* h, int v) { h->sean.opt.ahead_pixels = (long long)v * 512 * 512; }, nullptr},
+    // exact-f32 path: 3x3 convs as Winograd on the f32 matrix cores (conv_wino.h): 1 = F(2x2,3x3); 2 = + the ResBlock convs as F(4x4,3x3) (default)
+    {"sean.wino", BY_SEAN, CLAMP, 0, 2, SEAN_FIELD(wino)},
+    {"sean.lut_grouped", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(lut_grouped)},      // exact-f32 path: 1 = the style LUTs of a chunk from one grouped GEMM launch (default)
+    {"sean.overlap", BY_SEAN, CLAMP, 0, MAXI, SEAN_FIELD(overlap)},          // CUs of the side streams of the overlap mode (sean_model.h), 0 = off
+    {"sean.wino4_force", NEVER, BOOL, 0, 0, SEAN_FIELD(wino4_force)},        // 1 = F(4x4,3x3) wherever the shape allows, even with fewer tasks than CUs (tests / measurements)
+    {"sean.patch", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(patch)},                  // 1 = pre-gathered hidden-activation patches for levels with few boundary quads (default), 0 = planes only
+    {"sean.convt_gemm", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(convt_gemm)},        // exact-f32 Zencoder: 1 = the ConvTranspose as four phase GEMMs over shifted views (default), 0 = four Winograd phase convs
+    {"sean.edge", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(edge)},                    // 1 = straight-edge pixels from per-code table rows in the interior pass (default), 0 = through the boundary conv
+    {"sean.int_groups", NEVER, CLAMP, 0, MAXI, SEAN_FIELD(int_groups)},      // channel groups per block of the four-pixel interior pass: 0 = chosen per launch (default), n >= 1 = at most n
+    {"sean.batch_invariant", NEVER, BOOL, 0, 0, SEAN_FIELD(batch_inv)},      // exact-f32 path: 1 = kernel choices independent of the batch size of a call (default 0)
+    {"sean.wino4v", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(wino4v)},                // 1 = pre-transformed-input route of the F(4x4,3x3) layers with many GEMM rows (conv_wino4v.h; default), 0 = off
+    // plain F(4x4,3x3) convs on the position-split kernel (conv_wino4_split.h): 0 = never, 1 = wherever supported, < 0 = per shape (default)
+    {"sean.wino4_split", BY_SEAN, CLAMP, -1, 1, SEAN_FIELD(wino4_split)},
+    {"sean.wino4_ace", BY_SEAN, CLAMP, 0, MAXI, SEAN_FIELD(wino4_ace_max_r)},    // largest level (pixels) whose SPADE convs run as F(4x4,3x3) over every tile; 0 = none
+    {"sean.hidden_wq", NEVER, BOOL, 0, 0, SEAN_FIELD(hidden_wq)},            // Winograd ACE path: 1 = hidden activations + one-hot planes from spade_hidden_wq (default)
+    {"sean.wino_gather", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(wino_gather)},      // 1 = gather mode of the Winograd ACE kernel (default), 0 = tile mode
+    {"sean.wino_th", BY_SEAN, RAW, 0, 0, SEAN_FIELD(wino_th)},               // tile height 16 / 32 of the Winograd ACE kernel (0 = chosen per level)
+    // exact SPADE-interior reduction (ace_sparse.h); buffers are sized at ch_finalize
+    {"sean.sparse", NEVER, BOOL, 0, 0, [](ch_handle* h, int v) { h->sean.opt.sparse = v; }, guard_sparse},
+    {"sean.sh16_compact", BY_SEAN, CLAMP, 0, 2, SEAN_FIELD(sh16_compact)},   // f16x3 path: pixel-level compaction (1) or tile skipping only (0); 2: without pair entries (A/B)
+    {"sean.sparse_th", BY_SEAN, RAW, 0, 0, SEAN_FIELD(sparse_th)},           // tile height of the compaction: 8 / 16, 0 = chosen per layer
+    {"sean.sparse_min", BY_SEAN, RAW, 0, 0, SEAN_FIELD(sparse_min_r)},       // smallest ACE resolution served by the sparse path
+    {"sean.dbg_sel", NEVER, RAW, 0, 0, SEAN_FIELD(dbg_sel)},                 // index of the ACE launch that sean.dbg bit 256 cycle-stamps
+    {"sean.dbg", NEVER, RAW, 0, 0, [](ch_handle* h, int v) { h->sean.opt.dbg = v; }, guard_dbg},      // profiling switches (conv_mfma.h)
+};
+#undef SEAN_FIELD
+#undef OPT_FIELD
+}  // namespace
+
+extern "C" {
+
 int ch_set_option(ch_handle* h, const char* key, int value) {
     if (!h || !key) return CH_ERR_ARG;
-    if (std::strcmp(key, "sean.f16x3") == 0) {
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.f16x3) must precede ch_finalize");
-        // 0 exact f32 | 1 f16x3 split operands (f32-class) | 2 single-term f16 operands | 3 single-term bf16 operands
-        h->sean.use_sh16 = value != 0;
-        h->sean.terms = value == 2 ? 1 : (value == 3 ? 2 : 3);
-        return CH_OK;
-    }
-    if (std::strcmp(key, "shape.f16x3") == 0) {
-        if (h->shape.ready) return fail(h, CH_ERR_STATE, "ch_set_option(shape.f16x3) must precede ch_finalize");
-        h->shape.use_sh16 = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "shape.overlap") == 0) {     // 1 = the hair encoder / decoder on a side stream beside the face one (default), 0 = one after the other
-        if (h->shape.ready) return fail(h, CH_ERR_STATE, "ch_set_option(shape.overlap) must precede ch_finalize");
-        h->shape.overlap = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "shape.enc_lut") == 0) {     // exact-f32 shape encoders: 1 = layer 0 as a label table (default), 0 = through the conv kernel
-        if (h->shape.ready) return fail(h, CH_ERR_STATE, "ch_set_option(shape.enc_lut) must precede ch_finalize");
-        h->shape.enc_l0_lut = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "bisenet.f16x3") == 0) {
-        if (h->bisenet.ready) return fail(h, CH_ERR_STATE, "ch_set_option(bisenet.f16x3) must precede ch_finalize");
-        h->bisenet.use_sh16 = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "aux.wino") == 0) {        // exact-f32 kernels of the shape VAE / BiSeNet: 3x3 stride-1 convs as Winograd F(2x2,3x3) (default 1)
-        h->shape.wino = h->bisenet.wino = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.ahead") == 0) {      // run-ahead mode up to `value` images of 512x512 per chunk (0 = off)
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.ahead) must precede ch_finalize");
-        h->sean.ahead_pixels = (long long)value * 512 * 512;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.wino") == 0) {       // exact-f32 path: 3x3 convs as Winograd F(2x2,3x3) on the f32 matrix cores (conv_wino.h)
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino) must precede ch_finalize");
-        h->sean.wino = value < 0 ? 0 : (value > 2 ? 2 : value);      // 1 = F(2x2,3x3); 2 = + the ResBlock convs as F(4x4,3x3) (default)
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.lut_grouped") == 0) {    // exact-f32 path: 1 = the style LUTs of a chunk from one grouped GEMM launch (default)
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.lut_grouped) must precede ch_finalize");
-        h->sean.lut_grouped = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.overlap") == 0) {      // CUs of the side streams of the overlap mode (sean_model.h), 0 = off
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.overlap) must precede ch_finalize");
-        h->sean.overlap = value < 0 ? 0 : value;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.wino4_force") == 0) {  // 1 = F(4x4,3x3) wherever the shape allows, even with fewer tasks than CUs (tests / measurements)
-        h->sean.wino4_force = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.patch") == 0) {        // 1 = pre-gathered hidden-activation patches for levels with few boundary quads (default), 0 = planes only
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.patch) must precede ch_finalize");
-        h->sean.patch = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.convt_gemm") == 0) {   // exact-f32 Zencoder: 1 = the ConvTranspose as four phase GEMMs over shifted views (default), 0 = four Winograd phase convs
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.convt_gemm) must precede ch_finalize");
-        h->sean.convt_gemm = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.edge") == 0) {         // 1 = straight-edge pixels from per-code table rows in the interior pass (default), 0 = through the boundary conv
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.edge) must precede ch_finalize");
-        h->sean.edge = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.int_groups") == 0) {   // channel groups per block of the four-pixel interior pass: 0 = chosen per launch (default), n >= 1 = at most n
-        h->sean.int_groups = value < 0 ? 0 : value;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.batch_invariant") == 0) {      // exact-f32 path: 1 = kernel choices independent of the batch size of a call (default 0)
-        h->sean.batch_inv = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.wino4v") == 0) {       // 1 = pre-transformed-input route of the F(4x4,3x3) layers with many GEMM rows (conv_wino4v.h; default), 0 = off
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino4v) must precede ch_finalize");
-        h->sean.wino4v = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.wino4_split") == 0) {  // plain F(4x4,3x3) convs on the position-split kernel (conv_wino4_split.h): 0 = never, 1 = wherever supported, < 0 = per shape (default)
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino4_split) must precede ch_finalize");
-        h->sean.wino4_split = value < 0 ? -1 : (value != 0);
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.wino4_ace") == 0) {    // largest level (pixels) whose SPADE convs run as F(4x4,3x3) over every tile; 0 = none
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino4_ace) must precede ch_finalize");
-        h->sean.wino4_ace_max_r = value < 0 ? 0 : value;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.hidden_wq") == 0) {    // Winograd ACE path: 1 = hidden activations + one-hot planes from spade_hidden_wq (default)
-        h->sean.hidden_wq = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.wino_gather") == 0) {    // 1 = gather mode of the Winograd ACE kernel (default), 0 = tile mode
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino_gather) must precede ch_finalize");
-        h->sean.wino_gather = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.wino_th") == 0) {    // tile height 16 / 32 of the Winograd ACE kernel (0 = chosen per level)
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.wino_th) must precede ch_finalize");
-        h->sean.wino_th = value;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.sparse") == 0) {     // exact SPADE-interior reduction (ace_sparse.h); buffers are sized at ch_finalize
-        // after ch_finalize the reduction can be switched OFF (and back on); a handle finalised without it has no classification
-        // buffers, and turning it on would silently do nothing
-        if (h->sean_ready && value != 0 && !h->sean.gtab)
-            return fail(h, CH_ERR_STATE, "ch_set_option(sean.sparse = 1): the handle was finalised with sean.sparse = 0 (no buffers); set it before ch_finalize");
-        h->sean.sparse = value != 0;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.sh16_compact") == 0) {   // f16x3 path: pixel-level compaction (1) or tile skipping only (0)
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.sh16_compact) must precede ch_finalize");
-        h->sean.sh16_compact = value < 0 ? 0 : (value > 2 ? 2 : value);    // 2: without pair entries (A/B)
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.sparse_th") == 0) {  // tile height of the compaction: 8 / 16, 0 = chosen per layer
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.sparse_th) must precede ch_finalize");
-        h->sean.sparse_th = value;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.sparse_min") == 0) { // smallest ACE resolution served by the sparse path
-        if (h->sean_ready) return fail(h, CH_ERR_STATE, "ch_set_option(sean.sparse_min) must precede ch_finalize");
-        h->sean.sparse_min_r = value;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.dbg_sel") == 0) {
-        h->sean.dbg_sel = value;
-        return CH_OK;
-    }
-    if (std::strcmp(key, "sean.dbg") == 0) {
-#ifndef CH_ABLATE
-        if (value & CH_ABLATE_DBG_MASK)
-            return fail(h, CH_ERR_ARG, "ch_set_option(sean.dbg): timing-ablation / superseded-kernel bits need a library built with -DCH_ABLATE "
-                                       "(make -C ctrlhair_amd/csrc ABLATE=1)");
-#endif
-        h->sean.dbg = value;
+    for (const OptRow& r : OPTION_TABLE) {
+        if (std::strcmp(key, r.key) != 0) continue;
+        const bool frozen = r.frozen_by == BY_SEAN ? h->sean_ready : r.frozen_by == BY_SHAPE ? h->shape.ready : r.frozen_by == BY_BISENET && h->bisenet.ready;
+        if (frozen) return fail(h, CH_ERR_STATE, std::string("ch_set_option(") + key + ") must precede ch_finalize");
+        if (int rc = r.guard ? r.guard(h, value) : CH_OK) return rc;
+        r.set(h, r.map == BOOL ? value != 0 : (r.map == CLAMP ? std::max(r.lo, std::min(r.hi, value)) : value));
         return CH_OK;
     }
     return fail(h, CH_ERR_ARG, std::string("unknown option '") + key + "'");
@@ -798,16 +704,13 @@ int ch_profile_read_ex(ch_handle* h, int kind, int* launches, double* total_ms, 
         }
     }
     if (flops_executed) *flops_executed = fx;
-    if (kind < 0 || true) {
-        // records are consumed only by a read with kind < 0 (read specific kinds first)
-        if (kind < 0) {
-            for (auto& r : h->sean.prof) {
-                h->sean.ev_pool.push_back(r.e0);
-                h->sean.ev_pool.push_back(r.e1);
-            }
-            h->sean.prof.clear();
-            h->sean.prof_stats_used = 0;
+    if (kind < 0) {      // records are consumed only by a read with kind < 0 (read specific kinds first)
+        for (auto& r : h->sean.prof) {
+            h->sean.ev_pool.push_back(r.e0);
+            h->sean.ev_pool.push_back(r.e1);
         }
+        h->sean.prof.clear();
+        h->sean.prof_stats_used = 0;
     }
     if (launches) *launches = n;
     if (total_ms) *total_ms = ms;

@@ -25,12 +25,6 @@
 
 namespace chk {
 
-namespace {
-
-constexpr int LABEL_NC = 19, STYLE = 512, HID = 128;
-
-}  // namespace
-
 size_t SeanModel::noise_floats(int S) const {
     size_t n = 0;
     for (const auto& b : blocks) {
@@ -40,403 +34,469 @@ size_t SeanModel::noise_floats(int S) const {
     return n;
 }
 
-std::string SeanModel::build(const TensorStore& ts, int mb, int ms) {
-    Builder B(ts, allocs);
-    auto itfc = ts.find("fc.weight");
-    if (itfc == ts.end() || itfc->second.shape.size() != 4) return "missing tensor 'fc.weight'";
-    ngf = (int)itfc->second.shape[0] / 16;
-    if (ngf < 4 || (ngf & 3)) return "unsupported ngf";
-    if (ms % 32 != 0 || ms < 32 || mb < 1) return "max_size must be a multiple of 32 and max_batch >= 1";
-    max_batch = mb;
-    max_size = ms;
+namespace {
 
-    // ---- fc as label table: T[(j*9+t)*K + k] = W[k][j][t] --------------------------------------------------
-    {
-        const int K = 16 * ngf;
-        auto w = B.get("fc.weight", (size_t)K * LABEL_NC * 9);
-        auto b = B.get("fc.bias", K);
-        if (!w || !b) return B.err;
-        std::vector<float> T((size_t)LABEL_NC * 9 * K);
-        for (int k = 0; k < K; ++k)
-            for (int j = 0; j < LABEL_NC; ++j)
-                for (int t = 0; t < 9; ++t) T[((size_t)j * 9 + t) * K + k] = w->f32()[((size_t)k * LABEL_NC + j) * 9 + t];
-        fc_table = B.upload(T);
-        fc_bias = B.upload(std::vector<float>(b->f32(), b->f32() + K));
+constexpr int LABEL_NC = 19, STYLE = 512, HID = 128;
+
+// ---- build(): the stages, in call order ----------------------------------------------------------------------------------
+// spectral norm folded at load (torch eval semantics W / (u . W_mat v)); f16x3 path: per-row power-of-two scaling
+struct SN { const float* w = nullptr; double sigma = 1.0; int cout = 0, cin = 0, ks = 0; };
+auto sn_get(const SN& r) {
+    return [r](int row, int ci, int t) { return r.w[((size_t)row * r.cin + ci) * r.ks * r.ks + t] / (float)r.sigma; };
+}
+
+// host operands of one ACE, handed from part to part of SeanBuild::ace()
+struct AceSrc {
+    int C = 0;
+    const float *bs = nullptr, *wgp = nullptr, *wbp = nullptr;   // mlp_shared bias, mlp_gamma / mlp_beta weights
+    float ag = 0.f, ab = 0.f;                    // weight of the style branch
+    float sg = 1.f, sb = 1.f;                    // ... and of the SPADE branch (1 - ag, 1 - ab)
+    std::vector<float> va, vd, vn, vbg, vbb;     // eval BN + noise scaling as per-channel affine; blended biases
+    std::vector<float> T;                        // mlp_shared as label table
+    std::vector<double> edge_hv, edge_W6;        // straight-edge tables: host operands (contracted after the biases are final)
+};
+
+struct SeanBuild {
+    SeanModel& m;
+    const SeanOptions& opt;
+    Builder B;
+    const int mb, ms;
+    int ace_index = 0;
+    SeanBuild(SeanModel& mm, const TensorStore& ts, int mb_, int ms_) : m(mm), opt(mm.opt), B(ts, mm.allocs), mb(mb_), ms(ms_) {}
+
+    std::string dims() {
+        auto itfc = B.ts.find("fc.weight");
+        if (itfc == B.ts.end() || itfc->second.shape.size() != 4) return "missing tensor 'fc.weight'";
+        m.ngf = (int)itfc->second.shape[0] / 16;
+        if (m.ngf < 4 || (m.ngf & 3)) return "unsupported ngf";
+        if (ms % 32 != 0 || ms < 32 || mb < 1) return "max_size must be a multiple of 32 and max_batch >= 1";
+        m.max_batch = mb;
+        m.max_size = ms;
+        return "";
     }
-    {
+
+    std::string fc_and_img() {
+        const int ngf = m.ngf;
+        // ---- fc as label table: T[(j*9+t)*K + k] = W[k][j][t] --------------------------------------------------
+        {
+            const int K = 16 * ngf;
+            auto w = B.get("fc.weight", (size_t)K * LABEL_NC * 9);
+            auto b = B.get("fc.bias", K);
+            if (!w || !b) return B.err;
+            std::vector<float> T((size_t)LABEL_NC * 9 * K);
+            for (int k = 0; k < K; ++k)
+                for (int j = 0; j < LABEL_NC; ++j)
+                    for (int t = 0; t < 9; ++t) T[((size_t)j * 9 + t) * K + k] = w->f32()[((size_t)k * LABEL_NC + j) * 9 + t];
+            m.fc_table = B.upload(T);
+            m.fc_bias = B.upload(std::vector<float>(b->f32(), b->f32() + K));
+        }
         auto w = B.get("conv_img.weight", (size_t)3 * ngf * 9);
         auto b = B.get("conv_img.bias", 3);
         if (!w || !b) return B.err;
-        img_w = B.upload(std::vector<float>(w->f32(), w->f32() + 3 * ngf * 9));
-        {
-            std::vector<float> w4((size_t)(ngf / 4) * 27 * 4);
-            for (int g = 0; g < ngf / 4; ++g)
-                for (int t = 0; t < 9; ++t)
-                    for (int co = 0; co < 3; ++co)
-                        for (int e = 0; e < 4; ++e)
-                            w4[(((size_t)g * 9 + t) * 3 + co) * 4 + e] = w->f32()[((size_t)co * ngf + g * 4 + e) * 9 + t];
-            img_w4 = B.upload(w4);
-        }
-        img_b = B.upload(std::vector<float>(b->f32(), b->f32() + 3));
+        m.img_w = B.upload(std::vector<float>(w->f32(), w->f32() + 3 * ngf * 9));
+        std::vector<float> w4((size_t)(ngf / 4) * 27 * 4);
+        for (int g = 0; g < ngf / 4; ++g)
+            for (int t = 0; t < 9; ++t)
+                for (int co = 0; co < 3; ++co)
+                    for (int e = 0; e < 4; ++e)
+                        w4[(((size_t)g * 9 + t) * 3 + co) * 4 + e] = w->f32()[((size_t)co * ngf + g * 4 + e) * 9 + t];
+        m.img_w4 = B.upload(w4);
+        m.img_b = B.upload(std::vector<float>(b->f32(), b->f32() + 3));
+        return "";
     }
 
-    struct BS { const char* name; int fin, fout, res_div; bool up, styled; };
-    const BS specs[7] = {{"head_0", 16, 16, 32, false, true}, {"G_middle_0", 16, 16, 16, true, true},
-                         {"G_middle_1", 16, 16, 16, false, true}, {"up_0", 16, 8, 8, true, true},
-                         {"up_1", 8, 4, 4, true, true}, {"up_2", 4, 2, 2, true, true},
-                         {"up_3", 2, 1, 1, true, false}};
-    int ace_index = 0;
-    blocks.clear();
-    for (const auto& s : specs) {
-        BlockW bw;
-        bw.name = s.name;
-        bw.fin = s.fin * ngf;
-        bw.fout = s.fout * ngf;
-        bw.fmid = bw.fin < bw.fout ? bw.fin : bw.fout;
-        bw.res_div = s.res_div;
-        bw.up_before = s.up;
-        bw.styled = s.styled;
-        bw.learned = bw.fin != bw.fout;
-
-        // spectral norm folded at load (torch eval semantics W / (u . W_mat v)); f16x3 path: per-row power-of-two scaling
-        struct SN { const float* w = nullptr; double sigma = 1.0; int cout = 0, cin = 0, ks = 0; };
-        auto sn_read = [&](const std::string& p, int cout, int cin, int ks) {
-            SN r;
-            const size_t kk = (size_t)cin * ks * ks;
-            auto w = B.get(p + ".weight_orig", (size_t)cout * kk);
-            auto u = B.get(p + ".weight_u", cout);
-            auto v = B.get(p + ".weight_v", kk);
-            if (!w || !u || !v) return r;
-            double sigma = 0.0;   // u . (W_mat v)
-            for (int o = 0; o < cout; ++o) {
-                double acc = 0.0;
-                const float* wr = w->f32() + (size_t)o * kk;
-                for (size_t i = 0; i < kk; ++i) acc += (double)wr[i] * v->f32()[i];
-                sigma += acc * u->f32()[o];
-            }
-            r.w = w->f32();
-            r.sigma = sigma;
-            r.cout = cout; r.cin = cin; r.ks = ks;
-            return r;
-        };
-        auto sn_get = [](const SN& r) {
-            return [r](int row, int ci, int t) { return r.w[((size_t)row * r.cin + ci) * r.ks * r.ks + t] / (float)r.sigma; };
-        };
-        auto sn_pack = [&](const SN& r, const std::string& p, bool bias, const std::vector<int>* kexp, ConvW& cw) {
-            if (!r.w) return;
-            auto getw = sn_get(r);
-            if (use_sh16) {
-                cw.wpk = B.upload(pack_A_sh16(r.cout, r.cin, r.ks, getw, *kexp, terms == 2));
-                cw.wscale = B.upload(sh16_wscale(*kexp));
-            } else {
-                cw.wpk = B.upload(pack_A(r.cout, r.cin, r.ks, r.ks == 3 ? CK_KS3 : CK_KS1, getw));
-                if (wino && r.ks == 3 && r.cin % 8 == 0) cw.wino = B.upload(pack_wino_A(r.cout, r.cin, getw));
-                if (wino >= 2 && r.ks == 3 && r.cin % 8 == 0 && r.cin >= 16) {
-                    cw.wino4 = B.upload(pack_wino4_A(r.cout, r.cin, getw));
-                    if (wino4_split > 0 || (wino4_split < 0 && r.cout < 512)) cw.wino4s = B.upload(pack_wino4_A(r.cout, r.cin, getw, true));
-                }
-                if (wino && r.ks == 1 && r.cin % 16 == 0) cw.pw = B.upload(pack_pw_A(r.cout, r.cin, [&](int row, int ci) { return getw(row, ci, 0); }));
-            }
-            cw.Cout = r.cout;
-            cw.Cin = r.cin;
-            cw.KS = r.ks;
-            if (bias) {
-                auto bb = B.get(p + ".bias", r.cout);
-                if (bb) cw.bias = B.upload(std::vector<float>(bb->f32(), bb->f32() + r.cout));
-            }
-        };
-        int fuse_shift = 0;
-        {
-            const SN c0 = sn_read(bw.name + ".conv_0", bw.fmid, bw.fin, 3), c1 = sn_read(bw.name + ".conv_1", bw.fout, bw.fmid, 3);
-            SN cs;
-            if (bw.learned) cs = sn_read(bw.name + ".conv_s", bw.fout, bw.fin, 1);
+    // ---- the seven ResBlocks: convs, then the two or three ACEs ---------------------------------------------------
+    std::string res_blocks() {
+        struct BS { const char* name; int fin, fout, res_div; bool up, styled; };
+        const BS specs[7] = {{"head_0", 16, 16, 32, false, true}, {"G_middle_0", 16, 16, 16, true, true},
+                             {"G_middle_1", 16, 16, 16, false, true}, {"up_0", 16, 8, 8, true, true},
+                             {"up_1", 8, 4, 4, true, true}, {"up_2", 4, 2, 2, true, true},
+                             {"up_3", 2, 1, 1, true, false}};
+        m.blocks.clear();
+        for (const auto& s : specs) {
+            BlockW bw;
+            bw.name = s.name;
+            bw.fin = s.fin * m.ngf;
+            bw.fout = s.fout * m.ngf;
+            bw.fmid = bw.fin < bw.fout ? bw.fin : bw.fout;
+            bw.res_div = s.res_div;
+            bw.up_before = s.up;
+            bw.styled = s.styled;
+            bw.learned = bw.fin != bw.fout;
+            const int fuse_shift = block_convs(bw);
             if (!B.err.empty()) return B.err;
-            std::vector<int> k0, k1, ks_;
-            if (use_sh16) {
-                k0 = sh16_row_exponents(c0.cout, c0.cin, 3, sn_get(c0));
-                k1 = sh16_row_exponents(c1.cout, c1.cin, 3, sn_get(c1));
-                if (bw.learned) {
-                    // conv_s is folded into conv_1 as extra K chunks on the same accumulators: row by row the two operands
-                    // must share 2^k * s_in.  conv_1's rows keep their own exponents; conv_s's rows take k1[row] - D with
-                    // D = max over rows of (k1 - ks) (no row overflows, rows of similar relative size lose nothing), and the
-                    // 2^D is carried by the first-pass scale of the shortcut activations (ace_s writes hs * 8 * 2^D).
-                    ks_ = sh16_row_exponents(cs.cout, cs.cin, 1, sn_get(cs));
-                    int D = k1[0] - ks_[0];
-                    for (int r = 0; r < c1.cout; ++r) D = std::max(D, k1[r] - ks_[r]);
-                    D = std::max(-24, std::min(24, D));
-                    for (int r = 0; r < c1.cout; ++r) {       // exactly ks = k1 - D, neither above its own optimum
-                        ks_[r] = std::min(ks_[r], k1[r] - D);
-                        k1[r] = ks_[r] + D;
-                    }
-                    fuse_shift = D;
-                }
-            }
-            sn_pack(c0, bw.name + ".conv_0", true, &k0, bw.conv_0);
-            sn_pack(c1, bw.name + ".conv_1", true, &k1, bw.conv_1);
-            if (bw.learned) sn_pack(cs, bw.name + ".conv_s", false, &ks_, bw.conv_s);
+            if (bw.learned) ace(bw.name + ".ace_s", bw.fin, bw, bw.ace_s, std::ldexp(SH16_ACT_SCALE, fuse_shift));
+            ace(bw.name + ".ace_0", bw.fin, bw, bw.ace_0);
+            ace(bw.name + ".ace_1", bw.fmid, bw, bw.ace_1);
+            if (!B.err.empty()) return B.err;
+            m.blocks.push_back(bw);
         }
-        if (!B.err.empty()) return B.err;
+        m.n_aces = ace_index;
+        return "";
+    }
 
-        auto ace = [&](const std::string& p, int C, AceW& a, float out_scale = SH16_ACT_SCALE) {
-            a.out_scale = out_scale;
-            a.name = p;
-            a.C = C;
-            a.res_div = s.res_div;
-            a.styled = s.styled;
-            a.index = ace_index++;
-            auto nvar = B.get(p + ".noise_var", C);
-            auto rm = B.get(p + ".param_free_norm.running_mean", C);
-            auto rv = B.get(p + ".param_free_norm.running_var", C);
-            auto ws = B.get(p + ".Spade.mlp_shared.0.weight", (size_t)HID * LABEL_NC * 9);
-            auto bs = B.get(p + ".Spade.mlp_shared.0.bias", HID);
-            auto wg = B.get(p + ".Spade.mlp_gamma.weight", (size_t)C * HID * 9);
-            auto bg = B.get(p + ".Spade.mlp_gamma.bias", C);
-            auto wb = B.get(p + ".Spade.mlp_beta.weight", (size_t)C * HID * 9);
-            auto bb = B.get(p + ".Spade.mlp_beta.bias", C);
-            auto blg = B.get(p + ".blending_gamma", 1);
-            auto blb = B.get(p + ".blending_beta", 1);
-            if (!nvar || !rm || !rv || !ws || !bs || !wg || !bg || !wb || !bb || !blg || !blb) return;
-            float ag = 0.f, ab = 0.f;   // weight of the style branch
-            if (a.styled) {
-                ag = 1.f / (1.f + std::exp(-blg->f32()[0]));
-                ab = 1.f / (1.f + std::exp(-blb->f32()[0]));
+    SN sn_read(const std::string& p, int cout, int cin, int ks) {
+        SN r;
+        const size_t kk = (size_t)cin * ks * ks;
+        auto w = B.get(p + ".weight_orig", (size_t)cout * kk);
+        auto u = B.get(p + ".weight_u", cout);
+        auto v = B.get(p + ".weight_v", kk);
+        if (!w || !u || !v) return r;
+        double sigma = 0.0;   // u . (W_mat v)
+        for (int o = 0; o < cout; ++o) {
+            double acc = 0.0;
+            const float* wr = w->f32() + (size_t)o * kk;
+            for (size_t i = 0; i < kk; ++i) acc += (double)wr[i] * v->f32()[i];
+            sigma += acc * u->f32()[o];
+        }
+        r.w = w->f32();
+        r.sigma = sigma;
+        r.cout = cout; r.cin = cin; r.ks = ks;
+        return r;
+    }
+    void sn_pack(const SN& r, const std::string& p, bool bias, const std::vector<int>* kexp, ConvW& cw) {
+        if (!r.w) return;
+        auto getw = sn_get(r);
+        if (opt.use_sh16) {
+            cw.wpk = B.upload(pack_A_sh16(r.cout, r.cin, r.ks, getw, *kexp, opt.terms == 2));
+            cw.wscale = B.upload(sh16_wscale(*kexp));
+        } else {
+            cw.wpk = B.upload(pack_A(r.cout, r.cin, r.ks, r.ks == 3 ? CK_KS3 : CK_KS1, getw));
+            if (opt.wino && r.ks == 3 && r.cin % 8 == 0) cw.wino = B.upload(pack_wino_A(r.cout, r.cin, getw));
+            if (opt.wino >= 2 && r.ks == 3 && r.cin % 8 == 0 && r.cin >= 16) {
+                cw.wino4 = B.upload(pack_wino4_A(r.cout, r.cin, getw));
+                if (opt.wino4_split > 0 || (opt.wino4_split < 0 && r.cout < 512)) cw.wino4s = B.upload(pack_wino4_A(r.cout, r.cin, getw, true));
             }
-            // eval BN (eps 1e-5) + noise scaling as per-channel affine
-            std::vector<float> va(C), vd(C), vn(C), vbg(C), vbb(C);
+            if (opt.wino && r.ks == 1 && r.cin % 16 == 0) cw.pw = B.upload(pack_pw_A(r.cout, r.cin, [&](int row, int ci) { return getw(row, ci, 0); }));
+        }
+        cw.Cout = r.cout;
+        cw.Cin = r.cin;
+        cw.KS = r.ks;
+        if (bias) {
+            auto bb = B.get(p + ".bias", r.cout);
+            if (bb) cw.bias = B.upload(std::vector<float>(bb->f32(), bb->f32() + r.cout));
+        }
+    }
+    // conv_0 / conv_1 / conv_s of one block; returns the exponent D that aligns conv_s with conv_1 (f16x3 path, else 0). Errors: B.err
+    int block_convs(BlockW& bw) {
+        int fuse_shift = 0;
+        const SN c0 = sn_read(bw.name + ".conv_0", bw.fmid, bw.fin, 3), c1 = sn_read(bw.name + ".conv_1", bw.fout, bw.fmid, 3);
+        SN cs;
+        if (bw.learned) cs = sn_read(bw.name + ".conv_s", bw.fout, bw.fin, 1);
+        if (!B.err.empty()) return 0;
+        std::vector<int> k0, k1, ks_;
+        if (opt.use_sh16) {
+            k0 = sh16_row_exponents(c0.cout, c0.cin, 3, sn_get(c0));
+            k1 = sh16_row_exponents(c1.cout, c1.cin, 3, sn_get(c1));
+            if (bw.learned) {
+                // conv_s is folded into conv_1 as extra K chunks on the same accumulators: row by row the two operands
+                // must share 2^k * s_in.  conv_1's rows keep their own exponents; conv_s's rows take k1[row] - D with
+                // D = max over rows of (k1 - ks) (no row overflows, rows of similar relative size lose nothing), and the
+                // 2^D is carried by the first-pass scale of the shortcut activations (ace_s writes hs * 8 * 2^D).
+                ks_ = sh16_row_exponents(cs.cout, cs.cin, 1, sn_get(cs));
+                int D = k1[0] - ks_[0];
+                for (int r = 0; r < c1.cout; ++r) D = std::max(D, k1[r] - ks_[r]);
+                D = std::max(-24, std::min(24, D));
+                for (int r = 0; r < c1.cout; ++r) {       // exactly ks = k1 - D, neither above its own optimum
+                    ks_[r] = std::min(ks_[r], k1[r] - D);
+                    k1[r] = ks_[r] + D;
+                }
+                fuse_shift = D;
+            }
+        }
+        sn_pack(c0, bw.name + ".conv_0", true, &k0, bw.conv_0);
+        sn_pack(c1, bw.name + ".conv_1", true, &k1, bw.conv_1);
+        if (bw.learned) sn_pack(cs, bw.name + ".conv_s", false, &ks_, bw.conv_s);
+        return fuse_shift;
+    }
+
+    // ---- one ACE's weights, in four parts.  Errors: B.err ----------------------------------------------------------
+    void ace(const std::string& p, int C, const BlockW& bw, AceW& a, float out_scale = SH16_ACT_SCALE) {
+        a.out_scale = out_scale;
+        a.name = p;
+        a.C = C;
+        a.res_div = bw.res_div;
+        a.styled = bw.styled;
+        a.index = ace_index++;
+        AceSrc s;
+        s.C = C;
+        if (!ace_norm_and_table(p, a, s)) return;
+        ace_region_tables(a, s);
+        ace_spade_rows(a, s);
+        if (a.styled && !ace_style(p, a, s)) return;
+        if (!s.edge_hv.empty()) ace_edge_rows(p, a, s);
+        // (last: the style branch adds its biases to vbg / vbb)
+        a.bn_a = B.upload(s.va);
+        a.bn_d = B.upload(s.vd);
+        a.nv = B.upload(s.vn);
+        a.bias_g = B.upload(s.vbg);
+        a.bias_b = B.upload(s.vbb);
+    }
+
+    // part 1: norm / noise vectors, SPADE blend factors and weight pointers, mlp_shared as label table
+    bool ace_norm_and_table(const std::string& p, AceW& a, AceSrc& s) {
+        const int C = s.C;
+        auto nvar = B.get(p + ".noise_var", C);
+        auto rm = B.get(p + ".param_free_norm.running_mean", C);
+        auto rv = B.get(p + ".param_free_norm.running_var", C);
+        auto ws = B.get(p + ".Spade.mlp_shared.0.weight", (size_t)HID * LABEL_NC * 9);
+        auto bs = B.get(p + ".Spade.mlp_shared.0.bias", HID);
+        auto wg = B.get(p + ".Spade.mlp_gamma.weight", (size_t)C * HID * 9);
+        auto bg = B.get(p + ".Spade.mlp_gamma.bias", C);
+        auto wb = B.get(p + ".Spade.mlp_beta.weight", (size_t)C * HID * 9);
+        auto bb = B.get(p + ".Spade.mlp_beta.bias", C);
+        auto blg = B.get(p + ".blending_gamma", 1);
+        auto blb = B.get(p + ".blending_beta", 1);
+        if (!nvar || !rm || !rv || !ws || !bs || !wg || !bg || !wb || !bb || !blg || !blb) return false;
+        if (a.styled) {
+            s.ag = 1.f / (1.f + std::exp(-blg->f32()[0]));
+            s.ab = 1.f / (1.f + std::exp(-blb->f32()[0]));
+        }
+        const float ag = s.ag, ab = s.ab;
+        s.sg = 1.f - ag;
+        s.sb = 1.f - ab;
+        s.bs = bs->f32();
+        s.wgp = wg->f32();
+        s.wbp = wb->f32();
+        // eval BN (eps 1e-5) + noise scaling as per-channel affine
+        s.va.resize(C); s.vd.resize(C); s.vn.resize(C); s.vbg.resize(C); s.vbb.resize(C);
+        for (int c = 0; c < C; ++c) {
+            const float rstd = 1.f / std::sqrt(rv->f32()[c] + 1e-5f);
+            s.va[c] = rstd;
+            s.vd[c] = -rm->f32()[c] * rstd;
+            s.vn[c] = nvar->f32()[c] * rstd;
+            s.vbg[c] = (1.f - ag) * bg->f32()[c];
+            s.vbb[c] = (1.f - ab) * bb->f32()[c];
+        }
+        // mlp_shared as label table
+        std::vector<float>& T = s.T;
+        T.resize((size_t)LABEL_NC * 9 * HID);
+        for (int k = 0; k < HID; ++k)
+            for (int j = 0; j < LABEL_NC; ++j)
+                for (int t = 0; t < 9; ++t)
+                    T[((size_t)j * 9 + t) * HID + k] = ws->f32()[((size_t)k * LABEL_NC + j) * 9 + t];
+        a.actv_table = B.upload(T);
+        a.actv_bias = B.upload(std::vector<float>(bs->f32(), bs->f32() + HID));
+        // relu(bias + sum of one table entry per tap) <= bias + sum_t max(0, max_j T[j][t][k]): a bound that holds for
+        // every label map, so the SH16 scale of the hidden activations can never saturate
+        float bound = 0.f;
+        for (int k = 0; k < HID; ++k) {
+            float v = bs->f32()[k];
+            for (int t = 0; t < 9; ++t) {
+                float mx = 0.f;
+                for (int j = 0; j < LABEL_NC; ++j) mx = std::max(mx, T[((size_t)j * 9 + t) * HID + k]);
+                v += mx;
+            }
+            bound = std::max(bound, v);
+        }
+        a.actv_scale = sh16_scale_for_bound(bound);
+        return true;
+    }
+
+    // part 2: per-label constants of the SPADE gamma/beta for pixels with a uniform 5x5 label neighbourhood (ace_sparse.h):
+    // every tap sees a_j = relu(b_shared + sum_t' W_shared[:, j, t']), so gamma_j = (sum_t W[:, :, t]) a_j.  Double.
+    // Then the host operands of the straight-edge table (contracted on the device by ace_edge_rows).
+    void ace_region_tables(AceW& a, AceSrc& s) {
+        const int C = s.C;
+        const std::vector<float>& T = s.T;
+        const float *bs = s.bs, *wgp = s.wgp, *wbp = s.wbp;
+        std::vector<double> aj((size_t)LABEL_NC * HID);
+        for (int j = 0; j < LABEL_NC; ++j)
+            for (int k = 0; k < HID; ++k) {
+                double v = bs[k];
+                for (int t = 0; t < 9; ++t) v += T[((size_t)j * 9 + t) * HID + k];
+                aj[(size_t)j * HID + k] = v > 0.0 ? v : 0.0;
+            }
+        std::vector<float> gc((size_t)LABEL_NC * 2 * C);
+        std::vector<double> wsum(HID);
+        for (int gb = 0; gb < 2; ++gb)
             for (int c = 0; c < C; ++c) {
-                const float rstd = 1.f / std::sqrt(rv->f32()[c] + 1e-5f);
-                va[c] = rstd;
-                vd[c] = -rm->f32()[c] * rstd;
-                vn[c] = nvar->f32()[c] * rstd;
-                vbg[c] = (1.f - ag) * bg->f32()[c];
-                vbb[c] = (1.f - ab) * bb->f32()[c];
-            }
-            // mlp_shared as label table
-            std::vector<float> T((size_t)LABEL_NC * 9 * HID);
-            for (int k = 0; k < HID; ++k)
-                for (int j = 0; j < LABEL_NC; ++j)
-                    for (int t = 0; t < 9; ++t)
-                        T[((size_t)j * 9 + t) * HID + k] = ws->f32()[((size_t)k * LABEL_NC + j) * 9 + t];
-            a.actv_table = B.upload(T);
-            a.actv_bias = B.upload(std::vector<float>(bs->f32(), bs->f32() + HID));
-            {   // relu(bias + sum of one table entry per tap) <= bias + sum_t max(0, max_j T[j][t][k]): a bound that holds for
-                // every label map, so the SH16 scale of the hidden activations can never saturate
-                float bound = 0.f;
+                const float* w = (gb ? wbp : wgp) + (size_t)c * HID * 9;
                 for (int k = 0; k < HID; ++k) {
-                    float v = bs->f32()[k];
-                    for (int t = 0; t < 9; ++t) {
-                        float mx = 0.f;
-                        for (int j = 0; j < LABEL_NC; ++j) mx = std::max(mx, T[((size_t)j * 9 + t) * HID + k]);
-                        v += mx;
-                    }
-                    bound = std::max(bound, v);
+                    double acc = 0.0;
+                    for (int t = 0; t < 9; ++t) acc += w[k * 9 + t];
+                    wsum[k] = acc;
                 }
-                a.actv_scale = sh16_scale_for_bound(bound);
-            }
-            // SPADE gamma/beta rows: 64-row tiles = (gamma of 32 channels | beta of the same 32 channels)
-            const int tiles = (C + 31) / 32;
-            const float* wgp = wg->f32();
-            const float* wbp = wb->f32();
-            const float sg = 1.f - ag, sb = 1.f - ab;
-            auto getsp = [&](int row, int ci, int t) {
-                const int c = (row / 64) * 32 + (row & 31);
-                if (c >= C) return 0.f;
-                const bool beta = (row & 32) != 0;
-                const float w = (beta ? wbp : wgp)[((size_t)c * HID + ci) * 9 + t];
-                return w * (beta ? sb : sg);
-            };
-            std::vector<double> edge_hv, edge_W6;      // straight-edge tables: host operands (filled below, contracted after the biases are final)
-            {   // per-label constants of the SPADE gamma/beta for pixels with a uniform 5x5 label neighbourhood (ace_sparse.h):
-                // every tap sees a_j = relu(b_shared + sum_t' W_shared[:, j, t']), so gamma_j = (sum_t W[:, :, t]) a_j.  Double.
-                std::vector<double> aj((size_t)LABEL_NC * HID);
-                for (int j = 0; j < LABEL_NC; ++j)
-                    for (int k = 0; k < HID; ++k) {
-                        double v = bs->f32()[k];
-                        for (int t = 0; t < 9; ++t) v += T[((size_t)j * 9 + t) * HID + k];
-                        aj[(size_t)j * HID + k] = v > 0.0 ? v : 0.0;
-                    }
-                std::vector<float> gc((size_t)LABEL_NC * 2 * C);
-                std::vector<double> wsum(HID);
-                for (int gb = 0; gb < 2; ++gb)
-                    for (int c = 0; c < C; ++c) {
-                        const float* w = (gb ? wbp : wgp) + (size_t)c * HID * 9;
-                        for (int k = 0; k < HID; ++k) {
-                            double acc = 0.0;
-                            for (int t = 0; t < 9; ++t) acc += w[k * 9 + t];
-                            wsum[k] = acc;
-                        }
-                        for (int j = 0; j < LABEL_NC; ++j) {
-                            double acc = 0.0;
-                            for (int k = 0; k < HID; ++k) acc += wsum[k] * aj[(size_t)j * HID + k];
-                            gc[((size_t)j * 2 + gb) * C + c] = (float)(acc * (gb ? sb : sg));
-                        }
-                    }
-                a.gconst = B.upload(gc);
-                // straight-edge pixels (ace_sparse.h, option sean.edge): the per-code rows E[2888][gamma|beta][C] of the ACEs that can run at
-                // 128 pixels and more (res_div <= 4), from the hidden vectors of the windows AAB / ABB (double, host) and the column / row sums
-                // of the gamma / beta weights, contracted on the device in double (ace_edge_table).  vbg / vbb (blended biases) are added.
-                a.edge_tab = nullptr;
-                if (edge && (use_sh16 ? sparse : wino) && s.res_div <= 4) {
-                    edge_hv.assign((size_t)2 * 741 * HID, 0.0);
-                    edge_W6.assign((size_t)2 * HID * 6 * C, 0.0);
-                    std::vector<double>&hv = edge_hv, &W6 = edge_W6;
-                    for (int o = 0; o < 2; ++o) {
-                        auto line = [&](int j, int u, int k) {       // shared conv's taps of label j summed across the split: column u (o = 0) / row u (o = 1)
-                            double v = 0.0;
-                            for (int w = 0; w < 3; ++w) v += T[((size_t)j * 9 + (o == 0 ? w * 3 + u : u * 3 + w)) * HID + k];
-                            return v;
-                        };
-                        for (int j = 0; j < LABEL_NC; ++j)
-                            for (int k = 0; k < HID; ++k) hv[((size_t)o * 741 + j) * HID + k] = aj[(size_t)j * HID + k];
-                        for (int A = 0; A < LABEL_NC; ++A)
-                            for (int Bl = 0; Bl < LABEL_NC; ++Bl) {
-                                if (A == Bl) continue;
-                                for (int k = 0; k < HID; ++k) {
-                                    const double aab = bs->f32()[k] + line(A, 0, k) + line(A, 1, k) + line(Bl, 2, k);
-                                    const double abb = bs->f32()[k] + line(A, 0, k) + line(Bl, 1, k) + line(Bl, 2, k);
-                                    hv[((size_t)o * 741 + 19 + (A * 19 + Bl) * 2 + 0) * HID + k] = aab > 0.0 ? aab : 0.0;
-                                    hv[((size_t)o * 741 + 19 + (A * 19 + Bl) * 2 + 1) * HID + k] = abb > 0.0 ? abb : 0.0;
-                                }
-                            }
-                    }
-                    for (int gb = 0; gb < 2; ++gb)
-                        for (int c = 0; c < C; ++c) {
-                            const float* w = (gb ? wbp : wgp) + (size_t)c * HID * 9;
-                            for (int k = 0; k < HID; ++k)
-                                for (int d = 0; d < 3; ++d) {
-                                    double col = 0.0, row = 0.0;
-                                    for (int u = 0; u < 3; ++u) {
-                                        col += w[k * 9 + u * 3 + d];      // taps (dy = u - 1, dx = d - 1)
-                                        row += w[k * 9 + d * 3 + u];      // taps (dy = d - 1, dx = u - 1)
-                                    }
-                                    W6[(((size_t)gb * HID + k) * 6 + d) * C + c] = col;
-                                    W6[(((size_t)gb * HID + k) * 6 + 3 + d) * C + c] = row;
-                                }
-                        }
-                }
-            }
-            if (use_sh16) {
-                auto kexp = sh16_row_exponents(tiles * 64, HID, 3, getsp);
-                for (int t0 = 0; t0 < tiles * 64; t0 += 64) {     // one power of two per 64-row wave tile (a scalar in the ACE epilogue)
-                    int km = kexp[t0];
-                    for (int r = 0; r < 64; ++r) km = std::min(km, kexp[t0 + r]);
-                    for (int r = 0; r < 64; ++r) kexp[t0 + r] = km;
-                }
-                a.spade_wpk = B.upload(pack_A_sh16(tiles * 64, HID, 3, getsp, kexp, terms == 2));
-                a.spade_wscale = B.upload(sh16_wscale(kexp));
-            } else {
-                a.spade_wpk = B.upload(pack_A(tiles * 64, HID, 3, CK_KS3, getsp));
-                if (wino) {      // Winograd path: row tiles of 16 channels, rows 0-15 = gamma, 16-31 = beta (conv_wino.h)
-                    auto getw = [&](int row, int ci, int t) {
-                        const int c = (row / 32) * 16 + (row & 15);
-                        if (c >= C) return 0.f;
-                        const bool beta = (row & 16) != 0;
-                        return (beta ? wbp : wgp)[((size_t)c * HID + ci) * 9 + t] * (beta ? sb : sg);
-                    };
-                    a.spade_wino = B.upload(pack_wino_A(((C + 15) / 16) * 32, HID, getw));
-                    if (wino >= 2 && wino4_ace_max_r >= 32 && C % 2 == 0) {      // (any level can fall to <= wino4_ace_max_r pixels at a smaller image size)
-                        // F(4x4,3x3) image for the low-resolution levels: rows interleaved so that a lane holds gamma and beta of two channels
-                        auto getw4 = [&](int row, int ci, int t) {
-                            int c, beta;
-                            wino4_ace_row(row, c, beta);
-                            if (c >= C) return 0.f;
-                            return (beta ? wbp : wgp)[((size_t)c * HID + ci) * 9 + t] * (beta ? sb : sg);
-                        };
-                        a.spade_wino4 = B.upload(pack_wino4_A(((C + 15) / 16) * 32, HID, getw4));
-                    }
-                }
-            }
-            if (a.styled) {
-                auto cg = B.get(p + ".conv_gamma.weight", (size_t)C * STYLE * 9);
-                auto cgb = B.get(p + ".conv_gamma.bias", C);
-                auto cb = B.get(p + ".conv_beta.weight", (size_t)C * STYLE * 9);
-                auto cbb = B.get(p + ".conv_beta.bias", C);
-                if (!cg || !cgb || !cb || !cbb) return;
-                for (int c = 0; c < C; ++c) {
-                    vbg[c] += ag * cgb->f32()[c];
-                    vbb[c] += ab * cbb->f32()[c];
-                }
-                std::vector<float> fw((size_t)LABEL_NC * STYLE * STYLE), fb((size_t)LABEL_NC * STYLE);
                 for (int j = 0; j < LABEL_NC; ++j) {
-                    auto w = B.get(p + ".fc_mu" + std::to_string(j) + ".weight", (size_t)STYLE * STYLE);
-                    auto b = B.get(p + ".fc_mu" + std::to_string(j) + ".bias", STYLE);
-                    if (!w || !b) return;
-                    std::memcpy(&fw[(size_t)j * STYLE * STYLE], w->f32(), sizeof(float) * STYLE * STYLE);
-                    std::memcpy(&fb[(size_t)j * STYLE], b->f32(), sizeof(float) * STYLE);
-                }
-                a.fcmu_w = B.upload(fw);
-                a.fcmu_b = B.upload(fb);
-                // LUT GEMM rows (t, gamma|beta, c) <- alpha * W[c][k][t]
-                const float* cgp = cg->f32();
-                const float* cbp = cb->f32();
-                auto getl = [&](int row, int k, int) {
-                    const int t = row / (2 * C), gb = (row / C) & 1, c = row % C;
-                    return gb ? ab * cbp[((size_t)c * STYLE + k) * 9 + t] : ag * cgp[((size_t)c * STYLE + k) * 9 + t];
-                };
-                if (use_sh16) {
-                    const auto kexp = sh16_row_exponents(18 * C, STYLE, 1, getl);
-                    a.lut_wpk = B.upload(pack_A_sh16(18 * C, STYLE, 1, getl, kexp, terms == 2));
-                    a.lut_wscale = B.upload(sh16_wscale(kexp));
-                } else {
-                    a.lut_wpk = B.upload(pack_A(18 * C, STYLE, 1, CK_KS1, getl));
-                    if (max_batch * LABEL_NC > 64) {      // grouped LUT build (conv_pw.h): [k][row] image
-                        std::vector<float> wt((size_t)STYLE * 18 * C);
-                        for (int row = 0; row < 18 * C; ++row)
-                            for (int k = 0; k < STYLE; ++k) wt[(size_t)k * 18 * C + row] = getl(row, k, 0);
-                        a.lut_wt = B.upload(wt);
-                    }
-                }
-                if (max_batch * (LABEL_NC + 1) <= 64) {   // small batches (interactive use): the LUT build is a weight-streaming GEMV
-                    std::vector<float> rows((size_t)18 * C * STYLE);
-                    for (int row = 0; row < 18 * C; ++row) {
-                        const int t = row / (2 * C), gb = (row / C) & 1, cc = row % C;
-                        const float* src = gb ? cbp : cgp;
-                        const float al = gb ? ab : ag;
-                        // f16x3 path: the ACE epilogue expects the style LUT pre-multiplied by the output scale (conv_sh16.h)
-                        const float als = use_sh16 ? al * a.out_scale : al;
-                        for (int k = 0; k < STYLE; ++k) rows[(size_t)row * STYLE + k] = als * src[((size_t)cc * STYLE + k) * 9 + t];
-                    }
-                    a.lut_rows = B.upload(rows);
+                    double acc = 0.0;
+                    for (int k = 0; k < HID; ++k) acc += wsum[k] * aj[(size_t)j * HID + k];
+                    gc[((size_t)j * 2 + gb) * C + c] = (float)(acc * (gb ? s.sb : s.sg));
                 }
             }
-            if (!edge_hv.empty()) {      // (after the style branch's biases went into vbg / vbb: the table rows are complete gamma / beta)
-                const std::vector<double>&hv = edge_hv, &W6 = edge_W6;
-                double *dW = nullptr, *dH = nullptr;
-                float *dbg_ = B.upload(vbg), *dbb_ = B.upload(vbb);
-                a.edge_tab = B.falloc((size_t)ACE_EDGE_CODES * 2 * C);
-                if (B.err.empty() && hipMalloc(&dW, W6.size() * 8) == hipSuccess && hipMalloc(&dH, hv.size() * 8) == hipSuccess &&
-                    hipMemcpy(dW, W6.data(), W6.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(dH, hv.data(), hv.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
-                    ace_edge_table(dW, dH, dbg_, dbb_, sg, sb, a.edge_tab, C, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
-                } else if (B.err.empty()) {
-                    B.err = "edge table of " + p + " failed";
+        a.gconst = B.upload(gc);
+        // straight-edge pixels (ace_sparse.h, option sean.edge): the per-code rows E[2888][gamma|beta][C] of the ACEs that can run at
+        // 128 pixels and more (res_div <= 4), from the hidden vectors of the windows AAB / ABB (double, host) and the column / row sums
+        // of the gamma / beta weights, contracted on the device in double (ace_edge_table).  vbg / vbb (blended biases) are added.
+        a.edge_tab = nullptr;
+        if (!(opt.edge && (opt.use_sh16 ? opt.sparse : opt.wino) && a.res_div <= 4)) return;
+        s.edge_hv.assign((size_t)2 * 741 * HID, 0.0);
+        s.edge_W6.assign((size_t)2 * HID * 6 * C, 0.0);
+        std::vector<double>&hv = s.edge_hv, &W6 = s.edge_W6;
+        for (int o = 0; o < 2; ++o) {
+            auto line = [&](int j, int u, int k) {       // shared conv's taps of label j summed across the split: column u (o = 0) / row u (o = 1)
+                double v = 0.0;
+                for (int w = 0; w < 3; ++w) v += T[((size_t)j * 9 + (o == 0 ? w * 3 + u : u * 3 + w)) * HID + k];
+                return v;
+            };
+            for (int j = 0; j < LABEL_NC; ++j)
+                for (int k = 0; k < HID; ++k) hv[((size_t)o * 741 + j) * HID + k] = aj[(size_t)j * HID + k];
+            for (int A = 0; A < LABEL_NC; ++A)
+                for (int Bl = 0; Bl < LABEL_NC; ++Bl) {
+                    if (A == Bl) continue;
+                    for (int k = 0; k < HID; ++k) {
+                        const double aab = bs[k] + line(A, 0, k) + line(A, 1, k) + line(Bl, 2, k);
+                        const double abb = bs[k] + line(A, 0, k) + line(Bl, 1, k) + line(Bl, 2, k);
+                        hv[((size_t)o * 741 + 19 + (A * 19 + Bl) * 2 + 0) * HID + k] = aab > 0.0 ? aab : 0.0;
+                        hv[((size_t)o * 741 + 19 + (A * 19 + Bl) * 2 + 1) * HID + k] = abb > 0.0 ? abb : 0.0;
+                    }
                 }
-                if (dW) (void)hipFree(dW);
-                if (dH) (void)hipFree(dH);
+        }
+        for (int gb = 0; gb < 2; ++gb)
+            for (int c = 0; c < C; ++c) {
+                const float* w = (gb ? wbp : wgp) + (size_t)c * HID * 9;
+                for (int k = 0; k < HID; ++k)
+                    for (int d = 0; d < 3; ++d) {
+                        double col = 0.0, row = 0.0;
+                        for (int u = 0; u < 3; ++u) {
+                            col += w[k * 9 + u * 3 + d];      // taps (dy = u - 1, dx = d - 1)
+                            row += w[k * 9 + d * 3 + u];      // taps (dy = d - 1, dx = u - 1)
+                        }
+                        W6[(((size_t)gb * HID + k) * 6 + d) * C + c] = col;
+                        W6[(((size_t)gb * HID + k) * 6 + 3 + d) * C + c] = row;
+                    }
             }
-            a.bn_a = B.upload(va);
-            a.bn_d = B.upload(vd);
-            a.nv = B.upload(vn);
-            a.bias_g = B.upload(vbg);
-            a.bias_b = B.upload(vbb);
+    }
+    // ... and its device contraction (after the style branch's biases went into vbg / vbb: the table rows are complete gamma / beta)
+    void ace_edge_rows(const std::string& p, AceW& a, const AceSrc& s) {
+        const std::vector<double>&hv = s.edge_hv, &W6 = s.edge_W6;
+        double *dW = nullptr, *dH = nullptr;
+        float *dbg_ = B.upload(s.vbg), *dbb_ = B.upload(s.vbb);
+        a.edge_tab = B.falloc((size_t)ACE_EDGE_CODES * 2 * s.C);
+        if (B.err.empty() && hipMalloc(&dW, W6.size() * 8) == hipSuccess && hipMalloc(&dH, hv.size() * 8) == hipSuccess &&
+            hipMemcpy(dW, W6.data(), W6.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(dH, hv.data(), hv.size() * 8, hipMemcpyHostToDevice) == hipSuccess &&
+            ace_edge_table(dW, dH, dbg_, dbb_, s.sg, s.sb, a.edge_tab, s.C, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
+        } else if (B.err.empty()) {
+            B.err = "edge table of " + p + " failed";
+        }
+        if (dW) (void)hipFree(dW);
+        if (dH) (void)hipFree(dH);
+    }
+
+    // part 3: SPADE gamma/beta rows: 64-row tiles = (gamma of 32 channels | beta of the same 32 channels)
+    void ace_spade_rows(AceW& a, const AceSrc& s) {
+        const int C = s.C, tiles = (C + 31) / 32;
+        const float *wgp = s.wgp, *wbp = s.wbp;
+        const float sg = s.sg, sb = s.sb;
+        auto getsp = [&](int row, int ci, int t) {
+            const int c = (row / 64) * 32 + (row & 31);
+            if (c >= C) return 0.f;
+            const bool beta = (row & 32) != 0;
+            const float w = (beta ? wbp : wgp)[((size_t)c * HID + ci) * 9 + t];
+            return w * (beta ? sb : sg);
         };
-        if (bw.learned) ace(bw.name + ".ace_s", bw.fin, bw.ace_s, std::ldexp(SH16_ACT_SCALE, fuse_shift));
-        ace(bw.name + ".ace_0", bw.fin, bw.ace_0);
-        ace(bw.name + ".ace_1", bw.fmid, bw.ace_1);
-        if (!B.err.empty()) return B.err;
-        blocks.push_back(bw);
+        if (opt.use_sh16) {
+            auto kexp = sh16_row_exponents(tiles * 64, HID, 3, getsp);
+            for (int t0 = 0; t0 < tiles * 64; t0 += 64) {     // one power of two per 64-row wave tile (a scalar in the ACE epilogue)
+                int km = kexp[t0];
+                for (int r = 0; r < 64; ++r) km = std::min(km, kexp[t0 + r]);
+                for (int r = 0; r < 64; ++r) kexp[t0 + r] = km;
+            }
+            a.spade_wpk = B.upload(pack_A_sh16(tiles * 64, HID, 3, getsp, kexp, opt.terms == 2));
+            a.spade_wscale = B.upload(sh16_wscale(kexp));
+            return;
+        }
+        a.spade_wpk = B.upload(pack_A(tiles * 64, HID, 3, CK_KS3, getsp));
+        if (!opt.wino) return;
+        // Winograd path: row tiles of 16 channels, rows 0-15 = gamma, 16-31 = beta (conv_wino.h)
+        auto getw = [&](int row, int ci, int t) {
+            const int c = (row / 32) * 16 + (row & 15);
+            if (c >= C) return 0.f;
+            const bool beta = (row & 16) != 0;
+            return (beta ? wbp : wgp)[((size_t)c * HID + ci) * 9 + t] * (beta ? sb : sg);
+        };
+        a.spade_wino = B.upload(pack_wino_A(((C + 15) / 16) * 32, HID, getw));
+        if (opt.wino >= 2 && opt.wino4_ace_max_r >= 32 && C % 2 == 0) {      // (any level can fall to <= wino4_ace_max_r pixels at a smaller image size)
+            // F(4x4,3x3) image for the low-resolution levels: rows interleaved so that a lane holds gamma and beta of two channels
+            auto getw4 = [&](int row, int ci, int t) {
+                int c, beta;
+                wino4_ace_row(row, c, beta);
+                if (c >= C) return 0.f;
+                return (beta ? wbp : wgp)[((size_t)c * HID + ci) * 9 + t] * (beta ? sb : sg);
+            };
+            a.spade_wino4 = B.upload(pack_wino4_A(((C + 15) / 16) * 32, HID, getw4));
+        }
+    }
+
+    // part 4: the style branch: fc_mu, the style convs as LUT rows (GEMM image / transposed / plain rows for the GEMV)
+    bool ace_style(const std::string& p, AceW& a, AceSrc& s) {
+        const int C = s.C;
+        const float ag = s.ag, ab = s.ab;
+        auto cg = B.get(p + ".conv_gamma.weight", (size_t)C * STYLE * 9);
+        auto cgb = B.get(p + ".conv_gamma.bias", C);
+        auto cb = B.get(p + ".conv_beta.weight", (size_t)C * STYLE * 9);
+        auto cbb = B.get(p + ".conv_beta.bias", C);
+        if (!cg || !cgb || !cb || !cbb) return false;
+        for (int c = 0; c < C; ++c) {
+            s.vbg[c] += ag * cgb->f32()[c];
+            s.vbb[c] += ab * cbb->f32()[c];
+        }
+        std::vector<float> fw((size_t)LABEL_NC * STYLE * STYLE), fb((size_t)LABEL_NC * STYLE);
+        for (int j = 0; j < LABEL_NC; ++j) {
+            auto w = B.get(p + ".fc_mu" + std::to_string(j) + ".weight", (size_t)STYLE * STYLE);
+            auto b = B.get(p + ".fc_mu" + std::to_string(j) + ".bias", STYLE);
+            if (!w || !b) return false;
+            std::memcpy(&fw[(size_t)j * STYLE * STYLE], w->f32(), sizeof(float) * STYLE * STYLE);
+            std::memcpy(&fb[(size_t)j * STYLE], b->f32(), sizeof(float) * STYLE);
+        }
+        a.fcmu_w = B.upload(fw);
+        a.fcmu_b = B.upload(fb);
+        // LUT GEMM rows (t, gamma|beta, c) <- alpha * W[c][k][t]
+        const float* cgp = cg->f32();
+        const float* cbp = cb->f32();
+        auto getl = [&](int row, int k, int) {
+            const int t = row / (2 * C), gb = (row / C) & 1, c = row % C;
+            return gb ? ab * cbp[((size_t)c * STYLE + k) * 9 + t] : ag * cgp[((size_t)c * STYLE + k) * 9 + t];
+        };
+        if (opt.use_sh16) {
+            const auto kexp = sh16_row_exponents(18 * C, STYLE, 1, getl);
+            a.lut_wpk = B.upload(pack_A_sh16(18 * C, STYLE, 1, getl, kexp, opt.terms == 2));
+            a.lut_wscale = B.upload(sh16_wscale(kexp));
+        } else {
+            a.lut_wpk = B.upload(pack_A(18 * C, STYLE, 1, CK_KS1, getl));
+            if (mb * LABEL_NC > 64) {      // grouped LUT build (conv_pw.h): [k][row] image
+                std::vector<float> wt((size_t)STYLE * 18 * C);
+                for (int row = 0; row < 18 * C; ++row)
+                    for (int k = 0; k < STYLE; ++k) wt[(size_t)k * 18 * C + row] = getl(row, k, 0);
+                a.lut_wt = B.upload(wt);
+            }
+        }
+        if (mb * (LABEL_NC + 1) <= 64) {   // small batches (interactive use): the LUT build is a weight-streaming GEMV
+            std::vector<float> rows((size_t)18 * C * STYLE);
+            for (int row = 0; row < 18 * C; ++row) {
+                const int t = row / (2 * C), gb = (row / C) & 1, cc = row % C;
+                const float* src = gb ? cbp : cgp;
+                const float al = gb ? ab : ag;
+                // f16x3 path: the ACE epilogue expects the style LUT pre-multiplied by the output scale (conv_sh16.h)
+                const float als = opt.use_sh16 ? al * a.out_scale : al;
+                for (int k = 0; k < STYLE; ++k) rows[(size_t)row * STYLE + k] = als * src[((size_t)cc * STYLE + k) * 9 + t];
+            }
+            a.lut_rows = B.upload(rows);
+        }
+        return true;
     }
 
     // ---- Zencoder (optional: only when its tensors were loaded) ----------------------------------------------
-    has_zencoder = false;
-    if (ts.find("Zencoder.model.1.weight") != ts.end()) {
+    std::string zencoder() {
+        m.has_zencoder = false;
+        if (B.ts.find("Zencoder.model.1.weight") == B.ts.end()) return "";
         auto plain = [&](const std::string& p, int cout, int cin, int stride, ConvLayer& L) {
             L = make_conv(B, B.vec(p + ".weight", (size_t)cout * cin * 9), B.vec(p + ".bias", cout), cout, cin, 3, stride, 1, false);      // (z14: its own reflect-padded image)
         };
-        plain("Zencoder.model.1", 32, 3, 1, z1);
-        z1_w = B.upload(B.vec("Zencoder.model.1.weight", (size_t)32 * 3 * 9));      // raw [32][3][3][3] for the direct stem conv
-        plain("Zencoder.model.4", 64, 32, 2, z4);
-        plain("Zencoder.model.7", 128, 64, 2, z7);
+        plain("Zencoder.model.1", 32, 3, 1, m.z1);
+        m.z1_w = B.upload(B.vec("Zencoder.model.1.weight", (size_t)32 * 3 * 9));      // raw [32][3][3][3] for the direct stem conv
+        plain("Zencoder.model.4", 64, 32, 2, m.z4);
+        plain("Zencoder.model.7", 128, 64, 2, m.z7);
         {   // ConvTranspose2d(128,256,k3,s2,p1,op1): weight [in=128][out=256][3][3] -> plain conv over the
             // zero-inserted input with flipped taps: W'[co][ci][ky][kx] = Wt[ci][co][2-ky][2-kx]
             auto wt = B.vec("Zencoder.model.10.weight", (size_t)128 * 256 * 9);
@@ -444,379 +504,407 @@ std::string SeanModel::build(const TensorStore& ts, int mb, int ms) {
             for (int co = 0; co < 256; ++co)
                 for (int ci = 0; ci < 128; ++ci)
                     for (int t = 0; t < 9; ++t) w[((size_t)co * 128 + ci) * 9 + t] = wt[((size_t)ci * 256 + co) * 9 + (8 - t)];
-            z10 = make_conv(B, w, B.vec("Zencoder.model.10.bias", 256), 256, 128, 3, 1, 1, false);      // (its Winograd form is z10_wino: four phase convs)
+            m.z10 = make_conv(B, w, B.vec("Zencoder.model.10.bias", 256), 256, 128, 3, 1, 1, false);      // (its Winograd form is z10_wino: four phase convs)
         }
-        plain("Zencoder.model.14", 512, 256, 1, z14);
-        z14_wino = z10_wino = z14_wino4 = z14_wino4s = nullptr;
-        if (!use_sh16 && wino) {   // exact-f32 path: the 256 -> 512 conv (91 % of the Zencoder FLOPs) as Winograd F(2x2,3x3), reflection-padded
-            auto w14 = B.vec("Zencoder.model.14.weight", (size_t)512 * 256 * 9);
-            const float* wp = w14.data();
-            z14_wino = B.upload(pack_wino_A(512, 256, [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; }));
-            // "sean.wino" = 2: the same conv as F(4x4,3x3) (conv_wino4.h, reflection instantiation) where the half-resolution grid is a multiple of 32
-            if (wino >= 2) z14_wino4 = B.upload(pack_wino4_A(512, 256, [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; }));
-            if (wino >= 2 && wino4_split > 0)      // (512 GEMM rows: the V route by default; the split kernel only on request)
-                z14_wino4s = B.upload(pack_wino4_A(512, 256, [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; }, true));
-            // ConvTranspose2d(128, 256, k3, s2, p1, op1) (architecture.py:167-170) as four phase convs of the INPUT grid:
-            //   out[2y+py][2x+px] = sum over dy, dx in {0, 1} of x[y+dy][x+dx] * Wt[ci][co][py+1-2dy][px+1-2dx]   (taps outside 0..2 absent)
-            // each a 3x3 kernel with non-zero taps at offsets 0 / +1 only; as Winograd F(2x2,3x3) that is 4 products per output pixel,
-            // against 9 of the plain conv over the zero-inserted view (three quarters of them on inserted zeros).  Row = 4 co + phase.
-            auto wt10 = B.vec("Zencoder.model.10.weight", (size_t)128 * 256 * 9);
-            const float* w10 = wt10.data();
-            z10_wino = B.upload(pack_wino_A(1024, 128, [&](int row, int ci, int t) {
-                const int co = row >> 2, py = (row >> 1) & 1, px = row & 1, dy = t / 3 - 1, dx = t % 3 - 1;
-                if (dy < 0 || dx < 0) return 0.f;
-                const int ky = py + 1 - 2 * dy, kx = px + 1 - 2 * dx;
-                return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)ci * 256 + co) * 9 + ky * 3 + kx] : 0.f;
-            }));
-            // The same four phases as plain GEMMs (conv_pw.h) over shifted views of the input (misc_kernels.hip convt_shift4: planes
-            // (0,1) | (0,0) | (1,0) | (1,1)): phase (py, px) contracts only its OWN taps -- 1 + 2 + 2 + 4 = 9 products per 2 x 2 outputs and
-            // channel pair, against 16 of the Winograd phase convs above (whose 3x3 kernels are mostly zeros).  Option "sean.convt_gemm".
-            if (convt_gemm) {
-                static const int first[4] = {1, 0, 1, 0}, cnt[4] = {1, 2, 2, 4}, sdy[4] = {0, 0, 1, 1}, sdx[4] = {1, 0, 0, 1};
-                for (int ph = 0; ph < 4; ++ph) {
-                    const int py = ph >> 1, px = ph & 1;
-                    z10_pw[ph] = B.upload(pack_pw_A(256, cnt[ph] * 128, [&](int co, int ci) {
-                        const int sh = first[ph] + ci / 128, c = ci % 128;
-                        const int ky = py + 1 - 2 * sdy[sh], kx = px + 1 - 2 * sdx[sh];
-                        return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)c * 256 + co) * 9 + ky * 3 + kx] : 0.f;
-                    }));
-                }
-            }
-        }
-        if (use_sh16) {   // the 256->512 conv is 91 % of the Zencoder FLOPs: run it on the f16x3 path too
-            auto w14 = B.vec("Zencoder.model.14.weight", (size_t)512 * 256 * 9);
-            const float* wp = w14.data();
-            auto g14 = [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; };
-            const auto k14 = sh16_row_exponents(512, 256, 3, g14);
-            z14_sh = B.upload(pack_A_sh16(512, 256, 3, g14, k14));
-            z14_ws = B.upload(sh16_wscale(k14));
-            // the ConvTranspose too (a 3x3 conv over the zero-inserted view, flipped taps as above)
-            auto wt10 = B.vec("Zencoder.model.10.weight", (size_t)128 * 256 * 9);
-            const float* w10 = wt10.data();
-            auto g10 = [&](int row, int ci, int t) { return w10[((size_t)ci * 256 + row) * 9 + (8 - t)]; };
-            const auto k10 = sh16_row_exponents(256, 128, 3, g10);
-            z10_sh = B.upload(pack_A_sh16(256, 128, 3, g10, k10));
-            z10_ws = B.upload(sh16_wscale(k10));
-            {   // depth-to-space form of the same ConvTranspose: out[2y+py][2x+px] += x[y+dy][x+dx] * Wt[ci][co][py+1-2dy][px+1-2dx]
-                auto gd = [&](int row, int ci, int t) {
-                    const int ph = row / 256, co = row % 256;
-                    const int ky = (ph >> 1) + 1 - 2 * (t / 2), kx = (ph & 1) + 1 - 2 * (t % 2);
-                    return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)ci * 256 + co) * 9 + ky * 3 + kx] : 0.f;
-                };
-                const auto kd = sh16_row_exponents(1024, 128, 2, gd);
-                z10_d2s = B.upload(pack_A_sh16(1024, 128, 2, gd, kd));
-                z10_d2s_ws = B.upload(sh16_wscale(kd));
-            }
-            // and the two stride-2 convs (space-to-depth form)
-            z4_s2d = make_conv_s2d(B, B.vec("Zencoder.model.4.weight", (size_t)64 * 32 * 9), B.vec("Zencoder.model.4.bias", 64), 64, 32, 3);
-            z7_s2d = make_conv_s2d(B, B.vec("Zencoder.model.7.weight", (size_t)128 * 64 * 9), B.vec("Zencoder.model.7.bias", 128), 128, 64, 3);
-        }
+        plain("Zencoder.model.14", 512, 256, 1, m.z14);
+        m.z14_wino = m.z10_wino = m.z14_wino4 = m.z14_wino4s = nullptr;
+        if (!opt.use_sh16 && opt.wino) zencoder_wino();
+        if (opt.use_sh16) zencoder_sh16();
         if (!B.err.empty()) return B.err;
-        has_zencoder = true;
+        m.has_zencoder = true;
+        return "";
+    }
+    // exact-f32 path: the 256 -> 512 conv (91 % of the Zencoder FLOPs) as Winograd F(2x2,3x3), reflection-padded; the ConvTranspose
+    void zencoder_wino() {
+        auto w14 = B.vec("Zencoder.model.14.weight", (size_t)512 * 256 * 9);
+        const float* wp = w14.data();
+        auto g14 = [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; };
+        m.z14_wino = B.upload(pack_wino_A(512, 256, g14));
+        // "sean.wino" = 2: the same conv as F(4x4,3x3) (conv_wino4.h, reflection instantiation) where the half-resolution grid is a multiple of 32
+        if (opt.wino >= 2) m.z14_wino4 = B.upload(pack_wino4_A(512, 256, g14));
+        if (opt.wino >= 2 && opt.wino4_split > 0)      // (512 GEMM rows: the V route by default; the split kernel only on request)
+            m.z14_wino4s = B.upload(pack_wino4_A(512, 256, g14, true));
+        // ConvTranspose2d(128, 256, k3, s2, p1, op1) (architecture.py:167-170) as four phase convs of the INPUT grid:
+        //   out[2y+py][2x+px] = sum over dy, dx in {0, 1} of x[y+dy][x+dx] * Wt[ci][co][py+1-2dy][px+1-2dx]   (taps outside 0..2 absent)
+        // each a 3x3 kernel with non-zero taps at offsets 0 / +1 only; as Winograd F(2x2,3x3) that is 4 products per output pixel,
+        // against 9 of the plain conv over the zero-inserted view (three quarters of them on inserted zeros).  Row = 4 co + phase.
+        auto wt10 = B.vec("Zencoder.model.10.weight", (size_t)128 * 256 * 9);
+        const float* w10 = wt10.data();
+        m.z10_wino = B.upload(pack_wino_A(1024, 128, [&](int row, int ci, int t) {
+            const int co = row >> 2, py = (row >> 1) & 1, px = row & 1, dy = t / 3 - 1, dx = t % 3 - 1;
+            if (dy < 0 || dx < 0) return 0.f;
+            const int ky = py + 1 - 2 * dy, kx = px + 1 - 2 * dx;
+            return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)ci * 256 + co) * 9 + ky * 3 + kx] : 0.f;
+        }));
+        // The same four phases as plain GEMMs (conv_pw.h) over shifted views of the input (misc_kernels.hip convt_shift4: planes
+        // (0,1) | (0,0) | (1,0) | (1,1)): phase (py, px) contracts only its OWN taps -- 1 + 2 + 2 + 4 = 9 products per 2 x 2 outputs and
+        // channel pair, against 16 of the Winograd phase convs above (whose 3x3 kernels are mostly zeros).  Option "sean.convt_gemm".
+        if (!opt.convt_gemm) return;
+        static const int first[4] = {1, 0, 1, 0}, cnt[4] = {1, 2, 2, 4}, sdy[4] = {0, 0, 1, 1}, sdx[4] = {1, 0, 0, 1};
+        for (int ph = 0; ph < 4; ++ph) {
+            const int py = ph >> 1, px = ph & 1;
+            m.z10_pw[ph] = B.upload(pack_pw_A(256, cnt[ph] * 128, [&](int co, int ci) {
+                const int sh = first[ph] + ci / 128, c = ci % 128;
+                const int ky = py + 1 - 2 * sdy[sh], kx = px + 1 - 2 * sdx[sh];
+                return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)c * 256 + co) * 9 + ky * 3 + kx] : 0.f;
+            }));
+        }
+    }
+    // the 256->512 conv is 91 % of the Zencoder FLOPs: run it on the f16x3 path too
+    void zencoder_sh16() {
+        auto w14 = B.vec("Zencoder.model.14.weight", (size_t)512 * 256 * 9);
+        const float* wp = w14.data();
+        auto g14 = [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; };
+        const auto k14 = sh16_row_exponents(512, 256, 3, g14);
+        m.z14_sh = B.upload(pack_A_sh16(512, 256, 3, g14, k14));
+        m.z14_ws = B.upload(sh16_wscale(k14));
+        // the ConvTranspose too (a 3x3 conv over the zero-inserted view, flipped taps as above)
+        auto wt10 = B.vec("Zencoder.model.10.weight", (size_t)128 * 256 * 9);
+        const float* w10 = wt10.data();
+        auto g10 = [&](int row, int ci, int t) { return w10[((size_t)ci * 256 + row) * 9 + (8 - t)]; };
+        const auto k10 = sh16_row_exponents(256, 128, 3, g10);
+        m.z10_sh = B.upload(pack_A_sh16(256, 128, 3, g10, k10));
+        m.z10_ws = B.upload(sh16_wscale(k10));
+        {   // depth-to-space form of the same ConvTranspose: out[2y+py][2x+px] += x[y+dy][x+dx] * Wt[ci][co][py+1-2dy][px+1-2dx]
+            auto gd = [&](int row, int ci, int t) {
+                const int ph = row / 256, co = row % 256;
+                const int ky = (ph >> 1) + 1 - 2 * (t / 2), kx = (ph & 1) + 1 - 2 * (t % 2);
+                return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)ci * 256 + co) * 9 + ky * 3 + kx] : 0.f;
+            };
+            const auto kd = sh16_row_exponents(1024, 128, 2, gd);
+            m.z10_d2s = B.upload(pack_A_sh16(1024, 128, 2, gd, kd));
+            m.z10_d2s_ws = B.upload(sh16_wscale(kd));
+        }
+        // and the two stride-2 convs (space-to-depth form)
+        m.z4_s2d = make_conv_s2d(B, B.vec("Zencoder.model.4.weight", (size_t)64 * 32 * 9), B.vec("Zencoder.model.4.bias", 64), 64, 32, 3);
+        m.z7_s2d = make_conv_s2d(B, B.vec("Zencoder.model.7.weight", (size_t)128 * 64 * 9), B.vec("Zencoder.model.7.bias", 128), 128, 64, 3);
     }
 
-    amax_slots = static_cast<unsigned*>(B.dalloc(64 * sizeof(unsigned)));   // 2 per ACE: [output, style projections]
-    zero_page = static_cast<float*>(B.dalloc(256));
-    if (zero_page) (void)hipMemset(zero_page, 0, 256);
-    splitk_cap = (long long)16 << 20;     // 64 MiB of split-K slabs (low-resolution layers only)
-    splitk_ws = B.falloc((size_t)splitk_cap);
-    gb_small = nullptr;
-    gb_small_cap = 0;
-    if (!use_sh16) {
-        gb_small_cap = (long long)4 << 20;      // 16 MiB: rows x pixels of the tiny ACE launches that take the plain split-K route
-        gb_small = B.falloc((size_t)gb_small_cap);
-    }
-    n_aces = ace_index;
-    // Run-ahead mode of small jobs (Runner::prepare_all_ahead): a side stream, one join event and one set of buffers per ACE.
-    // Only when the handle is sized for interactive work -- for large batches the convs own every CU and nothing co-schedules.
-    // Default: interactive sizes only (up to 2 x 512^2 per chunk, where the win was measured: 3.3 -> 2.65 ms per render at
-    // 256^2).  The per-ACE buffers of the full mode cost mb * r^2 * 128 * 4 bytes each -- 4.3 GB for an 8 x 512^2 handle, for
-    // 1.6 % at that size -- so larger handles opt in explicitly: option "sean.ahead" = images of 512^2 per chunk (0 = never).
-    if (ahead_pixels < 0) ahead_pixels = (long long)2 * 512 * 512;
-    // Larger jobs keep the (HBM-write-bound) label-table kernels inline and run only the style LUT builds -- small,
-    // latency-bound GEMMs -- ahead (ahead_full = false) -- unless the overlap mode serves them (sean_model.h): then the label
-    // tables of every ACE run ahead too, on a side stream confined to a few CUs.
-    {
-        int ncu = 0, dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) num_cus = ncu;
-    }
-    overlap_on = false;
-    if (overlap > 0 && !use_sh16 && wino && (long long)mb * ms * ms > ahead_pixels && ms >= 128) {
+    // ---- run-ahead and overlap resources (after the scratch buffers every handle has) ------------------------------
+    std::string run_ahead() {
+        m.amax_slots = static_cast<unsigned*>(B.dalloc(64 * sizeof(unsigned)));   // 2 per ACE: [output, style projections]
+        m.zero_page = static_cast<float*>(B.dalloc(256));
+        if (m.zero_page) (void)hipMemset(m.zero_page, 0, 256);
+        m.splitk_cap = (long long)16 << 20;     // 64 MiB of split-K slabs (low-resolution layers only)
+        m.splitk_ws = B.falloc((size_t)m.splitk_cap);
+        m.gb_small = nullptr;
+        m.gb_small_cap = 0;
+        if (!opt.use_sh16) {
+            m.gb_small_cap = (long long)4 << 20;      // 16 MiB: rows x pixels of the tiny ACE launches that take the plain split-K route
+            m.gb_small = B.falloc((size_t)m.gb_small_cap);
+        }
+        const int n_aces = m.n_aces;
+        // Run-ahead mode of small jobs (Runner::prepare_all_ahead): a side stream, one join event and one set of buffers per ACE.
+        // Only when the handle is sized for interactive work -- for large batches the convs own every CU and nothing co-schedules.
+        // Default: interactive sizes only (up to 2 x 512^2 per chunk, where the win was measured: 3.3 -> 2.65 ms per render at
+        // 256^2).  The per-ACE buffers of the full mode cost mb * r^2 * 128 * 4 bytes each -- 4.3 GB for an 8 x 512^2 handle, for
+        // 1.6 % at that size -- so larger handles opt in explicitly: option "sean.ahead" = images of 512^2 per chunk (0 = never).
+        long long limit = opt.ahead_pixels < 0 ? (long long)2 * 512 * 512 : opt.ahead_pixels;
+        // Larger jobs keep the (HBM-write-bound) label-table kernels inline and run only the style LUT builds -- small,
+        // latency-bound GEMMs -- ahead (ahead_full = false) -- unless the overlap mode serves them (sean_model.h): then the label
+        // tables of every ACE run ahead too, on a side stream confined to a few CUs.
         int ncu = 0, dev = 0;
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 0;
-        const int want = std::min(overlap, ncu / 2) & ~7;
-        if (want >= 8) {
-            uint32_t mask[16] = {};
-            for (int i = 0; i < want; ++i) mask[i >> 5] |= 1u << (i & 31);      // (CU i of the mask sits on XCD i % 8)
-            const uint32_t words = (uint32_t)((ncu + 31) / 32);
-            if (hipExtStreamCreateWithCUMask(&side, words, mask) == hipSuccess && hipExtStreamCreateWithCUMask(&side_int, words, mask) == hipSuccess &&
-                hipStreamCreateWithFlags(&main_i, hipStreamNonBlocking) == hipSuccess &&
-                hipEventCreateWithFlags(&ev_in, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ev_out, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) == hipSuccess) {
-                overlap_on = true;
-            } else {
-                return "overlap mode: stream creation failed (hipExtStreamCreateWithCUMask)";
+        if (ncu > 0) m.num_cus = ncu;
+        m.overlap_on = false;
+        if (opt.overlap > 0 && !opt.use_sh16 && opt.wino && (long long)mb * ms * ms > limit && ms >= 128) {
+            const int want = std::min(opt.overlap, ncu / 2) & ~7;
+            if (want >= 8) {
+                uint32_t mask[16] = {};
+                for (int i = 0; i < want; ++i) mask[i >> 5] |= 1u << (i & 31);      // (CU i of the mask sits on XCD i % 8)
+                const uint32_t words = (uint32_t)((ncu + 31) / 32);
+                if (hipExtStreamCreateWithCUMask(&m.side, words, mask) == hipSuccess && hipExtStreamCreateWithCUMask(&m.side_int, words, mask) == hipSuccess &&
+                    hipStreamCreateWithFlags(&m.main_i, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&m.ev_in, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&m.ev_out, hipEventDisableTiming) == hipSuccess &&
+                    hipEventCreateWithFlags(&m.ev_fork, hipEventDisableTiming) == hipSuccess) {
+                    m.overlap_on = true;
+                } else {
+                    return "overlap mode: stream creation failed (hipExtStreamCreateWithCUMask)";
+                }
             }
         }
-    }
-    if (overlap_on) {
-        if (ahead_pixels <= 0) ahead_pixels = 1;      // (the per-ACE buffers below)
-        ev_x.assign(n_aces, nullptr);
-        ev_int.assign(n_aces, nullptr);
-        for (auto& e : ev_x)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return "event creation failed";
-        for (auto& e : ev_int)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return "event creation failed";
-        claim_pool = static_cast<unsigned*>(B.dalloc((size_t)CLAIM_SLOTS * CLAIM_WORDS * sizeof(unsigned)));
-    }
-    if (ahead_pixels > 0) {
-        ahead_full = overlap_on || (long long)mb * ms * ms <= ahead_pixels;
-        if (!overlap_on && (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess))
+        if (m.overlap_on) {
+            if (limit <= 0) limit = 1;      // (the per-ACE buffers below)
+            m.ev_x.assign(n_aces, nullptr);
+            m.ev_int.assign(n_aces, nullptr);
+            for (auto& e : m.ev_x)
+                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return "event creation failed";
+            for (auto& e : m.ev_int)
+                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return "event creation failed";
+            m.claim_pool = static_cast<unsigned*>(B.dalloc((size_t)SeanModel::CLAIM_SLOTS * SeanModel::CLAIM_WORDS * sizeof(unsigned)));
+        }
+        m.ahead_limit = limit;
+        if (limit <= 0) return "";
+        m.ahead_full = m.overlap_on || (long long)mb * ms * ms <= limit;
+        if (!m.overlap_on && (hipStreamCreateWithFlags(&m.side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&m.ev_fork, hipEventDisableTiming) != hipSuccess))
             return "side stream creation failed";
-        ev_join.assign(n_aces, nullptr);
-        actv_ahead.assign(n_aces, nullptr);
-        lut_ahead.assign(n_aces, nullptr);
-        for (auto& e : ev_join)
+        m.ev_join.assign(n_aces, nullptr);
+        m.actv_ahead.assign(n_aces, nullptr);
+        m.lut_ahead.assign(n_aces, nullptr);
+        for (auto& e : m.ev_join)
             if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return "event creation failed";
-        const size_t npad_b = ((size_t)mb * (LABEL_NC + 1) + 31) / 32 * 32;
-        for (const auto& b : blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1}) {
-                if (!a) continue;
-                const size_t r = (size_t)ms / a->res_div;
-                if (ahead_full) actv_ahead[a->index] = B.falloc((size_t)mb * r * (r + 64) * (HID + 20));
-                if (a->styled) lut_ahead[a->index] = B.falloc(npad_b * 18 * a->C);
-            }
-        splitk_side = B.falloc((size_t)splitk_cap);
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            const size_t r = (size_t)ms / a.res_div;
+            if (m.ahead_full) m.actv_ahead[a.index] = B.falloc((size_t)mb * r * (r + 64) * (HID + 20));
+            if (a.styled) m.lut_ahead[a.index] = B.falloc(npad() * 18 * a.C);
+        });
+        m.splitk_side = B.falloc((size_t)m.splitk_cap);
+        return "";
     }
 
     // ---- workspace arena --------------------------------------------------------------------------------
-    const size_t MB = mb, S = ms;
-    for (int k = 1; k <= 5; ++k) {   // res_div 2^k
-        const size_t r = S >> k;
-        lab_r[k] = static_cast<uint8_t*>(B.dalloc(MB * r * r));
+    size_t npad() const { return (((size_t)mb * (LABEL_NC + 1) + 31) / 32) * 32; }     // f16x3 path: 20 columns per sample (19 = zero column)
+    std::string arena() {
+        const size_t MB = mb, S = ms;
+        for (int k = 1; k <= 5; ++k) {   // res_div 2^k
+            const size_t r = S >> k;
+            m.lab_r[k] = static_cast<uint8_t*>(B.dalloc(MB * r * r));
+        }
+        size_t nf = m.noise_floats(ms);
+        m.noise_ws = static_cast<float*>(B.dalloc(MB * nf * 4));
+        m.mu_img = static_cast<float*>(B.dalloc((size_t)STYLE * npad() * 4));
+        if (m.mu_img) (void)hipMemset(m.mu_img, 0, (size_t)STYLE * npad() * 4);      // pad columns stay zero
+        style_projections();
+        style_lut_groups();
+        size_t lutmax = 0, h0max = 0, midmax = 0, outmax = 0;
+        for (const auto& b : m.blocks) {
+            const size_t r = S / b.res_div, px = MB * r * r;
+            if (b.styled) lutmax = std::max(lutmax, npad() * 18 * b.fin);      // npad columns: the f16x3 LUT GEMM writes the pad too
+            h0max = std::max(h0max, px * b.fin);
+            midmax = std::max(midmax, px * b.fmid);
+            outmax = std::max(outmax, px * b.fout);
+        }
+        outmax = std::max(outmax, (size_t)MB * 16 * m.ngf * (S / 32) * (S / 32));
+        if (m.has_zencoder) {   // Zencoder activations live in h0/hs (<= 512 ch at S/2) and dx/h1 (<= 64 ch at S/2)
+            h0max = std::max(h0max, MB * S * S * 128);
+            midmax = std::max(midmax, MB * S * S * (opt.use_sh16 ? 64 : 16));
+        }
+        m.lut = static_cast<float*>(B.dalloc(lutmax * 4));
+        m.actv = static_cast<float*>(B.dalloc(MB * S * S * HID * 4));      // (direct kernels; the Winograd ACE levels own padded buffers, actv_lvl)
+        m.h0 = static_cast<float*>(B.dalloc(h0max * 4));
+        m.hs = static_cast<float*>(B.dalloc(h0max * 4));
+        m.dx = static_cast<float*>(B.dalloc(midmax * 4));
+        m.h1 = static_cast<float*>(B.dalloc(midmax * 4));
+        m.xs = static_cast<float*>(B.dalloc(outmax * 4));
+        m.xa = static_cast<float*>(B.dalloc(outmax * 4));
+        m.xb = static_cast<float*>(B.dalloc(outmax * 4));
+        return "";
     }
-    size_t nf = noise_floats(ms);
-    noise_ws = static_cast<float*>(B.dalloc(MB * nf * 4));
-    const size_t npad = ((MB * (LABEL_NC + 1) + 31) / 32) * 32;     // f16x3 path: 20 columns per sample (19 = zero column)
-    mu_img = static_cast<float*>(B.dalloc((size_t)STYLE * npad * 4));
-    if (mu_img) (void)hipMemset(mu_img, 0, (size_t)STYLE * npad * 4);      // pad columns stay zero
     // one fc_mu launch per chunk for all styled ACEs (f16x3: SH16 images; exact f32: f32 images, batches of more than 64 (sample, label) columns)
-    fcmu_batched = use_sh16 ? max_batch * (LABEL_NC + 1) > 64 : max_batch * LABEL_NC > 64;
-    if (fcmu_batched) {
-        mu_stride = (long long)STYLE * npad;
-        mu_all = static_cast<float*>(B.dalloc((size_t)n_aces * mu_stride * 4));
-        if (mu_all) (void)hipMemset(mu_all, 0, (size_t)n_aces * mu_stride * 4);
+    void style_projections() {
+        const int n_aces = m.n_aces;
+        m.fcmu_batched = opt.use_sh16 ? mb * (LABEL_NC + 1) > 64 : mb * LABEL_NC > 64;
+        if (!m.fcmu_batched) return;
+        m.mu_stride = (long long)STYLE * npad();
+        m.mu_all = static_cast<float*>(B.dalloc((size_t)n_aces * m.mu_stride * 4));
+        if (m.mu_all) (void)hipMemset(m.mu_all, 0, (size_t)n_aces * m.mu_stride * 4);
         std::vector<const float*> wp(n_aces, nullptr), bp(n_aces, nullptr);
-        for (const auto& b : blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1})
-                if (a && a->styled) { wp[a->index] = a->fcmu_w; bp[a->index] = a->fcmu_b; }
-        fcmu_w_ptrs = static_cast<const float**>(B.dalloc(n_aces * sizeof(float*)));
-        fcmu_b_ptrs = static_cast<const float**>(B.dalloc(n_aces * sizeof(float*)));
-        if (fcmu_w_ptrs && fcmu_b_ptrs) {
-            (void)hipMemcpy(fcmu_w_ptrs, wp.data(), n_aces * sizeof(float*), hipMemcpyHostToDevice);
-            (void)hipMemcpy(fcmu_b_ptrs, bp.data(), n_aces * sizeof(float*), hipMemcpyHostToDevice);
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (a.styled) { wp[a.index] = a.fcmu_w; bp[a.index] = a.fcmu_b; }
+        });
+        m.fcmu_w_ptrs = static_cast<const float**>(B.dalloc(n_aces * sizeof(float*)));
+        m.fcmu_b_ptrs = static_cast<const float**>(B.dalloc(n_aces * sizeof(float*)));
+        if (m.fcmu_w_ptrs && m.fcmu_b_ptrs) {
+            (void)hipMemcpy(m.fcmu_w_ptrs, wp.data(), n_aces * sizeof(float*), hipMemcpyHostToDevice);
+            (void)hipMemcpy(m.fcmu_b_ptrs, bp.data(), n_aces * sizeof(float*), hipMemcpyHostToDevice);
         }
     }
-    lut_groups = nullptr;
-    lut_ngroups = lut_group_tiles = 0;
-    lut_group_rows = 0.0;
-    if (fcmu_batched && !use_sh16 && lut_grouped) {
-        if (lut_ahead.empty()) lut_ahead.assign(n_aces, nullptr);
+    // exact-f32 path: the group table of the one grouped GEMM launch that builds every style LUT of a chunk (Runner::luts_grouped)
+    void style_lut_groups() {
+        m.lut_groups = nullptr;
+        m.lut_ngroups = m.lut_group_tiles = 0;
+        m.lut_group_rows = 0.0;
+        if (!(m.fcmu_batched && !opt.use_sh16 && opt.lut_grouped)) return;
+        if (m.lut_ahead.empty()) m.lut_ahead.assign(m.n_aces, nullptr);
         std::vector<PwGroup> g;
         bool ok = true;                           // all styled ACEs or none: the consumers take every LUT from the same place
-        for (const auto& b : blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1})
-                if (a && a->styled && (!a->lut_wt || (18 * a->C) % 128)) ok = false;
-        for (const auto& b : blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1}) {
-                if (!ok || !a || !a->styled) continue;
-                if (!lut_ahead[a->index]) lut_ahead[a->index] = B.falloc(npad * 18 * a->C);
-                PwGroup e{};
-                e.in = a->lut_wt;
-                e.wpk = mu_all + (size_t)a->index * mu_stride;
-                e.out = lut_ahead[a->index];
-                e.HW = 18 * a->C;                 // (C % 64 == 0: 18 C % 128 == 0)
-                e.start = lut_group_tiles;        // in pixel tiles; the kernel multiplies by the call's row groups
-                if (!e.out) { ok = false; continue; }
-                lut_group_tiles += e.HW / 128;
-                lut_group_rows += e.HW;
-                g.push_back(e);
-            }
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (a.styled && (!a.lut_wt || (18 * a.C) % 128)) ok = false;
+        });
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (!ok || !a.styled) return;
+            if (!m.lut_ahead[a.index]) m.lut_ahead[a.index] = B.falloc(npad() * 18 * a.C);
+            PwGroup e{};
+            e.in = a.lut_wt;
+            e.wpk = m.mu_all + (size_t)a.index * m.mu_stride;
+            e.out = m.lut_ahead[a.index];
+            e.HW = 18 * a.C;                 // (C % 64 == 0: 18 C % 128 == 0)
+            e.start = m.lut_group_tiles;     // in pixel tiles; the kernel multiplies by the call's row groups
+            if (!e.out) { ok = false; return; }
+            m.lut_group_tiles += e.HW / 128;
+            m.lut_group_rows += e.HW;
+            g.push_back(e);
+        });
         if (ok && !g.empty()) {
-            lut_groups = B.dalloc(g.size() * sizeof(PwGroup));
-            if (lut_groups) (void)hipMemcpy(lut_groups, g.data(), g.size() * sizeof(PwGroup), hipMemcpyHostToDevice);
-            lut_ngroups = (int)g.size();
+            m.lut_groups = B.dalloc(g.size() * sizeof(PwGroup));
+            if (m.lut_groups) (void)hipMemcpy(m.lut_groups, g.data(), g.size() * sizeof(PwGroup), hipMemcpyHostToDevice);
+            m.lut_ngroups = (int)g.size();
         }
     }
-    size_t lutmax = 0, h0max = 0, midmax = 0, outmax = 0;
-    for (const auto& b : blocks) {
-        const size_t r = S / b.res_div, px = MB * r * r;
-        if (b.styled) lutmax = std::max(lutmax, npad * 18 * b.fin);      // npad columns: the f16x3 LUT GEMM writes the pad too
-        h0max = std::max(h0max, px * b.fin);
-        midmax = std::max(midmax, px * b.fmid);
-        outmax = std::max(outmax, px * b.fout);
-    }
-    outmax = std::max(outmax, (size_t)MB * 16 * ngf * (S / 32) * (S / 32));
-    if (has_zencoder) {   // Zencoder activations live in h0/hs (<= 512 ch at S/2) and dx/h1 (<= 64 ch at S/2)
-        h0max = std::max(h0max, MB * S * S * 128);
-        midmax = std::max(midmax, MB * S * S * (use_sh16 ? 64 : 16));
-    }
-    lut = static_cast<float*>(B.dalloc(lutmax * 4));
-    actv = static_cast<float*>(B.dalloc(MB * S * S * HID * 4));      // (direct kernels; the Winograd ACE levels own padded buffers, actv_lvl)
-    h0 = static_cast<float*>(B.dalloc(h0max * 4));
-    hs = static_cast<float*>(B.dalloc(h0max * 4));
-    dx = static_cast<float*>(B.dalloc(midmax * 4));
-    h1 = static_cast<float*>(B.dalloc(midmax * 4));
-    xs = static_cast<float*>(B.dalloc(outmax * 4));
-    xa = static_cast<float*>(B.dalloc(outmax * 4));
-    xb = static_cast<float*>(B.dalloc(outmax * 4));
+
     // ---- Winograd ACE path: boundary-quad lists per level, task lists per (level, row tiles), per-sample style images ------
-    for (int k = 0; k < 6; ++k) {
-        wq_level[k] = WinoLevel();
-        actv_lvl[k] = nullptr;
-    }
-    pad_state.clear();
-    wsty = wsty4 = nullptr;
-    if (wino && !use_sh16) {
+    std::string wino_levels() {
+        for (int k = 0; k < 6; ++k) {
+            m.wq_level[k] = SeanModel::WinoLevel();
+            m.actv_lvl[k] = nullptr;
+        }
+        m.pad_state.clear();
+        m.wsty = m.wsty4 = nullptr;
+        if (!(opt.wino && !opt.use_sh16)) return "";
         size_t wsty_max = 0, wsty4_max = 0;
         int lvl_planes[6] = {0, 0, 0, 0, 0, 0};        // planes of the level's padded hidden-activation buffer: what its ACEs write (ace_prepare: kout)
-        for (const auto& b : blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1}) {
-                if (!a || !a->spade_wino) continue;
-                int k = 0;
-                while ((1 << k) < a->res_div) ++k;
-                const int r = ms >> k;
-                if (r < 32 || r % 32) continue;
-                WinoLevel& L = wq_level[k];
-                if (!L.qlist) {
-                    const bool gather = wino_gather && mb <= 32 && (r / 2) * (r / 2) <= 2048 * 64;
-                    L.TH = gather ? 16 : wino_tile_h(r);
-                    L.cap_tiles = mb * (r / 32) * (r / L.TH);
-                    L.qlist = static_cast<uint8_t*>(B.dalloc((size_t)L.cap_tiles * 8 * L.TH));
-                    L.qcnt = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
-                    L.pcnt = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
-                    if (gather) {
-                        L.gq_cap = (r / 2) * (r / 2);
-                        L.gq = static_cast<unsigned*>(B.dalloc((size_t)mb * L.gq_cap * sizeof(unsigned)));
-                        L.gq_n = static_cast<int*>(B.dalloc(32 * sizeof(int)));
-                        L.qoff = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
-                        L.chunk_base = static_cast<int*>(B.dalloc(34 * sizeof(int)));
-                        L.patch_mode = static_cast<int*>(B.dalloc(sizeof(int)));
-                    }
-                }
-                const int nrt = (a->C + 15) / 16;
-                bool have = false;
-                for (const auto& w : L.works) have = have || w.nrt == nrt;
-                if (!have) {
-                    WinoWork w;
-                    w.nrt = nrt;
-                    w.work = static_cast<unsigned*>(B.dalloc(((size_t)L.cap_tiles * 4 + mb) * ((nrt + 1) / 2) * sizeof(unsigned)));
-                    w.total = static_cast<int*>(B.dalloc(8 * sizeof(int)));
-                    L.works.push_back(w);
-                }
-                lvl_planes[k] = std::max(lvl_planes[k], a->styled ? HID + 20 : HID);       // (up_3 is unstyled: 128 planes, no one-hot planes)
-                if (a->styled) wsty_max = std::max(wsty_max, (size_t)mb * nrt * 5 * 2048);
-                if (a->styled && a->spade_wino4) wsty4_max = std::max(wsty4_max, (size_t)mb * nrt * 6 * wino4::ADW);
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (!a.spade_wino) return;
+            const int k = level_of(a.res_div), r = ms >> k;
+            if (r < 32 || r % 32) return;
+            SeanModel::WinoLevel& L = m.wq_level[k];
+            if (!L.qlist) wino_level_lists(L, r);
+            const int nrt = (a.C + 15) / 16;
+            bool have = false;
+            for (const auto& w : L.works) have = have || w.nrt == nrt;
+            if (!have) {
+                SeanModel::WinoWork w;
+                w.nrt = nrt;
+                w.work = static_cast<unsigned*>(B.dalloc(((size_t)L.cap_tiles * 4 + mb) * ((nrt + 1) / 2) * sizeof(unsigned)));
+                w.total = static_cast<int*>(B.dalloc(8 * sizeof(int)));
+                L.works.push_back(w);
             }
-        if (wsty_max) wsty = B.falloc(wsty_max);
+            lvl_planes[k] = std::max(lvl_planes[k], a.styled ? HID + 20 : HID);       // (up_3 is unstyled: 128 planes, no one-hot planes)
+            if (a.styled) wsty_max = std::max(wsty_max, (size_t)mb * nrt * 5 * 2048);
+            if (a.styled && a.spade_wino4) wsty4_max = std::max(wsty4_max, (size_t)mb * nrt * 6 * wino4::ADW);
+        });
+        if (wsty_max) m.wsty = B.falloc(wsty_max);
         // patch source of the gather kernel (conv_wino.h): up to 32 chunks of 64 boundary quads per sample (3 % of the quads of a 512^2
         // level) x 148 channels x 4 KB -- what the straight-edge reduction leaves on label maps with straight region borders
-        patchbuf = nullptr;
-        patch_cap_chunks = 0;
-        if (patch && wino_gather && mb <= 32) {
-            patch_cap_chunks = 32 * mb;
-            patchbuf = B.falloc((size_t)patch_cap_chunks * (HID + 20) * 1024);
+        m.patchbuf = nullptr;
+        m.patch_cap_chunks = 0;
+        if (opt.patch && opt.wino_gather && mb <= 32) {
+            m.patch_cap_chunks = 32 * mb;
+            m.patchbuf = B.falloc((size_t)m.patch_cap_chunks * (HID + 20) * 1024);
         }
-        if (wsty4_max) wsty4 = B.falloc(wsty4_max);
-        // pre-transformed-input route (conv_wino4v.h): one V image, sized for the largest layer that takes it at (mb, ms)
-        vbuf = nullptr;
-        vbuf_bytes = 0;
-        if (wino >= 2 && wino4v) {
-            size_t need = 0;
-            for (const auto& b : blocks) {
-                int k = 0;
-                while ((1 << k) < b.ace_0.res_div) ++k;
-                const int r = ms >> k;
-                if (r < 32 || r % 32 || r > 64) continue;
-                for (const ConvW* c : {&b.conv_0, &b.conv_1})
-                    if (c->wino4 && wino4v_pays(c->Cout, r)) need = std::max(need, wino4v_bytes(mb, r, r, c->Cin / 4));
-                for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1})
-                    if (a && a->spade_wino4 && r <= wino4_ace_max_r && wino4v_pays(2 * a->C, r)) need = std::max(need, wino4v_bytes(mb, r, r, 38));
-            }
-            // the Zencoder's 256 -> 512 conv on the half-resolution grid: 9 bytes x 256 channels x (ms / 2)^2 per sample -- up to 2.5 GB only
-            if (z14_wino4 && (ms / 2) % 32 == 0 && wino4v_bytes(mb, ms / 2, ms / 2, 64) <= ((size_t)5 << 29)) need = std::max(need, wino4v_bytes(mb, ms / 2, ms / 2, 64));
-            if (need) {
-                vbuf = static_cast<float*>(B.dalloc(need));
-                vbuf_bytes = need;
-            }
-        }
+        if (wsty4_max) m.wsty4 = B.falloc(wsty4_max);
+        wino4v_buffer();
         for (int k = 0; k < 6; ++k)
-            if (wq_level[k].qlist) {
+            if (m.wq_level[k].qlist) {
                 const size_t r = (size_t)ms >> k;
-                actv_lvl[k] = B.falloc((size_t)mb * r * wino_apitch((int)r) * lvl_planes[k]);
+                m.actv_lvl[k] = B.falloc((size_t)mb * r * wino_apitch((int)r) * lvl_planes[k]);
             }
+        return "";
     }
-    prof_stats_cap = 16384;
-    prof_stats_used = 0;
-    prof_stats = static_cast<int*>(B.dalloc((size_t)prof_stats_cap * 4 * sizeof(int)));
+    void wino_level_lists(SeanModel::WinoLevel& L, int r) {
+        const bool gather = opt.wino_gather && mb <= 32 && (r / 2) * (r / 2) <= 2048 * 64;
+        L.TH = gather ? 16 : opt.wino_tile_h(r);
+        L.cap_tiles = mb * (r / 32) * (r / L.TH);
+        L.qlist = static_cast<uint8_t*>(B.dalloc((size_t)L.cap_tiles * 8 * L.TH));
+        L.qcnt = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
+        L.pcnt = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
+        if (gather) {
+            L.gq_cap = (r / 2) * (r / 2);
+            L.gq = static_cast<unsigned*>(B.dalloc((size_t)mb * L.gq_cap * sizeof(unsigned)));
+            L.gq_n = static_cast<int*>(B.dalloc(32 * sizeof(int)));
+            L.qoff = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
+            L.chunk_base = static_cast<int*>(B.dalloc(34 * sizeof(int)));
+            L.patch_mode = static_cast<int*>(B.dalloc(sizeof(int)));
+        }
+    }
+    // pre-transformed-input route (conv_wino4v.h): one V image, sized for the largest layer that takes it at (mb, ms)
+    void wino4v_buffer() {
+        m.vbuf = nullptr;
+        m.vbuf_bytes = 0;
+        if (!(opt.wino >= 2 && opt.wino4v)) return;
+        size_t need = 0;
+        auto level_r = [&](int res_div) {       // the level's size when it can take the route at max_size, else 0
+            const int r = ms >> level_of(res_div);
+            return (r < 32 || r % 32 || r > 64) ? 0 : r;
+        };
+        for (const auto& b : m.blocks)
+            for (const ConvW* c : {&b.conv_0, &b.conv_1})
+                if (const int r = level_r(b.res_div))
+                    if (c->wino4 && wino4v_pays(c->Cout, r)) need = std::max(need, wino4v_bytes(mb, r, r, c->Cin / 4));
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (const int r = level_r(a.res_div))
+                if (a.spade_wino4 && r <= opt.wino4_ace_max_r && wino4v_pays(2 * a.C, r)) need = std::max(need, wino4v_bytes(mb, r, r, 38));
+        });
+        // the Zencoder's 256 -> 512 conv on the half-resolution grid: 9 bytes x 256 channels x (ms / 2)^2 per sample -- up to 2.5 GB only
+        if (m.z14_wino4 && (ms / 2) % 32 == 0 && wino4v_bytes(mb, ms / 2, ms / 2, 64) <= ((size_t)5 << 29)) need = std::max(need, wino4v_bytes(mb, ms / 2, ms / 2, 64));
+        if (need) {
+            m.vbuf = static_cast<float*>(B.dalloc(need));
+            m.vbuf_bytes = need;
+        }
+    }
+
     // ---- exact SPADE-interior reduction: classification buffers per level, work lists per (level, row tiles) ------------
-    for (int k = 0; k < 6; ++k) {
-        sp_level[k][0] = sp_level[k][1] = SparseLevel();
-        sp_work[k].clear();
-    }
-    gtab = gtab_side = nullptr;
-    if (sparse) {
+    std::string sparse_levels() {
+        m.prof_stats_cap = 16384;
+        m.prof_stats_used = 0;
+        m.prof_stats = static_cast<int*>(B.dalloc((size_t)m.prof_stats_cap * 4 * sizeof(int)));
+        for (int k = 0; k < 6; ++k) {
+            m.sp_level[k][0] = m.sp_level[k][1] = SparseLevel();
+            m.sp_work[k].clear();
+        }
+        m.gtab = m.gtab_side = nullptr;
+        if (!opt.sparse) return "";
         int cmax = 0;
-        for (const auto& b : blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1}) {
-                if (!a) continue;
-                int k = 0;
-                while ((1 << k) < a->res_div) ++k;
-                const int r = ms >> k;
-                if (r < sparse_min_r || r < 32) continue;
-                const int mt = (a->C + 31) / 32;
-                // f16x3 path: tile-skip mode of the wave-specialised kernel, whose tiles are 32 x 16
-                const int th = use_sh16 ? 16 : sparse_tile_h(mt, r);
-                SparseLevel& L = sp_level[k][th == 16 ? 1 : 0];
-                if (!L.u5) {
-                    L.TH = th;
-                    L.cap_tiles = mb * ((r + 31) / 32) * ((r + L.TH - 1) / L.TH);
-                    L.u5 = static_cast<uint8_t*>(B.dalloc((size_t)mb * r * r));
-                    L.e16 = (edge && (use_sh16 || wino) && r >= 128) ? static_cast<uint16_t*>(B.dalloc((size_t)mb * r * r * sizeof(uint16_t))) : nullptr;
-                    L.need = static_cast<uint8_t*>(B.dalloc((size_t)mb * r * r));
-                    L.list = static_cast<uint16_t*>(B.dalloc((size_t)L.cap_tiles * 32 * L.TH * sizeof(uint16_t)));
-                    L.cnt = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
-                }
-                bool have = false;
-                for (const auto& w : sp_work[k]) have = have || w.mtiles == mt;
-                if (!have) {
-                    SparseWork w;
-                    w.mtiles = mt;
-                    w.TH = L.TH;
-                    w.mode = use_sh16 ? (sh16_compact ? (sh16_compact >= 2 ? 2 : 3) : 1) : 0;   // 3: with pair entries
-                    w.cap = (long long)L.cap_tiles * (use_sh16 ? mt : sparse_max_tasks(L.TH, mt));
-                    w.work = static_cast<unsigned*>(B.dalloc((size_t)w.cap * sizeof(unsigned)));
-                    w.total = static_cast<int*>(B.dalloc(4 * sizeof(int)));
-                    if (w.mode == 3) {
-                        w.work2 = static_cast<unsigned*>(B.dalloc((size_t)L.cap_tiles * ((mt + 1) / 2) * sizeof(unsigned)));
-                        w.total2 = static_cast<int*>(B.dalloc(4 * sizeof(int)));
-                        if (mt >= 4 && !(dbg & 67108864))
-                            w.work3 = static_cast<unsigned*>(B.dalloc((size_t)L.cap_tiles * ((mt + 3) / 4) * sizeof(unsigned)));
-                    }
-                    sp_work[k].push_back(w);
-                }
-                cmax = std::max(cmax, a->C);
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            const int k = level_of(a.res_div), r = ms >> k;
+            if (r < opt.sparse_min_r || r < 32) return;
+            const int mt = (a.C + 31) / 32;
+            // f16x3 path: tile-skip mode of the wave-specialised kernel, whose tiles are 32 x 16
+            const int th = opt.use_sh16 ? 16 : opt.sparse_tile_h(mt, r);
+            SparseLevel& L = m.sp_level[k][th == 16 ? 1 : 0];
+            if (!L.u5) {
+                L.TH = th;
+                L.cap_tiles = mb * ((r + 31) / 32) * ((r + L.TH - 1) / L.TH);
+                L.u5 = static_cast<uint8_t*>(B.dalloc((size_t)mb * r * r));
+                L.e16 = (opt.edge && (opt.use_sh16 || opt.wino) && r >= 128) ? static_cast<uint16_t*>(B.dalloc((size_t)mb * r * r * sizeof(uint16_t))) : nullptr;
+                L.need = static_cast<uint8_t*>(B.dalloc((size_t)mb * r * r));
+                L.list = static_cast<uint16_t*>(B.dalloc((size_t)L.cap_tiles * 32 * L.TH * sizeof(uint16_t)));
+                L.cnt = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
             }
-        if (cmax) gtab = B.falloc((size_t)mb * LABEL_NC * 2 * cmax);
-        if (cmax && overlap_on) gtab_side = B.falloc((size_t)mb * LABEL_NC * 2 * cmax);
-        p6 = (cmax && edge && (use_sh16 || wino)) ? B.falloc((size_t)mb * LABEL_NC * 6 * 2 * cmax) : nullptr;      // (straight-edge pixels: ace_sparse.h)
+            bool have = false;
+            for (const auto& w : m.sp_work[k]) have = have || w.mtiles == mt;
+            if (!have) {
+                SparseWork w;
+                w.mtiles = mt;
+                w.TH = L.TH;
+                w.mode = opt.use_sh16 ? (opt.sh16_compact ? (opt.sh16_compact >= 2 ? 2 : 3) : 1) : 0;   // 3: with pair entries
+                w.cap = (long long)L.cap_tiles * (opt.use_sh16 ? mt : sparse_max_tasks(L.TH, mt));
+                w.work = static_cast<unsigned*>(B.dalloc((size_t)w.cap * sizeof(unsigned)));
+                w.total = static_cast<int*>(B.dalloc(4 * sizeof(int)));
+                if (w.mode == 3) {
+                    w.work2 = static_cast<unsigned*>(B.dalloc((size_t)L.cap_tiles * ((mt + 1) / 2) * sizeof(unsigned)));
+                    w.total2 = static_cast<int*>(B.dalloc(4 * sizeof(int)));
+                    if (mt >= 4 && !(opt.dbg & 67108864))
+                        w.work3 = static_cast<unsigned*>(B.dalloc((size_t)L.cap_tiles * ((mt + 3) / 4) * sizeof(unsigned)));
+                }
+                m.sp_work[k].push_back(w);
+            }
+            cmax = std::max(cmax, a.C);
+        });
+        if (cmax) m.gtab = B.falloc((size_t)mb * LABEL_NC * 2 * cmax);
+        if (cmax && m.overlap_on) m.gtab_side = B.falloc((size_t)mb * LABEL_NC * 2 * cmax);
+        m.p6 = (cmax && opt.edge && (opt.use_sh16 || opt.wino)) ? B.falloc((size_t)mb * LABEL_NC * 6 * 2 * cmax) : nullptr;      // (straight-edge pixels: ace_sparse.h)
+        return "";
     }
-    if (!B.err.empty()) return B.err;
+};
+
+}  // namespace
+
+std::string SeanModel::build(const TensorStore& ts, int mb, int ms) {
+    SeanBuild s(*this, ts, mb, ms);
+    typedef std::string (SeanBuild::*Stage)();
+    static const Stage stages[] = {&SeanBuild::dims,      &SeanBuild::fc_and_img, &SeanBuild::res_blocks,  &SeanBuild::zencoder,
+                                   &SeanBuild::run_ahead, &SeanBuild::arena,      &SeanBuild::wino_levels, &SeanBuild::sparse_levels};
+    for (Stage stage : stages) {
+        const std::string e = (s.*stage)();
+        if (!e.empty()) return e;
+    }
+    if (!s.B.err.empty()) return s.B.err;
     if (hipDeviceSynchronize() != hipSuccess) return "hipDeviceSynchronize failed after weight upload";
     return "";
 }
+
 
 void SeanModel::destroy() {
     for (void* p : allocs) (void)hipFree(p);
@@ -915,15 +1003,15 @@ struct Runner {
     void tap_sh16(const std::string& name, const float* src, int C, size_t hw, const AceW& producer) {
         auto it = m.taps.find(name);
         if (it == m.taps.end() || !it->second) return;
-        if (m.use_sh16)
-            check(sh16_decode(src, it->second, B, C, (long long)hw, producer.out_scale, m.amax_slots + 2 * producer.index, st, m.terms == 2), "tap decode");
+        if (m.opt.use_sh16)
+            check(sh16_decode(src, it->second, B, C, (long long)hw, producer.out_scale, m.amax_slots + 2 * producer.index, st, m.opt.terms == 2), "tap decode");
         else check(hipMemcpyAsync(it->second, src, (size_t)B * C * hw * 4, hipMemcpyDeviceToDevice, st), "tap copy");
     }
     // f32 tensors between kernels are NCHW on the exact-f32 path and C4 ([B][C/4][HW][4]) on the f16x3 path
     void tap_c4(const std::string& name, const float* src, int C, size_t hw) {
         auto it = m.taps.find(name);
         if (it == m.taps.end() || !it->second) return;
-        if (m.use_sh16) check(c4_decode(src, it->second, B, C, (long long)hw, st), "tap decode");
+        if (m.opt.use_sh16) check(c4_decode(src, it->second, B, C, (long long)hw, st), "tap decode");
         else check(hipMemcpyAsync(it->second, src, (size_t)B * C * hw * 4, hipMemcpyDeviceToDevice, st), "tap copy");
     }
     void tap(const std::string& name, const float* src, size_t floats) {
@@ -938,19 +1026,13 @@ struct Runner {
         if (!m.claim_pool || claim_next >= SeanModel::CLAIM_SLOTS) return nullptr;
         return m.claim_pool + (size_t)SeanModel::CLAIM_WORDS * claim_next++;
     }
-    static int lk_of(const AceW& a) {
-        int k = 0;
-        while ((1 << k) < a.res_div) ++k;
-        return k;
-    }
     // exact SPADE-interior reduction: the level's classification and the work list of (level, row tiles), once per chunk
     bool lvl_done[6][2] = {};
     std::vector<int> work_done[6];
     const SparseWork* sparse_prepare(const AceW& a, const uint8_t* lab, int r) {
-        int k = 0;
-        while ((1 << k) < a.res_div) ++k;
+        const int k = level_of(a.res_div);
         const int mt = (a.C + 31) / 32;
-        if (!m.sparse || r < m.sparse_min_r || r < 32) return nullptr;
+        if (!m.opt.sparse || r < m.opt.sparse_min_r || r < 32) return nullptr;
         for (const auto& w : m.sp_work[k])
             if (w.mtiles == mt) {
                 const int ti = w.TH == 16 ? 1 : 0;
@@ -958,7 +1040,7 @@ struct Runner {
                 if (!L.u5) return nullptr;
                 const int ntiles = B * ((r + 31) / 32) * ((r + L.TH - 1) / L.TH);
                 // f16x3 / f16 / bf16 path, pixel-level compaction: the interior pass knows the straight-edge pixels (ace_interior_sh16_tile_kernel)
-                const bool want = m.use_sh16 && m.edge && L.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && w.mode >= 2;
+                const bool want = m.opt.use_sh16 && m.opt.edge && L.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && w.mode >= 2;
                 if (!lvl_done[k][ti] || lvl_edges[k][ti] != want) {
                     // (a level classified WITH straight-edge marks for the Winograd ACEs and then needed by the direct sparse kernels of the
                     //  exact-f32 path, which do not know them: classified again without, and the quad lists of the level with it -- not
@@ -990,8 +1072,7 @@ struct Runner {
     std::vector<int> wwork_done[6];
     WinoPrep wino_prepare(const AceW& a, const uint8_t* lab, int r) {
         WinoPrep o;
-        int k = 0;
-        while ((1 << k) < a.res_div) ++k;
+        const int k = level_of(a.res_div);
         const SeanModel::WinoLevel& L = m.wq_level[k];
         if (!L.qlist) return o;
         const int nrt = (a.C + 15) / 16;
@@ -999,14 +1080,14 @@ struct Runner {
             if (w.nrt == nrt) o.W = &w;
         if (!o.W) return o;
         o.L = &L;
-        if (m.sparse && r >= m.sparse_min_r) {
+        if (m.opt.sparse && r >= m.opt.sparse_min_r) {
             for (int ti = 1; ti >= 0 && !o.S; --ti)
                 if (m.sp_level[k][ti].u5) {
                     const SparseLevel& S = m.sp_level[k][ti];
                     if (!lvl_done[k][ti]) {
                         // straight-edge pixels (ace_sparse.h): marked on the levels whose interior pass knows them (128 pixels and more) when
                         // the ACE carries its table -- every ACE of such a level does (res_div <= 4), checked in ace()
-                        const bool edges = m.edge && S.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && !m.overlap_on;      // (overlap mode: quad_only interior pass)
+                        const bool edges = m.opt.edge && S.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && !m.overlap_on;      // (overlap mode: quad_only interior pass)
                         check(ace_classify(lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, edges ? S.e16 : nullptr), "ace_classify");
                         lvl_done[k][ti] = true;
                         lvl_edges[k][ti] = edges;
@@ -1032,16 +1113,12 @@ struct Runner {
         return o;
     }
     const uint8_t* labels_at(const uint8_t* full, int res_div) {
-        if (res_div == 1) return full;
-        int k = 0;
-        while ((1 << k) < res_div) ++k;
-        return m.lab_r[k];
+        return res_div == 1 ? full : m.lab_r[level_of(res_div)];
     }
     // the interior map of an ACE's level once its classification has run in this chunk (else nullptr)
     const uint8_t* level_u5(const AceW& a, int r) const {
-        if (!m.sparse || r < m.sparse_min_r) return nullptr;
-        int k = 0;
-        while ((1 << k) < a.res_div) ++k;
+        if (!m.opt.sparse || r < m.opt.sparse_min_r) return nullptr;
+        const int k = level_of(a.res_div);
         for (int ti = 1; ti >= 0; --ti)
             if (m.sp_level[k][ti].u5 && lvl_done[k][ti]) return m.sp_level[k][ti].u5;
         return nullptr;
@@ -1049,12 +1126,10 @@ struct Runner {
     // classification, quad lists and task lists of every Winograd ACE level up front (they depend on the labels only): the label
     // tables that run ahead on the side stream need the interior maps
     void prepass(const uint8_t* labfull) {
-        for (const auto& b : m.blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1}) {
-                if (!a) continue;
-                const int r = S / a->res_div;
-                if (use_wino_ace(*a, r) && !use_wino4_ace(*a, r)) (void)wino_prepare(*a, labels_at(labfull, a->res_div), r);
-            }
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            const int r = S / a.res_div;
+            if (use_wino_ace(a, r) && !use_wino4_ace(a, r)) (void)wino_prepare(a, labels_at(labfull, a.res_div), r);
+        });
     }
 
     // What an ACE needs that depends on the label map and the style codes only -- never on the activations flowing
@@ -1070,10 +1145,8 @@ struct Runner {
     // been sized at build time (they exist where (max_size >> k) % 32 == 0; a smaller S can reach a 32-grid level that max_size
     // does not have, e.g. max_size = 96, S = 64 -- ADVICE r04), else the ACE takes the direct kernels and their [B][128][H][W] layout
     bool use_wino_ace(const AceW& a, int r) const {
-        if (!(m.wino && !m.use_sh16 && a.spade_wino && r >= 32 && r % 32 == 0)) return false;
-        int k = 0;
-        while ((1 << k) < a.res_div) ++k;
-        const SeanModel::WinoLevel& L = m.wq_level[k];
+        if (!(m.opt.wino && !m.opt.use_sh16 && a.spade_wino && r >= 32 && r % 32 == 0)) return false;
+        const SeanModel::WinoLevel& L = m.wq_level[level_of(a.res_div)];
         if (!L.qlist) return false;
         const int nrt = (a.C + 15) / 16;
         for (const auto& w : L.works)
@@ -1085,8 +1158,8 @@ struct Runner {
     // SPADE conv of this ACE as F(4x4,3x3) over every tile of the level (conv_wino4.h): the low-resolution levels, where nearly every
     // tile holds a boundary pixel -- no classification, no interior pass, hidden activations at every pixel
     bool use_wino4_ace(const AceW& a, int r) const {
-        return use_wino_ace(a, r) && m.wino >= 2 && a.spade_wino4 && r <= m.wino4_ace_max_r && wino4_ace_supported(r, r, a.C) && (!a.styled || m.wsty4) &&
-               (m.wino4_force || m.batch_inv || wino4_pays((long long)B * (r / 32) * (r / 32) * ((a.C + 15) / 16), m.num_cus));      // (few tasks per CU -- single images -- : the gather kernel)
+        return use_wino_ace(a, r) && m.opt.wino >= 2 && a.spade_wino4 && r <= m.opt.wino4_ace_max_r && wino4_ace_supported(r, r, a.C) && (!a.styled || m.wsty4) &&
+               (m.opt.wino4_force || m.opt.batch_inv || wino4_pays((long long)B * (r / 32) * (r / 32) * ((a.C + 15) / 16), m.num_cus));      // (few tasks per CU -- single images -- : the gather kernel)
     }
     AcePrep ace_prepare(const AceW& a, const uint8_t* labfull, const float* codes, hipStream_t s, float* actv_buf, float* lut_buf,
                         float* splitk, bool prof, int what = 3, const uint8_t* need = nullptr, const int* tile_cnt = nullptr,
@@ -1103,17 +1176,17 @@ struct Runner {
         if (a.styled && (what & 1)) {
             q.lut = lut_buf;
             // f16x3 path: one extra all-zero column per sample (mu = 0 -> LUT = 0) that taps outside the image point at
-            const int bs = m.use_sh16 ? LABEL_NC + 1 : LABEL_NC;
+            const int bs = m.opt.use_sh16 ? LABEL_NC + 1 : LABEL_NC;
             const int N = B * bs, npad = ((N + 31) / 32) * 32;
             q.lut_bs = bs;
             const double fl = 2.0 * 18 * a.C * STYLE * N, by = 4.0 * (18.0 * a.C * STYLE + (double)STYLE * N + 18.0 * a.C * N);
-            if (a.lut_rows && N <= 64 && !m.batch_inv) {
+            if (a.lut_rows && N <= 64 && !m.opt.batch_inv) {
                 // interactive batch sizes: P[n][row] = sum_k W[row][k] mu[n][k] as a batched GEMV (weight-bandwidth bound)
                 check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, m.mu_img, 0, bs), "fc_mu");
                 tm(fl, by, [&] {
                     check(lut_gemv_mfma(m.mu_img, a.lut_rows, lut_buf, N, 18 * a.C, s), "lut gemv");
                 });
-            } else if (m.use_sh16) {
+            } else if (m.opt.use_sh16) {
                 // f16x3 LUT GEMM: 1x1 conv over the [npad/32 x 32] "image" of (sample, label) columns, C4 output
                 unsigned* mu_slot = m.amax_slots + 2 * a.index + 1;
                 const float* mu = m.mu_img;
@@ -1121,7 +1194,7 @@ struct Runner {
                     mu = m.mu_all + (size_t)a.index * m.mu_stride;
                 } else {
                     for (int pass = 0; pass < 2; ++pass)     // second pass: returns at once unless the first one left the f16 window
-                        check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 1, bs, SH16_ACT_SCALE, mu_slot, pass, m.terms == 2), "fc_mu");
+                        check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 1, bs, SH16_ACT_SCALE, mu_slot, pass, m.opt.terms == 2), "fc_mu");
                 }
                 ConvParams p{};
                 p.in = mu;
@@ -1134,7 +1207,7 @@ struct Runner {
                 p.Mrows = 18 * a.C;
                 p.pad = -1;
                 p.act = ACT_NONE;
-                p.terms = m.terms;
+                p.terms = m.opt.terms;
                 p.wscale = a.lut_wscale;
                 p.in_scale_inv = 1.f / SH16_ACT_SCALE;
                 p.in_amax = mu_slot;
@@ -1146,7 +1219,7 @@ struct Runner {
                 q.lut_ns = 4;
             } else {
                 const float* mu = m.mu_img;
-                if (m.fcmu_batched && (N > 64 || m.batch_inv)) mu = m.mu_all + (size_t)a.index * m.mu_stride;      // projected at the start of the chunk (generate())
+                if (m.fcmu_batched && (N > 64 || m.opt.batch_inv)) mu = m.mu_all + (size_t)a.index * m.mu_stride;      // projected at the start of the chunk (generate())
                 else check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s), "fc_mu");
                 ConvParams p{};
                 p.in = mu;
@@ -1166,10 +1239,10 @@ struct Runner {
         // a buffer that held the padded planes of a Winograd level (zero columns cleared once per geometry) and now receives the
         // direct [B][HID][r][r] layout -- the same ACE at another image size on a run-ahead handle -- must have its pads cleared again
         // before the next padded use: the direct kernels write over them
-        if (m.use_sh16 || !use_wino_ace(a, r)) m.pad_state.erase(actv_buf);
-        if (m.use_sh16)
-            check(onehot_conv3x3_sh16(lab, a.actv_table, a.actv_bias, actv_buf, B, r, r, HID, 1, a.actv_scale, s, m.terms == 2, need, tile_cnt,
-                                      (m.dbg & 33554432) ? 1 : 0), "mlp_shared");
+        if (m.opt.use_sh16 || !use_wino_ace(a, r)) m.pad_state.erase(actv_buf);
+        if (m.opt.use_sh16)
+            check(onehot_conv3x3_sh16(lab, a.actv_table, a.actv_bias, actv_buf, B, r, r, HID, 1, a.actv_scale, s, m.opt.terms == 2, need, tile_cnt,
+                                      (m.opt.dbg & 33554432) ? 1 : 0), "mlp_shared");
         else if (use_wino_ace(a, r)) {
             // Winograd ACE path: hidden activations (+ the one-hot planes of a styled ACE, which feed the style k-steps) in one
             // persistent pass into the padded planes the ACE kernels read (conv_wino.h WINO_AXOFF), whole 64-byte groups of pixels
@@ -1184,7 +1257,7 @@ struct Runner {
                 m.pad_state[actv_buf] = geo;
             }
             const bool pm = PL && PL->gq && PL->patch_mode && m.patchbuf;
-            check(spade_hidden_wq(lab, m.hidden_wq ? u5 : nullptr, a.actv_table, a.actv_bias, actv_buf, B, r, r, kout, a.styled ? 1 : 0, s,
+            check(spade_hidden_wq(lab, m.opt.hidden_wq ? u5 : nullptr, a.actv_table, a.actv_bias, actv_buf, B, r, r, kout, a.styled ? 1 : 0, s,
                                   wino_apitch(r), WINO_AXOFF, pm ? PL->patch_mode : nullptr), "mlp_shared (boundary-quad patches)");
             // few, scattered boundary quads: their patches pre-gathered instead (one of the two kernels returns at once: device flag)
             if (pm) check(spade_hidden_patch(lab, PL->gq, PL->gq_n, PL->gq_cap, PL->chunk_base, PL->patch_mode, a.actv_table, a.actv_bias, m.patchbuf,
@@ -1212,17 +1285,16 @@ struct Runner {
         prepared.assign(m.n_aces, AcePrep());
         check(hipEventRecord(m.ev_fork, st), "fork");
         check(hipStreamWaitEvent(m.side, m.ev_fork, 0), "fork wait");
-        for (const auto& b : m.blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1}) {
-                if (!a || (!full && !a->styled)) continue;
-                const int ra = S / a->res_div;
-                AcePrep e = ace_prepare(*a, labfull, codes, m.side, m.actv_ahead[a->index], m.lut_ahead[a->index], m.splitk_side, false,
-                                        full ? (luts_ready ? 2 : 3) : 1, nullptr, nullptr,
-                                        (use_wino_ace(*a, ra) && !use_wino4_ace(*a, ra)) ? level_u5(*a, ra) : nullptr);
-                if (luts_ready && a->styled) lut_entry(*a, e);          // (the grouped launch on the main stream built it)
-                prepared[a->index] = e;
-                check(hipEventRecord(m.ev_join[a->index], m.side), "join record");
-            }
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (!full && !a.styled) return;
+            const int ra = S / a.res_div;
+            AcePrep e = ace_prepare(a, labfull, codes, m.side, m.actv_ahead[a.index], m.lut_ahead[a.index], m.splitk_side, false,
+                                    full ? (luts_ready ? 2 : 3) : 1, nullptr, nullptr,
+                                    (use_wino_ace(a, ra) && !use_wino4_ace(a, ra)) ? level_u5(a, ra) : nullptr);
+            if (luts_ready && a.styled) lut_entry(a, e);          // (the grouped launch on the main stream built it)
+            prepared[a.index] = e;
+            check(hipEventRecord(m.ev_join[a.index], m.side), "join record");
+        });
     }
 
     // Exact-f32 path, more than 64 (sample, label) columns: the style LUTs P[(sample, label)][18 C] of ALL styled ACEs from one
@@ -1241,10 +1313,9 @@ struct Runner {
         timed(2, 2.0 * m.lut_group_rows * STYLE * N, 4.0 * (m.lut_group_rows * STYLE + m.lut_group_rows * N + (double)m.lut_ngroups * STYLE * N),
               [&] { check(conv_pw_grouped(q, m.lut_group_tiles * nrg, st), "style LUTs (grouped GEMM)"); });
         prepared.assign(m.n_aces, AcePrep());
-        for (const auto& b : m.blocks)
-            for (const AceW* a : {b.learned ? &b.ace_s : nullptr, &b.ace_0, &b.ace_1}) {
-                if (a && a->styled) lut_entry(*a, prepared[a->index]);
-            }
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (a.styled) lut_entry(a, prepared[a.index]);
+        });
         luts_ready = true;
     }
 
@@ -1260,39 +1331,30 @@ struct Runner {
         WinoPrep wp;
         if (wino_ace && !f4_ace) wp = wino_prepare(a, lab, r);
         const SparseWork* sw = (wino_ace && (wp.L || f4_ace)) ? nullptr : sparse_prepare(a, lab, r);
-        if (sw && m.use_sh16) {
+        if (sw && m.opt.use_sh16) {
             ConvParams t{};
             t.C = a.C;
             t.W = t.H = r;
             t.B = B;
             t.Cin = HID;
-            t.dbg = m.dbg;
+            t.dbg = m.opt.dbg;
             if (!sh16_ace_uses_ws(t)) sw = nullptr;
         }
-        const SparseLevel* SL = nullptr;
-        if (sw) {
-            int lk = 0;
-            while ((1 << lk) < a.res_div) ++lk;
-            SL = &m.sp_level[lk][sw->TH == 16 ? 1 : 0];
-        }
+        const SparseLevel* SL = sw ? &m.sp_level[level_of(a.res_div)][sw->TH == 16 ? 1 : 0] : nullptr;
         // the label-table kernel only writes the hidden activations the conv will read
         // (exact-f32 path: skipping pixels of the NCHW planes made the kernel slower at every granularity tried -- it is bound by
         // its LDS table reads, not by the writes; the map stays available behind sean.dbg bit 131072)
-        const uint8_t* need0 = (SL && !m.use_sh16 && (m.dbg & 131072)) ? SL->need : nullptr;
+        const uint8_t* need0 = (SL && !m.opt.use_sh16 && (m.opt.dbg & 131072)) ? SL->need : nullptr;
         const uint8_t* need = need0;
-        const bool compact = SL && m.use_sh16 && sw->mode >= 2;      // f16x3: pixel-level compaction inside the ws kernel
+        const bool compact = SL && m.opt.use_sh16 && sw->mode >= 2;      // f16x3: pixel-level compaction inside the ws kernel
         if (compact) need = SL->need;
-        const int* tile_cnt = (SL && m.use_sh16 && !compact) ? SL->cnt : nullptr;
+        const int* tile_cnt = (SL && m.opt.use_sh16 && !compact) ? SL->cnt : nullptr;
         AcePrep q;
         const uint8_t* u5 = (wino_ace && wp.L && wp.S) ? wp.S->u5 : nullptr;      // (F(4x4,3x3) levels: every pixel is read)
         // the level whose pre-gathered patches may serve this ACE (gather mode, not run-ahead: the ahead buffers are per ACE)
         const SeanModel::WinoLevel* patch_level = (wino_ace && !f4_ace && wp.L && wp.L->gq && !ahead && m.patchbuf && !overlap) ? wp.L : nullptr;
         float* abuf = m.actv;                      // hidden activations: the Winograd ACE levels own padded buffers (pads zeroed once per size)
-        if (wino_ace) {
-            int lk = 0;
-            while ((1 << lk) < a.res_div) ++lk;
-            if (m.actv_lvl[lk]) abuf = m.actv_lvl[lk];
-        }
+        if (wino_ace && m.actv_lvl[level_of(a.res_div)]) abuf = m.actv_lvl[level_of(a.res_div)];
         if (ahead) {
             q = prepared[a.index];
             check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
@@ -1331,7 +1393,7 @@ struct Runner {
             const int ktot = w.wsty ? 152 : 128;             // (38 / 32 k-steps of four channels)
             next_flops_exec = 2.0 * 32.0 * ((a.C + 15) / 16) * ktot * 36.0 * npix / 16.0;
             // 2 C GEMM rows over 128 (+ 20) input planes: the input transform once for all C / 8 row tiles (conv_wino4v.h)
-            const bool vroute = m.wino4v && wino4v_pays(2 * a.C, r) && m.wino4v_fits(B, r, w.wsty ? 38 : 32);
+            const bool vroute = m.opt.wino4v && wino4v_pays(2 * a.C, r) && m.wino4v_fits(B, r, w.wsty ? 38 : 32);
             timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 4.0 * (npix * (HID + (a.styled ? 20 : 0)) + npix * a.C / (x_up ? 4.0 : 1.0) + npix * a.C), [&] {
                 if (w.wsty) check(wino4_style_pack(q.lut, m.wsty4, B, a.C, st), "wino4_style_pack");
                 if (vroute) {
@@ -1378,7 +1440,7 @@ struct Runner {
                 // four pixels per thread (16-byte stores) from 128 pixels of width: 530 -> 420 us on the up-sampled 512^2 launches
                 // (tools/interior_bench.hip); level in the 100 ms step of round 3, measurable in this one
                 ip.impl = r >= 128 ? 2 : 0;
-                ip.groups = m.int_groups;       // (tile4 kernel: channel groups per block, 0 = the launcher's rule; ace_sparse.hip)
+                ip.groups = m.opt.int_groups;       // (tile4 kernel: channel groups per block, 0 = the launcher's rule; ace_sparse.hip)
                 if (wp.edges) {         // straight-edge pixels: table row of the code + three column / row sums of the style LUT (built below)
                     if (!a.edge_tab || r < 128) check(hipErrorInvalidValue, "straight-edge marks on a level whose ACE has no table");
                     ip.e16 = wp.S->e16;
@@ -1387,7 +1449,7 @@ struct Runner {
                 }
                 // (tile4 kernel, r >= 128: 0 = whole 128-byte lines that hold an interior pixel, ace_sparse.hip; sean.dbg bit 134217728: the
                 //  block rule of rounds 3-5 for A/B)
-                ip.fill_min = (x_up && r < 128) ? 257 : ((r >= 128 && !(m.dbg & 134217728)) ? 0 : 128);
+                ip.fill_min = (x_up && r < 128) ? 257 : ((r >= 128 && !(m.opt.dbg & 134217728)) ? 0 : 128);
                 if (overlap) {
                     // beside the boundary conv of the same ACE (disjoint output pixels -- so no block may fill its boundary pixels),
                     // on the few CUs of the side stream; the consumer of `hout` waits for ev_int below
@@ -1474,14 +1536,14 @@ struct Runner {
         p.lut_bs = q.lut_bs;
         p.act = act;
         p.pad = -1;
-        p.dbg = m.dbg;
-        p.terms = m.terms;
+        p.dbg = m.opt.dbg;
+        p.terms = m.opt.terms;
         p.wscale = a.spade_wscale;
         p.in_scale_inv = 1.f / a.actv_scale;
         p.out_scale = a.out_scale;
         const double xin = npix * a.C / (x_up ? 4.0 : 1.0);
         p.out_amax = m.amax_slots + 2 * a.index;
-        if ((m.dbg & 256) && a.index == m.dbg_sel) p.partial = m.splitk_ws;      // cycle stamps of this launch (profiling)
+        if ((m.opt.dbg & 256) && a.index == m.opt.dbg_sel) p.partial = m.splitk_ws;      // cycle stamps of this launch (profiling)
         else p.dbg &= ~256;
         if (sw) {
             // interior pixels: elementwise with the per-(sample, label) gamma/beta rows; the others: conv over the compacted
@@ -1507,26 +1569,26 @@ struct Runner {
             ip.act = act;
             ip.out_scale = a.out_scale;
             ip.out_amax = m.amax_slots + 2 * a.index;
-            ip.bf16 = m.terms == 2;
-            ip.single = (m.use_sh16 && m.terms != 3 && !(m.dbg & 268435456)) ? 1 : 0;      // (dbg bit: A/B)
-            ip.variant = m.use_sh16 ? (compact ? 1 : 0) : (CH_ABL(m.dbg & 65536) ? 1 : (CH_ABL(m.dbg & 1048576) ? 2 : 0));
+            ip.bf16 = m.opt.terms == 2;
+            ip.single = (m.opt.use_sh16 && m.opt.terms != 3 && !(m.opt.dbg & 268435456)) ? 1 : 0;      // (dbg bit: A/B)
+            ip.variant = m.opt.use_sh16 ? (compact ? 1 : 0) : (CH_ABL(m.opt.dbg & 65536) ? 1 : (CH_ABL(m.opt.dbg & 1048576) ? 2 : 0));
             // blocks of 32 x 8 pixels; mostly-interior blocks write every pixel (the conv below overwrites the boundary pixels).
             // Exact-f32 pass: filling pays only where x is read at full size (measured, tools/interior_bench.hip).
             // dbg bit 2097152: the row-shaped kernels of the first version (A/B)
-            ip.impl = CH_ABL(m.dbg & 2097152) ? 1 : 0;
-            ip.fill_min = m.use_sh16 ? 128 : (x_up ? 257 : 128);
-            if (m.use_sh16 && compact && lvl_edges[lk_of(a)][sw->TH == 16 ? 1 : 0]) {      // straight-edge pixels served by the interior pass
+            ip.impl = CH_ABL(m.opt.dbg & 2097152) ? 1 : 0;
+            ip.fill_min = m.opt.use_sh16 ? 128 : (x_up ? 257 : 128);
+            if (m.opt.use_sh16 && compact && lvl_edges[level_of(a.res_div)][sw->TH == 16 ? 1 : 0]) {      // straight-edge pixels served by the interior pass
                 ip.e16 = L.e16;
                 ip.etab = a.edge_tab;
                 ip.p6 = (a.styled && q.lut) ? m.p6 : nullptr;
             }
             // (impl 2, four pixels per thread: 10 % ahead at 512^2 in tools/interior_bench.hip, no difference in the generator
             // step -- 159.7 vs 159.9 images/s -- so the one-pixel kernel stays; dbg bit 16777216 selects it)
-            if (!m.use_sh16 && CH_ABL(m.dbg & 16777216) && r >= 128) {
+            if (!m.opt.use_sh16 && CH_ABL(m.opt.dbg & 16777216) && r >= 128) {
                 ip.impl = 2;
                 ip.fill_min = 128;
             }
-            p.sp_list = (m.use_sh16 && !compact) ? nullptr : L.list;      // f16x3: the lists request the compacting kernel
+            p.sp_list = (m.opt.use_sh16 && !compact) ? nullptr : L.list;      // f16x3: the lists request the compacting kernel
             p.sp_cnt = L.cnt;
             p.sp_work = sw->work;
             p.sp_total = sw->total;
@@ -1535,17 +1597,17 @@ struct Runner {
             p.sp_work3 = sw->work3;
             timed(3, 0.0, 0.0, sw->total, 0.0, xpp + opp + 5.0, 4.0 * 19 * 2 * a.C * B, npix, [&] {
                 // (the f16x3 LUT is stored pre-multiplied by the ACE output scale)
-                check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, m.use_sh16 ? 1.f / a.out_scale : 1.f,
+                check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, m.opt.use_sh16 ? 1.f / a.out_scale : 1.f,
                                  m.gtab, B, a.C, st), "ace_gtable");
                 if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f / a.out_scale, m.p6, B, a.C, st), "ace_p6table");
-                check(m.use_sh16 ? ace_interior_sh16(ip, st) : ace_interior_f32(ip, st), "ace interior");
+                check(m.opt.use_sh16 ? ace_interior_sh16(ip, st) : ace_interior_f32(ip, st), "ace interior");
             });
             timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 0.0, sw->total, 32.0 * 64 * 2.0 * HID * 9, 4.0 * HID + xpp + opp,
                   4.0 * 2.0 * a.C * HID * 9, npix, [&] {
-                      if (m.use_sh16) check(conv_sh16_ace(p, st), "spade conv (tiles with boundary pixels)");
+                      if (m.opt.use_sh16) check(conv_sh16_ace(p, st), "spade conv (tiles with boundary pixels)");
                       else check(conv_ace_sparse(p, L.TH, st), "spade conv (boundary pixels)");
                   });
-            if (m.use_sh16) {      // second passes: return at once unless the recorded maximum left the f16 window (sh16.h)
+            if (m.opt.use_sh16) {      // second passes: return at once unless the recorded maximum left the f16 window (sh16.h)
                 ip.pass = 1;
                 check(ace_interior_sh16(ip, st), "ace interior (second pass)");
                 p.pass = 1;
@@ -1553,7 +1615,7 @@ struct Runner {
             }
             return;
         }
-        if (!m.use_sh16 && m.gb_small && !m.batch_inv) {
+        if (!m.opt.use_sh16 && m.gb_small && !m.opt.batch_inv) {
             // Tiny levels at small batches (one image at 16 x 16: 16 blocks of the fused kernel, 8 % of the CUs, 200 us): the SPADE conv as a
             // PLAIN conv over the same packed image -- which splits K over blocks when its grid is small (conv_mfma.h launch_conv) -- into
             // a scratch of gamma | beta sums, then ace_finish_f32 (style-LUT gathers, biases, modulation).  Same sums per element, the
@@ -1579,7 +1641,7 @@ struct Runner {
             }
         }
         timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 4.0 * (npix * HID + xin + npix * a.C + 2.0 * a.C * HID * 9), [&] {
-            if (!m.use_sh16) {
+            if (!m.opt.use_sh16) {
                 check(conv_ace(p, st), "spade conv");
                 return;
             }
@@ -1591,11 +1653,11 @@ struct Runner {
 
     // fuse: optional (weights, input) of a 1x1 conv added into this 3x3 conv's accumulators (f16x3 path, W >= 32, no split-K)
     bool can_fuse_1x1(const ConvW& w, int r) const {
-        return !(m.dbg & 32) && w.KS == 3 && r >= 32 &&
+        return !(m.opt.dbg & 32) && w.KS == 3 && r >= 32 &&
                !(((w.Cout + 63) / 64) * (((long long)B * r * r + 511) / 512) < 192);
     }
     bool use_wino(const ConvW& w, int r) const {
-        return m.wino && !m.use_sh16 && w.wino && w.KS == 3 && (wino_supported(r, r, w.Cin) || (!m.batch_inv && wino_supported_pair16(B, r, r, w.Cin)));
+        return m.opt.wino && !m.opt.use_sh16 && w.wino && w.KS == 3 && (wino_supported(r, r, w.Cin) || (!m.opt.batch_inv && wino_supported_pair16(B, r, r, w.Cin)));
     }
     // `prod` / `prod2`: the ACEs that wrote `in` / `in2` (their slots hold the scale in effect)
     void conv(const ConvW& w, const float* in, const AceW& prod, float* out, int r, const float* res, int res_up,
@@ -1621,16 +1683,16 @@ struct Runner {
         p.res_up = res_up;
         p.act = ACT_NONE;
         p.pad = -1;
-        p.dbg = m.dbg;
-        p.terms = m.terms;
+        p.dbg = m.opt.dbg;
+        p.terms = m.opt.terms;
         p.wscale = w.wscale;                       // shared with w2's rows when a 1x1 operand is fused (build())
         p.in_scale_inv = 1.f / prod.out_scale;     // inputs are ACE outputs (a fused second operand: see sh16_in_scale_inv)
-        p.partial = m.batch_inv ? nullptr : m.splitk_ws;      // (split-K follows the grid size, i.e. the batch)
+        p.partial = m.opt.batch_inv ? nullptr : m.splitk_ws;      // (split-K follows the grid size, i.e. the batch)
         p.partial_cap = m.splitk_cap;
         p.mtiles_hint_small = (((w.Cout + 63) / 64) * (((long long)B * r * r + 511) / 512) < 192) ? 1 : 0;
         const double npix = (double)B * r * r, k2 = w.KS * w.KS, cin2 = w2 ? w2->Cin : 0;
-        if (m.wino >= 2 && !m.use_sh16 && w.wino4 && w.KS == 3 && !w2 && wino4_supported(r, r, w.Cin) &&
-            (!use_wino(w, r) || m.wino4_force || m.batch_inv || wino4_pays((long long)B * (r / 32) * (r / 32) * ((w.Cout + 31) / 32), m.num_cus))) {
+        if (m.opt.wino >= 2 && !m.opt.use_sh16 && w.wino4 && w.KS == 3 && !w2 && wino4_supported(r, r, w.Cin) &&
+            (!use_wino(w, r) || m.opt.wino4_force || m.opt.batch_inv || wino4_pays((long long)B * (r / 32) * (r / 32) * ((w.Cout + 31) / 32), m.num_cus))) {
             // Winograd F(4x4,3x3) on the exact-f32 matrix cores: 36 MFMA products per 4 x 4 tile and channel instead of 144
             Wino4Params q{};
             q.in = in;
@@ -1645,10 +1707,10 @@ struct Runner {
             q.res = res;
             q.res_up = res_up;
             q.wpk_split = w.wino4s;
-            q.split = m.wino4_split;
+            q.split = m.opt.wino4_split;
             next_flops_exec = 2.0 * w.Cout * w.Cin * 36.0 * npix / 16.0;
             // many GEMM rows on a small level: the input transform once, in its own pass, instead of in every row tile (conv_wino4v.h)
-            const bool vroute = m.wino4v && wino4v_pays(w.Cout, r) && m.wino4v_fits(B, r, w.Cin / 4);
+            const bool vroute = m.opt.wino4v && wino4v_pays(w.Cout, r) && m.wino4v_fits(B, r, w.Cin / 4);
             timed(0, 2.0 * w.Cout * w.Cin * 9.0 * npix,
                   4.0 * (npix * w.Cin + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * w.Cin * 36.0), [&] {
                       if (vroute) {
@@ -1684,7 +1746,7 @@ struct Runner {
             q.act = ACT_NONE;
             q.zero = m.zero_page;
             q.claim = next_claim();
-            q.partial = m.batch_inv ? nullptr : m.splitk_ws;               // (launches with far fewer tasks than CUs split K: conv_wino_plain)
+            q.partial = m.opt.batch_inv ? nullptr : m.splitk_ws;               // (launches with far fewer tasks than CUs split K: conv_wino_plain)
             q.partial_cap = m.splitk_cap;
             next_flops_exec = 2.0 * w.Cout * w.Cin * 16.0 * npix / 4.0;
             timed(0, 2.0 * w.Cout * w.Cin * 9.0 * npix,
@@ -1692,7 +1754,7 @@ struct Runner {
                   [&] { check(conv_wino_plain(q, st), "conv (winograd)"); });
             return;
         }
-        if (m.wino && !m.use_sh16 && w.pw && w.KS == 1 && !w2 && !res && !w.bias && pw_supported(w.Cin, w.Cout, r * r)) {
+        if (m.opt.wino && !m.opt.use_sh16 && w.pw && w.KS == 1 && !w2 && !res && !w.bias && pw_supported(w.Cin, w.Cout, r * r)) {
             PwParams q{};         // the learned shortcut conv_s: dedicated 1x1 kernel (conv_pw.h)
             q.in = in;
             q.wpk = w.pw;
@@ -1707,7 +1769,7 @@ struct Runner {
         }
         timed(0, 2.0 * w.Cout * (w.Cin * k2 + cin2) * npix,
               4.0 * (npix * (w.Cin + cin2) + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * (w.Cin * k2 + cin2)), [&] {
-                  if (m.use_sh16) check(conv_sh16_plain(p, w.KS, st), "conv");
+                  if (m.opt.use_sh16) check(conv_sh16_plain(p, w.KS, st), "conv");
                   else check(w.KS == 3 ? conv_plain3(p, st) : conv_plain1(p, st), "conv");
               });
     }
@@ -1761,9 +1823,9 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             nz = noise_ws;
         }
         for (int k = 1; k <= 5; ++k) R.check(label_downsample(lab, lab_r[k], B, S, S >> k, st), "label_downsample");
-        if (use_sh16) R.check(hipMemsetAsync(amax_slots, 0, 64 * sizeof(unsigned), st), "amax slots");
-        if (fcmu_batched && !use_sh16) {
-            if (B * LABEL_NC > 64 || batch_inv) {     // (smaller batches take the GEMV branch of ace_prepare, which projects per ACE)
+        if (opt.use_sh16) R.check(hipMemsetAsync(amax_slots, 0, 64 * sizeof(unsigned), st), "amax slots");
+        if (fcmu_batched && !opt.use_sh16) {
+            if (B * LABEL_NC > 64 || opt.batch_inv) {     // (smaller batches take the GEMV branch of ace_prepare, which projects per ACE)
                 // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout)
                 const bool grouped = lut_groups && lut_ngroups > 0;
                 R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, ((B * LABEL_NC + 31) / 32) * 32, LABEL_NC, 1.f,
@@ -1774,25 +1836,25 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             const int npad_c = ((B * (LABEL_NC + 1) + 31) / 32) * 32;
             for (int pass = 0; pass < 2; ++pass)         // second pass: returns at once unless a projection left the f16 window
                 R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, npad_c, LABEL_NC + 1, SH16_ACT_SCALE,
-                                      amax_slots, pass, terms == 2, st), "fc_mu (all ACEs)");
+                                      amax_slots, pass, opt.terms == 2, st), "fc_mu (all ACEs)");
         }
         // interactive-size jobs: everything that depends on labels / codes only runs ahead on the side stream
-        if (side && !prof_on && !(dbg & 4096)) {
-            const bool ov = overlap_on && (long long)B * S * S > ahead_pixels && R.luts_ready;
+        if (side && !prof_on && !(opt.dbg & 4096)) {
+            const bool ov = overlap_on && (long long)B * S * S > ahead_limit && R.luts_ready;
             if (ov) {      // large job on an overlap handle: label tables of every ACE ahead on the CU-masked side stream, interior passes beside the convs
                 R.prepass(lab);
                 R.overlap = gtab_side != nullptr;
                 R.prepare_all_ahead(lab, cd, true);
-            } else if (ahead_full && (long long)B * S * S <= ahead_pixels) R.prepare_all_ahead(lab, cd, true);
+            } else if (ahead_full && (long long)B * S * S <= ahead_limit) R.prepare_all_ahead(lab, cd, true);
             // large jobs: only the style LUT builds (small, latency-bound GEMMs) run ahead, in the tails of the conv kernels
             // (exact-f32 path, B = 16 at 512^2: 147.2 -> 148.3 images/s)
-            else if ((fcmu_batched || !use_sh16) && !(dbg & 8192) && !R.luts_ready) R.prepare_all_ahead(lab, cd, false);
+            else if ((fcmu_batched || !opt.use_sh16) && !(opt.dbg & 8192) && !R.luts_ready) R.prepare_all_ahead(lab, cd, false);
         }
 
         const int sw = S / 32;
         float* x = xa;
         float* y = xb;
-        R.check(onehot_conv3x3(lab_r[5], fc_table, fc_bias, x, B, sw, sw, 16 * ngf, 0, st, use_sh16 ? 1 : 0), "fc");
+        R.check(onehot_conv3x3(lab_r[5], fc_table, fc_bias, x, B, sw, sw, 16 * ngf, 0, st, opt.use_sh16 ? 1 : 0), "fc");
         R.tap_c4("fc", x, 16 * ngf, (size_t)sw * sw);
         size_t noff = 0;
         for (const auto& b : blocks) {
@@ -1832,7 +1894,7 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             R.tap_c4(b.name, y, b.fout, rr);
             std::swap(x, y);
         }
-        R.check(conv_img_tanh(x, img_w, img_b, out + (size_t)bo * 3 * S * S, B, ngf, S, S, st, use_sh16 ? 1 : 0, img_w4), "conv_img");
+        R.check(conv_img_tanh(x, img_w, img_b, out + (size_t)bo * 3 * S * S, B, ngf, S, S, st, opt.use_sh16 ? 1 : 0, img_w4), "conv_img");
         if (!R.err.empty()) return join(R.err);
     }
     return join("");
@@ -1864,7 +1926,7 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
         ConvOpts last = refl;
         last.act = ACT_TANH;
         const int h2 = S / 2, h4 = S / 4;
-        const bool f16path = use_sh16 && h4 * h4 >= 4096;
+        const bool f16path = opt.use_sh16 && h4 * h4 >= 4096;
         bool in4_done = false;       // the ConvTranspose route already applied the InstanceNorm + lrelu that follows it
         if (phase != 2) {
         ck(conv3x3_c3_reflect(x, z1_w, z1.bias, hs, B, 32, S, S, st), "zenc conv1");
@@ -1910,7 +1972,7 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
             t.bias = z10.bias;
             t.in_scale_inv = 1.f / instnorm_sh16_scale(h4 * h4);
             t.act = ACT_NONE;
-            if (dbg & 16384) {           // the earlier form, kept for comparison: 3x3 conv over the zero-inserted x2 view
+            if (opt.dbg & 16384) {           // the earlier form, kept for comparison: 3x3 conv over the zero-inserted x2 view
                 t.wpk = z10_sh;
                 t.wscale = z10_ws;
                 t.H = h2;
@@ -1930,7 +1992,7 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
         } else {
             ck(instnorm_act(h1, B * 128, h4 * h4, 1e-5f, ACT_LRELU, st), "zenc in3");
             const long long hw4 = (long long)h4 * h4;
-            if (z10_pw[3] && !use_sh16 && !batch_inv && pw_supported(128, 256, (int)hw4) && (h4 & 3) == 0 && (long long)B * hw4 >= 16384 && vbuf &&
+            if (z10_pw[3] && !opt.use_sh16 && !opt.batch_inv && pw_supported(128, 256, (int)hw4) && (h4 & 3) == 0 && (long long)B * hw4 >= 16384 && vbuf &&
                 (size_t)B * (512 + 4 * 256) * hw4 * sizeof(float) <= vbuf_bytes) {
                 // four phase GEMMs over the shifted views (enough pixel tiles to fill the device; the V buffer is free until conv5's transform pass);
                 // the InstanceNorm + lrelu that follows reads the phase planes and writes the depth-to-space plane
@@ -1951,7 +2013,7 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
                 }
                 ck(instnorm_act_d2s(tph, z10.bias, hs, B, 256, h4, h4, 1e-5f, ACT_LRELU, st), "zenc in4 (depth-to-space)");
                 in4_done = true;
-            } else if (z10_wino && !use_sh16 && wino_supported(h4, h4, 128)) {
+            } else if (z10_wino && !opt.use_sh16 && wino_supported(h4, h4, 128)) {
                 WinoParams q{};
                 q.in = h1;
                 q.wpk = z10_wino;
@@ -1968,9 +2030,9 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
                 ck(conv_wino_plain(q, st), "zenc convT (winograd phase convs)");
             } else
                 ck(run_conv(z10, h1, hs, B, h4, h4, zins, st), "zenc convT");
-            if (use_sh16) ck(instnorm_act(hs, B * 256, h2 * h2, 1e-5f, ACT_LRELU, st, h1, 256), "zenc in4");
+            if (opt.use_sh16) ck(instnorm_act(hs, B * 256, h2 * h2, 1e-5f, ACT_LRELU, st, h1, 256), "zenc in4");
         }
-        if (use_sh16) {
+        if (opt.use_sh16) {
             ConvParams p{};
             p.in = h1;
             p.wpk = z14_sh;
@@ -1988,7 +2050,7 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
             ck(conv_sh16_plain(p, 3, st), "zenc conv5 (f16x3)");
         } else {
             if (!in4_done) ck(instnorm_act(hs, B * 256, h2 * h2, 1e-5f, ACT_LRELU, st), "zenc in4");
-            if (z14_wino4 && wino4_supported(h2, h2, 256) && (wino4_force || batch_inv || wino4_pays((long long)B * (h2 / 32) * (h2 / 32) * 16, num_cus))) {
+            if (z14_wino4 && wino4_supported(h2, h2, 256) && (opt.wino4_force || opt.batch_inv || wino4_pays((long long)B * (h2 / 32) * (h2 / 32) * 16, num_cus))) {
                 Wino4Params q{};
                 q.in = hs;
                 q.wpk = z14_wino4;
@@ -2002,8 +2064,8 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
                 q.act = ACT_TANH;
                 q.reflect = 1;
                 q.wpk_split = z14_wino4s;
-                q.split = wino4_split;
-                if (wino4v && wino4v_fits(B, h2, 64)) {          // 512 GEMM rows: the (reflected) input transform in its own pass
+                q.split = opt.wino4_split;
+                if (opt.wino4v && wino4v_fits(B, h2, 64)) {          // 512 GEMM rows: the (reflected) input transform in its own pass
                     Wino4vPackParams vp{};
                     vp.in = hs;
                     vp.v = vbuf;
@@ -2041,10 +2103,10 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
             continue;
         }
         ck(region_mean(h0, labels + (size_t)bo * S * S, codes_out + (size_t)bo * LABEL_NC * STYLE, B, STYLE, h2, h2, S, st,
-                       use_sh16 ? 1 : 0), "region_mean");
+                       opt.use_sh16 ? 1 : 0), "region_mean");
         auto it = taps.find("zenc.feat");
         if (it != taps.end() && it->second) {
-            if (use_sh16) ck(c4_decode(h0, it->second, B, STYLE, (long long)h2 * h2, st), "tap");
+            if (opt.use_sh16) ck(c4_decode(h0, it->second, B, STYLE, (long long)h2 * h2, st), "tap");
             else ck(hipMemcpyAsync(it->second, h0, (size_t)B * STYLE * h2 * h2 * 4, hipMemcpyDeviceToDevice, st), "tap");
         }
         if (!err.empty()) return err;

@@ -77,3 +77,37 @@ def test_size_limits_and_option_order(hip_lib):
     lab64 = torch.from_numpy(P.blocky_labels(1, 64, grid=8)).cuda()
     img = gen.generate(lab64, codes, None, seed=3)
     assert torch.isfinite(img).all()
+
+
+# ch_set_option: which keys ch_finalize(SEAN) freezes, which another model freezes, which stay live (include/ctrlhair_hip.h)
+SEAN_FROZEN_KEYS = ['sean.f16x3', 'sean.ahead', 'sean.wino', 'sean.lut_grouped', 'sean.overlap', 'sean.patch', 'sean.convt_gemm',
+                    'sean.edge', 'sean.wino4v', 'sean.wino4_split', 'sean.wino4_ace', 'sean.wino_gather', 'sean.wino_th',
+                    'sean.sh16_compact', 'sean.sparse_th', 'sean.sparse_min']
+LIVE_KEYS = {'aux.wino': 1, 'sean.wino4_force': 0, 'sean.int_groups': 0, 'sean.batch_invariant': 0, 'sean.hidden_wq': 1,
+             'sean.dbg_sel': 16, 'sean.dbg': 0, 'sean.sparse': 1}          # with the values they have by default
+OTHER_MODEL_KEYS = ['shape.f16x3', 'shape.overlap', 'shape.enc_lut', 'bisenet.f16x3']
+
+
+def test_option_freeze_table(hip_lib):
+    from ctrlhair_amd.sean.generator import SeanGenerator
+    sd = P.sean_state_dict(0, 16)
+    gen = SeanGenerator(0).load_state_dict(sd, max_batch=1, max_size=64)     # shape model and BiSeNet not finalized
+    h = gen.handle
+    for key in SEAN_FROZEN_KEYS:
+        rc, msg = raw(h, 'ch_set_option', key.encode(), 1)
+        assert rc == ERR_STATE and 'precede' in msg, (key, rc, msg)
+    for key in LIVE_KEYS:
+        assert raw(h, 'ch_set_option', key.encode(), LIVE_KEYS[key])[0] == OK, key
+    for key in OTHER_MODEL_KEYS:
+        assert raw(h, 'ch_set_option', key.encode(), 1)[0] == OK, key
+    rc, msg = raw(h, 'ch_set_option', b'sean.no_such_switch', 1)
+    assert rc == ERR_ARG and 'sean.no_such_switch' in msg
+    # a handle finalised without the interior reduction has no buffers for it: off stays possible, on does not
+    gen2 = SeanGenerator(0, options={'sean.sparse': 0}).load_state_dict(sd, max_batch=1, max_size=64)
+    assert raw(gen2.handle, 'ch_set_option', b'sean.sparse', 1)[0] == ERR_STATE
+    assert raw(gen2.handle, 'ch_set_option', b'sean.sparse', 0)[0] == OK
+    # both handles survived
+    lab = torch.from_numpy(P.blocky_labels(1, 64, grid=8)).cuda()
+    codes = torch.from_numpy(P.style_codes(1)).cuda()
+    for g in (gen, gen2):
+        assert torch.isfinite(g.generate(lab, codes, None, seed=3)).all()
