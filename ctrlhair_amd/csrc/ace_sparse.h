@@ -26,6 +26,14 @@
 // u5 = 253 with their code in e16 and are modulated by the interior pass -- no convolution; only corners, curved pieces and the image
 // frame are left to the boundary conv.  Same real number, another association of the f32 sum (as the interior pixels).
 //
+// Round 9 -- FRAME pixels (option "sean.frame", on top of "sean.edge"; exact-f32 Winograd path only).  The two outermost pixel rings of a
+// level can never be interior, whatever the labels.  A pixel within 2 of exactly ONE image border whose in-image window is uniformly
+// A < 19 sees a straight edge between A and the pseudo-label OUTSIDE: taps of mlp_shared (and of the style LUT) that fall outside add
+// nothing, and a hidden position that itself lies outside is the zero padding of the gamma / beta conv (normalization.py:240-247), not
+// relu(bias).  2 x 19 x 4 = 152 more codes behind the 2888, code = 2888 + ((o * 19 + A) * 4 + (s - 1)): the five lines of the window are
+// OUTSIDE^s A^(5-s) for s = 1, 2 (left / top border) and A^s OUTSIDE^(5-s) for s = 3, 4 (right / bottom border).  The 2 x 2 pixels at each
+// image corner (both axes cut) stay boundary pixels.
+//
 // Per resolution level and generate() chunk, ace_classify builds
 //      u5   [B][H][W]  uint8   label if the pixel is interior, else 255
 //      need [B][H][W]  uint8   1 where the boundary conv reads the SPADE hidden activations (the label-table kernel skips the rest)
@@ -63,7 +71,8 @@ __host__ __device__ inline int sparse_max_tasks(int TH, int mtiles) {
 
 struct SparseLevel {            // device buffers of one resolution level (sean_model.cpp allocates them at build())
     uint8_t* u5 = nullptr;
-    uint16_t* e16 = nullptr;    // [B][H][W] code of a straight-edge pixel (u5 == 253): ((orientation * 19 + A) * 19 + B) * 4 + (s - 1); or null
+    uint16_t* e16 = nullptr;    // [B][H][W] code of a straight-edge / frame pixel (u5 == 253): ((orientation * 19 + A) * 19 + B) * 4 + (s - 1), frame
+                                // pixels ACE_PAIR_CODES + (orientation * 19 + A) * 4 + (s - 1) (ace_code_decode); or null
     uint8_t* need = nullptr;    // [B][H][W] 1 where the boundary conv reads the SPADE hidden activations (3x3 around a boundary pixel)
     uint16_t* list = nullptr;
     int* cnt = nullptr;
@@ -86,12 +95,41 @@ struct SparseWork {             // block tasks of one (level, mtiles) pair
 
 // lab: [B][H][W] labels of the level.  Tiles of 32 x TH pixels (TH = 8 or 16).
 // e16 (may be null): also recognise the straight-edge pixels (u5 = 253, e16 = code); they are NOT boundary pixels of the lists
-constexpr int ACE_EDGE = 253, ACE_EDGE_CODES = 2 * 19 * 19 * 4;
+// frame (with e16): also the frame pixels (same mark, codes from ACE_PAIR_CODES on)
+constexpr int ACE_EDGE = 253, ACE_PAIR_CODES = 2 * 19 * 19 * 4, ACE_FRAME_CODES = 2 * 19 * 4, ACE_EDGE_CODES = ACE_PAIR_CODES + ACE_FRAME_CODES;
+constexpr int ACE_EDGE_HV = 19 + 19 * 19 * 2 + 19 * 2;      // hidden vectors per orientation (ace_edge_table)
+// A code taken apart: orientation o (0: the lines are columns, 1: rows), the labels A / B of its two sides and the number s of leading
+// lines.  line(i), i = 0..4: label of window line i; -1: the line lies outside the image (frame codes only).
+struct AceCode {
+    int o, A, B, s;
+    bool frame;
+    __host__ __device__ int line(int i) const {
+        if (frame) return (s <= 2 ? i >= s : i < s) ? A : -1;
+        return i < s ? A : B;
+    }
+};
+__host__ __device__ inline AceCode ace_code_decode(int code) {
+    AceCode k;
+    k.frame = code >= ACE_PAIR_CODES;
+    k.s = (code & 3) + 1;      // (ACE_PAIR_CODES % 4 == 0)
+    if (k.frame) {
+        const int r = (code - ACE_PAIR_CODES) >> 2;
+        k.A = k.B = r % 19;
+        k.o = r / 19;
+    } else {
+        k.B = (code >> 2) % 19;
+        k.A = ((code >> 2) / 19) % 19;
+        k.o = (code >> 2) / 361;
+    }
+    return k;
+}
+__host__ __device__ inline int ace_frame_code(int o, int A, int s) { return ACE_PAIR_CODES + ((o * 19 + A) * 4 + (s - 1)); }
 hipError_t ace_classify(const uint8_t* lab, uint8_t* u5, uint8_t* need, uint16_t* list, int* cnt, int B, int H, int W, int TH,
-                        hipStream_t s, uint16_t* e16 = nullptr);
+                        hipStream_t s, uint16_t* e16 = nullptr, bool frame = false);
 // E[code][gamma|beta][C] (float) from the column / row sums of the SPADE gamma/beta weights W6[gb][k][6][C] (double; 0..2: sum over dy of
-// tap (dy, dx = -1, 0, 1), 3..5: sum over dx of tap (dy = -1, 0, 1)) and the hidden vectors hv[orientation][741][128] (double; index 0..18:
-// a_j, 19 + (A * 19 + B) * 2 + (0: window X X Y = AAB | 1: window X Y Y = ABB)); scale_g / scale_b: the SPADE share of the blend;
+// tap (dy, dx = -1, 0, 1), 3..5: sum over dx of tap (dy = -1, 0, 1)) and the hidden vectors hv[orientation][ACE_EDGE_HV][128] (double; index
+// 0..18: a_j, 19 + (A * 19 + B) * 2 + (0: window X X Y = AAB | 1: window X Y Y = ABB), 741 + A * 2 + (0: window OUTSIDE A A | 1: window
+// A A OUTSIDE)); a hidden position of a frame code that lies outside adds nothing; scale_g / scale_b: the SPADE share of the blend;
 // bias_g / bias_b are added (the table rows are complete gamma / beta of an unstyled ACE)
 hipError_t ace_edge_table(const double* W6, const double* hv, const float* bias_g, const float* bias_b, float scale_g, float scale_b,
                           float* E, int C, hipStream_t s);
@@ -127,8 +165,8 @@ struct AceInteriorParams {
                                 // pixels -- the boundary conv, launched after this pass, overwrites the others; 0 = 128
     int quad_only;              // exact-f32 tile kernels: 1 = write an interior pixel only when its whole 2 x 2 quad is interior (the Winograd
                                 // boundary conv writes all four pixels of a boundary quad; needed when the two run concurrently)
-    const uint16_t* e16;        // exact-f32 tile4 kernel: codes of the straight-edge pixels (u5 == 253), or null
-    const float* etab;          //   E[2888][2][C] of this ACE (bias included)
+    const uint16_t* e16;        // exact-f32 tile4 kernel: codes of the straight-edge and frame pixels (u5 == 253), or null
+    const float* etab;          //   E[ACE_EDGE_CODES][2][C] of this ACE (bias included)
     const float* p6;            //   P6[(b, j)][6][2][C] of this call, or null (unstyled ACE)
     int variant;                // exact-f32 kernel: 0 = one pixel per thread (default), 1 = four pixels per thread (16-byte
                                 // accesses), 2 = one pixel per thread writing whole 32-byte sectors (A/B measurements)

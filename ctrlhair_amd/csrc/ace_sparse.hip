@@ -14,6 +14,9 @@ namespace chk {
 // e16 != nullptr: a pixel that is not interior but whose 5x5 neighbourhood (inside the image, labels < 19) is five uniform columns
 // A^s B^(5-s) or five uniform rows likewise (s = 1..4, A != B) is a STRAIGHT-EDGE pixel: u5 = 253, e16 = its code (ace_sparse.h); it is
 // not a boundary pixel for `need`, `list` and `cnt`.
+// frame (with e16): a pixel that is neither, has lines of its 5x5 window outside the image along exactly ONE axis and whose in-image window
+// labels all equal its own label A < 19 is a FRAME pixel: same mark, frame code (ace_sparse.h).  "Outside" is decided from the coordinates:
+// the patch value 255 is also the in-image label "no class", whose hidden activation is relu(...) and not the conv's zero padding.
 __device__ __forceinline__ int ace_edge_code(const uint8_t* w, int PW) {      // w: top-left of the 5x5 window in the LDS patch; -1: none
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
@@ -42,7 +45,7 @@ template <int TH>
 __global__ __launch_bounds__(32 * TH) void ace_classify_kernel(const uint8_t* __restrict__ lab, uint8_t* __restrict__ u5,
                                                              uint8_t* __restrict__ need, uint16_t* __restrict__ list,
                                                              int* __restrict__ cnt, int H, int W, int tiles_x, int tiles_y,
-                                                             uint16_t* __restrict__ e16) {
+                                                             uint16_t* __restrict__ e16, bool frame) {
     constexpr int NT = 32 * TH, PW = 38, PH = TH + 6, BW = 34, BH = TH + 2, NW = NT / 64;
     __shared__ uint8_t patch[PH * PW];       // labels of the tile + 3 pixels around it (255 outside the image)
     __shared__ uint8_t bflag[BH * BW];       // boundary flags of the tile + 1 pixel around it
@@ -73,6 +76,24 @@ __global__ __launch_bounds__(32 * TH) void ace_classify_kernel(const uint8_t* __
             if (code >= 0) {
                 f = (uint8_t)ACE_EDGE;
                 ecode[i] = (uint16_t)code;
+            } else if (frame && c < 19) {
+                // window lines outside the image: columns left / right of it, rows above / below (at most one side per axis from 5 pixels on)
+                const int cl = x < 2 ? 2 - x : 0, cr = x + 3 > W ? x + 3 - W : 0, rt = y < 2 ? 2 - y : 0, rb = y + 3 > H ? y + 3 - H : 0;
+                if (((cl + cr) != 0) != ((rt + rb) != 0) && cl * cr == 0 && rt * rb == 0) {
+                    bool same = true;
+#pragma unroll
+                    for (int dy = 0; dy < 5; ++dy)
+#pragma unroll
+                        for (int dx = 0; dx < 5; ++dx) {
+                            const bool in = (unsigned)(y - 2 + dy) < (unsigned)H && (unsigned)(x - 2 + dx) < (unsigned)W;
+                            same = same && (!in || patch[(by + dy) * PW + bx + dx] == c);
+                        }
+                    if (same) {
+                        const int o = (cl + cr) ? 0 : 1, lead = o ? rt : cl, trail = o ? rb : cr;
+                        f = (uint8_t)ACE_EDGE;
+                        ecode[i] = (uint16_t)ace_frame_code(o, c, lead ? lead : 5 - trail);
+                    }
+                }
             }
         }
         bflag[i] = f;
@@ -108,10 +129,11 @@ __global__ __launch_bounds__(32 * TH) void ace_classify_kernel(const uint8_t* __
 }
 
 hipError_t ace_classify(const uint8_t* lab, uint8_t* u5, uint8_t* need, uint16_t* list, int* cnt, int B, int H, int W, int TH,
-                        hipStream_t s, uint16_t* e16) {
+                        hipStream_t s, uint16_t* e16, bool frame) {
     const int tx = (W + 31) / 32, ty = (H + TH - 1) / TH;
-    if (TH == 8) hipLaunchKernelGGL(ace_classify_kernel<8>, dim3(B * tx * ty), dim3(256), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16);
-    else if (TH == 16) hipLaunchKernelGGL(ace_classify_kernel<16>, dim3(B * tx * ty), dim3(512), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16);
+    frame = frame && e16;
+    if (TH == 8) hipLaunchKernelGGL(ace_classify_kernel<8>, dim3(B * tx * ty), dim3(256), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16, frame);
+    else if (TH == 16) hipLaunchKernelGGL(ace_classify_kernel<16>, dim3(B * tx * ty), dim3(512), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16, frame);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -230,22 +252,30 @@ hipError_t ace_gtable(const float* bias_g, const float* bias_b, const float* gco
 
 // ---- straight-edge pixels: the per-code rows of an ACE (ch_finalize) and the per-call column / row sums of the style LUT ----------------
 // hidden-vector index of the window (X, Y, Z) of three column (row) labels out of {A, B}, monotone: XXX -> a_X; AAB / ABB -> pair entries
-__host__ __device__ inline int ace_edge_hv(int X, int Y, int Z) { return (X == Z) ? X : 19 + (X * 19 + Z) * 2 + (Y == X ? 0 : 1); }
+// frame codes: OUTSIDE A A / A A OUTSIDE (OUTSIDE = -1; the middle line, the hidden position's own, is inside)
+__host__ __device__ inline int ace_edge_hv(int X, int Y, int Z) {
+    if (X < 0) return 741 + Y * 2;
+    if (Z < 0) return 741 + Y * 2 + 1;
+    return (X == Z) ? X : 19 + (X * 19 + Z) * 2 + (Y == X ? 0 : 1);
+}
 // labels of the five columns (rows) of code (A, B, s): A for index < s, B from s on; hidden position d = -1, 0, 1 sees columns 1 + d .. 3 + d
+// (frame codes, AceCode::line: a hidden position whose own line lies outside is the zero padding of the gamma / beta conv)
 __global__ __launch_bounds__(256) void ace_edge_table_kernel(const double* __restrict__ W6, const double* __restrict__ hv, const float* __restrict__ bias_g,
                                                              const float* __restrict__ bias_b, float scale_g, float scale_b, float* __restrict__ E, int C) {
     const long long n = (long long)ACE_EDGE_CODES * 2 * C;
     const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(i % C), gb = (int)((i / C) & 1), code = (int)(i / (2LL * C));
-    const int s = (code & 3) + 1, Bl = (code >> 2) % 19, A = ((code >> 2) / 19) % 19, o = (code >> 2) / 361;
+    const AceCode cd = ace_code_decode(code);
+    const int o = cd.o;
     double acc = 0.0;
-    if (A != Bl) {
+    if (cd.frame || cd.A != cd.B) {
         const double* w = W6 + (long long)gb * 128 * 6 * C + (long long)(o * 3) * C + c;      // [gb][k][6][C]: consecutive threads, consecutive c
 #pragma unroll
         for (int d = 0; d < 3; ++d) {                            // hidden position d - 1: window = line labels d, d + 1, d + 2
-            const int X = d < s ? A : Bl, Y = d + 1 < s ? A : Bl, Z = d + 2 < s ? A : Bl;
-            const double* h = hv + ((long long)o * 741 + ace_edge_hv(X, Y, Z)) * 128;
+            const int X = cd.line(d), Y = cd.line(d + 1), Z = cd.line(d + 2);
+            if (Y < 0) continue;
+            const double* h = hv + ((long long)o * ACE_EDGE_HV + ace_edge_hv(X, Y, Z)) * 128;
             double a = 0.0;
             for (int k = 0; k < 128; ++k) a += w[((long long)k * 6 + d) * C] * h[k];
             acc += a;
@@ -598,11 +628,12 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
                         const float* ep = q.etab + (long long)code * 2 * q.C + c;
                         v = make_float2(ep[0], ep[q.C]);
                         if (q.p6) {
-                            const int sn = (code & 3) + 1, Bl = (code >> 2) % 19, A = ((code >> 2) / 19) % 19, o = (code >> 2) / 361;
+                            const AceCode cd = ace_code_decode(code);
 #pragma unroll
                             for (int t = 0; t < 3; ++t) {
-                                const int l = (1 + t < sn) ? A : Bl;        // line label 1 + t of A^s B^(5-s)
-                                const float* pq = q.p6 + (((long long)b * 19 + l) * 6 + o * 3 + t) * 2 * q.C + c;
+                                const int l = cd.line(1 + t);                // line label 1 + t of A^s B^(5-s); frame codes: < 0 = the tap falls outside
+                                if (l < 0) continue;
+                                const float* pq = q.p6 + (((long long)b * 19 + l) * 6 + cd.o * 3 + t) * 2 * q.C + c;
                                 v.x += pq[0];
                                 v.y += pq[q.C];
                             }

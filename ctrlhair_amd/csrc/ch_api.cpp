@@ -624,6 +624,7 @@ const OptRow OPTION_TABLE[] = {
     {"sean.patch", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(patch)},                  // 1 = pre-gathered hidden-activation patches for levels with few boundary quads (default), 0 = planes only
     {"sean.convt_gemm", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(convt_gemm)},        // exact-f32 Zencoder: 1 = the ConvTranspose as four phase GEMMs over shifted views (default), 0 = four Winograd phase convs
     {"sean.edge", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(edge)},                    // 1 = straight-edge pixels from per-code table rows in the interior pass (default), 0 = through the boundary conv
+    {"sean.frame", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(frame)},                  // with sean.edge, exact-f32 Winograd path: 1 = frame pixels with a uniform in-image window from table rows too (default), 0 = boundary conv
     {"sean.int_groups", NEVER, CLAMP, 0, MAXI, SEAN_FIELD(int_groups)},      // channel groups per block of the four-pixel interior pass: 0 = chosen per launch (default), n >= 1 = at most n
     {"sean.batch_invariant", NEVER, BOOL, 0, 0, SEAN_FIELD(batch_inv)},      // exact-f32 path: 1 = kernel choices independent of the batch size of a call (default 0)
     {"sean.wino4v", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(wino4v)},                // 1 = pre-transformed-input route of the F(4x4,3x3) layers with many GEMM rows (conv_wino4v.h; default), 0 = off

@@ -324,12 +324,12 @@ struct SeanBuild {
                 }
             }
         a.gconst = B.upload(gc);
-        // straight-edge pixels (ace_sparse.h, option sean.edge): the per-code rows E[2888][gamma|beta][C] of the ACEs that can run at
+        // straight-edge and frame pixels (ace_sparse.h, options sean.edge / sean.frame): the per-code rows E[3040][gamma|beta][C] of the ACEs that can run at
         // 128 pixels and more (res_div <= 4), from the hidden vectors of the windows AAB / ABB (double, host) and the column / row sums
         // of the gamma / beta weights, contracted on the device in double (ace_edge_table).  vbg / vbb (blended biases) are added.
         a.edge_tab = nullptr;
         if (!(opt.edge && (opt.use_sh16 ? opt.sparse : opt.wino) && a.res_div <= 4)) return;
-        s.edge_hv.assign((size_t)2 * 741 * HID, 0.0);
+        s.edge_hv.assign((size_t)2 * ACE_EDGE_HV * HID, 0.0);
         s.edge_W6.assign((size_t)2 * HID * 6 * C, 0.0);
         std::vector<double>&hv = s.edge_hv, &W6 = s.edge_W6;
         for (int o = 0; o < 2; ++o) {
@@ -339,16 +339,24 @@ struct SeanBuild {
                 return v;
             };
             for (int j = 0; j < LABEL_NC; ++j)
-                for (int k = 0; k < HID; ++k) hv[((size_t)o * 741 + j) * HID + k] = aj[(size_t)j * HID + k];
+                for (int k = 0; k < HID; ++k) hv[((size_t)o * ACE_EDGE_HV + j) * HID + k] = aj[(size_t)j * HID + k];
             for (int A = 0; A < LABEL_NC; ++A)
                 for (int Bl = 0; Bl < LABEL_NC; ++Bl) {
                     if (A == Bl) continue;
                     for (int k = 0; k < HID; ++k) {
                         const double aab = bs[k] + line(A, 0, k) + line(A, 1, k) + line(Bl, 2, k);
                         const double abb = bs[k] + line(A, 0, k) + line(Bl, 1, k) + line(Bl, 2, k);
-                        hv[((size_t)o * 741 + 19 + (A * 19 + Bl) * 2 + 0) * HID + k] = aab > 0.0 ? aab : 0.0;
-                        hv[((size_t)o * 741 + 19 + (A * 19 + Bl) * 2 + 1) * HID + k] = abb > 0.0 ? abb : 0.0;
+                        hv[((size_t)o * ACE_EDGE_HV + 19 + (A * 19 + Bl) * 2 + 0) * HID + k] = aab > 0.0 ? aab : 0.0;
+                        hv[((size_t)o * ACE_EDGE_HV + 19 + (A * 19 + Bl) * 2 + 1) * HID + k] = abb > 0.0 ? abb : 0.0;
                     }
+                }
+            // frame pixels (option sean.frame): the windows (outside, A, A) and (A, A, outside) -- a line outside the image adds nothing
+            for (int A = 0; A < LABEL_NC; ++A)
+                for (int k = 0; k < HID; ++k) {
+                    const double oaa = bs[k] + line(A, 1, k) + line(A, 2, k);
+                    const double aao = bs[k] + line(A, 0, k) + line(A, 1, k);
+                    hv[((size_t)o * ACE_EDGE_HV + 741 + A * 2 + 0) * HID + k] = oaa > 0.0 ? oaa : 0.0;
+                    hv[((size_t)o * ACE_EDGE_HV + 741 + A * 2 + 1) * HID + k] = aao > 0.0 ? aao : 0.0;
                 }
         }
         for (int gb = 0; gb < 2; ++gb)
@@ -1066,9 +1074,10 @@ struct Runner {
         return nullptr;
     }
     // Winograd ACE path: classification of the level (when the interior reduction serves it), boundary-quad lists, task list
+    // (edges: the level's interior map carries straight-edge marks -- and, with option sean.frame, frame marks)
     struct WinoPrep { const SeanModel::WinoLevel* L = nullptr; const SeanModel::WinoWork* W = nullptr; const SparseLevel* S = nullptr; bool edges = false; };
     bool wq_done[6] = {};
-    bool lvl_edges[6][2] = {};          // the level's interior map carries straight-edge marks (u5 == 253 + e16)
+    bool lvl_edges[6][2] = {};          // the level's interior map carries straight-edge marks (u5 == 253 + e16; Winograd path with sean.frame: frame marks too)
     std::vector<int> wwork_done[6];
     WinoPrep wino_prepare(const AceW& a, const uint8_t* lab, int r) {
         WinoPrep o;
@@ -1088,7 +1097,8 @@ struct Runner {
                         // straight-edge pixels (ace_sparse.h): marked on the levels whose interior pass knows them (128 pixels and more) when
                         // the ACE carries its table -- every ACE of such a level does (res_div <= 4), checked in ace()
                         const bool edges = m.opt.edge && S.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && !m.overlap_on;      // (overlap mode: quad_only interior pass)
-                        check(ace_classify(lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, edges ? S.e16 : nullptr), "ace_classify");
+                        // frame pixels (option sean.frame): marked with them; only this path's interior pass (tile4 kernel) knows their codes
+                        check(ace_classify(lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, edges ? S.e16 : nullptr, edges && m.opt.frame), "ace_classify");
                         lvl_done[k][ti] = true;
                         lvl_edges[k][ti] = edges;
                     }

@@ -41,7 +41,7 @@ struct AceW {
                                                 //   shortcut's ace_s carries the 2^D aligning conv_s with conv_1, sean_model.cpp)
     float actv_scale = 1.f;                     // f16x3 path: SH16 scale of the SPADE hidden activations (from a table bound)
     float* spade_wino = nullptr;                // exact-f32 Winograd path: pack_wino_A image of the (gamma | beta) rows, 16-channel row tiles
-    float* edge_tab = nullptr;                  // sean.edge: E[2888][gamma|beta][C] of the straight-edge pixels (ace_sparse.h), ACEs with res_div <= 4
+    float* edge_tab = nullptr;                  // sean.edge: E[3040][gamma|beta][C] of the straight-edge and frame pixels (ace_sparse.h), ACEs with res_div <= 4
     float* spade_wino4 = nullptr;               // sean.wino = 2: the same rows as an F(4x4,3x3) image (conv_wino4.h wino4_ace_row), levels <= wino4_ace_max_r
     float* gconst = nullptr;                    // [19][gamma|beta][C]: SPADE gamma/beta of a pixel whose 5x5 label neighbourhood
                                                 //   is uniformly j (blend factor folded in, biases not) -- ace_sparse.h
@@ -101,6 +101,8 @@ struct SeanOptions {
     int convt_gemm = 1;                        // option "sean.convt_gemm": the Zencoder's ConvTranspose as four phase GEMMs (SeanModel::z10_pw), 0 = four Winograd phase convs
     int edge = 1;                              // option "sean.edge": 1 = straight-edge pixels of the levels >= 128 pixels are modulated by the interior pass from
                                                //   per-code table rows instead of going through the boundary conv (exact-f32 Winograd path, f16 paths in compaction mode; ace_sparse.h)
+    int frame = 1;                             // option "sean.frame": 1 = with sean.edge on the exact-f32 Winograd path, the pixels of the two outermost rings of a level
+                                               //   >= 128 pixels whose in-image 5x5 window is uniform are served the same way (frame codes, ace_sparse.h); 0 = boundary conv
     int int_groups = 0;                        // option "sean.int_groups": channel groups of 32 per block of the four-pixel interior kernel (levels >= 128 pixels,
                                                //   exact-f32 Winograd path): 0 = chosen per launch (ace_interior_groups), n >= 1 = at most n (1 = one group per block)
     int batch_inv = 0;                         // option "sean.batch_invariant": 1 = every choice that follows the number of tasks of a call (F(4x4) vs F(2x2),

@@ -94,7 +94,13 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   LUT, in the interior pass, on the levels of 128 pixels and more; only corners, curved pieces and the image frame go through the
  *   boundary conv (csrc/ace_sparse.h).  Same real number, another association of the f32 sums (<= 1e-6 against "sean.edge" = 0;
  *   f16x3: <= 5e-6; on the single-term f16 / bf16 paths the table rows are exact f32 where the conv they replace is not).
- *   Costs 52 MB of tables at ngf = 64.  0 = every non-interior pixel through the conv.
+ *   Costs 55 MB of tables at ngf = 64 (3040 rows per ACE on every path that builds them: the 152 rows of "sean.frame" are always there).  0 = every non-interior pixel through the conv.
+ * "sean.frame" (default 1; before ch_finalize; effective only with "sean.edge" = 1 on the exact-f32 Winograd path, levels of 128 pixels and
+ *   more): a pixel of the two outermost rings of a level whose 5 x 5 window reaches outside the image along exactly one axis, and whose
+ *   labels inside the image all equal its own label A < 19, is served like a straight-edge pixel: both SPADE convs and the style convs
+ *   zero-pad, so a tap outside adds nothing and a hidden position outside is zero (2 x 19 x 4 = 152 more rows per ACE behind the 2888:
+ *   orientation, A, which border and distance).  The 2 x 2 pixels at each image corner stay with the boundary conv.  <= 1e-5 against
+ *   "sean.frame" = 0.  The f16x3 / f16 / bf16 paths do not use it.  0 = frame pixels through the boundary conv.
  * "sean.convt_gemm" (default 1; before ch_finalize; exact-f32 path): the Zencoder's ConvTranspose2d(128, 256, k3, s2, p1, op1)
  *   (architecture.py:167-170) as four phase GEMMs over shifted views of its input -- 9 products per 2 x 2 outputs and channel pair -- with the
  *   InstanceNorm + lrelu that follows reading the phase planes; calls with fewer than 16384 input pixels and 0 = four Winograd F(2x2,3x3)
