@@ -537,6 +537,35 @@ int ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, i
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_hair_color_stats: ") + hipGetErrorString(e));
 }
 
+int ch_sheet_compose(ch_handle* h, const void* src, int kind, int n, int Hs, int Ws, const int32_t* cells, const uint8_t* lut, uint8_t* canvas,
+                     int rows, int cols, int H, int W, int margin, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!src || !cells || !canvas || kind < 0 || kind > 2 || (kind == 2 && !lut))
+        return fail(h, CH_ERR_ARG, "ch_sheet_compose: null pointer or unknown source kind");
+    if (n < 1 || n > 65535) return fail(h, CH_ERR_ARG, "ch_sheet_compose: n outside 1..65535");
+    if (Hs < 1 || Ws < 1 || rows < 1 || cols < 1 || H < 1 || W < 1 || margin < 0)
+        return fail(h, CH_ERR_ARG, "ch_sheet_compose: sizes must be positive (margin >= 0)");
+    if ((int64_t)rows * H > INT32_MAX || (int64_t)cols * ((int64_t)W + margin) * 3 > INT32_MAX || (int64_t)Hs * Ws > INT32_MAX)
+        return fail(h, CH_ERR_ARG, "ch_sheet_compose: sheet or source too large");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::sheet_compose(src, kind, n, Hs, Ws, cells, lut, canvas, rows, cols, H, W, margin, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_sheet_compose: ") + hipGetErrorString(e));
+}
+
+int ch_sweep_stats(ch_handle* h, const void* img, int kind, const uint8_t* labels, const int32_t* ref, int N, int H, int W, int lh, int lw,
+                   int64_t* stats, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!img || !labels || !ref || !stats || kind < 0 || kind > 1)
+        return fail(h, CH_ERR_ARG, "ch_sweep_stats: null pointer or unknown image kind");
+    if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, "ch_sweep_stats: N outside 1..65535");
+    if (H < 1 || W < 1 || lh < 1 || lw < 1) return fail(h, CH_ERR_ARG, "ch_sweep_stats: sizes must be positive");
+    if (H > 32768 || W > 32768 || (int64_t)H * W > (1 << 30) || (int64_t)lh * lw > (1 << 30))
+        return fail(h, CH_ERR_ARG, "ch_sweep_stats: image or label map too large (sides <= 32768, H * W <= 2^30)");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::sweep_stats(img, kind, labels, ref, N, H, W, lh, lw, stats, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_sweep_stats: ") + hipGetErrorString(e));
+}
+
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {
     if (!h || !name) return CH_ERR_ARG;
     if (dev_ptr) h->sean.taps[name] = dev_ptr;

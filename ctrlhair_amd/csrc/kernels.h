@@ -129,6 +129,14 @@ hipError_t hair_erode(const uint8_t* labels, int B, int Hl, int Wl, int label, c
                       hipStream_t s);
 hipError_t hair_color_stats(const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums, hipStream_t s);
 
+// sheet.hip: contact sheets and per-render measurements of a direction search (shape_branch/script_find_direction.py:55-76,
+// util/canvas_grid.py:15-31).  See ch_sheet_compose / ch_sweep_stats in ctrlhair_hip.h.
+constexpr int SWEEP_NSTAT = 16;               // == CH_SWEEP_STATS
+hipError_t sheet_compose(const void* src, int kind, int n, int Hs, int Ws, const int* cells, const uint8_t* lut, uint8_t* canvas, int rows,
+                         int cols, int H, int W, int margin, hipStream_t s);
+hipError_t sweep_stats(const void* img, int kind, const uint8_t* labels, const int* ref, int N, int H, int W, int h, int w, int64_t* stats,
+                       hipStream_t s);
+
 // mask_warp.hip: hair-shape transfer warp (wrap_codes/mask_adaptor.py:87-143): batched ARAP solve of packed 2-D triangle meshes, then
 // UV render + mask sampling + compose into uint8 [B,512,512] label maps.  desc_host: B x {v_off, n_v, f_off, n_f, b_off, n_b} (host).
 constexpr int WARP_MAX_V = 2048;              // vertices / triangles of one pair's mesh (LDS budget of arap_solve_kernel)

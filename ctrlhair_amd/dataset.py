@@ -38,6 +38,16 @@ On-disk formats are the reference's:
                                            for many hair / face pairs and write <pool_dir>/<hair_dir>___<hair_num>___<face_dir>___
                                            <face_num>___<rank:02d>.png; landmarks: name -> [81,2] in [0,1]; meshing and warp are
                                            batched on the GPU: warping.MaskWarper.warp_batch(mesher='device'))
+    python -m ctrlhair_amd.dataset directions <img_dir> --att shape|texture [--weights procedural|<checkpoint root>] [--used-dir DIR]
+                                          [--out DIR] [--n 300] [--images 10] [--values 6] [--max-val 2.5] [--seed 0] [--noise-seed 0]
+                                          [--size 256|512] [--cell PX] [--sheets all|top:K|none] [--list FILE] [--batch 16]
+                                          (shape_branch/ and color_texture_branch/script_find_direction.py: random candidate directions
+                                           orthogonal to the ones in <used-dir>, each swept over the first --images images of <img_dir> (or
+                                           the names in --list) at --values slider values; writes <out>/<att>_dir_<k+1>/<i>.pkl,
+                                           <out>/<att>_<k+1>/<i>.png and <out>/scores.json, k = the number of directions in use;
+                                           candidates are sharded over ranks: ctrlhair_amd.directions)
+    python -m ctrlhair_amd.dataset use-direction <out> <att> <index> <used-dir>
+                                          (copy candidate <index> of that search into the used set under the next free name)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -379,6 +389,85 @@ def _main_warp_pool(argv):
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
 
 
+def load_search_images(img_dir: str, size: int, count: int, list_file: str = None) -> np.ndarray:
+    """The images of a direction search: the first `count` of the sorted directory (or of the names in `list_file`, one per line), each
+    as HairEditor.preprocess_img makes it: cv2-bilinear resize to size x size, / 127.5 - 1, float32 [I,3,size,size]."""
+    from . import hostutil as U
+    if list_file is not None:
+        with open(list_file) as f:
+            names = [ln.strip() for ln in f if ln.strip() and not ln.startswith('#')]
+    else:
+        names = list_images(img_dir)
+    names = names[:count]
+    if not names:
+        raise ValueError(f'{img_dir}: no images to search on')
+    imgs = [U.resize_bilinear(read_rgb(os.path.join(img_dir, n)).astype('uint8'), (size, size)) for n in names]
+    return np.stack([(np.transpose(im, [2, 0, 1]) / 127.5 - 1.0).astype(np.float32) for im in imgs])
+
+
+def _main_directions(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog='ctrlhair_amd.dataset directions', description='Search editing directions of the shape / texture latent')
+    ap.add_argument('img_dir')
+    ap.add_argument('--att', choices=('shape', 'texture'), required=True)
+    ap.add_argument('--weights', default='procedural', help="'procedural' or the root of the reference's checkpoint tree")
+    ap.add_argument('--used-dir', default=None, help='folder of the direction pickles already in use (*_dir_used)')
+    ap.add_argument('--out', default='direction_find')
+    ap.add_argument('--n', type=int, default=300, help='candidates')
+    ap.add_argument('--images', type=int, default=10)
+    ap.add_argument('--values', type=int, default=6, help='slider values per image, linspace(-max_val, max_val)')
+    ap.add_argument('--max-val', type=float, default=2.5)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--noise-seed', type=int, default=0)
+    ap.add_argument('--size', type=int, default=256, choices=(256, 512))
+    ap.add_argument('--cell', type=int, default=None, help='side of a sheet cell in pixels (default: the image size)')
+    ap.add_argument('--sheets', default='all', help='all | top:K | none.  top:K scores every candidate first, then sweeps the K best of EACH rank a second time into sheets: '
+                                                     'W ranks write up to W * K sheets')
+    ap.add_argument('--list', default=None, help='file with the image names to use, one per line')
+    ap.add_argument('--batch', type=int, default=16)
+    args = ap.parse_args(argv)
+    import torch
+    from . import directions as DS
+    from .pipeline import EditPipeline
+    DS.parse_sheets(args.sheets)
+    rank, world, local = _dist_env()
+    dist = None
+    if world > 1:
+        import torch.distributed as dist
+        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+        dist.init_process_group('gloo', rank=rank, world_size=world)      # only a barrier before the merge
+    torch.cuda.set_device(local)
+    weights = None
+    if args.weights != 'procedural':
+        from .checkpoints import reference_checkpoints
+        weights = reference_checkpoints(args.weights)
+    pipe = EditPipeline(weights, device=local, img_size=args.size, max_batch=args.batch)
+    imgs = torch.from_numpy(load_search_images(args.img_dir, args.size, args.images, args.list))
+    search = DS.DirectionSearch(pipe, imgs, noise_seed=args.noise_seed)
+    recs = DS.find_directions(search, args.att, DS.load_used(args.used_dir), args.out, n=args.n,
+                              values=np.linspace(-args.max_val, args.max_val, args.values), seed=args.seed, rank=rank, world=world,
+                              sheets=args.sheets, cell=args.cell)
+    if dist is not None:
+        dist.barrier()
+    if rank == 0:
+        DS.merge_scores(args.out, world)
+    print(f'rank {rank}/{world}: {len(recs)} candidates')
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def _main_use_direction(argv):
+    import argparse
+    ap = argparse.ArgumentParser(prog='ctrlhair_amd.dataset use-direction', description='Copy a found direction into the used set')
+    ap.add_argument('out', help='the --out folder of the directions job')
+    ap.add_argument('att', choices=('shape', 'texture'))
+    ap.add_argument('index', type=int)
+    ap.add_argument('used_dir')
+    args = ap.parse_args(argv)
+    from .directions import use_direction
+    print(use_direction(args.out, args.att, args.index, args.used_dir))
+
+
 def _dist_env():
     return int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('LOCAL_RANK', '0'))
 
@@ -395,6 +484,10 @@ def main(argv=None):
         return _main_warp_pool(argv[1:])
     if argv and argv[0] == 'median':
         return _main_median(argv[1:])
+    if argv and argv[0] == 'directions':
+        return _main_directions(argv[1:])
+    if argv and argv[0] == 'use-direction':
+        return _main_use_direction(argv[1:])
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('job', choices=('masks', 'codes') + tuple(COLOR_JOBS))
     ap.add_argument('root')

@@ -295,6 +295,28 @@ class Backend(HairEditor):
             self.cur_latent, self.cur_mask = saved, saved_mask
         return self.outputs(latents, noise=noise)
 
+    def sweep_direction(self, att_name, direction, values, noise=None):
+        """sweep() along an arbitrary direction of the shape (16-d) or texture (8-d) latent: the images output() would give after
+        continue_change_with_direction(att_name, direction, v) for each v in `values`, rendered as one batch
+        (sweep(att_name, idx, values) is the case direction = shape_dirs[idx] / texture_dirs[idx]).  What a direction search
+        renders per candidate (shape_branch/script_find_direction.py:69-75).  cur_latent and cur_mask are left as they were."""
+        if att_name not in ('shape', 'texture'):
+            raise ValueError(f"sweep_direction moves the 'shape' or the 'texture' latent, got {att_name!r}")
+        saved, saved_mask = self.cur_latent, self.cur_mask
+        direction = torch.as_tensor(direction).float().to(self.device)
+        if direction.shape != getattr(saved, att_name).shape[1:]:
+            raise ValueError(f'a {att_name} direction has {getattr(saved, att_name).shape[1]} entries, got {tuple(direction.shape)}')
+        latents = []
+        try:
+            for v in values:
+                self.cur_latent = self.copy_latent(saved)
+                cur = getattr(self.cur_latent, att_name)      # continue_change_with_direction without its mask decode per value
+                setattr(self.cur_latent, att_name, cur + (v - torch.dot(cur[0], direction)) * direction)
+                latents.append(self.cur_latent)
+        finally:
+            self.cur_latent, self.cur_mask = saved, saved_mask
+        return self.outputs(latents, noise=noise)
+
     def interpolate_grid(self, latent1, latent2, alphas, att_name=None, noise=None):
         """Images along latent1 -> latent2 for every alpha, one batch: interpolate() (all attributes) or
         interpolate_each_att(att_name) per alpha (ui/backend.py:323-395)."""

@@ -288,6 +288,37 @@ int  ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, i
 int  ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums,
                          ch_stream_t stream);
 
+/* ---- Direction search: contact sheets and per-render measurements (shape_branch/script_find_direction.py:55-76,
+ *      color_texture_branch/script_find_direction.py:55-74, util/canvas_grid.py:15-31) ------------------------------------------
+ * ch_sheet_compose replaces Canvas.process_draw_image for n sources at once: source s goes to cell (cells[2s], cells[2s+1]) =
+ *   (row i, column j) of the sheet, whose top-left pixel is y = i * H, x = j * (W + margin) (canvas_grid.py:21,30-31).
+ *   canvas uint8 [rows * H, cols * W + margin * (cols - 1), 3] device pointer; cells int32 [n,2] device pointer.  A source whose
+ *   cell lies outside the grid is skipped.  The canvas is NOT cleared: pixels of untouched cells and of the margins keep their
+ *   bytes (fill it once, e.g. with 255 as Canvas does).  Two sources in one cell of one call: either may win.
+ *   kind 0: src float32 [n,3,Hs,Ws] in [-1,1] -> uint8 as the project's to_u8: x * 127.5 rounded to float32, + 127.5 rounded to
+ *           float32 (never a fused multiply-add: it gives another byte for ~2 inputs per million), clamped to [0,255], truncated;
+ *           NaN -> 0.
+ *   kind 1: src uint8 [n,Hs,Ws,3], copied.
+ *   kind 2: src uint8 label maps [n,Hs,Ws], coloured by lut uint8 [256,3] (device pointer; hostutil.mask_to_rgb's table of a
+ *           draw type: labels 19..254 black, 255 white).  lut is read for kind 2 only.
+ *   (Hs, Ws) != (H, W): nearest source pixel, row min((int)(y * ((double)Hs / H)), Hs - 1), columns likewise (cv2 INTER_NEAREST,
+ *   as ch_hair_erode).  1 <= n <= 65535, all sizes >= 1, margin >= 0.
+ * ch_sweep_stats measures N renders: img as kind 0 ([N,3,H,W] float32) or kind 1 ([N,H,W,3] uint8) above, labels uint8
+ *   [N,lh,lw] nearest-mapped to H x W by the same rule, ref int32 [N] (device pointers): ref[n] is the render that render n is
+ *   compared with, or < 0 for none; a ref[n] >= N is treated as none.  stats int64 [N,CH_SWEEP_STATS] device pointer,
+ *   overwritten.  "Hair" = label 13.  Per render: [0] hair pixels, [1..4] sum x, sum y, sum x^2, sum y^2 over hair pixels (image
+ *   coordinates), [5..8] y_min, y_max, x_min, x_max of hair (all -1 without hair), [9..11] sum R, G, B over hair (uint8 values,
+ *   after the kind-0 conversion), [12] pixels whose label differs from render ref[n], [13] pixels that are hair in both,
+ *   [14] sum |dR| + |dG| + |dB| over pixels that are hair in either, [15] pixels that are hair in either; [12..15] = 0 for
+ *   ref[n] < 0.  1 <= N <= 65535, H, W <= 32768, H * W <= 2^30.  Integer sums, minima and maxima combined with integer atomics:
+ *   independent of the order of the blocks, so run-to-run deterministic.
+ * Both enqueue on `stream` without synchronising or allocating. */
+#define CH_SWEEP_STATS 16
+int  ch_sheet_compose(ch_handle* h, const void* src, int kind, int n, int Hs, int Ws, const int32_t* cells, const uint8_t* lut,
+                      uint8_t* canvas, int rows, int cols, int H, int W, int margin, ch_stream_t stream);
+int  ch_sweep_stats(ch_handle* h, const void* img, int kind, const uint8_t* labels, const int32_t* ref, int N, int H, int W, int lh,
+                    int lw, int64_t* stats, ch_stream_t stream);
+
 /* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
  * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image
  * edge extended 10 px, mask_adaptor.py:119-131), the pair's triangle mesh is deformed as rigidly as possible (libigl's per-element
