@@ -1,5 +1,6 @@
 """ORACLE (test infrastructure, NOT product code) -- CPU restatement of the SEAN generator
-forward of XuyangGuo/CtrlHair, in plain functional PyTorch fp32.
+forward of XuyangGuo/CtrlHair, in plain functional PyTorch fp32 (the default) or, with ``dtype=torch.float64``, with
+every tensor -- weights, one-hot, codes, noise, the ``mu`` buffer, the taps -- in double: the reference of tests/stage_parity.py.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this file.
 The product path (ctrlhair_amd + libctrlhair_hip.so) never does and fails loudly without its
@@ -38,6 +39,13 @@ def to_torch(sd: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
     return {k: _t(v) for k, v in sd.items()}
 
 
+def _cast_sd(sd, dtype):
+    """The state dict with its floating-point tensors in `dtype`; the dict itself when they already are (the fp32 default: no copy)."""
+    if all(v.dtype == dtype for v in sd.values() if v.is_floating_point()):
+        return sd
+    return {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
+
+
 def spectral_weight(sd, prefix):
     """torch.nn.utils.spectral_norm in eval mode: W = W_orig / (u . (W_mat v)), no power
     iteration (torch/nn/utils/spectral_norm.py compute_weight(do_power_iteration=False));
@@ -48,13 +56,13 @@ def spectral_weight(sd, prefix):
     return w / sigma
 
 
-def one_hot(labels: torch.Tensor) -> torch.Tensor:
-    """pix2pix_model.py:133-138: scatter_ of the label map into a [B,19,H,W] fp32 one-hot."""
+def one_hot(labels: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """pix2pix_model.py:133-138: scatter_ of the label map into a [B,19,H,W] one-hot (fp32 in the reference)."""
     lab = labels.long().unsqueeze(1)
     B, _, H, W = lab.shape
     # ids >= 19 ("no class", e.g. 255) make scatter_ raise in the reference; the library defines them as an all-zero
     # one-hot (include/ctrlhair_hip.h), restated here through a 20th channel that is dropped
-    oh = torch.zeros(B, LABEL_NC + 1, H, W, dtype=torch.float32).scatter_(1, lab.clamp(max=LABEL_NC), 1.0)
+    oh = torch.zeros(B, LABEL_NC + 1, H, W, dtype=dtype).scatter_(1, lab.clamp(max=LABEL_NC), 1.0)
     return oh[:, :LABEL_NC].contiguous()
 
 
@@ -93,7 +101,7 @@ def ace(sd, p, x, seg, codes, noise_plane, styled, stats_out=None):
     # :117-153 -- middle_avg[b,:,p] = relu(fc_mu_j(code[b,j])) for j = label(p) (only labels with >=1 px
     # at this resolution are ever written; all others stay zero -- and are never read back).
     lab = segmap.argmax(dim=1)                                        # [B,H,W]
-    mu = torch.zeros(B, LABEL_NC, STYLE_LEN)
+    mu = torch.zeros(B, LABEL_NC, STYLE_LEN, dtype=x.dtype)
     for j in range(LABEL_NC):
         mu[:, j] = F.relu(F.linear(codes[:, j], sd[f'{p}.fc_mu{j}.weight'], sd[f'{p}.fc_mu{j}.bias']))
     middle_avg = torch.gather(mu, 1, lab.reshape(B, H * W, 1).expand(B, H * W, STYLE_LEN))
@@ -108,42 +116,45 @@ def ace(sd, p, x, seg, codes, noise_plane, styled, stats_out=None):
     return normalized * (1 + gamma_final) + beta_final                # :182
 
 
-def resblock(sd, blk, x, seg, codes, noise_iter, weights_cache, stats_out=None, taps=None):
-    """architecture.py:69-96 (SPADEResnetBlock.forward / shortcut / actvn)."""
+def resblock(sd, blk, x, seg, codes, noise_iter, weights_cache, stats_out=None, taps=None, replace=None):
+    """architecture.py:69-96 (SPADEResnetBlock.forward / shortcut / actvn).  replace: see generator_forward."""
     name, styled = blk.name, blk.styled
 
     def w(prefix):
-        if prefix not in weights_cache:
+        if prefix not in weights_cache or weights_cache[prefix].dtype != x.dtype:      # (a cache shared between runs of two dtypes)
             weights_cache[prefix] = spectral_weight(sd, prefix)
         return weights_cache[prefix]
 
     def tap(k, v):
+        if replace is not None and name + k in replace:
+            v = replace[name + k]
         if taps is not None:
             taps[name + k] = v
+        return v
 
     if blk.learned_shortcut:
         x_s = ace(sd, name + '.ace_s', x, seg, codes, next(noise_iter), styled, stats_out)
-        tap('.hs', x_s)
+        x_s = tap('.hs', x_s)
         x_s = F.conv2d(x_s, w(name + '.conv_s'))
-        tap('.xs', x_s)
+        x_s = tap('.xs', x_s)
     else:
         x_s = x
     dx = F.leaky_relu(ace(sd, name + '.ace_0', x, seg, codes, next(noise_iter), styled, stats_out), 0.2)
-    tap('.h0', dx)
+    dx = tap('.h0', dx)
     dx = F.conv2d(dx, w(name + '.conv_0'), sd[name + '.conv_0.bias'], padding=1)
-    tap('.dx', dx)
+    dx = tap('.dx', dx)
     dx = F.leaky_relu(ace(sd, name + '.ace_1', dx, seg, codes, next(noise_iter), styled, stats_out), 0.2)
-    tap('.h1', dx)
+    dx = tap('.h1', dx)
     dx = F.conv2d(dx, w(name + '.conv_1'), sd[name + '.conv_1.bias'], padding=1)
     return x_s + dx
 
 
 @torch.no_grad()
-def zencoder_forward(sd: Dict[str, torch.Tensor], img, labels, taps: Optional[dict] = None) -> torch.Tensor:
+def zencoder_forward(sd: Dict[str, torch.Tensor], img, labels, taps: Optional[dict] = None, dtype=torch.float32) -> torch.Tensor:
     """architecture.py:155-207 (Zencoder.__init__ layer list + forward), fed like
     Pix2PixModel.forward(mode='style_code') (pix2pix_model.py:69-72).
     img f32 [B,3,S,S]; labels uint8 [B,S,S] -> codes [B,19,512]."""
-    img, labels = _t(img).float(), _t(labels)
+    img, labels, sd = _t(img).to(dtype), _t(labels), _cast_sd(sd, dtype)
     p = 'Zencoder.model.'
     x = F.conv2d(F.pad(img, (1, 1, 1, 1), mode='reflect'), sd[p + '1.weight'], sd[p + '1.bias'])      # :158-159
     x = F.leaky_relu(F.instance_norm(x, eps=1e-5), 0.2)
@@ -155,9 +166,9 @@ def zencoder_forward(sd: Dict[str, torch.Tensor], img, labels, taps: Optional[di
     codes = torch.tanh(F.conv2d(F.pad(x, (1, 1, 1, 1), mode='reflect'), sd[p + '14.weight'], sd[p + '14.bias']))  # :174
     if taps is not None:
         taps['zenc.feat'] = codes
-    seg = F.interpolate(one_hot(labels), size=codes.shape[2:], mode='nearest')                        # :181
+    seg = F.interpolate(one_hot(labels, dtype), size=codes.shape[2:], mode='nearest')                     # :181
     B, Fd = codes.shape[:2]
-    out = torch.zeros(B, LABEL_NC, Fd)
+    out = torch.zeros(B, LABEL_NC, Fd, dtype=dtype)
     for b in range(B):                                                                                # :195-203
         for j in range(LABEL_NC):
             m = seg[b, j].bool()
@@ -181,15 +192,20 @@ def split_noise(noise: torch.Tensor, S: int, ngf: int) -> List[torch.Tensor]:
 @torch.no_grad()
 def generator_forward(sd: Dict[str, torch.Tensor], labels, codes, noise, ngf: int = 64,
                       stats_out: Optional[dict] = None, taps: Optional[dict] = None,
-                      weights_cache: Optional[dict] = None) -> torch.Tensor:
+                      weights_cache: Optional[dict] = None, dtype=torch.float32,
+                      replace: Optional[dict] = None) -> torch.Tensor:
     """generator.py:72-109 (SPADEGenerator.forward) fed by pix2pix_model.py:119-144 (one-hot).
 
-    labels uint8 [B,S,S]; codes f32 [B,19,512]; noise f32 [B,NF] -> image f32 [B,3,S,S] in [-1,1].
+    labels uint8 [B,S,S]; codes f32 [B,19,512]; noise f32 [B,NF] -> image [B,3,S,S] in [-1,1].
+    dtype: torch.float32 (the reference's arithmetic) or torch.float64 (inputs and weights widened exactly, then every operation --
+    spectral sigma, BN statistics, sigmoid blends included -- in double); the image and the taps come back in `dtype`.
+    replace: {'<block>.hs' | '.xs' | '.h0' | '.dx' | '.h1': tensor} -- the tensor takes the place of that stage and the forward goes on
+    from it (fault injection of tests/test_stage_parity_model.py: what a wrong stage does to the image).
     """
     from ctrlhair_amd.sean import arch
-    labels, codes, noise = _t(labels), _t(codes).float(), _t(noise).float()
+    labels, codes, noise, sd = _t(labels), _t(codes).to(dtype), _t(noise).to(dtype), _cast_sd(sd, dtype)
     B, S = labels.shape[0], labels.shape[-1]
-    seg = one_hot(labels)
+    seg = one_hot(labels, dtype)
     planes = iter(split_noise(noise, S, ngf))
     wc = {} if weights_cache is None else weights_cache
     sw = S // (2 ** arch.NUM_UP)                                      # generator.py:56-70
@@ -200,7 +216,7 @@ def generator_forward(sd: Dict[str, torch.Tensor], labels, codes, noise, ngf: in
     for blk in arch.blocks(ngf):
         if blk.up_before:
             x = F.interpolate(x, scale_factor=2, mode='nearest')      # nn.Upsample(scale_factor=2), :53
-        x = resblock(sd, blk, x, seg, codes, planes, wc, stats_out, taps)
+        x = resblock(sd, blk, x, seg, codes, planes, wc, stats_out, taps, replace)
         if taps is not None:
             taps[blk.name] = x
     x = F.conv2d(F.leaky_relu(x, 0.2), sd['conv_img.weight'], sd['conv_img.bias'], padding=1)  # :107
