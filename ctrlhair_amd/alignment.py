@@ -21,6 +21,9 @@ UNALIGN_PLAN_LEN = 16           # CH_UNALIGN_PLAN_LEN
 UNALIGN_MAX_SCALE = 16          # CH_UNALIGN_MAX_SCALE
 MAX_TRANSFORM = 16384           # CH_ALIGN_MAX_TRANSFORM
 GAUSS_TRUNCATE = 4.0            # scipy.ndimage.gaussian_filter's default
+MATTE_MAX_RADIUS = 64           # CH_MATTE_MAX_RADIUS
+MATTE_DEFAULT_EPS = 1e-4
+MATTE_CROP_PIXELS = 4.0         # default radius: this many crop pixels, in photo pixels
 
 
 def gaussian_weights(sigma):
@@ -196,6 +199,34 @@ def pack_unalign(plan_u):
     return v
 
 
+def matte_params(matte, scale):
+    """(radius, eps) of the guided-filter matte of paste_back (ch_face_unalign_matte).  matte: True, or a dict with 'radius' (photo
+    pixels) and / or 'eps' (regularisation, in units of a guide scaled to [0, 1]); scale: crop pixels per photo pixel (unalign_plan's
+    'scale').  Defaults: radius min(64, max(1, ceil(4 / scale))) photo pixels -- four crop pixels of label uncertainty -- and eps
+    1e-4.  Both defaults are design choices with no measurement behind them: nothing here has compared mattes on real photos.
+    Raises ValueError for a radius outside [1, 64] or an eps that is not positive and finite."""
+    if matte is True:
+        matte = {}
+    if not isinstance(matte, dict):
+        raise ValueError(f'matte must be True or a dict with radius and / or eps, got {matte!r}')
+    unknown = set(matte) - {'radius', 'eps'}
+    if unknown:
+        raise ValueError(f'matte: unknown keys {sorted(unknown)} (radius, eps)')
+    scale = float(scale)
+    if not scale > 0 or not np.isfinite(scale):
+        raise ValueError(f'scale must be positive, got {scale}')
+    radius = matte.get('radius')
+    if radius is None:
+        radius = min(MATTE_MAX_RADIUS, max(1, int(np.ceil(MATTE_CROP_PIXELS / scale))))
+    if int(radius) != radius or not 1 <= int(radius) <= MATTE_MAX_RADIUS:
+        raise ValueError(f'matte radius must be an integer in [1, {MATTE_MAX_RADIUS}] photo pixels, got {radius!r}')
+    eps = matte.get('eps')
+    eps = MATTE_DEFAULT_EPS if eps is None else float(eps)
+    if not eps > 0 or not np.isfinite(eps):
+        raise ValueError(f'matte eps must be positive and finite, got {eps!r}')
+    return int(radius), eps
+
+
 class FaceAligner:
     """recreate_aligned_images on the device.  Attached to HipModels as `aligner`; also usable alone (no network weights)."""
 
@@ -317,12 +348,19 @@ class FaceAligner:
             return self.run_plan(img_rgb_u8, plan), plan
         return self.run_plan(img_rgb_u8, plan), plan['landmarks']
 
-    def paste_back(self, photo, edits, plan, weight=None, feather=None):
+    def paste_back(self, photo, edits, plan, weight=None, feather=None, matte=None, return_alpha=False):
         """The way back: composite edited crops into the photo they were aligned from, ONE ch_face_unalign call for all of them.
         photo uint8 [H,W,3]; edits uint8 [S,S,3] or [N,S,S,3] (numpy is uploaded); plan: align_plan's dict (align(...,
         return_plan=True)) or unalign_plan's; weight: optional uint8 [S,S] map, 255 = the edit, 0 = the photo; feather: width in crop
-        pixels of the ramp at the crop's border (default S / 16, <= 0 = hard edge).  -> uint8 [N,H,W,3] device tensor."""
+        pixels of the ramp at the crop's border (default S / 16, <= 0 = hard edge).  -> uint8 [N,H,W,3] device tensor.
+        matte (True or a dict, see matte_params): the weight map, sampled nearest, is refined by a guided filter whose guide is the
+        photo (ONE ch_face_unalign_matte call), so the pasted region follows the photo's edges; needs `weight`.  return_alpha=True
+        (with matte) -> (out, alpha float32 [bh,bw] over the plan's bbox)."""
         import torch
+        if matte is None and return_alpha:
+            raise ValueError('return_alpha needs matte (the plain paste-back keeps no alpha plane)')
+        if matte is not None and weight is None:
+            raise ValueError('matte refines a weight map: pass weight=')
         x = self._u8(photo, 3)
         H, W = int(x.shape[0]), int(x.shape[1])
         pu = plan if 'A' in plan else unalign_plan(plan, H, W)
@@ -348,6 +386,16 @@ class FaceAligner:
         N = int(e.shape[0])
         pv, pp = self._f64(pack_unalign(pu))
         out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=self.device)
-        self.handle.call('ch_face_unalign', x.data_ptr(), H, W, e.data_ptr(), N, wp, pp, float(S / 16.0 if feather is None else feather),
-                         out.data_ptr(), self._stream())
-        return out
+        feather = float(S / 16.0 if feather is None else feather)
+        if matte is None:
+            self.handle.call('ch_face_unalign', x.data_ptr(), H, W, e.data_ptr(), N, wp, pp, feather, out.data_ptr(), self._stream())
+            return out
+        radius, eps = matte_params(matte, pu['scale'])
+        need = int(self.handle.lib.ch_face_unalign_matte_workspace_bytes(H, W, pp, radius))
+        if need == 0:
+            raise ValueError('the plan does not fit the photo (see ch_face_unalign_matte in include/ctrlhair_hip.h)')
+        ws = self._workspace(need)
+        alpha = torch.empty(bx[3] - bx[1], bx[2] - bx[0], dtype=torch.float32, device=self.device) if return_alpha else None
+        self.handle.call('ch_face_unalign_matte', x.data_ptr(), H, W, e.data_ptr(), N, wp, pp, feather, radius, eps, out.data_ptr(),
+                         None if alpha is None else alpha.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+        return (out, alpha) if return_alpha else out

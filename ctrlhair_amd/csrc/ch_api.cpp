@@ -85,6 +85,25 @@ std::string parse_plan(const double* d, int H, int W, chk::AlignPlan& p) {
     if (p.S < 1 || p.T < p.S || p.T > CH_ALIGN_MAX_TRANSFORM) return "need 1 <= output_size <= transform_size <= " + std::to_string(CH_ALIGN_MAX_TRANSFORM);
     return "";
 }
+// the checks both paste-back entries share; "" or what is wrong with the arguments
+std::string parse_unalign(const uint8_t* photo, int H, int W, const uint8_t* edits, int N, const double* plan, double feather_px,
+                          const uint8_t* out, chk::UnalignPlan& p) {
+    if (!photo || !edits || !plan || !out || !align_dims_ok(H, W) || N < 1 || N > 65535 || !std::isfinite(feather_px))
+        return "bad argument (null pointer, photo side outside [1, 32768], N outside [1, 65535])";
+    for (int i = 0; i < CH_UNALIGN_PLAN_LEN; ++i)
+        if (!std::isfinite(plan[i])) return "plan[" + std::to_string(i) + "] is not finite";
+    for (int i = 6; i < 12; ++i)
+        if (i != 10 && (plan[i] != std::floor(plan[i]) || std::fabs(plan[i]) > 1e9)) return "plan[" + std::to_string(i) + "] is not an integer";
+    for (int i = 0; i < 6; ++i) p.A[i] = plan[i];
+    p.x0 = (int)plan[6], p.y0 = (int)plan[7], p.x1 = (int)plan[8], p.y1 = (int)plan[9];
+    p.scale = plan[10], p.S = (int)plan[11];
+    if (p.x0 < 0 || p.y0 < 0 || p.x1 > W || p.y1 > H || p.x0 >= p.x1 || p.y0 >= p.y1) return "bbox empty or outside the photo";
+    if (!(p.scale > 0.0) || p.scale > CH_UNALIGN_MAX_SCALE) return "scale outside (0, " + std::to_string(CH_UNALIGN_MAX_SCALE) + "]";
+    if (p.S < 1 || p.S > CH_ALIGN_MAX_TRANSFORM) return "output_size outside [1, " + std::to_string(CH_ALIGN_MAX_TRANSFORM) + "]";
+    const size_t bytes = (size_t)H * W * 3;
+    if (out < photo + bytes && photo < out + bytes * (size_t)N) return "out overlaps photo";
+    return "";
+}
 }  // namespace
 
 extern "C" {
@@ -441,31 +460,47 @@ int ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* 
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_align: ") + hipGetErrorString(e));
 }
 
-// ---- paste-back (face_unalign.hip) -------------------------------------------------------------------------------------------------
+// ---- paste-back (face_unalign.hip, face_matte.hip) ------------------------------------------------------------------------------------
 int ch_face_unalign(ch_handle* h, const uint8_t* photo, int H, int W, const uint8_t* edits, int N, const uint8_t* weight, const double* plan,
                     double feather_px, uint8_t* out, ch_stream_t stream) {
     if (!h) return CH_ERR_ARG;
-    if (!photo || !edits || !plan || !out || !align_dims_ok(H, W) || N < 1 || N > 65535 || !std::isfinite(feather_px))
-        return fail(h, CH_ERR_ARG, "ch_face_unalign: bad argument (null pointer, photo side outside [1, 32768], N outside [1, 65535])");
-    for (int i = 0; i < CH_UNALIGN_PLAN_LEN; ++i)
-        if (!std::isfinite(plan[i])) return fail(h, CH_ERR_ARG, "ch_face_unalign: plan[" + std::to_string(i) + "] is not finite");
-    for (int i = 6; i < 12; ++i)
-        if (i != 10 && (plan[i] != std::floor(plan[i]) || std::fabs(plan[i]) > 1e9))
-            return fail(h, CH_ERR_ARG, "ch_face_unalign: plan[" + std::to_string(i) + "] is not an integer");
     chk::UnalignPlan p;
-    for (int i = 0; i < 6; ++i) p.A[i] = plan[i];
-    p.x0 = (int)plan[6], p.y0 = (int)plan[7], p.x1 = (int)plan[8], p.y1 = (int)plan[9];
-    p.scale = plan[10], p.S = (int)plan[11];
-    if (p.x0 < 0 || p.y0 < 0 || p.x1 > W || p.y1 > H || p.x0 >= p.x1 || p.y0 >= p.y1)
-        return fail(h, CH_ERR_ARG, "ch_face_unalign: bbox empty or outside the photo");
-    if (!(p.scale > 0.0) || p.scale > CH_UNALIGN_MAX_SCALE)
-        return fail(h, CH_ERR_ARG, "ch_face_unalign: scale outside (0, " + std::to_string(CH_UNALIGN_MAX_SCALE) + "]");
-    if (p.S < 1 || p.S > CH_ALIGN_MAX_TRANSFORM) return fail(h, CH_ERR_ARG, "ch_face_unalign: output_size outside [1, " + std::to_string(CH_ALIGN_MAX_TRANSFORM) + "]");
-    const size_t bytes = (size_t)H * W * 3;
-    if (out < photo + bytes && photo < out + bytes * (size_t)N) return fail(h, CH_ERR_ARG, "ch_face_unalign: out overlaps photo");
+    const std::string why = parse_unalign(photo, H, W, edits, N, plan, feather_px, out, p);
+    if (!why.empty()) return fail(h, CH_ERR_ARG, "ch_face_unalign: " + why);
     DeviceGuard guard(h->device);
     hipError_t e = chk::face_unalign(photo, edits, weight, p, H, W, N, feather_px, out, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_unalign: ") + hipGetErrorString(e));
+}
+
+size_t ch_face_unalign_matte_workspace_bytes(int H, int W, const double* plan, int radius) {
+    if (!plan || !align_dims_ok(H, W) || radius < 1 || radius > CH_MATTE_MAX_RADIUS) return 0;
+    for (int i = 6; i < 10; ++i)
+        if (!std::isfinite(plan[i]) || plan[i] != std::floor(plan[i]) || std::fabs(plan[i]) > 1e9) return 0;
+    const int x0 = (int)plan[6], y0 = (int)plan[7], x1 = (int)plan[8], y1 = (int)plan[9];
+    if (x0 < 0 || y0 < 0 || x1 > W || y1 > H || x0 >= x1 || y0 >= y1) return 0;
+    return chk::face_matte_workspace_bytes(x1 - x0, y1 - y0);
+}
+
+int ch_face_unalign_matte(ch_handle* h, const uint8_t* photo, int H, int W, const uint8_t* edits, int N, const uint8_t* weight, const double* plan,
+                          double feather_px, int radius, double eps, uint8_t* out, float* alpha_out, void* workspace, size_t workspace_bytes,
+                          ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    chk::UnalignPlan p;
+    const std::string why = parse_unalign(photo, H, W, edits, N, plan, feather_px, out, p);
+    if (!why.empty()) return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: " + why);
+    if (!weight) return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: weight is null (the matte refines a weight map)");
+    if (radius < 1 || radius > CH_MATTE_MAX_RADIUS)
+        return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: radius outside [1, " + std::to_string(CH_MATTE_MAX_RADIUS) + "]");
+    if (!(eps > 0.0) || !std::isfinite(eps)) return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: eps must be positive and finite");
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
+        return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: workspace is null or not 256-byte aligned");
+    if (workspace_bytes < chk::face_matte_workspace_bytes(p.x1 - p.x0, p.y1 - p.y0))
+        return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: workspace smaller than ch_face_unalign_matte_workspace_bytes");
+    if (reinterpret_cast<uintptr_t>(alpha_out) % 4 != 0) return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: alpha_out is not 4-byte aligned");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::face_unalign_matte(photo, edits, weight, p, H, W, N, feather_px, radius, eps, out, alpha_out, workspace,
+                                           static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_unalign_matte: ") + hipGetErrorString(e));
 }
 
 // ---- median style codes (style_medoid.hip) ---------------------------------------------------------------------------------------

@@ -215,6 +215,13 @@ struct UnalignPlan {
 hipError_t face_unalign(const uint8_t* photo, const uint8_t* edits, const uint8_t* weight, const UnalignPlan& p, int H, int W, int N,
                         double feather_px, uint8_t* out, hipStream_t s);
 
+// face_matte.hip: the same paste-back with alpha = a colour guided filter of the nearest-sampled weight map (guide: the photo's RGB
+// over the bounding box, exact integer window moments, float64 solve) times the border ramp.  ws: face_matte_workspace_bytes(bw, bh)
+// bytes, 256-byte aligned; alpha_out: optional float [bh,bw].  See ch_face_unalign_matte in ctrlhair_hip.h.
+size_t face_matte_workspace_bytes(int bw, int bh);
+hipError_t face_unalign_matte(const uint8_t* photo, const uint8_t* edits, const uint8_t* weight, const UnalignPlan& p, int H, int W, int N,
+                              double feather_px, int radius, double eps, uint8_t* out, float* alpha_out, void* ws, hipStream_t s);
+
 // style_medoid.hip: per-segment medoid (first minimum of the float64 row sums of float32 difference-form distances) and float64 mean
 // of compacted style codes (sean_codes/get_mean_code.py); seg_offsets is a host array [R + 1].  See ch_style_medoid in ctrlhair_hip.h.
 size_t style_medoid_workspace_bytes(const int64_t* seg_offsets, int R, int n_split);

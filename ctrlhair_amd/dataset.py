@@ -24,8 +24,11 @@ On-disk formats are the reference's:
                                           (dataset_scripts/script_crop.py: FFHQ-align every photo of <src_dir> into
                                            <root>/<dataset>/images_256/<name>; no network weights: ctrlhair_amd.alignment)
     python -m ctrlhair_amd.dataset uncrop <photos> <edits> <out> --landmarks <file> [--size S]
+                                          [--labels DIR [--matte] [--matte-radius R] [--matte-eps E]]
                                           (the inverse of crop: paste the edited crop <edits>/<name> back into <photos>/<name> with the
-                                           same landmarks and write the photo-sized result to <out>/<name>; ctrlhair_amd.alignment)
+                                           same landmarks and write the photo-sized result to <out>/<name>; ctrlhair_amd.alignment.
+                                           --labels: 8-bit label PNGs <DIR>/<stem>.png of the crops; only their hair is pasted, and with
+                                           --matte that region is refined by a guided filter of the photo: ch_face_unalign_matte)
     python -m ctrlhair_amd.dataset median <root> [--out FILE] [--tree DIR]
                                           (sean_codes/get_mean_code.py: the per-region medoid of <root>/sean_code_dict.pkl, written as
                                            <root>/mean_style_code.npz for HairEditor(mean_style_code=...); no network weights:
@@ -257,14 +260,30 @@ def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dic
     return done, skipped
 
 
+def label_weight(label_path: str, S: int) -> np.ndarray:
+    """The paste-back weight of a crop's label PNG: uint8 [S,S], 255 on hair (HAIR_IDX), 0 elsewhere; a label map of another size is
+    resized nearest, like everywhere labels meet images here."""
+    from PIL import Image
+    from .hostutil import HAIR_IDX
+    lab = Image.open(label_path)
+    if lab.mode not in ('L', 'P'):
+        raise ValueError(f'{label_path}: expected an 8-bit single-channel label PNG, got mode {lab.mode}')
+    if lab.size != (S, S):
+        lab = lab.resize((S, S), Image.NEAREST)
+    return ((np.asarray(lab) == HAIR_IDX) * 255).astype(np.uint8)
+
+
 def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = None,
-                 rank: int = 0, world: int = 1):
+                 rank: int = 0, world: int = 1, label_dir: str = None, matte=None):
     """The inverse of crop_faces for this rank's shard of `photo_dir`: paste the edited crop `edit_dir/<name>` back into the photo
     `photo_dir/<name>` it was aligned from (same landmarks, same file names) and write the photo-sized result to `out_dir/<name>`.
-    size: the crops' side (default: each edit's own).  Returns (done, skipped); a photo without landmarks or without an edit is
-    reported and left out."""
+    size: the crops' side (default: each edit's own).  label_dir: per-image weight from `label_dir/<stem>.png` (hair = 255); matte
+    (True or a dict, alignment.matte_params; needs label_dir): that weight refined by a guided filter of the photo.  Returns
+    (done, skipped); a photo without landmarks, without an edit or (with label_dir) without a label map is reported and left out."""
     from PIL import Image
     from .alignment import align_plan
+    if matte is not None and label_dir is None:
+        raise ValueError('matte refines a weight map: it needs label_dir')
     os.makedirs(out_dir, exist_ok=True)
     done, skipped = [], []
     for n in shard(list_images(photo_dir), rank, world):
@@ -273,11 +292,20 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
             print(f'uncrop: no {"landmarks" if lm is None else "edit"} for {n}, skipped')
             skipped.append(n)
             continue
+        label = None if label_dir is None else os.path.join(label_dir, os.path.splitext(n)[0] + '.png')
+        if label is not None and not os.path.exists(label):
+            print(f'uncrop: no label map for {n}, skipped')
+            skipped.append(n)
+            continue
         photo, edit = read_rgb(os.path.join(photo_dir, n)), read_rgb(os.path.join(edit_dir, n))
         S = int(edit.shape[0]) if size is None else int(size)
         if edit.shape[:2] != (S, S):
             raise ValueError(f'{os.path.join(edit_dir, n)}: expected a {S} x {S} crop, got {edit.shape[1]} x {edit.shape[0]}')
-        out = aligner.paste_back(photo, edit, align_plan(lm[:68], photo.shape[0], photo.shape[1], S))[0]
+        plan = align_plan(lm[:68], photo.shape[0], photo.shape[1], S)
+        if label is None:
+            out = aligner.paste_back(photo, edit, plan)[0]
+        else:
+            out = aligner.paste_back(photo, edit, plan, weight=label_weight(label, S), matte=matte)[0]
         Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n))
         done.append(n)
     return done, skipped
@@ -566,7 +594,21 @@ def _main_uncrop(argv):
     ap.add_argument('--landmarks', required=True, help='.npz or pickled dict: image name -> [68,2] pixel landmarks (the crop job\'s file)')
     ap.add_argument('--size', type=int, default=None, help="the crops' side (default: each edit's own)")
     ap.add_argument('--dataset', default='', help="dataset name of '<dataset>___<name>' landmark keys")
+    ap.add_argument('--labels', default=None, help='directory of 8-bit label PNGs of the crops (<stem>.png): paste only their hair')
+    ap.add_argument('--matte', action='store_true', help='refine the hair region with a guided filter of the photo (needs --labels)')
+    ap.add_argument('--matte-radius', type=int, default=None, help='matte window radius in photo pixels, 1..64 (default: 4 crop pixels)')
+    ap.add_argument('--matte-eps', type=float, default=None, help='matte regularisation (default 1e-4)')
     args = ap.parse_args(argv)
+    matte = None
+    if args.matte or args.matte_radius is not None or args.matte_eps is not None:
+        if args.labels is None:
+            ap.error('--matte, --matte-radius and --matte-eps need --labels DIR (the matte refines a per-image weight)')
+        matte = {k: v for k, v in (('radius', args.matte_radius), ('eps', args.matte_eps)) if v is not None}
+        from .alignment import matte_params
+        try:
+            matte_params(matte, 1.0)
+        except ValueError as e:
+            ap.error(str(e))
     import torch
     from . import lib
     from .alignment import FaceAligner
@@ -574,7 +616,7 @@ def _main_uncrop(argv):
     torch.cuda.set_device(local)
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = uncrop_faces(aligner, args.photos, args.edits, args.out, args.dataset, load_landmarks(args.landmarks), args.size,
-                                 rank, world)
+                                 rank, world, label_dir=args.labels, matte=matte)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
 
 

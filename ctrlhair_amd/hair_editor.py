@@ -413,11 +413,12 @@ class HairEditor:
             Image.fromarray(img).save(save_path)
         return img
 
-    def paste_back(self, edited, photo=None, plan=None, weight=None, feather=None):
+    def paste_back(self, edited, photo=None, plan=None, weight=None, feather=None, matte=None):
         """The way back from crop_face: composite edited crops (uint8 [S,S,3] or [N,S,S,3], numpy or device tensors) into the photo
         they were aligned from, on the device (FaceAligner.paste_back, one ch_face_unalign call) -> uint8 [N,H,W,3] device tensor.
         photo / plan default to those of the last crop_face call (`self.last_alignment`); weight: optional uint8 [S,S] map (255 =
-        the edit, 0 = the photo) on top of the feathered border."""
+        the edit, 0 = the photo) on top of the feathered border; matte (True or a dict, alignment.matte_params): refine the weight
+        with a guided filter of the photo (one ch_face_unalign_matte call), needs `weight`."""
         last = getattr(self, 'last_alignment', None)
         if photo is None or plan is None:
             if last is None:
@@ -433,4 +434,6 @@ class HairEditor:
         if aligner is None:
             raise RuntimeError('paste_back needs the HIP models (HipModels.aligner, ctrlhair_amd.alignment.FaceAligner: the library '
                                'and a GPU); there is no CPU path')
-        return aligner.paste_back(photo, edited, plan, weight=weight, feather=feather)
+        if matte is None:
+            return aligner.paste_back(photo, edited, plan, weight=weight, feather=feather)
+        return aligner.paste_back(photo, edited, plan, weight=weight, feather=feather, matte=matte)

@@ -58,6 +58,8 @@ SYMBOLS = {
     'ch_face_align_workspace_bytes': (C.c_size_t, [_I, _I, _VP, _I]),
     'ch_face_align': (_I, [_VP, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, C.c_size_t, _VP]),
     'ch_face_unalign': (_I, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP, _D, _VP, _VP]),
+    'ch_face_unalign_matte_workspace_bytes': (C.c_size_t, [_I, _I, _VP, _I]),
+    'ch_face_unalign_matte': (_I, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP, _D, _I, _D, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_style_medoid_workspace_bytes': (C.c_size_t, [_VP, _I, _I, _I]),
     'ch_style_medoid': (_I, [_VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_sean_set_tap': (_I, [_VP, C.c_char_p, _VP]),

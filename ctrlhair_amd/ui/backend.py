@@ -234,14 +234,25 @@ class Backend(HairEditor):
         return out, masks_np
 
     # ---- rendering into the user's photo -------------------------------------------------------------------------------
-    def _region_weight(self, region, masks):
+    def _region_weight(self, region, masks, matte=None):
         """The paste-back weight of `region` for N rendered label maps (uint8 [N,h,w]): None for 'crop' (the whole crop, feathered at
         its border); for 'hair' 255 where postprocess_blending keeps the generated image -- the dilated union of the input's and the
-        N results' hair (ch_blend_mask at the image size), one map for all N."""
+        N results' hair (ch_blend_mask at the image size), one map for all N.  With `matte` the union is NOT dilated (the dilation
+        gives Poisson blending room inside the crop; a matte that follows the photo's edges starts from the region itself), built
+        on the device; 'crop' has no weight to refine and raises."""
         if region == 'crop':
+            if matte is not None:
+                raise ValueError("matte refines the weight of a region: use region='hair' (region='crop' has no weight)")
             return None
         if region != 'hair':
             raise ValueError(f"region must be 'crop' or 'hair', got {region!r}")
+        if matte is not None:
+            S = (self.img_size, self.img_size)
+            tp = np.stack([m if m.shape == S else U.resize_nearest(m, S) for m in np.asarray(masks).astype('uint8')])
+            fp = np.asarray(self.input_mask).astype('uint8')
+            fp = fp if fp.shape == S else U.resize_nearest(fp, S)
+            labels = torch.from_numpy(np.concatenate([tp, fp.reshape((1,) + S)])).to(self.device)
+            return (labels == HAIR_IDX).any(dim=0).to(torch.uint8) * 255
         blender = getattr(getattr(self, 'models', None), 'blender', None)
         if blender is None:
             raise RuntimeError("region='hair' needs the HIP models (HipModels.blender); there is no CPU path")
@@ -252,23 +263,30 @@ class Backend(HairEditor):
         kept = blender.blend_mask(tp, fp)                     # [N,S,S], 1 = generated image kept
         return kept.amax(dim=0) * 255
 
-    def outputs_in_photo(self, latents, photo=None, plan=None, region='crop', noise=None, feather=None):
+    def outputs_in_photo(self, latents, photo=None, plan=None, region='crop', noise=None, feather=None, matte=None):
         """outputs(latents), then ONE paste-back call that composites the N images into the photo the input crop was aligned from
         (HairEditor.paste_back: by default the photo and plan of the last crop_face call).  region: 'crop' pastes the whole crop,
-        'hair' only the dilated hair region (see _region_weight).  Returns (uint8 [N,H,W,3] device tensor, uint8 label maps
-        [N,256,256])."""
+        'hair' only the dilated hair region (see _region_weight).  matte (True or a dict, alignment.matte_params; region='hair'
+        only): the undilated hair region refined by a guided filter of the photo, so the paste follows the hair outline visible in
+        the photo.  Returns (uint8 [N,H,W,3] device tensor, uint8 label maps [N,256,256])."""
+        if region == 'crop' and matte is not None:
+            self._region_weight(region, None, matte)          # raises before anything is rendered
         imgs, masks = self.outputs(latents, noise=noise)
         if len(imgs) == 0:
             raise ValueError('outputs_in_photo needs at least one latent')
-        weight = self._region_weight(region, masks)
-        return self.paste_back(np.stack([np.asarray(i) for i in imgs]), photo=photo, plan=plan, weight=weight, feather=feather), masks
+        weight = self._region_weight(region, masks, matte)
+        return self.paste_back(np.stack([np.asarray(i) for i in imgs]), photo=photo, plan=plan, weight=weight, feather=feather,
+                               matte=matte), masks
 
-    def output_in_photo(self, target_latent=None, feature=None, photo=None, plan=None, region='crop', feather=None):
-        """output(target_latent, feature), then the image pasted into the photo -> uint8 [H,W,3] device tensor."""
+    def output_in_photo(self, target_latent=None, feature=None, photo=None, plan=None, region='crop', feather=None, matte=None):
+        """output(target_latent, feature), then the image pasted into the photo -> uint8 [H,W,3] device tensor (matte: as in
+        outputs_in_photo)."""
+        if region == 'crop' and matte is not None:
+            self._region_weight(region, None, matte)
         img = self.output(target_latent, feature)
         mask = self.cur_mask if target_latent is None else self.refresh_cur_mask(target_latent)[0]
-        weight = self._region_weight(region, np.asarray(mask)[None])
-        return self.paste_back(np.asarray(img), photo=photo, plan=plan, weight=weight, feather=feather)[0]
+        weight = self._region_weight(region, np.asarray(mask)[None], matte)
+        return self.paste_back(np.asarray(img), photo=photo, plan=plan, weight=weight, feather=feather, matte=matte)[0]
 
     def sweep(self, att_name, idx, values, noise=None):
         """Slider sweep: the images output() would give after change_<att_name>(v, idx) for each v in `values`, rendered as

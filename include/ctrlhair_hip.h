@@ -443,6 +443,34 @@ int  ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double*
 int  ch_face_unalign(ch_handle* h, const uint8_t* photo, int H, int W, const uint8_t* edits, int N, const uint8_t* weight,
                      const double* plan, double feather_px, uint8_t* out, ch_stream_t stream);
 
+/* ---- Paste-back with an edge-aware matte: the weight map refined by a colour guided filter of the photo --------------------------
+ * He, Sun, Tang, "Guided Image Filtering", colour guide: the weight is fitted locally as a linear function of the photo's RGB, so
+ * the matte follows the photo's edges instead of the staircase of an up-sampled label map.  plan, photo, edits, out, feather_px,
+ * the coordinates (x, y) and the Lanczos resample e are exactly those of ch_face_unalign.  weight uint8 [S,S] is required.
+ * The domain D is the plan's bbox, bw x bh pixels.  1 <= radius <= CH_MATTE_MAX_RADIUS (at r = 64 the sum of I I over a window is at
+ * most 255^2 129^2 ~ 1.08e9, which fits int32); eps > 0 and finite, in units of a guide scaled to [0, 1].  Per pixel (X, Y) of D:
+ *   1. p8 = weight[clamp(floor(y))][clamp(floor(x))] when min(x, S - x, y, S - y) > 0, else 0 (nearest: an exact integer).
+ *   2. Over the window [X - r, X + r] x [Y - r, Y + r] clipped to D, n pixels: the 13 integer sums of p, I_c (3), I_c p (3) and
+ *      I_c I_d (6), I = the photo's bytes.  All exact.
+ *   3. n sum(I_c p) - sum(I_c) sum(p) and n sum(I_c I_d) - sum(I_c) sum(I_d) as exact int64, converted to float64 and divided by
+ *      n^2 255^2; (cov + eps Id) a = cov_Ip solved in float64 by LDL^T (Cholesky without square roots; the matrix is symmetric
+ *      positive definite); b = sum(p) / (255 n) - a . sum(I) / (255 n).  a (3 values) and b are rounded to float32.
+ *   4. q = mean_w(a) . I / 255 + mean_w(b) over the same clipped window, the sums accumulated in float64; m = clamp(q, 0, 1) as
+ *      float32.
+ *   5. alpha = m * ramp in float32, ramp = clamp(min(x, S - x, y, S - y) / feather_px, 0, 1) (feather_px <= 0: 1 inside the quad,
+ *      0 outside): alpha is 0 outside the quad whatever the filter leaks.  out = clamp(floor(alpha e + (1 - alpha) p + 0.5), 0, 255)
+ *      as in ch_face_unalign; alpha == 0 and everything outside D: the photo's bytes.
+ * The matte is computed once and shared by all N edits; image n of a batch is bit-identical to an N = 1 call.
+ * alpha_out: optional device float [bh,bw], receives alpha over D.
+ * workspace: caller-owned device buffer (256-byte aligned) of ch_face_unalign_matte_workspace_bytes(H, W, plan, radius) bytes
+ *   (0 = bad argument; 21 bytes per pixel of D), contents undefined.  Five launches on `stream`: no synchronisation, no
+ *   allocation, no atomics, no waiting between workgroups; the cost does not grow with radius beyond halo and warm-up rows. */
+#define CH_MATTE_MAX_RADIUS 64
+size_t ch_face_unalign_matte_workspace_bytes(int H, int W, const double* plan, int radius);
+int  ch_face_unalign_matte(ch_handle* h, const uint8_t* photo, int H, int W, const uint8_t* edits, int N, const uint8_t* weight,
+                           const double* plan, double feather_px, int radius, double eps, uint8_t* out, float* alpha_out,
+                           void* workspace, size_t workspace_bytes, ch_stream_t stream);
+
 /* ---- Median style codes: sean_codes/get_mean_code.py for R segments (the 19 regions) in one call -----------------------------
  * For each segment the medoid is the row whose summed Euclidean distance to the segment's rows is smallest.  The reference builds
  * the n x n matrix from the Gram identity in float32; here the matrix is never stored and the arithmetic is fixed as follows:
