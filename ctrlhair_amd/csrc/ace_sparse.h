@@ -143,6 +143,21 @@ hipError_t ace_worklist(const int* cnt, int ntiles, int mtiles, unsigned* work, 
 // lut element (row = (t*2+gb)*C + c, n = b*lut_bs + j) at lut[row*lut_rs + n*lut_ns]; lut_mul undoes a pre-multiplied LUT
 hipError_t ace_gtable(const float* bias_g, const float* bias_b, const float* gconst, const float* lut, int lut_rs, int lut_ns,
                       int lut_bs, float lut_mul, float* gtab, int B, int C, hipStream_t s);
+// ACE prologue (sean_model.cpp): gtab and, where p6 is set, P6 of several ACEs from ONE launch.  The group is filled per call and travels
+// by value as the kernel argument; LUT layout as lut_ns = 18 C per entry with the group's lut_rs / lut_bs / lut_mul.  The caller fills
+// bias_g .. C; the launcher fills start and nblk_g.
+struct AceTableGroup {
+    static constexpr int MAX = 24;
+    struct Entry {
+        const float *bias_g, *bias_b, *gconst, *lut;      // lut may be null: unstyled ACE (then p6 must be null)
+        float *gtab, *p6;
+        int C, start, nblk_g;
+    };
+    Entry e[MAX];
+    int n, B, lut_rs, lut_bs;
+    float lut_mul;
+};
+hipError_t ace_tables_grouped(AceTableGroup& g, hipStream_t s);
 
 struct AceInteriorParams {
     const float* x;             // exact-f32 path: NCHW [B][C][H>>x_up][W>>x_up]; f16x3 path: C4 [B][C/4][h][w][4]

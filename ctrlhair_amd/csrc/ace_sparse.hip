@@ -219,12 +219,11 @@ hipError_t ace_worklist(const int* cnt, int ntiles, int mtiles, unsigned* work, 
 }
 
 // ---- per-(sample, label) gamma/beta rows of the interior pixels ------------------------------------------------------------
-__global__ __launch_bounds__(256) void ace_gtable_kernel(const float* __restrict__ bias_g, const float* __restrict__ bias_b,
-                                                         const float* __restrict__ gconst, const float* __restrict__ lut,
-                                                         int lut_rs, int lut_ns, int lut_bs, float lut_mul,
-                                                         float* __restrict__ gtab, int B, int C) {
+__device__ __forceinline__ void ace_gtable_elem(const float* __restrict__ bias_g, const float* __restrict__ bias_b,
+                                                const float* __restrict__ gconst, const float* __restrict__ lut,
+                                                int lut_rs, int lut_ns, int lut_bs, float lut_mul,
+                                                float* __restrict__ gtab, int B, int C, long long i) {
     const long long n = (long long)B * 19 * 2 * C;
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(i % C), gb = (int)((i / C) & 1), j = (int)((i / (2 * C)) % 19), b = (int)(i / (2LL * C * 19));
     float v = (gb ? bias_b : bias_g)[c] + gconst[((long long)j * 2 + gb) * C + c];
@@ -240,6 +239,12 @@ __global__ __launch_bounds__(256) void ace_gtable_kernel(const float* __restrict
         v += sacc * lut_mul;
     }
     gtab[i] = v;
+}
+__global__ __launch_bounds__(256) void ace_gtable_kernel(const float* __restrict__ bias_g, const float* __restrict__ bias_b,
+                                                         const float* __restrict__ gconst, const float* __restrict__ lut,
+                                                         int lut_rs, int lut_ns, int lut_bs, float lut_mul,
+                                                         float* __restrict__ gtab, int B, int C) {
+    ace_gtable_elem(bias_g, bias_b, gconst, lut, lut_rs, lut_ns, lut_bs, lut_mul, gtab, B, C, blockIdx.x * 256LL + threadIdx.x);
 }
 
 hipError_t ace_gtable(const float* bias_g, const float* bias_b, const float* gconst, const float* lut, int lut_rs, int lut_ns,
@@ -289,10 +294,9 @@ hipError_t ace_edge_table(const double* W6, const double* hv, const float* bias_
     hipLaunchKernelGGL(ace_edge_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W6, hv, bias_g, bias_b, scale_g, scale_b, E, C);
     return hipGetLastError();
 }
-__global__ __launch_bounds__(256) void ace_p6table_kernel(const float* __restrict__ lut, int lut_rs, int lut_ns, int lut_bs, float lut_mul,
-                                                          float* __restrict__ p6, int B, int C) {
+__device__ __forceinline__ void ace_p6table_elem(const float* __restrict__ lut, int lut_rs, int lut_ns, int lut_bs, float lut_mul,
+                                                 float* __restrict__ p6, int B, int C, long long i) {
     const long long n = (long long)B * 19 * 6 * 2 * C;
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= n) return;
     const int c = (int)(i % C), gb = (int)((i / C) & 1), k = (int)((i / (2 * C)) % 6), j = (int)((i / (12LL * C)) % 19), b = (int)(i / (12LL * C * 19));
     const long long col = (long long)(b * lut_bs + j) * lut_ns;
@@ -305,9 +309,41 @@ __global__ __launch_bounds__(256) void ace_p6table_kernel(const float* __restric
     }
     p6[i] = sacc * lut_mul;
 }
+__global__ __launch_bounds__(256) void ace_p6table_kernel(const float* __restrict__ lut, int lut_rs, int lut_ns, int lut_bs, float lut_mul,
+                                                          float* __restrict__ p6, int B, int C) {
+    ace_p6table_elem(lut, lut_rs, lut_ns, lut_bs, lut_mul, p6, B, C, blockIdx.x * 256LL + threadIdx.x);
+}
 hipError_t ace_p6table(const float* lut, int lut_rs, int lut_ns, int lut_bs, float lut_mul, float* p6, int B, int C, hipStream_t s) {
     const long long n = (long long)B * 19 * 6 * 2 * C;
     hipLaunchKernelGGL(ace_p6table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lut, lut_rs, lut_ns, lut_bs, lut_mul, p6, B, C);
+    return hipGetLastError();
+}
+
+// ACE prologue (sean_model.cpp): the gamma / beta rows and the column / row sums of several ACEs from one launch -- every entry owns a run
+// of blocks, first those of its gtab, then (p6 != nullptr) those of its p6; the element functions are the ones of the two kernels above
+__global__ __launch_bounds__(256) void ace_tables_grouped_kernel(AceTableGroup g) {
+    int k = 0;
+    while (k + 1 < g.n && (int)blockIdx.x >= g.e[k + 1].start) ++k;
+    const AceTableGroup::Entry& e = g.e[k];
+    const int lb = (int)blockIdx.x - e.start;
+    if (lb < e.nblk_g)
+        ace_gtable_elem(e.bias_g, e.bias_b, e.gconst, e.lut, g.lut_rs, 18 * e.C, g.lut_bs, g.lut_mul, e.gtab, g.B, e.C, lb * 256LL + threadIdx.x);
+    else
+        ace_p6table_elem(e.lut, g.lut_rs, 18 * e.C, g.lut_bs, g.lut_mul, e.p6, g.B, e.C, (lb - e.nblk_g) * 256LL + threadIdx.x);
+}
+hipError_t ace_tables_grouped(AceTableGroup& g, hipStream_t s) {
+    if (g.n < 0 || g.n > AceTableGroup::MAX || g.B < 1) return hipErrorInvalidValue;
+    if (g.n == 0) return hipSuccess;
+    long long grid = 0;
+    for (int k = 0; k < g.n; ++k) {
+        AceTableGroup::Entry& e = g.e[k];
+        if (!e.bias_g || !e.bias_b || !e.gconst || !e.gtab || e.C < 1 || (e.p6 && !e.lut)) return hipErrorInvalidValue;
+        e.start = (int)grid;
+        e.nblk_g = (int)(((long long)g.B * 19 * 2 * e.C + 255) / 256);
+        grid += e.nblk_g + (e.p6 ? ((long long)g.B * 19 * 6 * 2 * e.C + 255) / 256 : 0);
+    }
+    if (grid >= (1ll << 30)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ace_tables_grouped_kernel, dim3((unsigned)grid), dim3(256), 0, s, g);
     return hipGetLastError();
 }
 

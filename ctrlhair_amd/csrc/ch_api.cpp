@@ -683,7 +683,10 @@ const OptRow OPTION_TABLE[] = {
     // exact-f32 path: 3x3 convs as Winograd on the f32 matrix cores (conv_wino.h): 1 = F(2x2,3x3); 2 = + the ResBlock convs as F(4x4,3x3) (default)
     {"sean.wino", BY_SEAN, CLAMP, 0, 2, SEAN_FIELD(wino)},
     {"sean.lut_grouped", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(lut_grouped)},      // exact-f32 path: 1 = the style LUTs of a chunk from one grouped GEMM launch (default)
-    {"sean.overlap", BY_SEAN, CLAMP, 0, MAXI, SEAN_FIELD(overlap)},          // CUs of the side streams of the overlap mode (sean_model.h), 0 = off
+    // exact-f32 Winograd path, handles beyond the run-ahead sizes: 1 = the label / code-only products of the ACEs from grouped launches at the start
+    // of a chunk (default; off by itself with sean.f16x3, sean.overlap or while profiling is enabled), 0 = every ACE launches its own, inline
+    {"sean.prologue", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(prologue)},
+    {"sean.overlap", BY_SEAN, CLAMP, 0, MAXI, SEAN_FIELD(overlap)},        // CUs of the side streams of the overlap mode (sean_model.h), 0 = off
     {"sean.wino4_force", NEVER, BOOL, 0, 0, SEAN_FIELD(wino4_force)},        // 1 = F(4x4,3x3) wherever the shape allows, even with fewer tasks than CUs (tests / measurements)
     {"sean.patch", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(patch)},                  // 1 = pre-gathered hidden-activation patches for levels with few boundary quads (default), 0 = planes only
     {"sean.convt_gemm", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(convt_gemm)},        // exact-f32 Zencoder: 1 = the ConvTranspose as four phase GEMMs over shifted views (default), 0 = four Winograd phase convs

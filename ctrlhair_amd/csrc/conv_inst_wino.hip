@@ -174,10 +174,10 @@ hipError_t conv_wino_ace(WinoAceParams p, hipStream_t s) {
 }
 
 // ---- gather mode: per-tile lists (tiles of 32 x 16) -> one list of boundary quads per sample, tasks of 64 consecutive entries --------
-__global__ __launch_bounds__(1024) void wino_gather_scan_kernel(const int* __restrict__ qcnt, int* __restrict__ qoff, int* __restrict__ gq_n, int tps) {
+__device__ __forceinline__ void wino_gather_scan_block(const int* __restrict__ qcnt, int* __restrict__ qoff, int* __restrict__ gq_n, int tps, int b) {
     __shared__ int wsum[16];
     __shared__ int carry;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) carry = 0;
     __syncthreads();
     for (int t0 = 0; t0 < tps; t0 += 1024) {
@@ -200,14 +200,21 @@ __global__ __launch_bounds__(1024) void wino_gather_scan_kernel(const int* __res
     }
     if (tid == 0) gq_n[b] = carry;
 }
-__global__ __launch_bounds__(128) void wino_gather_fill_kernel(const uint8_t* __restrict__ qlist, const int* __restrict__ qcnt, const int* __restrict__ qoff,
-                                                               unsigned* __restrict__ gq, int gq_cap, int ntx, int nty) {
-    const int tile = blockIdx.x, i = threadIdx.x;
+__global__ __launch_bounds__(1024) void wino_gather_scan_kernel(const int* __restrict__ qcnt, int* __restrict__ qoff, int* __restrict__ gq_n, int tps) {
+    wino_gather_scan_block(qcnt, qoff, gq_n, tps, (int)blockIdx.x);
+}
+__device__ __forceinline__ void wino_gather_fill_block(const uint8_t* __restrict__ qlist, const int* __restrict__ qcnt, const int* __restrict__ qoff,
+                                                       unsigned* __restrict__ gq, int gq_cap, int ntx, int nty, int tile) {
+    const int i = threadIdx.x;
     if (i >= qcnt[tile]) return;
     const int b = tile / (ntx * nty), tr = tile % (ntx * nty);
     const int q = qlist[(long long)tile * 128 + i];
     const unsigned y = (unsigned)((tr / ntx) * 16 + 2 * (q >> 4)), x = (unsigned)((tr % ntx) * 32 + 2 * (q & 15));
     gq[(long long)b * gq_cap + qoff[tile] + i] = y << 16 | x;
+}
+__global__ __launch_bounds__(128) void wino_gather_fill_kernel(const uint8_t* __restrict__ qlist, const int* __restrict__ qcnt, const int* __restrict__ qoff,
+                                                               unsigned* __restrict__ gq, int gq_cap, int ntx, int nty) {
+    wino_gather_fill_block(qlist, qcnt, qoff, gq, gq_cap, ntx, nty, (int)blockIdx.x);
 }
 hipError_t wino_gather_lists(const uint8_t* qlist, const int* qcnt, int* qoff, unsigned* gq, int* gq_n, int gq_cap, int B, int H, int W, hipStream_t s) {
     if (H % 16 || W % 32 || B > 32 || H > 65535 || W > 65535) return hipErrorInvalidValue;
@@ -216,8 +223,8 @@ hipError_t wino_gather_lists(const uint8_t* qlist, const int* qcnt, int* qoff, u
     hipLaunchKernelGGL(wino_gather_fill_kernel, dim3(B * ntx * nty), dim3(128), 0, s, qlist, qcnt, qoff, gq, gq_cap, ntx, nty);
     return hipGetLastError();
 }
-__global__ __launch_bounds__(1024) void wino_gather_worklist_kernel(const int* __restrict__ gq_n, const int* __restrict__ pcnt, int B, int tps, int nrt,
-                                                                    unsigned* __restrict__ work, int* __restrict__ total) {
+__device__ __forceinline__ void wino_gather_worklist_block(const int* __restrict__ gq_n, const int* __restrict__ pcnt, int B, int tps, int nrt,
+                                                           unsigned* __restrict__ work, int* __restrict__ total) {
     __shared__ int base[33];
     __shared__ int stat[4];
     const int tid = threadIdx.x;
@@ -253,6 +260,10 @@ __global__ __launch_bounds__(1024) void wino_gather_worklist_kernel(const int* _
         total[3] = total[7] = stat[1] * nrt;
     }
 }
+__global__ __launch_bounds__(1024) void wino_gather_worklist_kernel(const int* __restrict__ gq_n, const int* __restrict__ pcnt, int B, int tps, int nrt,
+                                                                    unsigned* __restrict__ work, int* __restrict__ total) {
+    wino_gather_worklist_block(gq_n, pcnt, B, tps, nrt, work, total);
+}
 hipError_t wino_gather_worklist(const int* gq_n, const int* pcnt, int B, int tiles_per_sample, int nrt, unsigned* work, int* total, hipStream_t s) {
     if (B > 32 || nrt > 2 * 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(wino_gather_worklist_kernel, dim3(1), dim3(1024), 0, s, gq_n, pcnt, B, tiles_per_sample, nrt, work, total);
@@ -261,11 +272,11 @@ hipError_t wino_gather_worklist(const int* gq_n, const int* pcnt, int B, int til
 
 // ---- boundary quads of a tile of 32 x TH pixels: one block of 8 TH threads = the tile's 16 x TH / 2 quads, ordered compaction -----
 template <int TH>
-__global__ __launch_bounds__(8 * TH) void wino_quad_list_kernel(const uint8_t* __restrict__ u5, uint8_t* __restrict__ qlist, int* __restrict__ qcnt,
-                                                                int* __restrict__ pcnt, int H, int W, int ntx, int nty) {
+__device__ __forceinline__ void wino_quad_list_block(const uint8_t* __restrict__ u5, uint8_t* __restrict__ qlist, int* __restrict__ qcnt,
+                                                     int* __restrict__ pcnt, int H, int W, int ntx, int nty, int tile) {
     constexpr int NW = TH / 8;
     __shared__ int wc[NW], pc[NW];
-    const int tile = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int b = tile / (ntx * nty), tr = tile % (ntx * nty);
     const int y = (tr / ntx) * TH + 2 * (tid >> 4), x = (tr % ntx) * 32 + 2 * (tid & 15);
     int npx = 4;                                               // boundary pixels of the quad (u5 == nullptr: every pixel is one)
@@ -291,11 +302,74 @@ __global__ __launch_bounds__(8 * TH) void wino_quad_list_kernel(const uint8_t* _
     if (bnd) qlist[(long long)tile * (8 * TH) + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)tid;
     if (tid == 0) { qcnt[tile] = tq; pcnt[tile] = tp; }
 }
+template <int TH>
+__global__ __launch_bounds__(8 * TH) void wino_quad_list_kernel(const uint8_t* __restrict__ u5, uint8_t* __restrict__ qlist, int* __restrict__ qcnt,
+                                                                int* __restrict__ pcnt, int H, int W, int ntx, int nty) {
+    wino_quad_list_block<TH>(u5, qlist, qcnt, pcnt, H, W, ntx, nty, (int)blockIdx.x);
+}
 hipError_t wino_quad_lists(const uint8_t* u5, uint8_t* qlist, int* qcnt, int* pcnt, int B, int H, int W, int TH, hipStream_t s) {
     if ((TH != 16 && TH != 32) || H % TH || W % 32) return hipErrorInvalidValue;
     const int ntx = W / 32, nty = H / TH;
     if (TH == 32) hipLaunchKernelGGL(wino_quad_list_kernel<32>, dim3(B * ntx * nty), dim3(256), 0, s, u5, qlist, qcnt, pcnt, H, W, ntx, nty);
     else hipLaunchKernelGGL(wino_quad_list_kernel<16>, dim3(B * ntx * nty), dim3(128), 0, s, u5, qlist, qcnt, pcnt, H, W, ntx, nty);
+    return hipGetLastError();
+}
+
+// ---- ACE prologue: the gather-mode geometry of several levels, one launch per stage (WinoGeoGroup, conv_wino.h) -----------------------
+__device__ __forceinline__ int wino_geo_level(const WinoGeoGroup& g, int tile) {      // the level whose run of tiles holds `tile`
+    int k = 0;
+    while (k + 1 < g.nl && tile >= g.l[k + 1].tile0) ++k;
+    return k;
+}
+__global__ __launch_bounds__(128) void wino_quad_list_grouped_kernel(WinoGeoGroup g) {
+    const WinoGeoGroup::Level& L = g.l[wino_geo_level(g, (int)blockIdx.x)];
+    wino_quad_list_block<16>(L.u5, L.qlist, L.qcnt, L.pcnt, L.H, L.W, L.W / 32, L.H / 16, (int)blockIdx.x - L.tile0);
+}
+__global__ __launch_bounds__(1024) void wino_gather_scan_grouped_kernel(WinoGeoGroup g) {
+    const WinoGeoGroup::Level& L = g.l[blockIdx.x / g.B];
+    wino_gather_scan_block(L.qcnt, L.qoff, L.gq_n, (L.W / 32) * (L.H / 16), (int)(blockIdx.x % g.B));
+}
+__global__ __launch_bounds__(128) void wino_gather_fill_grouped_kernel(WinoGeoGroup g) {
+    const WinoGeoGroup::Level& L = g.l[wino_geo_level(g, (int)blockIdx.x)];
+    wino_gather_fill_block(L.qlist, L.qcnt, L.qoff, L.gq, L.gq_cap, L.W / 32, L.H / 16, (int)blockIdx.x - L.tile0);
+}
+// blocks 0 .. nw - 1: the task lists; blocks nw .. nw + nl - 1: the chunk bases and patch flags of the levels (wino_chunk_base's loop)
+__global__ __launch_bounds__(1024) void wino_geo_tail_grouped_kernel(WinoGeoGroup g) {
+    if ((int)blockIdx.x < g.nw) {
+        const WinoGeoGroup::Work& w = g.w[blockIdx.x];
+        const WinoGeoGroup::Level& L = g.l[w.level];
+        wino_gather_worklist_block(L.gq_n, L.pcnt, g.B, (L.W / 32) * (L.H / 16), w.nrt, w.work, w.total);
+        return;
+    }
+    const WinoGeoGroup::Level& L = g.l[(int)blockIdx.x - g.nw];
+    if (threadIdx.x != 0 || !L.chunk_base) return;
+    int o = 0;
+    for (int b = 0; b < g.B; ++b) {
+        L.chunk_base[b] = o;
+        o += (L.gq_n[b] + 63) >> 6;
+    }
+    L.chunk_base[g.B] = o;
+    *L.patch_mode = (o > 0 && o <= L.cap_chunks) ? 1 : 0;
+}
+hipError_t wino_geometry_grouped(WinoGeoGroup& g, hipStream_t s) {
+    if (g.nl < 0 || g.nl > WinoGeoGroup::MAX_L || g.nw < 0 || g.nw > WinoGeoGroup::MAX_W || g.B < 1 || g.B > 32) return hipErrorInvalidValue;
+    if (g.nl == 0) return g.nw == 0 ? hipSuccess : hipErrorInvalidValue;
+    long long tiles = 0;
+    for (int k = 0; k < g.nl; ++k) {
+        WinoGeoGroup::Level& L = g.l[k];
+        if (L.H % 16 || L.W % 32 || L.H > 65535 || L.W > 65535 || !L.qlist || !L.qcnt || !L.pcnt || !L.qoff || !L.gq || !L.gq_n ||
+            (L.chunk_base && !L.patch_mode))
+            return hipErrorInvalidValue;
+        L.tile0 = (int)tiles;
+        tiles += (long long)g.B * (L.W / 32) * (L.H / 16);
+    }
+    for (int i = 0; i < g.nw; ++i)
+        if (g.w[i].level < 0 || g.w[i].level >= g.nl || g.w[i].nrt > 2 * 65535 || !g.w[i].work || !g.w[i].total) return hipErrorInvalidValue;
+    if (tiles >= (1ll << 30)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wino_quad_list_grouped_kernel, dim3((unsigned)tiles), dim3(128), 0, s, g);
+    hipLaunchKernelGGL(wino_gather_scan_grouped_kernel, dim3(g.nl * g.B), dim3(1024), 0, s, g);
+    hipLaunchKernelGGL(wino_gather_fill_grouped_kernel, dim3((unsigned)tiles), dim3(128), 0, s, g);
+    hipLaunchKernelGGL(wino_geo_tail_grouped_kernel, dim3(g.nw + g.nl), dim3(1024), 0, s, g);
     return hipGetLastError();
 }
 
@@ -365,9 +439,8 @@ hipError_t wino_ace_worklist(const int* qcnt, const int* pcnt, int ntiles, int n
 // lut[((b*19 + j)*9 + t)*2C + gb*C + c]  (P = W[:, :, t] relu(fc_mu_j(code)), blend factor folded in; sean_model.cpp)
 // wsty[((b*nrt + rt)*5 + s)*2048 + (idx*64 + lane)*4 + e]: fragment a = 4 idx + e = (xi = a >> 1, m = a & 1) of row (m ? beta : gamma) of
 // channel 16 rt + (lane & 15), input "channel" = label j = 4 s + (lane >> 4) (j = 19: the zero plane).  U = G P G^T in f32.
-__global__ __launch_bounds__(256) void wino_style_pack_kernel(const float* __restrict__ lut, float* __restrict__ wsty, int B, int C, int nrt) {
+__device__ __forceinline__ void wino_style_pack_unit(const float* __restrict__ lut, float* __restrict__ wsty, int B, int C, int nrt, long long i) {
     const long long n = (long long)B * nrt * 5 * 512;
-    const long long i = blockIdx.x * 256LL + threadIdx.x;
     if (i >= n) return;
     const int lane = (int)(i & 63), idx = (int)((i >> 6) & 7), s = (int)((i >> 9) % 5);
     const int rt = (int)((i / (512 * 5)) % nrt), b = (int)(i / (512LL * 5 * nrt));
@@ -396,10 +469,34 @@ __global__ __launch_bounds__(256) void wino_style_pack_kernel(const float* __res
     }
     reinterpret_cast<float4*>(wsty)[i] = o;
 }
+__global__ __launch_bounds__(256) void wino_style_pack_kernel(const float* __restrict__ lut, float* __restrict__ wsty, int B, int C, int nrt) {
+    wino_style_pack_unit(lut, wsty, B, C, nrt, blockIdx.x * 256LL + threadIdx.x);
+}
 hipError_t wino_style_pack(const float* lut, float* wsty, int B, int C, hipStream_t s) {
     const int nrt = (C + 15) / 16;
     const long long n = (long long)B * nrt * 5 * 512;
     hipLaunchKernelGGL(wino_style_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lut, wsty, B, C, nrt);
+    return hipGetLastError();
+}
+// ACE prologue: the images of several ACEs from one launch; every entry owns the run of blocks its own launch would have
+__global__ __launch_bounds__(256) void wino_style_pack_grouped_kernel(StylePackGroup g) {
+    int k = 0;
+    while (k + 1 < g.n && (int)blockIdx.x >= g.e[k + 1].start) ++k;
+    const StylePackGroup::Entry& e = g.e[k];
+    wino_style_pack_unit(e.lut, e.wsty, g.B, e.C, (e.C + 15) / 16, ((int)blockIdx.x - e.start) * 256LL + threadIdx.x);
+}
+hipError_t wino_style_pack_grouped(StylePackGroup& g, hipStream_t s) {
+    if (g.n < 0 || g.n > StylePackGroup::MAX || g.B < 1) return hipErrorInvalidValue;
+    if (g.n == 0) return hipSuccess;
+    long long grid = 0;
+    for (int k = 0; k < g.n; ++k) {
+        StylePackGroup::Entry& e = g.e[k];
+        if (!e.lut || !e.wsty || e.C < 1) return hipErrorInvalidValue;
+        e.start = (int)grid;
+        grid += ((long long)g.B * ((e.C + 15) / 16) * 5 * 512 + 255) / 256;
+    }
+    if (grid >= (1ll << 30)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(wino_style_pack_grouped_kernel, dim3((unsigned)grid), dim3(256), 0, s, g);
     return hipGetLastError();
 }
 

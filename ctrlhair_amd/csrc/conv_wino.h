@@ -1265,6 +1265,20 @@ hipError_t conv_wino_plain(WinoParams p, hipStream_t s);     // conv_inst_wino.h
 hipError_t conv_wino_ace(WinoAceParams p, hipStream_t s);
 // wsty[b][rt][s][idx][lane][4] <- Winograd transform of the style LUT lut[(b*19 + j)][tap][gamma|beta][C] (exact-f32 layout)
 hipError_t wino_style_pack(const float* lut, float* wsty, int B, int C, hipStream_t s);
+// ACE prologue (sean_model.cpp): the style images of several ACEs from ONE launch.  (The F(4x4) images, wino4_style_pack, stay one launch
+// per ACE: 113 MB each, bandwidth-bound.)  The group is filled per call and travels by value as the kernel argument; the caller fills lut,
+// wsty, C, the launcher start (first block of the entry's run).
+struct StylePackGroup {
+    static constexpr int MAX = 24;
+    struct Entry {
+        const float* lut;
+        float* wsty;
+        int C, start;
+    };
+    Entry e[MAX];
+    int n, B;
+};
+hipError_t wino_style_pack_grouped(StylePackGroup& g, hipStream_t s);
 // boundary quads of every 32 x TH tile (from the interior map u5 of ace_classify) and the block tasks of conv_wino_ace
 // (u5 == nullptr: every quad is a boundary quad -- levels without the interior reduction); pcnt: boundary pixels per tile; total: 8 ints
 hipError_t wino_quad_lists(const uint8_t* u5, uint8_t* qlist, int* qcnt, int* pcnt, int B, int H, int W, int TH, hipStream_t s);
@@ -1272,6 +1286,29 @@ hipError_t wino_ace_worklist(const int* qcnt, const int* pcnt, int ntiles, int n
 // gather mode: the per-tile lists (tiles of 32 x 16) -> one list per sample gq[b][gq_cap] (tile order), counts gq_n[b], scratch
 // qoff[ntiles]; then the tasks (sample | chunk << 5 | row pair << 16; chunk-major) and the statistics of wino_ace_worklist
 hipError_t wino_gather_lists(const uint8_t* qlist, const int* qcnt, int* qoff, unsigned* gq, int* gq_n, int gq_cap, int B, int H, int W, hipStream_t s);
+// ACE prologue (sean_model.cpp): the gather-mode geometry of SEVERAL levels (tiles of 32 x 16) in four launches instead of four per level
+// and one per task list -- quad lists, per-sample scans, list fill, then one launch whose blocks are the task lists (wino_gather_worklist)
+// and the chunk bases (wino_chunk_base, kernels.h) of all levels.  The group is filled per call and travels by value as the kernel
+// argument; the launcher fills tile0.  The block bodies are the ones of the per-level kernels.
+struct WinoGeoGroup {
+    static constexpr int MAX_L = 4, MAX_W = 8;
+    struct Level {
+        const uint8_t* u5;          // interior map of the level or nullptr (wino_quad_lists)
+        uint8_t* qlist;
+        int *qcnt, *pcnt, *qoff;
+        unsigned* gq;
+        int* gq_n;
+        int* chunk_base;            // nullptr: no patch source on this level
+        int* patch_mode;
+        int gq_cap, cap_chunks, H, W;
+        int tile0;                  // first block of the level in the per-tile launches
+    };
+    struct Work { int level, nrt; unsigned* work; int* total; };
+    Level l[MAX_L];
+    Work w[MAX_W];
+    int nl, nw, B;
+};
+hipError_t wino_geometry_grouped(WinoGeoGroup& g, hipStream_t s);
 hipError_t wino_gather_worklist(const int* gq_n, const int* pcnt, int B, int tiles_per_sample, int nrt, unsigned* work, int* total, hipStream_t s);
 
 }  // namespace chk

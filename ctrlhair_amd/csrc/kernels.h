@@ -31,10 +31,33 @@ hipError_t ace_finish_f32(const float* gb, int rowsP, const float* x, int x_up, 
                           float* out, int B, int C, int H, int W, int act, hipStream_t s);
 hipError_t spade_hidden_wq(const uint8_t* lab, const uint8_t* u5, const float* table, const float* bias, float* out, int B, int H, int W,
                            int kout, int onehot, hipStream_t s, int pitch = 0, int xoff = 0, const int* skip_if_patch = nullptr);
+// ACE prologue (sean_model.cpp): the same pass for several ACEs in ONE launch.  The group travels by value as the kernel argument: it is
+// filled per call (the label pointers, the level sizes and the set of ACEs follow the call's B and S), so no device copy of it can go stale.
+// The caller fills lab .. xoff of each entry; the launcher fills tcs, start, nblk.
+struct HiddenGroup {
+    static constexpr int MAX = 24;
+    struct Entry {
+        const uint8_t* lab;
+        const uint8_t* u5;
+        const float* table;
+        const float* bias;
+        float* out;
+        int H, W, kout, onehot, pitch, xoff;
+        int tcs, start, nblk;
+    };
+    Entry e[MAX];
+    int n, B;
+};
+hipError_t spade_hidden_wq_grouped(HiddenGroup& g, hipStream_t s);
 // the same activations as pre-gathered 4 x 4 patches of the boundary quads, chunk by chunk of 64 (conv_wino.h WinoAceParams::patch); both
 // kernels read the device flag *mode (wino_chunk_base): exactly one of them does the work
 hipError_t spade_hidden_patch(const uint8_t* lab, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,
                               const float* table, const float* bias, float* patch, int B, int H, int W, int kout, hipStream_t s);
+// spade_hidden_wq(..., skip_if_patch = mode) followed by spade_hidden_patch(..., mode) as ONE launch: each block reads the flag and runs the
+// body of the kernel that would not have returned at once (chunks with the ACE prologue, sean_model.cpp)
+hipError_t spade_hidden_level(const uint8_t* lab, const uint8_t* u5, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,
+                              const float* table, const float* bias, float* out, float* patch, int B, int H, int W, int kout, int onehot, int pitch,
+                              int xoff, hipStream_t s);
 hipError_t wino_chunk_base(const int* gq_n, int B, int cap_chunks, int* chunk_base, int* mode, hipStream_t s);
 // `scale`: power-of-two scale of an SH16 output / input tensor (sh16.h)
 hipError_t onehot_conv3x3_sh16(const uint8_t* lab, const float* table, const float* bias, void* out, int B, int H, int W,

@@ -220,14 +220,14 @@ constexpr int LDS_BYTES = (T_FLOATS + A_FLOATS + K) * 4 + LP_BYTES + QF_BYTES + 
 #ifndef HID_DBG
 #define HID_DBG 0      // tools/hidden_bench.hip: 1 = no stores, 2 = no work items (timing ablations)
 #endif
-__global__ __launch_bounds__(1024) void spade_hidden_wq_kernel(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ u5,
-                                                               const float* __restrict__ table, const float* __restrict__ bias,
-                                                               float* __restrict__ out, int B, int H, int W, int kout, int onehot,
-                                                               int tcs,        // tcs = log2(TC)
-                                                               int pitch, int xoff,        // output planes: H rows of `pitch` floats, image column x at x + xoff
-                                                               const int* __restrict__ skip_if_patch) {      // device flag: 1 = spade_hidden_patch serves this level
+// the work of block `blk` of `nblk` (one launch per ACE: the grid; the grouped launch of the ACE prologue: the blocks of this ACE's entry)
+__device__ __forceinline__ void spade_hidden_wq_block(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ u5,
+                                                      const float* __restrict__ table, const float* __restrict__ bias,
+                                                      float* __restrict__ out, int B, int H, int W, int kout, int onehot,
+                                                      int tcs,        // tcs = log2(TC)
+                                                      int pitch, int xoff,        // output planes: H rows of `pitch` floats, image column x at x + xoff
+                                                      int blk, int nblk) {
     using namespace hid;
-    if (skip_if_patch && *skip_if_patch == 1) return;
     extern __shared__ __attribute__((aligned(16))) float hsm[];
     float* T = hsm;
     float* A = T + T_FLOATS;
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(1024) void spade_hidden_wq_kernel(const uint8_t* __
     const int txn = W >> tcs, tyn = H / TR, ntasks = B * txn * tyn;
     const long long HW = (long long)H * W;
     const long long PL = (long long)H * pitch;                       // floats per output plane
-    for (int task = blockIdx.x; task < ntasks; task += gridDim.x) {
+    for (int task = blk; task < ntasks; task += nblk) {
         const int b = task / (txn * tyn), tr = task - b * (txn * tyn);
         const int y0 = (tr / txn) * TR, x0 = (tr % txn) << tcs;
         const uint8_t* lb = lab + (long long)b * HW;
@@ -374,17 +374,36 @@ __global__ __launch_bounds__(1024) void spade_hidden_wq_kernel(const uint8_t* __
     }
 }
 
+__global__ __launch_bounds__(1024) void spade_hidden_wq_kernel(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ u5,
+                                                               const float* __restrict__ table, const float* __restrict__ bias,
+                                                               float* __restrict__ out, int B, int H, int W, int kout, int onehot, int tcs,
+                                                               int pitch, int xoff,
+                                                               const int* __restrict__ skip_if_patch) {      // device flag: 1 = spade_hidden_patch serves this level
+    if (skip_if_patch && *skip_if_patch == 1) return;
+    spade_hidden_wq_block(lab, u5, table, bias, out, B, H, W, kout, onehot, tcs, pitch, xoff, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// ACE prologue (sean_model.cpp): the hidden planes of several ACEs from one launch -- block -> (entry, block of the entry); a block
+// keeps ONE label table in LDS, so the entries own disjoint runs of blocks
+__global__ __launch_bounds__(1024) void spade_hidden_wq_grouped_kernel(HiddenGroup g) {
+    int k = 0;
+    while (k + 1 < g.n && (int)blockIdx.x >= g.e[k + 1].start) ++k;
+    const HiddenGroup::Entry& e = g.e[k];
+    spade_hidden_wq_block(e.lab, e.u5, e.table, e.bias, e.out, g.B, e.H, e.W, e.kout, e.onehot, e.tcs, e.pitch, e.xoff, (int)blockIdx.x - e.start,
+                          e.nblk);
+}
+
 bool spade_hidden_wq_supported(int H, int W) {
     if (H % 32 || W % 32 || H < 32 || W < 32) return false;
     const int TC = (W & (W - 1)) ? 32 : (W < 512 ? W : 512), TR = 1024 / TC;      // (widths that are not powers of two: tiles of 32 x 32)
     return H % TR == 0;
 }
 
-hipError_t spade_hidden_wq(const uint8_t* lab, const uint8_t* u5, const float* table, const float* bias, float* out, int B, int H, int W,
-                           int kout, int onehot, hipStream_t s, int pitch, int xoff, const int* skip_if_patch) {
-    if (!spade_hidden_wq_supported(H, W) || kout < hid::K + (onehot ? 20 : 0)) return hipErrorInvalidValue;
-    if (pitch <= 0) { pitch = W; xoff = 0; }
-    if (xoff < 0 || (xoff > 0 && pitch < W + xoff + 1)) return hipErrorInvalidValue;
+__global__ void spade_hidden_level_kernel(const uint8_t* lab, const uint8_t* u5, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base,
+                                          const int* mode, const float* table, const float* bias, float* out, float* patch, int B, int H, int W, int kout,
+                                          int onehot, int tcs, int pitch, int xoff);      // (below, beside the patch kernel)
+// LDS limit of the three kernels and the CU count of the current device, once per device
+static hipError_t spade_hidden_wq_device(int& ncu) {
     static bool done[64] = {};
     static int cus[64] = {};
     int dev = 0;
@@ -393,18 +412,60 @@ hipError_t spade_hidden_wq(const uint8_t* lab, const uint8_t* u5, const float* t
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(spade_hidden_wq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            hid::LDS_BYTES);
         if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(spade_hidden_wq_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                hid::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(spade_hidden_level_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, hid::LDS_BYTES);
+        if (e != hipSuccess) return e;
         int v = 0;
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus[dev] = v;
         done[dev] = true;
     }
+    ncu = cus[dev];
+    return hipSuccess;
+}
+static int spade_hidden_wq_tcs(int W) {
     const int TC = (W & (W - 1)) ? 32 : (W < 512 ? W : 512);
     int tcs = 0;
     while ((1 << tcs) < TC) ++tcs;
+    return tcs;
+}
+
+hipError_t spade_hidden_wq(const uint8_t* lab, const uint8_t* u5, const float* table, const float* bias, float* out, int B, int H, int W,
+                           int kout, int onehot, hipStream_t s, int pitch, int xoff, const int* skip_if_patch) {
+    if (!spade_hidden_wq_supported(H, W) || kout < hid::K + (onehot ? 20 : 0)) return hipErrorInvalidValue;
+    if (pitch <= 0) { pitch = W; xoff = 0; }
+    if (xoff < 0 || (xoff > 0 && pitch < W + xoff + 1)) return hipErrorInvalidValue;
+    int ncu = 0;
+    if (hipError_t e = spade_hidden_wq_device(ncu)) return e;
+    const int tcs = spade_hidden_wq_tcs(W);
     const int ntasks = B * (H * W / 1024);
-    const int grid = ntasks < cus[dev] ? ntasks : cus[dev];
+    const int grid = ntasks < ncu ? ntasks : ncu;
     hipLaunchKernelGGL(spade_hidden_wq_kernel, dim3(grid), dim3(1024), hid::LDS_BYTES, s, lab, u5, table, bias, out, B, H, W, kout, onehot, tcs,
                        pitch, xoff, skip_if_patch);
+    return hipGetLastError();
+}
+
+// every entry gets the blocks its own launch would get (one per task, at most one per CU); the entries' runs of blocks follow each other
+hipError_t spade_hidden_wq_grouped(HiddenGroup& g, hipStream_t s) {
+    if (g.n < 0 || g.n > HiddenGroup::MAX || g.B < 1) return hipErrorInvalidValue;
+    if (g.n == 0) return hipSuccess;
+    int ncu = 0;
+    if (hipError_t e = spade_hidden_wq_device(ncu)) return e;
+    int grid = 0;
+    for (int k = 0; k < g.n; ++k) {
+        HiddenGroup::Entry& e = g.e[k];
+        if (!spade_hidden_wq_supported(e.H, e.W) || e.kout < hid::K + (e.onehot ? 20 : 0) || !e.lab || !e.table || !e.bias || !e.out) return hipErrorInvalidValue;
+        if (e.pitch <= 0) { e.pitch = e.W; e.xoff = 0; }
+        if (e.xoff < 0 || (e.xoff > 0 && e.pitch < e.W + e.xoff + 1)) return hipErrorInvalidValue;
+        e.tcs = spade_hidden_wq_tcs(e.W);
+        const int ntasks = g.B * (e.H * e.W / 1024);
+        e.start = grid;
+        e.nblk = ntasks < ncu ? ntasks : ncu;
+        grid += e.nblk;
+    }
+    hipLaunchKernelGGL(spade_hidden_wq_grouped_kernel, dim3(grid), dim3(1024), hid::LDS_BYTES, s, g);
     return hipGetLastError();
 }
 
@@ -414,12 +475,11 @@ hipError_t spade_hidden_wq(const uint8_t* lab, const uint8_t* u5, const float* t
 // channels (bias + nine table rows in tap order + ReLU: the arithmetic of spade_hidden_wq_kernel, bit for bit) and, for a styled ACE, the
 // 20 one-hot planes -- written as [channel][py][slot][px]: 256 consecutive threads store one contiguous KB.  A pixel outside the image
 // is zero in every channel (the zero padding of the gamma / beta conv).  Runs only when *mode == 1 (wino_chunk_base).
-__global__ __launch_bounds__(1024) void spade_hidden_patch_kernel(const uint8_t* __restrict__ lab, const unsigned* __restrict__ gq, const int* __restrict__ gq_n,
-                                                                  int gq_cap, const int* __restrict__ chunk_base, const int* __restrict__ mode,
-                                                                  const float* __restrict__ table, const float* __restrict__ bias, float* __restrict__ patch,
-                                                                  int B, int H, int W, int kout) {
+__device__ __forceinline__ void spade_hidden_patch_block(const uint8_t* __restrict__ lab, const unsigned* __restrict__ gq, const int* __restrict__ gq_n,
+                                                         int gq_cap, const int* __restrict__ chunk_base,
+                                                         const float* __restrict__ table, const float* __restrict__ bias, float* __restrict__ patch,
+                                                         int B, int H, int W, int kout, int blk, int nblk) {
     using namespace hid;
-    if (*mode != 1) return;
     extern __shared__ __attribute__((aligned(16))) float hsm[];
     float* T = hsm;
     float* bs = T + T_FLOATS;
@@ -435,7 +495,7 @@ __global__ __launch_bounds__(1024) void spade_hidden_patch_kernel(const uint8_t*
     const int py = tid >> 8, slot = (tid >> 2) & 63, px = tid & 3;
     const int total = cb[B];
     const long long HW = (long long)H * W;
-    for (int g = blockIdx.x; g < total; g += gridDim.x) {
+    for (int g = blk; g < total; g += nblk) {
         int b = 0;
         while (b + 1 < B && cb[b + 1] <= g) ++b;
         const int chunk = g - cb[b], nq = gq_n[b];
@@ -472,6 +532,37 @@ __global__ __launch_bounds__(1024) void spade_hidden_patch_kernel(const uint8_t*
             for (int j = 0; j < 20; ++j) op[j * 1024] = (in && j == jc && jc < 19) ? 1.f : 0.f;      // (plane K + 19 stays zero)
         }
     }
+}
+__global__ __launch_bounds__(1024) void spade_hidden_patch_kernel(const uint8_t* __restrict__ lab, const unsigned* __restrict__ gq, const int* __restrict__ gq_n,
+                                                                  int gq_cap, const int* __restrict__ chunk_base, const int* __restrict__ mode,
+                                                                  const float* __restrict__ table, const float* __restrict__ bias, float* __restrict__ patch,
+                                                                  int B, int H, int W, int kout) {
+    if (*mode != 1) return;
+    spade_hidden_patch_block(lab, gq, gq_n, gq_cap, chunk_base, table, bias, patch, B, H, W, kout, (int)blockIdx.x, (int)gridDim.x);
+}
+// Both sources of a gather-mode level from ONE launch (chunks with the ACE prologue): the device flag picks the body -- *mode == 1 the
+// pre-gathered patches, else the padded planes -- where the two kernels above are launched one after the other and one returns at once.
+// One block per CU, as both take when the level has at least that many tasks; a block beyond the planes' task count only loads its table.
+__global__ __launch_bounds__(1024) void spade_hidden_level_kernel(const uint8_t* __restrict__ lab, const uint8_t* __restrict__ u5, const unsigned* __restrict__ gq,
+                                                                  const int* __restrict__ gq_n, int gq_cap, const int* __restrict__ chunk_base,
+                                                                  const int* __restrict__ mode, const float* __restrict__ table,
+                                                                  const float* __restrict__ bias, float* __restrict__ out, float* __restrict__ patch, int B,
+                                                                  int H, int W, int kout, int onehot, int tcs, int pitch, int xoff) {
+    if (*mode == 1) spade_hidden_patch_block(lab, gq, gq_n, gq_cap, chunk_base, table, bias, patch, B, H, W, kout, (int)blockIdx.x, (int)gridDim.x);
+    else spade_hidden_wq_block(lab, u5, table, bias, out, B, H, W, kout, onehot, tcs, pitch, xoff, (int)blockIdx.x, (int)gridDim.x);
+}
+hipError_t spade_hidden_level(const uint8_t* lab, const uint8_t* u5, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,
+                              const float* table, const float* bias, float* out, float* patch, int B, int H, int W, int kout, int onehot, int pitch,
+                              int xoff, hipStream_t s) {
+    if (B < 1 || B > 32 || kout != hid::K + (onehot ? 20 : 0) || !spade_hidden_wq_supported(H, W) || !mode || !chunk_base || !gq || !gq_n || !patch || !out)
+        return hipErrorInvalidValue;
+    if (pitch <= 0) { pitch = W; xoff = 0; }
+    if (xoff < 0 || (xoff > 0 && pitch < W + xoff + 1)) return hipErrorInvalidValue;
+    int ncu = 0;
+    if (hipError_t e = spade_hidden_wq_device(ncu)) return e;
+    hipLaunchKernelGGL(spade_hidden_level_kernel, dim3(ncu), dim3(1024), hid::LDS_BYTES, s, lab, u5, gq, gq_n, gq_cap, chunk_base, mode, table, bias, out, patch,
+                       B, H, W, kout, onehot, spade_hidden_wq_tcs(W), pitch, xoff);
+    return hipGetLastError();
 }
 hipError_t spade_hidden_patch(const uint8_t* lab, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,
                               const float* table, const float* bias, float* patch, int B, int H, int W, int kout, hipStream_t s) {

@@ -895,6 +895,41 @@ struct SeanBuild {
         m.p6 = (cmax && opt.edge && (opt.use_sh16 || opt.wino)) ? B.falloc((size_t)mb * LABEL_NC * 6 * 2 * cmax) : nullptr;      // (straight-edge pixels: ace_sparse.h)
         return "";
     }
+
+    // ---- ACE prologue (Runner::prologue): per-ACE destinations, sized by the route the ACE takes at (mb, ms) -----------------------
+    // Handles beyond the run-ahead sizes only (interactive handles run everything ahead on the side stream); not in overlap mode, whose side
+    // streams own the same work.  A call at a smaller S moves every ACE down a level: an ACE whose buffer exists and still fits its route uses
+    // it, any other takes its inline launches -- Runner::prologue decides per call, from the predicates Runner::ace uses.
+    std::string prologue_buffers() {
+        const int n_aces = m.n_aces;
+        m.pro_actv.assign(n_aces, nullptr);
+        m.pro_gtab.assign(n_aces, nullptr);
+        m.pro_p6.assign(n_aces, nullptr);
+        m.pro_wsty.assign(n_aces, nullptr);
+        m.pro_bytes = 0;
+        m.pro_on = opt.prologue && opt.wino && !opt.use_sh16 && !m.overlap_on && (long long)mb * ms * ms > m.ahead_limit;
+        if (!m.pro_on) return "";
+        auto alloc = [&](size_t floats) {
+            m.pro_bytes += floats * 4;
+            return B.falloc(floats);
+        };
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            if (!a.spade_wino) return;
+            const int k = level_of(a.res_div), r = ms >> k;
+            if (r < 32 || r % 32 || !m.wq_level[k].qlist) return;
+            const bool f4 = opt.wino >= 2 && a.spade_wino4 && r <= opt.wino4_ace_max_r && wino4_ace_supported(r, r, a.C) && (!a.styled || m.wsty4);
+            if (f4) {
+                m.pro_actv[a.index] = alloc((size_t)mb * r * wino_apitch(r) * (a.styled ? HID + 20 : HID));
+                return;
+            }
+            if (opt.sparse && r >= opt.sparse_min_r && m.gtab) {
+                m.pro_gtab[a.index] = alloc((size_t)mb * LABEL_NC * 2 * a.C);
+                if (a.styled && m.p6) m.pro_p6[a.index] = alloc((size_t)mb * LABEL_NC * 6 * 2 * a.C);
+            }
+            if (a.styled && m.wsty) m.pro_wsty[a.index] = alloc((size_t)mb * ((a.C + 15) / 16) * 5 * 2048);
+        });
+        return "";
+    }
 };
 
 }  // namespace
@@ -903,7 +938,8 @@ std::string SeanModel::build(const TensorStore& ts, int mb, int ms) {
     SeanBuild s(*this, ts, mb, ms);
     typedef std::string (SeanBuild::*Stage)();
     static const Stage stages[] = {&SeanBuild::dims,      &SeanBuild::fc_and_img, &SeanBuild::res_blocks,  &SeanBuild::zencoder,
-                                   &SeanBuild::run_ahead, &SeanBuild::arena,      &SeanBuild::wino_levels, &SeanBuild::sparse_levels};
+                                   &SeanBuild::run_ahead, &SeanBuild::arena,      &SeanBuild::wino_levels, &SeanBuild::sparse_levels,
+                                   &SeanBuild::prologue_buffers};
     for (Stage stage : stages) {
         const std::string e = (s.*stage)();
         if (!e.empty()) return e;
@@ -940,6 +976,11 @@ void SeanModel::destroy() {
     claim_pool = nullptr;
     actv_ahead.clear();
     lut_ahead.clear();
+    pro_actv.clear();
+    pro_gtab.clear();
+    pro_p6.clear();
+    pro_wsty.clear();
+    pro_on = false;
     splitk_side = nullptr;
     for (auto& r : prof) {
         ev_pool.push_back(r.e0);
@@ -1107,20 +1148,58 @@ struct Runner {
                 }
         }
         const int ntiles = B * (r / 32) * (r / L.TH);
+        // the prologue collects the lists of gather-mode levels into one group (geo) instead of launching them level by level
+        const bool collect = geo && L.gq && L.TH == 16 && geo->nl < WinoGeoGroup::MAX_L;
         if (!wq_done[k]) {
-            check(wino_quad_lists(o.S ? o.S->u5 : nullptr, L.qlist, L.qcnt, L.pcnt, B, r, r, L.TH, st), "wino_quad_lists");
-            if (L.gq) check(wino_gather_lists(L.qlist, L.qcnt, L.qoff, L.gq, L.gq_n, L.gq_cap, B, r, r, st), "wino_gather_lists");
-            if (L.gq && L.chunk_base) check(wino_chunk_base(L.gq_n, B, m.patchbuf ? m.patch_cap_chunks : 0, L.chunk_base, L.patch_mode, st), "wino_chunk_base");
+            if (collect) {
+                geo_slot[k] = geo->nl;
+                WinoGeoGroup::Level& g = geo->l[geo->nl++];
+                g.u5 = o.S ? o.S->u5 : nullptr;
+                g.qlist = L.qlist;
+                g.qcnt = L.qcnt;
+                g.pcnt = L.pcnt;
+                g.qoff = L.qoff;
+                g.gq = L.gq;
+                g.gq_n = L.gq_n;
+                g.chunk_base = L.chunk_base;
+                g.patch_mode = L.patch_mode;
+                g.gq_cap = L.gq_cap;
+                g.cap_chunks = m.patchbuf ? m.patch_cap_chunks : 0;
+                g.H = g.W = r;
+            } else {
+                check(wino_quad_lists(o.S ? o.S->u5 : nullptr, L.qlist, L.qcnt, L.pcnt, B, r, r, L.TH, st), "wino_quad_lists");
+                if (L.gq) check(wino_gather_lists(L.qlist, L.qcnt, L.qoff, L.gq, L.gq_n, L.gq_cap, B, r, r, st), "wino_gather_lists");
+                if (L.gq && L.chunk_base) check(wino_chunk_base(L.gq_n, B, m.patchbuf ? m.patch_cap_chunks : 0, L.chunk_base, L.patch_mode, st), "wino_chunk_base");
+            }
             wq_done[k] = true;
         }
         bool done = false;
         for (int d : wwork_done[k]) done = done || d == nrt;
         if (!done) {
-            if (L.gq) check(wino_gather_worklist(L.gq_n, L.pcnt, B, ntiles / B, nrt, o.W->work, o.W->total, st), "wino_gather_worklist");
-            else check(wino_ace_worklist(L.qcnt, L.pcnt, ntiles, nrt, o.W->work, o.W->total, st), "wino_ace_worklist");
+            if (geo && geo_slot[k] >= 0 && geo->nw < WinoGeoGroup::MAX_W) {
+                WinoGeoGroup::Work& w = geo->w[geo->nw++];
+                w.level = geo_slot[k];
+                w.nrt = nrt;
+                w.work = o.W->work;
+                w.total = o.W->total;
+            } else {
+                // (a level collected by the prologue whose group has no room for this list: the group is launched first, prologue())
+                if (geo && geo_slot[k] >= 0) geo_flush();
+                if (L.gq) check(wino_gather_worklist(L.gq_n, L.pcnt, B, ntiles / B, nrt, o.W->work, o.W->total, st), "wino_gather_worklist");
+                else check(wino_ace_worklist(L.qcnt, L.pcnt, ntiles, nrt, o.W->work, o.W->total, st), "wino_ace_worklist");
+            }
             wwork_done[k].push_back(nrt);
         }
         return o;
+    }
+    // the geometry group of the prologue (set only while prologue() runs) and each level's slot in it
+    WinoGeoGroup* geo = nullptr;
+    int geo_slot[6] = {-1, -1, -1, -1, -1, -1};
+    void geo_flush() {
+        if (!geo) return;
+        if (geo->nl) check(wino_geometry_grouped(*geo, st), "level geometry (grouped)");
+        geo->nl = geo->nw = 0;
+        for (int& s : geo_slot) s = -1;
     }
     const uint8_t* labels_at(const uint8_t* full, int res_div) {
         return res_div == 1 ? full : m.lab_r[level_of(res_div)];
@@ -1267,6 +1346,13 @@ struct Runner {
                 m.pad_state[actv_buf] = geo;
             }
             const bool pm = PL && PL->gq && PL->patch_mode && m.patchbuf;
+            if (pm && pro_active && PL->chunk_base) {
+                // chunks with the prologue: both sources from one launch, the device flag picks the body (kernels.h)
+                check(spade_hidden_level(lab, m.opt.hidden_wq ? u5 : nullptr, PL->gq, PL->gq_n, PL->gq_cap, PL->chunk_base, PL->patch_mode, a.actv_table,
+                                         a.actv_bias, actv_buf, m.patchbuf, B, r, r, kout, a.styled ? 1 : 0, wino_apitch(r), WINO_AXOFF, s),
+                      "mlp_shared (planes or pre-gathered patches)");
+                return q;
+            }
             check(spade_hidden_wq(lab, m.opt.hidden_wq ? u5 : nullptr, a.actv_table, a.actv_bias, actv_buf, B, r, r, kout, a.styled ? 1 : 0, s,
                                   wino_apitch(r), WINO_AXOFF, pm ? PL->patch_mode : nullptr), "mlp_shared (boundary-quad patches)");
             // few, scattered boundary quads: their patches pre-gathered instead (one of the two kernels returns at once: device flag)
@@ -1329,6 +1415,98 @@ struct Runner {
         luts_ready = true;
     }
 
+    // ACE prologue (SeanModel::pro_on; large chunks of the exact-f32 Winograd path): what the ACEs of the chunk build from labels, codes and
+    // weights alone, from a few grouped launches ahead of the first conv instead of small launches per level and per ACE between the convs
+    // (profiles/r10_ace_prologue_kernel_trace.md: the dispatches of a step run back to back, a launch of a few blocks costs its 4.6 us floor
+    // or, the 16 / 64-block hidden passes, 35 us of set-up latency whatever its size):
+    //   * quad lists, per-sample lists, task lists and chunk bases of every gather-mode level (wino_geometry_grouped: four launches);
+    //   * the padded hidden planes of every F(4x4)-route ACE (spade_hidden_wq_grouped);
+    //   * gtab and P6 of every gather-route ACE (ace_tables_grouped) and its F(2x2) style images (wino_style_pack_grouped) -- these read the
+    //     style LUTs, so they need the grouped LUT GEMM of the chunk (luts_ready); without it only unstyled ACEs join.
+    // The groups are filled here, per call: the set of ACEs, their level sizes and label pointers follow B and S.  pro_*[index] != nullptr
+    // tells ace() that the product is in place; every other ACE keeps its inline launches.  The level geometry of the gather-route ACEs
+    // (classification, quad lists, task lists: wino_prepare) runs here too, since gtab / P6 depend on what it decides (edges).
+    // With the prologue on, the gather-mode levels also take their hidden activations -- planes or pre-gathered patches, a device flag decides
+    // -- from one launch per ACE (spade_hidden_level) instead of two of which one returns at once.
+    std::vector<const float*> pro_hidden, pro_gtab, pro_p6, pro_wsty;
+    bool pro_active = false;
+    void prologue(const uint8_t* labfull) {
+        if (!m.pro_on || m.prof_on || ahead || overlap || (long long)B * S * S <= m.ahead_limit) return;
+        pro_active = true;
+        pro_hidden.assign(m.n_aces, nullptr);
+        pro_gtab.assign(m.n_aces, nullptr);
+        pro_p6.assign(m.n_aces, nullptr);
+        pro_wsty.assign(m.n_aces, nullptr);
+        HiddenGroup hg{};
+        AceTableGroup tg{};
+        StylePackGroup sg{};
+        WinoGeoGroup gg{};
+        hg.B = tg.B = sg.B = gg.B = B;
+        geo = &gg;
+        tg.lut_rs = 1;
+        tg.lut_bs = LABEL_NC;
+        tg.lut_mul = 1.f;
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            const int r = S / a.res_div;
+            if (!use_wino_ace(a, r)) return;
+            if (use_wino4_ace(a, r)) {
+                float* buf = m.pro_actv[a.index];
+                if (!buf || hg.n >= HiddenGroup::MAX) return;
+                // (the zero columns of the padded planes: cleared once per geometry, as ace_prepare does for the level buffers)
+                const int kout = a.styled ? HID + 20 : HID;
+                const long long geo = ((long long)r << 20) | ((long long)kout << 8) | 1;
+                auto it = m.pad_state.find(buf);
+                if (it == m.pad_state.end() || it->second != geo) {
+                    check(hipMemsetAsync(buf, 0, (size_t)m.max_batch * kout * r * wino_apitch(r) * sizeof(float), st), "hidden activations: zero pads");
+                    m.pad_state[buf] = geo;
+                }
+                HiddenGroup::Entry& e = hg.e[hg.n++];
+                e.lab = labels_at(labfull, a.res_div);
+                e.u5 = nullptr;                              // (F(4x4) levels: every pixel is read)
+                e.table = a.actv_table;
+                e.bias = a.actv_bias;
+                e.out = buf;
+                e.H = e.W = r;
+                e.kout = kout;
+                e.onehot = a.styled ? 1 : 0;
+                e.pitch = wino_apitch(r);
+                e.xoff = WINO_AXOFF;
+                pro_hidden[a.index] = buf;
+                return;
+            }
+            const WinoPrep wp = wino_prepare(a, labels_at(labfull, a.res_div), r);      // (lists and task lists: into the geometry group)
+            if (!wp.L || (a.styled && !luts_ready)) return;
+            const float* lut = a.styled ? prepared[a.index].lut : nullptr;
+            if (a.styled && !lut) return;
+            const bool p6 = wp.edges && a.styled;
+            if (wp.S && m.pro_gtab[a.index] && (!p6 || m.pro_p6[a.index]) && tg.n < AceTableGroup::MAX) {
+                AceTableGroup::Entry& e = tg.e[tg.n++];
+                e.bias_g = a.bias_g;
+                e.bias_b = a.bias_b;
+                e.gconst = a.gconst;
+                e.lut = lut;
+                e.gtab = m.pro_gtab[a.index];
+                e.p6 = p6 ? m.pro_p6[a.index] : nullptr;
+                e.C = a.C;
+                pro_gtab[a.index] = e.gtab;
+                pro_p6[a.index] = e.p6;
+            }
+            if (a.styled && m.pro_wsty[a.index] && sg.n < StylePackGroup::MAX) {
+                StylePackGroup::Entry& e = sg.e[sg.n++];
+                e.lut = lut;
+                e.wsty = m.pro_wsty[a.index];
+                e.C = a.C;
+                pro_wsty[a.index] = e.wsty;
+            }
+        });
+        geo_flush();
+        geo = nullptr;
+        check(spade_hidden_wq_grouped(hg, st), "mlp_shared (grouped, F(4x4)-route ACEs)");
+        check(ace_tables_grouped(tg, st), "ace tables (grouped)");
+        check(wino_style_pack_grouped(sg, st), "wino_style_pack (grouped)");
+    }
+    const float* pro_get(const std::vector<const float*>& v, const AceW& a) const { return v.empty() ? nullptr : v[a.index]; }
+
     // one ACE: SPADE hidden activations (label LUT) -> fused gamma/beta conv + modulation -> h
     void ace(const AceW& a, const uint8_t* labfull, const float* codes, const float* noise, size_t nf, size_t noff,
              const float* x, int x_up, int act, float* hout) {
@@ -1365,21 +1543,24 @@ struct Runner {
         const SeanModel::WinoLevel* patch_level = (wino_ace && !f4_ace && wp.L && wp.L->gq && !ahead && m.patchbuf && !overlap) ? wp.L : nullptr;
         float* abuf = m.actv;                      // hidden activations: the Winograd ACE levels own padded buffers (pads zeroed once per size)
         if (wino_ace && m.actv_lvl[level_of(a.res_div)]) abuf = m.actv_lvl[level_of(a.res_div)];
+        const float* pre_actv = f4_ace ? pro_get(pro_hidden, a) : nullptr;      // the prologue wrote this ACE's hidden planes: no label-table launch here
+        const int lt = pre_actv ? 0 : 2;
         if (ahead) {
             q = prepared[a.index];
             check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
         } else if (luts_ready && a.styled) {
-            (void)ace_prepare(a, labfull, codes, st, abuf, nullptr, m.splitk_ws, true, 2, need, tile_cnt, u5, patch_level);     // label table inline
+            if (lt) (void)ace_prepare(a, labfull, codes, st, abuf, nullptr, m.splitk_ws, true, 2, need, tile_cnt, u5, patch_level);     // label table inline
             q = prepared[a.index];
             q.actv = abuf;
         } else if (ahead_luts && a.styled) {
-            (void)ace_prepare(a, labfull, codes, st, abuf, nullptr, m.splitk_ws, true, 2, need, tile_cnt, u5, patch_level);     // label table inline
+            if (lt) (void)ace_prepare(a, labfull, codes, st, abuf, nullptr, m.splitk_ws, true, 2, need, tile_cnt, u5, patch_level);     // label table inline
             q = prepared[a.index];
             q.actv = abuf;
             check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
         } else {
-            q = ace_prepare(a, labfull, codes, st, abuf, m.lut, m.splitk_ws, true, 3, need, tile_cnt, u5, patch_level);
+            q = ace_prepare(a, labfull, codes, st, abuf, m.lut, m.splitk_ws, true, 1 | lt, need, tile_cnt, u5, patch_level);
         }
+        if (pre_actv) q.actv = pre_actv;
         if (f4_ace) {
             Wino4AceParams w{};
             w.actv = q.actv;
@@ -1472,9 +1653,19 @@ struct Runner {
                     check(ace_interior_f32(ip, m.side_int), "ace interior");
                     check(hipEventRecord(m.ev_int[a.index], m.side_int), "interior done");
                 } else {
+                    // tables from the prologue: only when it built exactly what this pass reads (P6 follows the level's straight-edge marks)
+                    const float* pre_gtab = pro_get(pro_gtab, a);
+                    const float* pre_p6 = pro_get(pro_p6, a);
+                    const bool pre = pre_gtab && (ip.p6 != nullptr) == (pre_p6 != nullptr);
+                    if (pre) {
+                        ip.gtab = pre_gtab;
+                        ip.p6 = pre_p6;
+                    }
                     timed(3, 0.0, 0.0, wp.W->total + 4, 0.0, xpp + opp + 5.0, 4.0 * 19 * 2 * a.C * B, npix, [&] {
-                        check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.gtab, B, a.C, st), "ace_gtable");
-                        if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.p6, B, a.C, st), "ace_p6table");
+                        if (!pre) {
+                            check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.gtab, B, a.C, st), "ace_gtable");
+                            if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.p6, B, a.C, st), "ace_p6table");
+                        }
                         check(ace_interior_f32(ip, st), "ace interior");
                     });
                 }
@@ -1482,7 +1673,8 @@ struct Runner {
             WinoAceParams w{};
             w.actv = q.actv;
             w.wpk = a.spade_wino;
-            w.wsty = (a.styled && q.lut) ? m.wsty : nullptr;
+            const float* pre_wsty = (a.styled && q.lut) ? pro_get(pro_wsty, a) : nullptr;      // style images from the prologue
+            w.wsty = (a.styled && q.lut) ? (pre_wsty ? pre_wsty : m.wsty) : nullptr;
             w.out = hout;
             w.x = x;
             w.x_up = x_up;
@@ -1514,7 +1706,7 @@ struct Runner {
             // executed FLOPs = wave tasks x (32 rows x 16 quads x 16 positions x K) x 2; dense = the direct conv over every pixel
             timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 0.0, wp.W->total + 4, 2.0 * 32 * 16 * 16 * ktot, 4.0 * ktot + xpp + opp,
                   4.0 * 2.0 * a.C * ktot * 16, npix, [&] {
-                      if (w.wsty) check(wino_style_pack(q.lut, m.wsty, B, a.C, st), "wino_style_pack");
+                      if (w.wsty && !pre_wsty) check(wino_style_pack(q.lut, m.wsty, B, a.C, st), "wino_style_pack");
                       check(conv_wino_ace(w, st), "spade conv (winograd, boundary quads)");
                   });
             if (overlap && wp.S) check(hipStreamWaitEvent(st, m.ev_int[a.index], 0), "interior done wait");
@@ -1860,6 +2052,8 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             // (exact-f32 path, B = 16 at 512^2: 147.2 -> 148.3 images/s)
             else if ((fcmu_batched || !opt.use_sh16) && !(opt.dbg & 8192) && !R.luts_ready) R.prepare_all_ahead(lab, cd, false);
         }
+        // large chunks: the label / code-only products of the ACEs from grouped launches, ahead of the first conv (no tap reads any of them)
+        R.prologue(lab);
 
         const int sw = S / 32;
         float* x = xa;

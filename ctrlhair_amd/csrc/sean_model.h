@@ -89,6 +89,9 @@ struct SeanOptions {
                                                //   1 = F(2x2,3x3) everywhere (conv_wino.h); 2 = the ResBlock convs from 32 x 32 pixels as
                                                //   F(4x4,3x3) (conv_wino4.h), the rest F(2x2,3x3); 0 = direct evaluation (conv_mfma.h)
     int lut_grouped = 1;                       // option "sean.lut_grouped": exact-f32 path, style LUTs of all styled ACEs from one grouped GEMM launch
+    int prologue = 1;                          // option "sean.prologue": exact-f32 Winograd path, handles beyond the run-ahead sizes: what the ACEs build from
+                                               //   labels, codes and weights alone comes from a few grouped launches at the start of a chunk, into per-ACE
+                                               //   buffers (SeanModel::pro_on); 0 = every ACE launches its own, inline
     // Overlap mode (round 5; option "sean.overlap" = CUs of the side streams, 0 = off; exact-f32 Winograd path, jobs beyond the
     // run-ahead sizes): the HBM-bound kernels -- label tables of all ACEs, interior passes -- run on streams whose CU mask holds
     // `overlap` CUs (hipExtStreamCreateWithCUMask: every XCD gives overlap / 8 of its CUs), beside the matrix-bound convs on the
@@ -226,6 +229,12 @@ struct SeanModel {
     float* vbuf = nullptr;                     // the pre-transformed input V of the layer being run (conv_wino4v.h)
     size_t vbuf_bytes = 0;
     bool wino4v_fits(int Bn, int r, int nks) const;      // sean_model.cpp
+    // ACE prologue (option "sean.prologue", Runner::prologue): per-ACE destinations of the grouped launches, sized by the route the ACE takes at
+    // (max_batch, max_size) -- F(4x4) route (32 / 64 pixels): its own padded hidden planes; gather route (128 pixels and more): its own gamma / beta
+    // table, column / row sums and F(2x2) style images.  nullptr: the ACE keeps its inline launches and the shared buffers above.
+    bool pro_on = false;
+    std::vector<float*> pro_actv, pro_gtab, pro_p6, pro_wsty;
+    size_t pro_bytes = 0;                      // what these buffers add to the handle
 
     // ---- sparse levels ----
     // exact SPADE-interior reduction (ace_sparse.h): per resolution level (index = log2(res_div)) the classification buffers

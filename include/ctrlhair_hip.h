@@ -135,6 +135,11 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   SLOWER than the serial order at every setting on MI355X: kept as an option, not used.
  * "sean.lut_grouped" (default 1; exact-f32 path, calls with more than 64 (sample, label) columns): the style LUTs of all styled ACEs
  *   of a chunk come from ONE grouped GEMM launch at its start (csrc/conv_pw.h); 0 = one launch of the generic 1x1 kernel per ACE.
+ * "sean.prologue" (default 1; before ch_finalize; exact-f32 Winograd path, handles beyond the run-ahead sizes of "sean.ahead"): what the ACEs
+ *   of a chunk build from labels, codes and weights alone -- level geometry, hidden planes of the 32 / 64-pixel ACEs, gamma / beta tables,
+ *   column / row sums and F(2x2) style images of the ACEs from 128 pixels -- comes from a few grouped launches at the start of the chunk,
+ *   into per-ACE buffers (+456 MiB on a 16 x 512^2 handle at ngf = 64).  Bit-identical results.  Off by
+ *   itself with "sean.f16x3", "sean.overlap" and while ch_profile_enable is on.  0 = every ACE launches its own kernels, inline.
  * "sean.hidden_wq" (default 1; any time): every Winograd ACE level (32 pixels and more) takes the SPADE hidden activations and the
  *   one-hot planes from one persistent kernel (csrc/sean_kernels.hip spade_hidden_wq).  1 = on the gather levels it writes only the
  *   64-byte pixel groups that a boundary quad's patch touches; 0 = the same kernel over every pixel (bit-identical results).  The dense
