@@ -12,6 +12,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "ace_sparse.h"
 #include "conv_ace_sparse.h"
@@ -761,7 +762,7 @@ struct SeanBuild {
         m.wsty = m.wsty4 = nullptr;
         if (!(opt.wino && !opt.use_sh16)) return "";
         size_t wsty_max = 0, wsty4_max = 0;
-        int lvl_planes[6] = {0, 0, 0, 0, 0, 0};        // planes of the level's padded hidden-activation buffer: what its ACEs write (ace_prepare: kout)
+        int lvl_planes[6] = {0, 0, 0, 0, 0, 0};        // planes of the level's padded hidden-activation buffer: what its ACEs write (AcePlan::kout)
         for_each_ace(m.blocks, [&](const AceW& a) {
             if (!a.spade_wino) return;
             const int k = level_of(a.res_div), r = ms >> k;
@@ -832,7 +833,7 @@ struct SeanBuild {
                     if (c->wino4 && wino4v_pays(c->Cout, r)) need = std::max(need, wino4v_bytes(mb, r, r, c->Cin / 4));
         for_each_ace(m.blocks, [&](const AceW& a) {
             if (const int r = level_r(a.res_div))
-                if (a.spade_wino4 && r <= opt.wino4_ace_max_r && wino4v_pays(2 * a.C, r)) need = std::max(need, wino4v_bytes(mb, r, r, 38));
+                if (m.ace_route_shape(a, r) == AceRoute::F4 && wino4v_pays(2 * a.C, r)) need = std::max(need, wino4v_bytes(mb, r, r, 38));
         });
         // the Zencoder's 256 -> 512 conv on the half-resolution grid: 9 bytes x 256 channels x (ms / 2)^2 per sample -- up to 2.5 GB only
         if (m.z14_wino4 && (ms / 2) % 32 == 0 && wino4v_bytes(mb, ms / 2, ms / 2, 64) <= ((size_t)5 << 29)) need = std::max(need, wino4v_bytes(mb, ms / 2, ms / 2, 64));
@@ -899,7 +900,7 @@ struct SeanBuild {
     // ---- ACE prologue (Runner::prologue): per-ACE destinations, sized by the route the ACE takes at (mb, ms) -----------------------
     // Handles beyond the run-ahead sizes only (interactive handles run everything ahead on the side stream); not in overlap mode, whose side
     // streams own the same work.  A call at a smaller S moves every ACE down a level: an ACE whose buffer exists and still fits its route uses
-    // it, any other takes its inline launches -- Runner::prologue decides per call, from the predicates Runner::ace uses.
+    // it, any other takes its inline launches -- Runner::prologue decides per call, from the chunk's plan (the same SeanModel::ace_route).
     std::string prologue_buffers() {
         const int n_aces = m.n_aces;
         m.pro_actv.assign(n_aces, nullptr);
@@ -914,11 +915,9 @@ struct SeanBuild {
             return B.falloc(floats);
         };
         for_each_ace(m.blocks, [&](const AceW& a) {
-            if (!a.spade_wino) return;
-            const int k = level_of(a.res_div), r = ms >> k;
-            if (r < 32 || r % 32 || !m.wq_level[k].qlist) return;
-            const bool f4 = opt.wino >= 2 && a.spade_wino4 && r <= opt.wino4_ace_max_r && wino4_ace_supported(r, r, a.C) && (!a.styled || m.wsty4);
-            if (f4) {
+            const int r = ms >> level_of(a.res_div);
+            if (!m.wino_work(a, r)) return;
+            if (m.ace_route_shape(a, r) == AceRoute::F4) {
                 m.pro_actv[a.index] = alloc((size_t)mb * r * wino_apitch(r) * (a.styled ? HID + 20 : HID));
                 return;
             }
@@ -994,12 +993,43 @@ void SeanModel::destroy() {
 
 namespace {
 
+// What an ACE needs that depends on the label map and the style codes only -- never on the activations flowing
+// through the generator: the SPADE hidden activations (label table) and the style LUT (fc_mu + LUT GEMM / GEMV).
+struct AcePrep {
+    const float* actv = nullptr;
+    const float* lut = nullptr;
+    int lut_rs = 1, lut_ns = 0, lut_bs = LABEL_NC;
+};
+// One ACE of one chunk: its route and what that route works on, decided once (Runner::plan_aces) and read by everything else
+struct AcePlan {
+    const AceW* a = nullptr;
+    AceRoute route = AceRoute::Dense;
+    int r = 0, k = 0;                                    // level size of this call, level index
+    const uint8_t* lab = nullptr;                        // the level's label map
+    const SeanModel::WinoLevel* L = nullptr;             // WinoQuads: quad lists of the level ...
+    const SeanModel::WinoWork* W = nullptr;              // ... and the task list of the ACE's row tiles
+    const SeanModel::WinoLevel* patch = nullptr;         // ... the level, when its pre-gathered patches may serve this ACE
+    const SparseWork* sw = nullptr;                      // direct routes: work list to prepare (f16x3: also where the route then fell to Dense)
+    const SparseLevel* SL = nullptr;                     // Sparse: the classified level
+    bool compact = false;                                // Sparse, f16x3: pixel-level compaction inside the wave-specialised kernel
+    const uint8_t* need = nullptr;                       // inline label-table kernel: the pixels / tiles the conv will read (nullptr: all)
+    const int* tile_cnt = nullptr;
+    float* abuf = nullptr;                               // hidden activations of an inline launch: actv, or the level's padded planes
+    int kout = HID;                                      // ... planes of the padded layout (one-hot planes behind the hidden channels)
+    const float *pre_actv = nullptr, *pre_gtab = nullptr, *pre_p6 = nullptr, *pre_wsty = nullptr;      // what the prologue built for this ACE (F4: hidden planes)
+    AcePrep ahead;                                       // operands built ahead of the ACE: by the side stream, or the LUT by the grouped GEMM
+    bool wino() const { return route == AceRoute::F4 || route == AceRoute::WinoQuads; }      // padded layout, Winograd ACE kernels
+};
+struct AceIO { const float* noise; long long nf; const float* x; int x_up, act; float* out; };      // the operands every ACE parameter struct carries under the same names
+struct SpStat { const int* stat = nullptr; double unit = 0.0, bytes_px = 0.0, bytes_fixed = 0.0, npix = 0.0; };      // work-list statistics of a sparse launch for its ProfRec (timed())
+
 struct Runner {
     SeanModel& m;
     hipStream_t st;
     std::string err;
     int B, S;
-    Runner(SeanModel& mm, hipStream_t s, int b, int sz) : m(mm), st(s), B(b), S(sz) {}
+    const SeanModel::ChunkMode mode;
+    Runner(SeanModel& mm, hipStream_t s, int b, int sz, const uint8_t* labfull) : m(mm), st(s), B(b), S(sz), mode(mm.chunk_mode(b, sz)) { plan_aces(labfull); }
 
     void check(hipError_t e, const char* what) {
         if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
@@ -1015,11 +1045,10 @@ struct Runner {
         return e;
     }
     template <class F>
-    void timed(int kind, double flops, double bytes, F launch) { timed(kind, flops, bytes, nullptr, 0.0, 0.0, 0.0, 0.0, launch); }
+    void timed(int kind, double flops, double bytes, F launch) { timed(kind, flops, bytes, SpStat(), launch); }
     double next_flops_exec = -1.0;      // set before a timed() whose matrix cores run fewer FLOPs than the dense count
     template <class F>
-    void timed(int kind, double flops, double bytes, const int* sp_stat, double sp_unit, double sp_bytes_px, double sp_bytes_fixed,
-               double sp_npix, F launch) {
+    void timed(int kind, double flops, double bytes, const SpStat& sp, F launch) {
         if (!m.prof_on) {
             next_flops_exec = -1.0;
             launch();
@@ -1029,17 +1058,17 @@ struct Runner {
         r.kind = kind;
         r.flops = flops;
         r.bytes = bytes;
-        r.sp_stat = sp_stat;
-        if (sp_stat && m.prof_stats && m.prof_stats_used < m.prof_stats_cap) {
+        r.sp_stat = sp.stat;
+        if (sp.stat && m.prof_stats && m.prof_stats_used < m.prof_stats_cap) {
             // snapshot of the work list's statistics on the stream: a later chunk / step rebuilds the list
             int* slot = m.prof_stats + 4 * (size_t)m.prof_stats_used++;
-            check(hipMemcpyAsync(slot, sp_stat, 4 * sizeof(int), hipMemcpyDeviceToDevice, st), "profile statistics snapshot");
+            check(hipMemcpyAsync(slot, sp.stat, 4 * sizeof(int), hipMemcpyDeviceToDevice, st), "profile statistics snapshot");
             r.sp_stat = slot;
         }
-        r.sp_flops_unit = sp_unit;
-        r.sp_bytes_px = sp_bytes_px;
-        r.sp_bytes_fixed = sp_bytes_fixed;
-        r.sp_npix = sp_npix;
+        r.sp_flops_unit = sp.unit;
+        r.sp_bytes_px = sp.bytes_px;
+        r.sp_bytes_fixed = sp.bytes_fixed;
+        r.sp_npix = sp.npix;
         r.flops_exec = next_flops_exec;
         next_flops_exec = -1.0;
         r.e0 = ev();
@@ -1068,91 +1097,82 @@ struct Runner {
         if (it != m.taps.end() && it->second)
             check(hipMemcpyAsync(it->second, src, floats * 4, hipMemcpyDeviceToDevice, st), "tap copy");
     }
-    // overlap mode (sean_model.h): interior passes on m.side_int beside the boundary convs, dynamic task claiming in the convs
-    bool overlap = false;
+    // overlap mode (sean_model.h, mode.overlap): interior passes on m.side_int beside the boundary convs, dynamic task claiming in the convs
     int claim_next = 0;
     unsigned* next_claim() {
         if (!m.claim_pool || claim_next >= SeanModel::CLAIM_SLOTS) return nullptr;
         return m.claim_pool + (size_t)SeanModel::CLAIM_WORDS * claim_next++;
     }
     // exact SPADE-interior reduction: the level's classification and the work list of (level, row tiles), once per chunk
-    bool lvl_done[6][2] = {};
-    std::vector<int> work_done[6];
-    const SparseWork* sparse_prepare(const AceW& a, const uint8_t* lab, int r) {
-        const int k = level_of(a.res_div);
-        const int mt = (a.C + 31) / 32;
-        if (!m.opt.sparse || r < m.opt.sparse_min_r || r < 32) return nullptr;
-        for (const auto& w : m.sp_work[k])
-            if (w.mtiles == mt) {
-                const int ti = w.TH == 16 ? 1 : 0;
-                const SparseLevel& L = m.sp_level[k][ti];
-                if (!L.u5) return nullptr;
-                const int ntiles = B * ((r + 31) / 32) * ((r + L.TH - 1) / L.TH);
-                // f16x3 / f16 / bf16 path, pixel-level compaction: the interior pass knows the straight-edge pixels (ace_interior_sh16_tile_kernel)
-                const bool want = m.opt.use_sh16 && m.opt.edge && L.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && w.mode >= 2;
-                if (!lvl_done[k][ti] || lvl_edges[k][ti] != want) {
-                    // (a level classified WITH straight-edge marks for the Winograd ACEs and then needed by the direct sparse kernels of the
-                    //  exact-f32 path, which do not know them: classified again without, and the quad lists of the level with it -- not
-                    //  expected to happen: every ACE of a level takes the same route)
-                    check(ace_classify(lab, L.u5, L.need, L.list, L.cnt, B, r, r, L.TH, st, want ? L.e16 : nullptr), "ace_classify");
-                    const bool again = lvl_done[k][ti];
-                    lvl_done[k][ti] = true;
-                    lvl_edges[k][ti] = want;
-                    if (again) {
-                        wq_done[k] = false;
-                        wwork_done[k].clear();
-                        work_done[k].clear();
-                    }
-                }
-                bool done = false;
-                for (int d : work_done[k]) done = done || d == mt;
-                if (!done) {
-                    check(ace_worklist(L.cnt, ntiles, mt, w.work, w.total, st, w.mode, 32 * L.TH, w.work2, w.total2, w.work3), "ace_worklist");
-                    work_done[k].push_back(mt);
-                }
-                return &w;
+    // What this chunk has launched for a level so far.  A level is classified on its first visit (in for_each_ace order) and the ACE that makes
+    // that visit decides whether the interior map carries straight-edge marks; lists and task lists follow lazily, where the first ACE needs them.
+    struct LevelState {
+        bool done[2] = {}, edges[2] = {};      // [tiles of 32 x 8 | 32 x 16]: classified; with straight-edge marks (u5 == 253 + e16; Winograd path with sean.frame: frame marks too)
+        bool wq_done = false;                  // boundary-quad lists
+        std::vector<int> work_done, wwork_done;      // task lists built: row-tile counts of the sparse / the Winograd route
+        int geo_slot = -1;                     // the level's slot in the prologue's geometry group
+    } lvl[6];
+    void sparse_prepare(const AcePlan& p) {
+        const SparseWork& w = *p.sw;
+        const int r = p.r, mt = w.mtiles, ti = w.TH == 16 ? 1 : 0;
+        LevelState& ls = lvl[p.k];
+        const SparseLevel& L = m.sp_level[p.k][ti];
+        const int ntiles = B * ((r + 31) / 32) * ((r + L.TH - 1) / L.TH);
+        // f16x3 / f16 / bf16 path, pixel-level compaction: the interior pass knows the straight-edge pixels (ace_interior_sh16_tile_kernel)
+        const bool want = m.opt.use_sh16 && m.opt.edge && L.e16 && r >= 128 && p.a->edge_tab && (!p.a->styled || m.p6) && w.mode >= 2;
+        if (!ls.done[ti] || ls.edges[ti] != want) {
+            // (a level classified WITH straight-edge marks for the Winograd ACEs and then needed by the direct sparse kernels of the
+            //  exact-f32 path, which do not know them: classified again without, and the quad lists of the level with it -- not
+            //  expected to happen: every ACE of a level takes the same route)
+            check(ace_classify(p.lab, L.u5, L.need, L.list, L.cnt, B, r, r, L.TH, st, want ? L.e16 : nullptr), "ace_classify");
+            const bool again = ls.done[ti];
+            ls.done[ti] = true;
+            ls.edges[ti] = want;
+            if (again) {
+                ls.wq_done = false;
+                ls.wwork_done.clear();
+                ls.work_done.clear();
             }
-        return nullptr;
+        }
+        bool done = false;
+        for (int d : ls.work_done) done = done || d == mt;
+        if (!done) {
+            check(ace_worklist(L.cnt, ntiles, mt, w.work, w.total, st, w.mode, 32 * L.TH, w.work2, w.total2, w.work3), "ace_worklist");
+            ls.work_done.push_back(mt);
+        }
     }
     // Winograd ACE path: classification of the level (when the interior reduction serves it), boundary-quad lists, task list
     // (edges: the level's interior map carries straight-edge marks -- and, with option sean.frame, frame marks)
-    struct WinoPrep { const SeanModel::WinoLevel* L = nullptr; const SeanModel::WinoWork* W = nullptr; const SparseLevel* S = nullptr; bool edges = false; };
-    bool wq_done[6] = {};
-    bool lvl_edges[6][2] = {};          // the level's interior map carries straight-edge marks (u5 == 253 + e16; Winograd path with sean.frame: frame marks too)
-    std::vector<int> wwork_done[6];
-    WinoPrep wino_prepare(const AceW& a, const uint8_t* lab, int r) {
+    struct WinoPrep { const SparseLevel* S = nullptr; bool edges = false; };
+    WinoPrep wino_prepare(const AcePlan& p) {
         WinoPrep o;
-        const int k = level_of(a.res_div);
-        const SeanModel::WinoLevel& L = m.wq_level[k];
-        if (!L.qlist) return o;
-        const int nrt = (a.C + 15) / 16;
-        for (const auto& w : L.works)
-            if (w.nrt == nrt) o.W = &w;
-        if (!o.W) return o;
-        o.L = &L;
+        const AceW& a = *p.a;
+        const int k = p.k, r = p.r, nrt = p.W->nrt;
+        const SeanModel::WinoLevel& L = *p.L;
+        LevelState& ls = lvl[k];
         if (m.opt.sparse && r >= m.opt.sparse_min_r) {
             for (int ti = 1; ti >= 0 && !o.S; --ti)
                 if (m.sp_level[k][ti].u5) {
                     const SparseLevel& S = m.sp_level[k][ti];
-                    if (!lvl_done[k][ti]) {
+                    if (!ls.done[ti]) {
                         // straight-edge pixels (ace_sparse.h): marked on the levels whose interior pass knows them (128 pixels and more) when
                         // the ACE carries its table -- every ACE of such a level does (res_div <= 4), checked in ace()
                         const bool edges = m.opt.edge && S.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && !m.overlap_on;      // (overlap mode: quad_only interior pass)
                         // frame pixels (option sean.frame): marked with them; only this path's interior pass (tile4 kernel) knows their codes
-                        check(ace_classify(lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, edges ? S.e16 : nullptr, edges && m.opt.frame), "ace_classify");
-                        lvl_done[k][ti] = true;
-                        lvl_edges[k][ti] = edges;
+                        check(ace_classify(p.lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, edges ? S.e16 : nullptr, edges && m.opt.frame), "ace_classify");
+                        ls.done[ti] = true;
+                        ls.edges[ti] = edges;
                     }
                     o.S = &S;
-                    o.edges = lvl_edges[k][ti];
+                    o.edges = ls.edges[ti];
                 }
         }
         const int ntiles = B * (r / 32) * (r / L.TH);
         // the prologue collects the lists of gather-mode levels into one group (geo) instead of launching them level by level
         const bool collect = geo && L.gq && L.TH == 16 && geo->nl < WinoGeoGroup::MAX_L;
-        if (!wq_done[k]) {
+        if (!ls.wq_done) {
             if (collect) {
-                geo_slot[k] = geo->nl;
+                ls.geo_slot = geo->nl;
                 WinoGeoGroup::Level& g = geo->l[geo->nl++];
                 g.u5 = o.S ? o.S->u5 : nullptr;
                 g.qlist = L.qlist;
@@ -1171,226 +1191,203 @@ struct Runner {
                 if (L.gq) check(wino_gather_lists(L.qlist, L.qcnt, L.qoff, L.gq, L.gq_n, L.gq_cap, B, r, r, st), "wino_gather_lists");
                 if (L.gq && L.chunk_base) check(wino_chunk_base(L.gq_n, B, m.patchbuf ? m.patch_cap_chunks : 0, L.chunk_base, L.patch_mode, st), "wino_chunk_base");
             }
-            wq_done[k] = true;
+            ls.wq_done = true;
         }
         bool done = false;
-        for (int d : wwork_done[k]) done = done || d == nrt;
+        for (int d : ls.wwork_done) done = done || d == nrt;
         if (!done) {
-            if (geo && geo_slot[k] >= 0 && geo->nw < WinoGeoGroup::MAX_W) {
+            if (geo && ls.geo_slot >= 0 && geo->nw < WinoGeoGroup::MAX_W) {
                 WinoGeoGroup::Work& w = geo->w[geo->nw++];
-                w.level = geo_slot[k];
+                w.level = ls.geo_slot;
                 w.nrt = nrt;
-                w.work = o.W->work;
-                w.total = o.W->total;
+                w.work = p.W->work;
+                w.total = p.W->total;
             } else {
                 // (a level collected by the prologue whose group has no room for this list: the group is launched first, prologue())
-                if (geo && geo_slot[k] >= 0) geo_flush();
-                if (L.gq) check(wino_gather_worklist(L.gq_n, L.pcnt, B, ntiles / B, nrt, o.W->work, o.W->total, st), "wino_gather_worklist");
-                else check(wino_ace_worklist(L.qcnt, L.pcnt, ntiles, nrt, o.W->work, o.W->total, st), "wino_ace_worklist");
+                if (geo && ls.geo_slot >= 0) geo_flush();
+                if (L.gq) check(wino_gather_worklist(L.gq_n, L.pcnt, B, ntiles / B, nrt, p.W->work, p.W->total, st), "wino_gather_worklist");
+                else check(wino_ace_worklist(L.qcnt, L.pcnt, ntiles, nrt, p.W->work, p.W->total, st), "wino_ace_worklist");
             }
-            wwork_done[k].push_back(nrt);
+            ls.wwork_done.push_back(nrt);
         }
         return o;
     }
-    // the geometry group of the prologue (set only while prologue() runs) and each level's slot in it
+    // the geometry group of the prologue (set only while prologue() runs; each level's slot in it: LevelState::geo_slot)
     WinoGeoGroup* geo = nullptr;
-    int geo_slot[6] = {-1, -1, -1, -1, -1, -1};
     void geo_flush() {
         if (!geo) return;
         if (geo->nl) check(wino_geometry_grouped(*geo, st), "level geometry (grouped)");
         geo->nl = geo->nw = 0;
-        for (int& s : geo_slot) s = -1;
-    }
-    const uint8_t* labels_at(const uint8_t* full, int res_div) {
-        return res_div == 1 ? full : m.lab_r[level_of(res_div)];
+        for (LevelState& s : lvl) s.geo_slot = -1;
     }
     // the interior map of an ACE's level once its classification has run in this chunk (else nullptr)
-    const uint8_t* level_u5(const AceW& a, int r) const {
-        if (!m.opt.sparse || r < m.opt.sparse_min_r) return nullptr;
-        const int k = level_of(a.res_div);
+    const uint8_t* level_u5(const AcePlan& p) const {
+        if (!m.opt.sparse || p.r < m.opt.sparse_min_r) return nullptr;
         for (int ti = 1; ti >= 0; --ti)
-            if (m.sp_level[k][ti].u5 && lvl_done[k][ti]) return m.sp_level[k][ti].u5;
+            if (m.sp_level[p.k][ti].u5 && lvl[p.k].done[ti]) return m.sp_level[p.k][ti].u5;
         return nullptr;
     }
-    // classification, quad lists and task lists of every Winograd ACE level up front (they depend on the labels only): the label
-    // tables that run ahead on the side stream need the interior maps
-    void prepass(const uint8_t* labfull) {
+    // The plan of the chunk: every ACE's route at (B, S) and the lists, buffers and maps that route works on.  Decides only -- launches nothing.
+    std::vector<AcePlan> plans;
+    void plan_aces(const uint8_t* labfull) {
+        plans.assign(m.n_aces, AcePlan());
         for_each_ace(m.blocks, [&](const AceW& a) {
-            const int r = S / a.res_div;
-            if (use_wino_ace(a, r) && !use_wino4_ace(a, r)) (void)wino_prepare(a, labels_at(labfull, a.res_div), r);
+            AcePlan& p = plans[a.index];
+            p.a = &a;
+            p.k = level_of(a.res_div);
+            p.r = S / a.res_div;
+            p.lab = a.res_div == 1 ? labfull : m.lab_r[p.k];
+            p.route = m.ace_route(a, p.r, B);
+            p.abuf = (p.wino() && m.actv_lvl[p.k]) ? m.actv_lvl[p.k] : m.actv;
+            p.kout = a.styled ? HID + 20 : HID;
+            p.ahead.lut_ns = 18 * a.C;
+            if (p.wino()) {
+                p.L = &m.wq_level[p.k];
+                p.W = m.wino_work(a, p.r);
+                // (pre-gathered patches: gather mode, not run-ahead -- the ahead buffers are per ACE -- and not beside an interior pass)
+                if (p.route == AceRoute::WinoQuads && p.L->gq && mode.ahead != SeanModel::ChunkMode::FULL && m.patchbuf && !mode.overlap) p.patch = p.L;
+                return;
+            }
+            // exact SPADE-interior reduction (ace_sparse.h).  f16x3 path: tile-skip mode, honoured by the wave-specialised kernel only
+            // (conv_sh16.h) -- the lists of an ACE that kernel does not serve are still built
+            p.sw = m.sparse_work(a, p.r);
+            if (p.route != AceRoute::Sparse) return;
+            p.SL = &m.sp_level[p.k][p.sw->TH == 16 ? 1 : 0];
+            p.compact = m.opt.use_sh16 && p.sw->mode >= 2;
+            if (mode.ahead == SeanModel::ChunkMode::FULL) return;      // (label tables ahead of the classification: every pixel)
+            // the label-table kernel only writes the hidden activations the conv will read
+            // (exact-f32 path: skipping pixels of the NCHW planes made the kernel slower at every granularity tried -- it is bound by
+            // its LDS table reads, not by the writes; the map stays available behind sean.dbg bit 131072)
+            if (m.opt.use_sh16 ? p.compact : (m.opt.dbg & 131072) != 0) p.need = p.SL->need;
+            if (m.opt.use_sh16 && !p.compact) p.tile_cnt = p.SL->cnt;
         });
     }
+    // classification, quad lists and task lists of every Winograd ACE level up front (labels only): the label tables that run ahead need the interior maps
+    void prepass() {
+        for (const AcePlan& p : plans)
+            if (p.route == AceRoute::WinoQuads) (void)wino_prepare(p);
+    }
 
-    // What an ACE needs that depends on the label map and the style codes only -- never on the activations flowing
-    // through the generator: the SPADE hidden activations (label table) and the style LUT (fc_mu + LUT GEMM / GEMV).
-    struct AcePrep {
-        const float* actv = nullptr;
-        const float* lut = nullptr;
-        int lut_rs = 1, lut_ns = 0, lut_bs = LABEL_NC;
-    };
-    // what: bit 0 = style LUT, bit 1 = SPADE hidden activations
-    // ONE predicate decides both the layout of the hidden activations (148 planes per sample with the one-hot planes behind the
-    // hidden channels) and the kernel that reads them: the level's quad lists and the task list of this row-tile count must have
-    // been sized at build time (they exist where (max_size >> k) % 32 == 0; a smaller S can reach a 32-grid level that max_size
-    // does not have, e.g. max_size = 96, S = 64 -- ADVICE r04), else the ACE takes the direct kernels and their [B][128][H][W] layout
-    bool use_wino_ace(const AceW& a, int r) const {
-        if (!(m.opt.wino && !m.opt.use_sh16 && a.spade_wino && r >= 32 && r % 32 == 0)) return false;
-        const SeanModel::WinoLevel& L = m.wq_level[level_of(a.res_div)];
-        if (!L.qlist) return false;
-        const int nrt = (a.C + 15) / 16;
-        for (const auto& w : L.works)
-            if (w.nrt == nrt) return true;
-        return false;
-    }
-    // u5 (Winograd ACE path): the level's interior map when the SPADE-interior reduction serves it -- the label-table kernel then
-    // writes the hidden activations only where a boundary quad's patch reads them (nullptr: everywhere)
-    // SPADE conv of this ACE as F(4x4,3x3) over every tile of the level (conv_wino4.h): the low-resolution levels, where nearly every
-    // tile holds a boundary pixel -- no classification, no interior pass, hidden activations at every pixel
-    bool use_wino4_ace(const AceW& a, int r) const {
-        return use_wino_ace(a, r) && m.opt.wino >= 2 && a.spade_wino4 && r <= m.opt.wino4_ace_max_r && wino4_ace_supported(r, r, a.C) && (!a.styled || m.wsty4) &&
-               (m.opt.wino4_force || m.opt.batch_inv || wino4_pays((long long)B * (r / 32) * (r / 32) * ((a.C + 15) / 16), m.num_cus));      // (few tasks per CU -- single images -- : the gather kernel)
-    }
-    AcePrep ace_prepare(const AceW& a, const uint8_t* labfull, const float* codes, hipStream_t s, float* actv_buf, float* lut_buf,
-                        float* splitk, bool prof, int what = 3, const uint8_t* need = nullptr, const int* tile_cnt = nullptr,
-                        const uint8_t* u5 = nullptr, const SeanModel::WinoLevel* PL = nullptr) {      // PL: the level, when its patch source may serve this ACE
-        const int r = S / a.res_div;
-        const uint8_t* lab = labels_at(labfull, a.res_div);
+    // The style LUT of one ACE (fc_mu + LUT GEMM / GEMV) into lut_buf, on stream s; prof: the GEMM is a timed launch of the main stream.
+    // An unstyled ACE has none: only the default view comes back.
+    AcePrep build_lut(const AcePlan& pl, const float* codes, hipStream_t s, float* lut_buf, float* splitk, bool prof) {
+        const AceW& a = *pl.a;
         AcePrep q;
-        q.actv = actv_buf;
         q.lut_ns = 18 * a.C;
-        auto tm = [&](double flops, double bytes, auto launch) {
-            if (prof) timed(2, flops, bytes, launch);
-            else launch();
-        };
-        if (a.styled && (what & 1)) {
-            q.lut = lut_buf;
-            // f16x3 path: one extra all-zero column per sample (mu = 0 -> LUT = 0) that taps outside the image point at
-            const int bs = m.opt.use_sh16 ? LABEL_NC + 1 : LABEL_NC;
-            const int N = B * bs, npad = ((N + 31) / 32) * 32;
-            q.lut_bs = bs;
-            const double fl = 2.0 * 18 * a.C * STYLE * N, by = 4.0 * (18.0 * a.C * STYLE + (double)STYLE * N + 18.0 * a.C * N);
-            if (a.lut_rows && N <= 64 && !m.opt.batch_inv) {
-                // interactive batch sizes: P[n][row] = sum_k W[row][k] mu[n][k] as a batched GEMV (weight-bandwidth bound)
-                check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, m.mu_img, 0, bs), "fc_mu");
-                tm(fl, by, [&] {
-                    check(lut_gemv_mfma(m.mu_img, a.lut_rows, lut_buf, N, 18 * a.C, s), "lut gemv");
-                });
-            } else if (m.opt.use_sh16) {
-                // f16x3 LUT GEMM: 1x1 conv over the [npad/32 x 32] "image" of (sample, label) columns, C4 output
-                unsigned* mu_slot = m.amax_slots + 2 * a.index + 1;
-                const float* mu = m.mu_img;
-                if (m.fcmu_batched) {                    // projected at the start of the chunk, all ACEs in one launch
-                    mu = m.mu_all + (size_t)a.index * m.mu_stride;
-                } else {
-                    for (int pass = 0; pass < 2; ++pass)     // second pass: returns at once unless the first one left the f16 window
-                        check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 1, bs, SH16_ACT_SCALE, mu_slot, pass, m.opt.terms == 2), "fc_mu");
-                }
-                ConvParams p{};
-                p.in = mu;
-                p.wpk = a.lut_wpk;
-                p.out = lut_buf;
-                p.B = 1;
-                p.Cin = STYLE;
-                p.H = npad / 32;
-                p.W = 32;
-                p.Mrows = 18 * a.C;
-                p.pad = -1;
-                p.act = ACT_NONE;
-                p.terms = m.opt.terms;
-                p.wscale = a.lut_wscale;
-                p.in_scale_inv = 1.f / SH16_ACT_SCALE;
-                p.in_amax = mu_slot;
-                p.out_mul = a.out_scale;           // the ACE epilogue takes the LUT pre-multiplied by its output scale
-                p.partial = splitk;                // K = 512 in 32 chunks on few tiles (C <= 512): split-K fills the chip
-                p.partial_cap = m.splitk_cap;
-                tm(fl, by, [&] { check(conv_sh16_plain(p, 1, s), "lut gemm"); });
-                q.lut_rs = npad;
-                q.lut_ns = 4;
-            } else {
-                const float* mu = m.mu_img;
-                if (m.fcmu_batched && (N > 64 || m.opt.batch_inv)) mu = m.mu_all + (size_t)a.index * m.mu_stride;      // projected at the start of the chunk (generate())
-                else check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s), "fc_mu");
-                ConvParams p{};
-                p.in = mu;
-                p.wpk = a.lut_wpk;
-                p.out = lut_buf;
-                p.B = 1;
-                p.Cin = STYLE;
-                p.H = npad / 32;
-                p.W = 32;
-                p.Mrows = 18 * a.C;
-                p.npix_valid = N;
-                p.pad = -1;
-                tm(fl, by, [&] { check(conv_nhwc1x1(p, s), "lut gemm"); });
-            }
+        if (!a.styled) return q;
+        q.lut = lut_buf;
+        // f16x3 path: one extra all-zero column per sample (mu = 0 -> LUT = 0) that taps outside the image point at
+        const int bs = m.opt.use_sh16 ? LABEL_NC + 1 : LABEL_NC;
+        const int N = B * bs, npad = ((N + 31) / 32) * 32;
+        q.lut_bs = bs;
+        const double fl = 2.0 * 18 * a.C * STYLE * N, by = 4.0 * (18.0 * a.C * STYLE + (double)STYLE * N + 18.0 * a.C * N);
+        auto tm = [&](auto launch) { prof ? timed(2, fl, by, launch) : launch(); };
+        if (a.lut_rows && N <= 64 && !m.opt.batch_inv) {
+            // interactive batch sizes: P[n][row] = sum_k W[row][k] mu[n][k] as a batched GEMV (weight-bandwidth bound)
+            check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, m.mu_img, 0, bs), "fc_mu");
+            tm([&] { check(lut_gemv_mfma(m.mu_img, a.lut_rows, lut_buf, N, 18 * a.C, s), "lut gemv"); });
+            return q;
         }
-        if (!(what & 2)) return q;
+        // LUT GEMM: 1x1 conv over the [npad/32 x 32] "image" of (sample, label) columns
+        ConvParams p{};
+        p.in = m.mu_img;
+        p.wpk = a.lut_wpk;
+        p.out = lut_buf;
+        p.B = 1;
+        p.Cin = STYLE;
+        p.H = npad / 32;
+        p.W = 32;
+        p.Mrows = 18 * a.C;
+        p.pad = -1;
+        if (m.opt.use_sh16) {      // f16x3: C4 output
+            unsigned* mu_slot = m.amax_slots + 2 * a.index + 1;
+            if (m.fcmu_batched) {                    // projected at the start of the chunk, all ACEs in one launch
+                p.in = m.mu_all + (size_t)a.index * m.mu_stride;
+            } else {
+                for (int pass = 0; pass < 2; ++pass)     // second pass: returns at once unless the first one left the f16 window
+                    check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 1, bs, SH16_ACT_SCALE, mu_slot, pass, m.opt.terms == 2), "fc_mu");
+            }
+            p.act = ACT_NONE;
+            p.terms = m.opt.terms;
+            p.wscale = a.lut_wscale;
+            p.in_scale_inv = 1.f / SH16_ACT_SCALE;
+            p.in_amax = mu_slot;
+            p.out_mul = a.out_scale;           // the ACE epilogue takes the LUT pre-multiplied by its output scale
+            p.partial = splitk;                // K = 512 in 32 chunks on few tiles (C <= 512): split-K fills the chip
+            p.partial_cap = m.splitk_cap;
+            tm([&] { check(conv_sh16_plain(p, 1, s), "lut gemm"); });
+            q.lut_rs = npad;
+            q.lut_ns = 4;
+        } else {
+            if (m.fcmu_batched && (N > 64 || m.opt.batch_inv)) p.in = m.mu_all + (size_t)a.index * m.mu_stride;      // projected at the start of the chunk (generate())
+            else check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s), "fc_mu");
+            p.npix_valid = N;
+            tm([&] { check(conv_nhwc1x1(p, s), "lut gemm"); });
+        }
+        return q;
+    }
+    // the zero columns left and right of the image in a padded hidden buffer: the label-table kernels never write them, so they are cleared
+    // whenever the buffer changes its geometry (first use, another image size) -- per-pixel pad stores cost 200 us per 512^2 launch
+    void zero_pads(float* buf, int r, int kout, hipStream_t s) {
+        const long long geo = ((long long)r << 20) | ((long long)kout << 8) | 1;
+        auto it = m.pad_state.find(buf);
+        if (it != m.pad_state.end() && it->second == geo) return;
+        check(hipMemsetAsync(buf, 0, (size_t)m.max_batch * kout * r * wino_apitch(r) * sizeof(float), s), "hidden activations: zero pads");
+        m.pad_state[buf] = geo;
+    }
+    // The SPADE hidden activations of one ACE (label table) into actv_buf, on stream s.  The route decides both the layout (Winograd routes:
+    // padded planes, the one-hot planes of a styled ACE behind the hidden channels; else [B][128][H][W]) and the kernel that reads it.
+    void build_hidden(const AcePlan& pl, hipStream_t s, float* actv_buf) {
+        const AceW& a = *pl.a;
+        const int r = pl.r, kout = pl.kout;
+        const uint8_t* lab = pl.lab;
         // a buffer that held the padded planes of a Winograd level (zero columns cleared once per geometry) and now receives the
         // direct [B][HID][r][r] layout -- the same ACE at another image size on a run-ahead handle -- must have its pads cleared again
         // before the next padded use: the direct kernels write over them
-        if (m.opt.use_sh16 || !use_wino_ace(a, r)) m.pad_state.erase(actv_buf);
+        if (!pl.wino()) m.pad_state.erase(actv_buf);
         if (m.opt.use_sh16)
-            check(onehot_conv3x3_sh16(lab, a.actv_table, a.actv_bias, actv_buf, B, r, r, HID, 1, a.actv_scale, s, m.opt.terms == 2, need, tile_cnt,
+            check(onehot_conv3x3_sh16(lab, a.actv_table, a.actv_bias, actv_buf, B, r, r, HID, 1, a.actv_scale, s, m.opt.terms == 2, pl.need, pl.tile_cnt,
                                       (m.opt.dbg & 33554432) ? 1 : 0), "mlp_shared");
-        else if (use_wino_ace(a, r)) {
+        else if (pl.wino()) {
             // Winograd ACE path: hidden activations (+ the one-hot planes of a styled ACE, which feed the style k-steps) in one
             // persistent pass into the padded planes the ACE kernels read (conv_wino.h WINO_AXOFF), whole 64-byte groups of pixels
-            // that a boundary quad's patch touches only (sean.hidden_wq = 0: every pixel)
-            // the zero columns left and right of the image: the kernel never writes them, so they are cleared whenever the buffer
-            // changes its geometry (first use, another image size) -- per-pixel pad stores cost 200 us per 512^2 launch
-            const int kout = a.styled ? HID + 20 : HID;
-            const long long geo = ((long long)r << 20) | ((long long)kout << 8) | 1;
-            auto it = m.pad_state.find(actv_buf);
-            if (it == m.pad_state.end() || it->second != geo) {
-                check(hipMemsetAsync(actv_buf, 0, (size_t)m.max_batch * kout * r * wino_apitch(r) * sizeof(float), s), "hidden activations: zero pads");
-                m.pad_state[actv_buf] = geo;
-            }
+            // that a boundary quad's patch touches only (sean.hidden_wq = 0, F(4x4) levels, level not classified yet: every pixel)
+            zero_pads(actv_buf, r, kout, s);
+            const uint8_t* u5 = (pl.route == AceRoute::WinoQuads && m.opt.hidden_wq) ? level_u5(pl) : nullptr;
+            const SeanModel::WinoLevel* PL = pl.patch;
             const bool pm = PL && PL->gq && PL->patch_mode && m.patchbuf;
-            if (pm && pro_active && PL->chunk_base) {
+            if (pm && mode.prologue && PL->chunk_base) {
                 // chunks with the prologue: both sources from one launch, the device flag picks the body (kernels.h)
-                check(spade_hidden_level(lab, m.opt.hidden_wq ? u5 : nullptr, PL->gq, PL->gq_n, PL->gq_cap, PL->chunk_base, PL->patch_mode, a.actv_table,
+                check(spade_hidden_level(lab, u5, PL->gq, PL->gq_n, PL->gq_cap, PL->chunk_base, PL->patch_mode, a.actv_table,
                                          a.actv_bias, actv_buf, m.patchbuf, B, r, r, kout, a.styled ? 1 : 0, wino_apitch(r), WINO_AXOFF, s),
                       "mlp_shared (planes or pre-gathered patches)");
-                return q;
+                return;
             }
-            check(spade_hidden_wq(lab, m.opt.hidden_wq ? u5 : nullptr, a.actv_table, a.actv_bias, actv_buf, B, r, r, kout, a.styled ? 1 : 0, s,
+            check(spade_hidden_wq(lab, u5, a.actv_table, a.actv_bias, actv_buf, B, r, r, kout, a.styled ? 1 : 0, s,
                                   wino_apitch(r), WINO_AXOFF, pm ? PL->patch_mode : nullptr), "mlp_shared (boundary-quad patches)");
             // few, scattered boundary quads: their patches pre-gathered instead (one of the two kernels returns at once: device flag)
             if (pm) check(spade_hidden_patch(lab, PL->gq, PL->gq_n, PL->gq_cap, PL->chunk_base, PL->patch_mode, a.actv_table, a.actv_bias, m.patchbuf,
                                              B, r, r, kout, s), "mlp_shared (pre-gathered patches)");
         } else
-            check(onehot_conv3x3(lab, a.actv_table, a.actv_bias, actv_buf, B, r, r, HID, 1, s, 0, need), "mlp_shared");
-        return q;
+            check(onehot_conv3x3(lab, a.actv_table, a.actv_bias, actv_buf, B, r, r, HID, 1, s, 0, pl.need), "mlp_shared");
     }
 
     // Small jobs (interactive renders: the chip is mostly empty) run every ACE's prepare step AHEAD on the model's side
     // stream, into per-ACE buffers, while the main stream walks the dependent chain of convs; an event per ACE joins them.
-    // full = false (large jobs): only the style LUT builds run ahead; the label-table kernels stay inline.
-    bool ahead = false, ahead_luts = false;
-    std::vector<AcePrep> prepared;
-    bool luts_ready = false;
-    void lut_entry(const AceW& a, AcePrep& e) const {
-        e.lut = m.lut_ahead[a.index];
-        e.lut_rs = 1;
-        e.lut_ns = 18 * a.C;
-        e.lut_bs = LABEL_NC;
-    }
-    void prepare_all_ahead(const uint8_t* labfull, const float* codes, bool full) {
-        ahead = full;
-        ahead_luts = !full;
-        prepared.assign(m.n_aces, AcePrep());
+    // mode.ahead == LUTS (large jobs): only the style LUT builds run ahead; the label-table kernels stay inline.
+    void prepare_all_ahead(const float* codes) {
+        const bool full = mode.ahead == SeanModel::ChunkMode::FULL;
         check(hipEventRecord(m.ev_fork, st), "fork");
         check(hipStreamWaitEvent(m.side, m.ev_fork, 0), "fork wait");
-        for_each_ace(m.blocks, [&](const AceW& a) {
-            if (!full && !a.styled) return;
-            const int ra = S / a.res_div;
-            AcePrep e = ace_prepare(a, labfull, codes, m.side, m.actv_ahead[a.index], m.lut_ahead[a.index], m.splitk_side, false,
-                                    full ? (luts_ready ? 2 : 3) : 1, nullptr, nullptr,
-                                    (use_wino_ace(a, ra) && !use_wino4_ace(a, ra)) ? level_u5(a, ra) : nullptr);
-            if (luts_ready && a.styled) lut_entry(a, e);          // (the grouped launch on the main stream built it)
-            prepared[a.index] = e;
+        for (AcePlan& p : plans) {
+            const AceW& a = *p.a;
+            if (!full && !a.styled) continue;
+            // (grouped LUT build: the launch on the main stream built it)
+            if (!(mode.grouped && a.styled)) p.ahead = build_lut(p, codes, m.side, m.lut_ahead[a.index], m.splitk_side, false);
+            p.ahead.actv = m.actv_ahead[a.index];
+            if (full) build_hidden(p, m.side, m.actv_ahead[a.index]);
             check(hipEventRecord(m.ev_join[a.index], m.side), "join record");
-        });
+        }
     }
 
     // Exact-f32 path, more than 64 (sample, label) columns: the style LUTs P[(sample, label)][18 C] of ALL styled ACEs from one
@@ -1408,11 +1405,8 @@ struct Runner {
         const int nrg = ((N + 31) / 32 + 3) / 4;
         timed(2, 2.0 * m.lut_group_rows * STYLE * N, 4.0 * (m.lut_group_rows * STYLE + m.lut_group_rows * N + (double)m.lut_ngroups * STYLE * N),
               [&] { check(conv_pw_grouped(q, m.lut_group_tiles * nrg, st), "style LUTs (grouped GEMM)"); });
-        prepared.assign(m.n_aces, AcePrep());
-        for_each_ace(m.blocks, [&](const AceW& a) {
-            if (a.styled) lut_entry(a, prepared[a.index]);
-        });
-        luts_ready = true;
+        for (AcePlan& p : plans)
+            if (p.a->styled) p.ahead.lut = m.lut_ahead[p.a->index];      // (the view: AcePrep's defaults, lut_ns from the plan)
     }
 
     // ACE prologue (SeanModel::pro_on; large chunks of the exact-f32 Winograd path): what the ACEs of the chunk build from labels, codes and
@@ -1422,21 +1416,13 @@ struct Runner {
     //   * quad lists, per-sample lists, task lists and chunk bases of every gather-mode level (wino_geometry_grouped: four launches);
     //   * the padded hidden planes of every F(4x4)-route ACE (spade_hidden_wq_grouped);
     //   * gtab and P6 of every gather-route ACE (ace_tables_grouped) and its F(2x2) style images (wino_style_pack_grouped) -- these read the
-    //     style LUTs, so they need the grouped LUT GEMM of the chunk (luts_ready); without it only unstyled ACEs join.
-    // The groups are filled here, per call: the set of ACEs, their level sizes and label pointers follow B and S.  pro_*[index] != nullptr
-    // tells ace() that the product is in place; every other ACE keeps its inline launches.  The level geometry of the gather-route ACEs
-    // (classification, quad lists, task lists: wino_prepare) runs here too, since gtab / P6 depend on what it decides (edges).
+    //     style LUTs, so they need the grouped LUT GEMM of the chunk (mode.grouped); without it only unstyled ACEs join.
+    // The groups are filled here, per call: the set of ACEs, their level sizes and label pointers follow B and S.  AcePlan::pre_* != nullptr
+    // tells the ACE functions that the product is in place; every other ACE keeps its inline launches.  The level geometry of the gather-route
+    // ACEs (classification, quad lists, task lists: wino_prepare) runs here too, since gtab / P6 depend on what it decides (edges).
     // With the prologue on, the gather-mode levels also take their hidden activations -- planes or pre-gathered patches, a device flag decides
-    // -- from one launch per ACE (spade_hidden_level) instead of two of which one returns at once.
-    std::vector<const float*> pro_hidden, pro_gtab, pro_p6, pro_wsty;
-    bool pro_active = false;
-    void prologue(const uint8_t* labfull) {
-        if (!m.pro_on || m.prof_on || ahead || overlap || (long long)B * S * S <= m.ahead_limit) return;
-        pro_active = true;
-        pro_hidden.assign(m.n_aces, nullptr);
-        pro_gtab.assign(m.n_aces, nullptr);
-        pro_p6.assign(m.n_aces, nullptr);
-        pro_wsty.assign(m.n_aces, nullptr);
+    // -- from one launch per ACE (spade_hidden_level) instead of two of which one returns at once.  Runs where mode.prologue says so.
+    void prologue() {
         HiddenGroup hg{};
         AceTableGroup tg{};
         StylePackGroup sg{};
@@ -1446,38 +1432,32 @@ struct Runner {
         tg.lut_rs = 1;
         tg.lut_bs = LABEL_NC;
         tg.lut_mul = 1.f;
-        for_each_ace(m.blocks, [&](const AceW& a) {
-            const int r = S / a.res_div;
-            if (!use_wino_ace(a, r)) return;
-            if (use_wino4_ace(a, r)) {
+        for (AcePlan& p : plans) {
+            const AceW& a = *p.a;
+            const int r = p.r;
+            if (p.route == AceRoute::F4) {
                 float* buf = m.pro_actv[a.index];
-                if (!buf || hg.n >= HiddenGroup::MAX) return;
-                // (the zero columns of the padded planes: cleared once per geometry, as ace_prepare does for the level buffers)
-                const int kout = a.styled ? HID + 20 : HID;
-                const long long geo = ((long long)r << 20) | ((long long)kout << 8) | 1;
-                auto it = m.pad_state.find(buf);
-                if (it == m.pad_state.end() || it->second != geo) {
-                    check(hipMemsetAsync(buf, 0, (size_t)m.max_batch * kout * r * wino_apitch(r) * sizeof(float), st), "hidden activations: zero pads");
-                    m.pad_state[buf] = geo;
-                }
+                if (!buf || hg.n >= HiddenGroup::MAX) continue;
+                zero_pads(buf, r, p.kout, st);
                 HiddenGroup::Entry& e = hg.e[hg.n++];
-                e.lab = labels_at(labfull, a.res_div);
+                e.lab = p.lab;
                 e.u5 = nullptr;                              // (F(4x4) levels: every pixel is read)
                 e.table = a.actv_table;
                 e.bias = a.actv_bias;
                 e.out = buf;
                 e.H = e.W = r;
-                e.kout = kout;
+                e.kout = p.kout;
                 e.onehot = a.styled ? 1 : 0;
                 e.pitch = wino_apitch(r);
                 e.xoff = WINO_AXOFF;
-                pro_hidden[a.index] = buf;
-                return;
+                p.pre_actv = buf;
+                continue;
             }
-            const WinoPrep wp = wino_prepare(a, labels_at(labfull, a.res_div), r);      // (lists and task lists: into the geometry group)
-            if (!wp.L || (a.styled && !luts_ready)) return;
-            const float* lut = a.styled ? prepared[a.index].lut : nullptr;
-            if (a.styled && !lut) return;
+            if (p.route != AceRoute::WinoQuads) continue;
+            const WinoPrep wp = wino_prepare(p);      // (lists and task lists: into the geometry group)
+            if (a.styled && !mode.grouped) continue;
+            const float* lut = a.styled ? p.ahead.lut : nullptr;
+            if (a.styled && !lut) continue;
             const bool p6 = wp.edges && a.styled;
             if (wp.S && m.pro_gtab[a.index] && (!p6 || m.pro_p6[a.index]) && tg.n < AceTableGroup::MAX) {
                 AceTableGroup::Entry& e = tg.e[tg.n++];
@@ -1488,361 +1468,304 @@ struct Runner {
                 e.gtab = m.pro_gtab[a.index];
                 e.p6 = p6 ? m.pro_p6[a.index] : nullptr;
                 e.C = a.C;
-                pro_gtab[a.index] = e.gtab;
-                pro_p6[a.index] = e.p6;
+                p.pre_gtab = e.gtab;
+                p.pre_p6 = e.p6;
             }
             if (a.styled && m.pro_wsty[a.index] && sg.n < StylePackGroup::MAX) {
                 StylePackGroup::Entry& e = sg.e[sg.n++];
                 e.lut = lut;
                 e.wsty = m.pro_wsty[a.index];
                 e.C = a.C;
-                pro_wsty[a.index] = e.wsty;
+                p.pre_wsty = e.wsty;
             }
-        });
+        }
         geo_flush();
         geo = nullptr;
         check(spade_hidden_wq_grouped(hg, st), "mlp_shared (grouped, F(4x4)-route ACEs)");
         check(ace_tables_grouped(tg, st), "ace tables (grouped)");
         check(wino_style_pack_grouped(sg, st), "wino_style_pack (grouped)");
     }
-    const float* pro_get(const std::vector<const float*>& v, const AceW& a) const { return v.empty() ? nullptr : v[a.index]; }
 
-    // one ACE: SPADE hidden activations (label LUT) -> fused gamma/beta conv + modulation -> h
-    void ace(const AceW& a, const uint8_t* labfull, const float* codes, const float* noise, size_t nf, size_t noff,
-             const float* x, int x_up, int act, float* hout) {
-        const int r = S / a.res_div;
-        const uint8_t* lab = labels_at(labfull, a.res_div);
-        const double npix = (double)B * r * r;
-        // exact SPADE-interior reduction (ace_sparse.h): classification of the level + work list of this layer's row tiles.
-        // f16x3 path: tile-skip mode, honoured by the wave-specialised kernel only (conv_sh16.h)
-        const bool wino_ace = use_wino_ace(a, r), f4_ace = use_wino4_ace(a, r);
-        WinoPrep wp;
-        if (wino_ace && !f4_ace) wp = wino_prepare(a, lab, r);
-        const SparseWork* sw = (wino_ace && (wp.L || f4_ace)) ? nullptr : sparse_prepare(a, lab, r);
-        if (sw && m.opt.use_sh16) {
-            ConvParams t{};
-            t.C = a.C;
-            t.W = t.H = r;
-            t.B = B;
-            t.Cin = HID;
-            t.dbg = m.opt.dbg;
-            if (!sh16_ace_uses_ws(t)) sw = nullptr;
+    // one ACE: SPADE hidden activations (label LUT) -> fused gamma/beta conv + modulation -> h.  The plan names the route; what the routes
+    // share -- the level's lists, the operands -- is launched here, then the route's own function runs.
+    void ace(const AceW& a, const float* codes, const float* noise, size_t nf, size_t noff, const float* x, int x_up, int act, float* hout) {
+        const AcePlan& p = plans[a.index];
+        const AceIO io{noise + noff, (long long)nf, x, x_up, act, hout};
+        const WinoPrep wp = p.route == AceRoute::WinoQuads ? wino_prepare(p) : WinoPrep();
+        if (p.sw) sparse_prepare(p);
+        const AcePrep q = operands(p, codes);
+        switch (p.route) {
+            case AceRoute::F4: return ace_f4(p, q, io);
+            case AceRoute::WinoQuads: return ace_wino(p, wp, q, io);
+            case AceRoute::Sparse: return ace_sparse(p, q, io);
+            case AceRoute::TinySplitK: return ace_tiny(p, q, io);
+            case AceRoute::Dense: return ace_dense(p, q, io);
         }
-        const SparseLevel* SL = sw ? &m.sp_level[level_of(a.res_div)][sw->TH == 16 ? 1 : 0] : nullptr;
-        // the label-table kernel only writes the hidden activations the conv will read
-        // (exact-f32 path: skipping pixels of the NCHW planes made the kernel slower at every granularity tried -- it is bound by
-        // its LDS table reads, not by the writes; the map stays available behind sean.dbg bit 131072)
-        const uint8_t* need0 = (SL && !m.opt.use_sh16 && (m.opt.dbg & 131072)) ? SL->need : nullptr;
-        const uint8_t* need = need0;
-        const bool compact = SL && m.opt.use_sh16 && sw->mode >= 2;      // f16x3: pixel-level compaction inside the ws kernel
-        if (compact) need = SL->need;
-        const int* tile_cnt = (SL && m.opt.use_sh16 && !compact) ? SL->cnt : nullptr;
+    }
+    // The operands of this ACE: hidden planes and LUT view.  Full run-ahead: both wait on the side stream.  Else the hidden activations are built
+    // here (unless the prologue wrote them), and the style LUT is the chunk's grouped one, the one built ahead (joined here), or built here first.
+    AcePrep operands(const AcePlan& p, const float* codes) {
+        const AceW& a = *p.a;
         AcePrep q;
-        const uint8_t* u5 = (wino_ace && wp.L && wp.S) ? wp.S->u5 : nullptr;      // (F(4x4,3x3) levels: every pixel is read)
-        // the level whose pre-gathered patches may serve this ACE (gather mode, not run-ahead: the ahead buffers are per ACE)
-        const SeanModel::WinoLevel* patch_level = (wino_ace && !f4_ace && wp.L && wp.L->gq && !ahead && m.patchbuf && !overlap) ? wp.L : nullptr;
-        float* abuf = m.actv;                      // hidden activations: the Winograd ACE levels own padded buffers (pads zeroed once per size)
-        if (wino_ace && m.actv_lvl[level_of(a.res_div)]) abuf = m.actv_lvl[level_of(a.res_div)];
-        const float* pre_actv = f4_ace ? pro_get(pro_hidden, a) : nullptr;      // the prologue wrote this ACE's hidden planes: no label-table launch here
-        const int lt = pre_actv ? 0 : 2;
-        if (ahead) {
-            q = prepared[a.index];
-            check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
-        } else if (luts_ready && a.styled) {
-            if (lt) (void)ace_prepare(a, labfull, codes, st, abuf, nullptr, m.splitk_ws, true, 2, need, tile_cnt, u5, patch_level);     // label table inline
-            q = prepared[a.index];
-            q.actv = abuf;
-        } else if (ahead_luts && a.styled) {
-            if (lt) (void)ace_prepare(a, labfull, codes, st, abuf, nullptr, m.splitk_ws, true, 2, need, tile_cnt, u5, patch_level);     // label table inline
-            q = prepared[a.index];
-            q.actv = abuf;
+        if (mode.ahead == SeanModel::ChunkMode::FULL) {
+            q = p.ahead;
             check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
         } else {
-            q = ace_prepare(a, labfull, codes, st, abuf, m.lut, m.splitk_ws, true, 1 | lt, need, tile_cnt, u5, patch_level);
+            const bool lut_made = a.styled && (mode.grouped || mode.ahead == SeanModel::ChunkMode::LUTS);
+            if (!lut_made) q = build_lut(p, codes, st, m.lut, m.splitk_ws, true);
+            if (!p.pre_actv) build_hidden(p, st, p.abuf);      // label table inline
+            if (lut_made) q = p.ahead;
+            q.actv = p.abuf;
+            if (lut_made && !mode.grouped) check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
         }
-        if (pre_actv) q.actv = pre_actv;
-        if (f4_ace) {
-            Wino4AceParams w{};
-            w.actv = q.actv;
-            w.wpk = a.spade_wino4;
-            w.wsty = (a.styled && q.lut) ? m.wsty4 : nullptr;
-            w.out = hout;
-            w.x = x;
-            w.x_up = x_up;
-            w.act = act;
-            w.B = B;
-            w.C = a.C;
-            w.H = r;
-            w.W = r;
-            w.bias_g = a.bias_g;
-            w.bias_b = a.bias_b;
-            w.bn_a = a.bn_a;
-            w.bn_d = a.bn_d;
-            w.nv = a.nv;
-            w.noise = noise + noff;
-            w.noise_bstride = (long long)nf;
-            const int ktot = w.wsty ? 152 : 128;             // (38 / 32 k-steps of four channels)
-            next_flops_exec = 2.0 * 32.0 * ((a.C + 15) / 16) * ktot * 36.0 * npix / 16.0;
-            // 2 C GEMM rows over 128 (+ 20) input planes: the input transform once for all C / 8 row tiles (conv_wino4v.h)
-            const bool vroute = m.opt.wino4v && wino4v_pays(2 * a.C, r) && m.wino4v_fits(B, r, w.wsty ? 38 : 32);
-            timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 4.0 * (npix * (HID + (a.styled ? 20 : 0)) + npix * a.C / (x_up ? 4.0 : 1.0) + npix * a.C), [&] {
-                if (w.wsty) check(wino4_style_pack(q.lut, m.wsty4, B, a.C, st), "wino4_style_pack");
-                if (vroute) {
-                    Wino4vPackParams vp{};
-                    vp.in = q.actv;
-                    vp.v = m.vbuf;
-                    vp.B = B;
-                    vp.K = HID + (a.styled ? 20 : 0);       // (the buffer's plane count: ace_prepare; an ACE without LUT reads the first 128 only)
-                    vp.H = vp.W = r;
-                    vp.nks = w.wsty ? 38 : 32;
-                    vp.pitch = wino_apitch(r);
-                    vp.xoff = WINO_AXOFF;
-                    vp.padded = 1;
-                    check(wino4v_pack(vp, st), "hidden activation transform (winograd F(4x4,3x3))");
-                    w.v = m.vbuf;
-                    check(conv_wino4v_ace(w, st), "spade conv (winograd F(4x4,3x3), every tile, pre-transformed input)");
-                } else
-                    check(conv_wino4_ace(w, st), "spade conv (winograd F(4x4,3x3), every tile)");
-            });
-            return;
+        if (p.pre_actv) q.actv = p.pre_actv;
+        return q;
+    }
+    // the same-named modulation operands of any ACE parameter struct (the interior pass takes its biases through gtab)
+    template <class P>
+    void fill_mod(P& t, const AcePlan& p, const AceIO& io) {
+        const AceW& a = *p.a;
+        t.x = io.x;
+        t.x_up = io.x_up;
+        t.act = io.act;
+        t.out = io.out;
+        t.B = B;
+        t.C = a.C;
+        t.H = t.W = p.r;
+        t.bn_a = a.bn_a;
+        t.bn_d = a.bn_d;
+        t.nv = a.nv;
+        t.noise = io.noise;
+        t.noise_bstride = io.nf;
+        if constexpr (!std::is_same<P, AceInteriorParams>::value) {
+            t.bias_g = a.bias_g;
+            t.bias_b = a.bias_b;
         }
-        if (wino_ace && wp.L) {
-            const double xpp = 4.0 * a.C / (x_up ? 4.0 : 1.0), opp = 4.0 * a.C;
-            const int ktot = HID + (a.styled ? 20 : 0);
-            if (wp.S) {          // interior pixels: elementwise with the per-(sample, label) gamma/beta rows (ace_sparse.h)
-                AceInteriorParams ip{};
-                ip.x = x;
-                ip.out = hout;
-                ip.u5 = wp.S->u5;
-                ip.cnt = wp.S->cnt;
-                ip.gtab = m.gtab;
-                ip.bn_a = a.bn_a;
-                ip.bn_d = a.bn_d;
-                ip.nv = a.nv;
-                ip.noise = noise + noff;
-                ip.noise_bstride = (long long)nf;
-                ip.B = B;
-                ip.C = a.C;
-                ip.H = r;
-                ip.W = r;
-                ip.x_up = x_up;
-                ip.act = act;
-                ip.variant = 0;
-                // four pixels per thread (16-byte stores) from 128 pixels of width: 530 -> 420 us on the up-sampled 512^2 launches
-                // (tools/interior_bench.hip); level in the 100 ms step of round 3, measurable in this one
-                ip.impl = r >= 128 ? 2 : 0;
-                ip.groups = m.opt.int_groups;       // (tile4 kernel: channel groups per block, 0 = the launcher's rule; ace_sparse.hip)
-                if (wp.edges) {         // straight-edge pixels: table row of the code + three column / row sums of the style LUT (built below)
-                    if (!a.edge_tab || r < 128) check(hipErrorInvalidValue, "straight-edge marks on a level whose ACE has no table");
-                    ip.e16 = wp.S->e16;
-                    ip.etab = a.edge_tab;
-                    ip.p6 = (a.styled && q.lut) ? m.p6 : nullptr;
-                }
-                // (tile4 kernel, r >= 128: 0 = whole 128-byte lines that hold an interior pixel, ace_sparse.hip; sean.dbg bit 134217728: the
-                //  block rule of rounds 3-5 for A/B)
-                ip.fill_min = (x_up && r < 128) ? 257 : ((r >= 128 && !(m.opt.dbg & 134217728)) ? 0 : 128);
-                if (overlap) {
-                    // beside the boundary conv of the same ACE (disjoint output pixels -- so no block may fill its boundary pixels),
-                    // on the few CUs of the side stream; the consumer of `hout` waits for ev_int below
-                    ip.fill_min = 257;
-                    ip.quad_only = 1;
-                    ip.gtab = m.gtab_side;
-                    check(hipEventRecord(m.ev_x[a.index], st), "x ready");
-                    check(hipStreamWaitEvent(m.side_int, m.ev_x[a.index], 0), "x ready wait");
-                    check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.gtab_side, B, a.C, m.side_int), "ace_gtable");
-                    check(ace_interior_f32(ip, m.side_int), "ace interior");
-                    check(hipEventRecord(m.ev_int[a.index], m.side_int), "interior done");
-                } else {
-                    // tables from the prologue: only when it built exactly what this pass reads (P6 follows the level's straight-edge marks)
-                    const float* pre_gtab = pro_get(pro_gtab, a);
-                    const float* pre_p6 = pro_get(pro_p6, a);
-                    const bool pre = pre_gtab && (ip.p6 != nullptr) == (pre_p6 != nullptr);
-                    if (pre) {
-                        ip.gtab = pre_gtab;
-                        ip.p6 = pre_p6;
-                    }
-                    timed(3, 0.0, 0.0, wp.W->total + 4, 0.0, xpp + opp + 5.0, 4.0 * 19 * 2 * a.C * B, npix, [&] {
-                        if (!pre) {
-                            check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.gtab, B, a.C, st), "ace_gtable");
-                            if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.p6, B, a.C, st), "ace_p6table");
-                        }
-                        check(ace_interior_f32(ip, st), "ace interior");
-                    });
-                }
+    }
+    // the interior pass over the classified level L: elementwise with the per-(sample, label) gamma/beta rows (ace_sparse.h); the route
+    // sets what differs (impl, fill_min, variant, straight-edge tables, overlap and f16 fields)
+    AceInteriorParams interior_params(const AcePlan& p, const AceIO& io, const SparseLevel& L) {
+        AceInteriorParams ip{};
+        fill_mod(ip, p, io);
+        ip.u5 = L.u5;
+        ip.cnt = L.cnt;
+        ip.gtab = m.gtab;
+        return ip;
+    }
+    void interior_edges(AceInteriorParams& ip, const AcePlan& p, const AcePrep& q, const SparseLevel& L) {
+        ip.e16 = L.e16;      // straight-edge pixels served by the interior pass: table row of the code + three column / row sums of the style LUT
+        ip.etab = p.a->edge_tab;
+        ip.p6 = (p.a->styled && q.lut) ? m.p6 : nullptr;
+    }
+    double dense_flops(const AcePlan& p) const { return 2.0 * 2 * p.a->C * HID * 9 * ((double)B * p.r * p.r); }
+
+    // F(4x4,3x3) over every tile of a low-resolution level (conv_wino4.h): nearly every tile holds a boundary pixel there -- no classification,
+    // no interior pass, hidden activations at every pixel
+    void ace_f4(const AcePlan& p, const AcePrep& q, const AceIO& io) {
+        const AceW& a = *p.a;
+        const int r = p.r;
+        const double npix = (double)B * r * r;
+        Wino4AceParams w{};
+        fill_mod(w, p, io);
+        w.actv = q.actv;
+        w.wpk = a.spade_wino4;
+        w.wsty = (a.styled && q.lut) ? m.wsty4 : nullptr;
+        const int nks = w.wsty ? 38 : 32, ktot = 4 * nks;             // (38 / 32 k-steps of four channels)
+        next_flops_exec = 2.0 * 32.0 * ((a.C + 15) / 16) * ktot * 36.0 * npix / 16.0;
+        // 2 C GEMM rows over 128 (+ 20) input planes: the input transform once for all C / 8 row tiles (conv_wino4v.h; K: the buffer's plane count)
+        Wino4vPackParams vp;
+        const bool vroute = m.wino4v_route(wino4v_pays(2 * a.C, r), q.actv, B, r, p.kout, nks, vp, true);
+        timed(1, dense_flops(p), 4.0 * (npix * p.kout + npix * a.C / (io.x_up ? 4.0 : 1.0) + npix * a.C), [&] {
+            if (w.wsty) check(wino4_style_pack(q.lut, m.wsty4, B, a.C, st), "wino4_style_pack");
+            if (vroute) {
+                check(wino4v_pack(vp, st), "hidden activation transform (winograd F(4x4,3x3))");
+                w.v = m.vbuf;
+                check(conv_wino4v_ace(w, st), "spade conv (winograd F(4x4,3x3), every tile, pre-transformed input)");
+            } else
+                check(conv_wino4_ace(w, st), "spade conv (winograd F(4x4,3x3), every tile)");
+        });
+    }
+    // F(2x2,3x3) over the boundary quads of the level (gather or tile mode, conv_wino.h); where the interior reduction serves the level (wp.S),
+    // the interior pixels first, from tables
+    void ace_wino(const AcePlan& p, const WinoPrep& wp, const AcePrep& q, const AceIO& io) {
+        const AceW& a = *p.a;
+        const int r = p.r, x_up = io.x_up;
+        const double npix = (double)B * r * r;
+        const double xpp = 4.0 * a.C / (x_up ? 4.0 : 1.0), opp = 4.0 * a.C;
+        const int ktot = p.kout;
+        if (wp.S) {
+            AceInteriorParams ip = interior_params(p, io, *wp.S);
+            // four pixels per thread (16-byte stores) from 128 pixels of width: 530 -> 420 us on the up-sampled 512^2 launches
+            // (tools/interior_bench.hip); level in the 100 ms step of round 3, measurable in this one
+            ip.impl = r >= 128 ? 2 : 0;
+            ip.groups = m.opt.int_groups;       // (tile4 kernel: channel groups per block, 0 = the launcher's rule; ace_sparse.hip)
+            if (wp.edges) {         // (P6 is built below)
+                if (!a.edge_tab || r < 128) check(hipErrorInvalidValue, "straight-edge marks on a level whose ACE has no table");
+                interior_edges(ip, p, q, *wp.S);
             }
-            WinoAceParams w{};
-            w.actv = q.actv;
-            w.wpk = a.spade_wino;
-            const float* pre_wsty = (a.styled && q.lut) ? pro_get(pro_wsty, a) : nullptr;      // style images from the prologue
-            w.wsty = (a.styled && q.lut) ? (pre_wsty ? pre_wsty : m.wsty) : nullptr;
-            w.out = hout;
-            w.x = x;
-            w.x_up = x_up;
-            w.act = act;
-            w.B = B;
-            w.C = a.C;
-            w.H = r;
-            w.W = r;
-            w.bias_g = a.bias_g;
-            w.bias_b = a.bias_b;
-            w.bn_a = a.bn_a;
-            w.bn_d = a.bn_d;
-            w.nv = a.nv;
-            w.noise = noise + noff;
-            w.noise_bstride = (long long)nf;
-            w.patch = patch_level ? m.patchbuf : nullptr;
-            w.chunk_base = wp.L->chunk_base;
-            w.patch_mode = wp.L->patch_mode;
-            w.qlist = wp.L->qlist;
-            w.TH = wp.L->TH;
-            w.qcnt = wp.L->qcnt;
-            w.work = wp.W->work;
-            w.total = wp.W->total;
-            w.zero = m.zero_page;
-            w.gq = wp.L->gq;
-            w.gq_n = wp.L->gq_n;
-            w.gq_cap = wp.L->gq_cap;
-            w.claim = w.gq ? next_claim() : nullptr;
-            // executed FLOPs = wave tasks x (32 rows x 16 quads x 16 positions x K) x 2; dense = the direct conv over every pixel
-            timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 0.0, wp.W->total + 4, 2.0 * 32 * 16 * 16 * ktot, 4.0 * ktot + xpp + opp,
-                  4.0 * 2.0 * a.C * ktot * 16, npix, [&] {
-                      if (w.wsty && !pre_wsty) check(wino_style_pack(q.lut, m.wsty, B, a.C, st), "wino_style_pack");
-                      check(conv_wino_ace(w, st), "spade conv (winograd, boundary quads)");
-                  });
-            if (overlap && wp.S) check(hipStreamWaitEvent(st, m.ev_int[a.index], 0), "interior done wait");
-            return;
+            // (tile4 kernel, r >= 128: 0 = whole 128-byte lines that hold an interior pixel, ace_sparse.hip; sean.dbg bit 134217728: the
+            //  block rule of rounds 3-5 for A/B)
+            ip.fill_min = (x_up && r < 128) ? 257 : ((r >= 128 && !(m.opt.dbg & 134217728)) ? 0 : 128);
+            if (mode.overlap) {
+                // beside the boundary conv of the same ACE (disjoint output pixels -- so no block may fill its boundary pixels),
+                // on the few CUs of the side stream; the consumer of `out` waits for ev_int below
+                ip.fill_min = 257;
+                ip.quad_only = 1;
+                ip.gtab = m.gtab_side;
+                check(hipEventRecord(m.ev_x[a.index], st), "x ready");
+                check(hipStreamWaitEvent(m.side_int, m.ev_x[a.index], 0), "x ready wait");
+                check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.gtab_side, B, a.C, m.side_int), "ace_gtable");
+                check(ace_interior_f32(ip, m.side_int), "ace interior");
+                check(hipEventRecord(m.ev_int[a.index], m.side_int), "interior done");
+            } else {
+                // tables from the prologue: only when it built exactly what this pass reads (P6 follows the level's straight-edge marks)
+                const bool pre = p.pre_gtab && (ip.p6 != nullptr) == (p.pre_p6 != nullptr);
+                if (pre) {
+                    ip.gtab = p.pre_gtab;
+                    ip.p6 = p.pre_p6;
+                }
+                timed(3, 0.0, 0.0, SpStat{p.W->total + 4, 0.0, xpp + opp + 5.0, 4.0 * 19 * 2 * a.C * B, npix}, [&] {
+                    if (!pre) {
+                        check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.gtab, B, a.C, st), "ace_gtable");
+                        if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.p6, B, a.C, st), "ace_p6table");
+                    }
+                    check(ace_interior_f32(ip, st), "ace interior");
+                });
+            }
         }
+        const SeanModel::WinoLevel& L = *p.L;
+        WinoAceParams w{};
+        fill_mod(w, p, io);
+        w.actv = q.actv;
+        w.wpk = a.spade_wino;
+        const float* pre_wsty = (a.styled && q.lut) ? p.pre_wsty : nullptr;      // style images from the prologue
+        w.wsty = (a.styled && q.lut) ? (pre_wsty ? pre_wsty : m.wsty) : nullptr;
+        w.patch = p.patch ? m.patchbuf : nullptr;
+        w.chunk_base = L.chunk_base;
+        w.patch_mode = L.patch_mode;
+        w.qlist = L.qlist;
+        w.TH = L.TH;
+        w.qcnt = L.qcnt;
+        w.work = p.W->work;
+        w.total = p.W->total;
+        w.zero = m.zero_page;
+        w.gq = L.gq;
+        w.gq_n = L.gq_n;
+        w.gq_cap = L.gq_cap;
+        w.claim = w.gq ? next_claim() : nullptr;
+        // executed FLOPs = wave tasks x (32 rows x 16 quads x 16 positions x K) x 2; dense = the direct conv over every pixel
+        timed(1, dense_flops(p), 0.0, SpStat{p.W->total + 4, 2.0 * 32 * 16 * 16 * ktot, 4.0 * ktot + xpp + opp, 4.0 * 2.0 * a.C * ktot * 16, npix}, [&] {
+            if (w.wsty && !pre_wsty) check(wino_style_pack(q.lut, m.wsty, B, a.C, st), "wino_style_pack");
+            check(conv_wino_ace(w, st), "spade conv (winograd, boundary quads)");
+        });
+        if (mode.overlap && wp.S) check(hipStreamWaitEvent(st, m.ev_int[a.index], 0), "interior done wait");
+    }
+    // the fused ACE conv of the direct routes (conv_mfma.h / conv_sh16.h): every pixel, or the work list the Sparse route adds
+    ConvParams ace_conv_params(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
+        const AceW& a = *pl.a;
         ConvParams p{};
+        fill_mod(p, pl, io);
         p.in = q.actv;
         p.wpk = a.spade_wpk;
-        p.out = hout;
-        p.B = B;
         p.Cin = HID;
-        p.H = r;
-        p.W = r;
         p.Mrows = 2 * a.C;
-        p.x = x;
-        p.x_up = x_up;
-        p.C = a.C;
-        p.bias_g = a.bias_g;
-        p.bias_b = a.bias_b;
-        p.bn_a = a.bn_a;
-        p.bn_d = a.bn_d;
-        p.nv = a.nv;
-        p.noise = noise + noff;
-        p.noise_bstride = (long long)nf;
-        p.lab = lab;
+        p.lab = pl.lab;
         p.lut = q.lut;
         p.lut_rs = q.lut_rs;
         p.lut_ns = q.lut_ns;
         p.lut_bs = q.lut_bs;
-        p.act = act;
         p.pad = -1;
         p.dbg = m.opt.dbg;
         p.terms = m.opt.terms;
         p.wscale = a.spade_wscale;
         p.in_scale_inv = 1.f / a.actv_scale;
         p.out_scale = a.out_scale;
-        const double xin = npix * a.C / (x_up ? 4.0 : 1.0);
         p.out_amax = m.amax_slots + 2 * a.index;
         if ((m.opt.dbg & 256) && a.index == m.opt.dbg_sel) p.partial = m.splitk_ws;      // cycle stamps of this launch (profiling)
         else p.dbg &= ~256;
-        if (sw) {
-            // interior pixels: elementwise with the per-(sample, label) gamma/beta rows; the others: conv over the compacted
-            // boundary pixels (exact-f32 path) / over the tiles that hold a boundary pixel (f16x3 path)
-            const SparseLevel& L = *SL;
-            const double xpp = 4.0 * a.C / (x_up ? 4.0 : 1.0), opp = 4.0 * a.C;
-            AceInteriorParams ip{};
-            ip.x = x;
-            ip.out = hout;
-            ip.u5 = L.u5;
-            ip.cnt = L.cnt;
-            ip.gtab = m.gtab;
-            ip.bn_a = a.bn_a;
-            ip.bn_d = a.bn_d;
-            ip.nv = a.nv;
-            ip.noise = noise + noff;
-            ip.noise_bstride = (long long)nf;
-            ip.B = B;
-            ip.C = a.C;
-            ip.H = r;
-            ip.W = r;
-            ip.x_up = x_up;
-            ip.act = act;
-            ip.out_scale = a.out_scale;
-            ip.out_amax = m.amax_slots + 2 * a.index;
-            ip.bf16 = m.opt.terms == 2;
-            ip.single = (m.opt.use_sh16 && m.opt.terms != 3 && !(m.opt.dbg & 268435456)) ? 1 : 0;      // (dbg bit: A/B)
-            ip.variant = m.opt.use_sh16 ? (compact ? 1 : 0) : (CH_ABL(m.opt.dbg & 65536) ? 1 : (CH_ABL(m.opt.dbg & 1048576) ? 2 : 0));
-            // blocks of 32 x 8 pixels; mostly-interior blocks write every pixel (the conv below overwrites the boundary pixels).
-            // Exact-f32 pass: filling pays only where x is read at full size (measured, tools/interior_bench.hip).
-            // dbg bit 2097152: the row-shaped kernels of the first version (A/B)
-            ip.impl = CH_ABL(m.opt.dbg & 2097152) ? 1 : 0;
-            ip.fill_min = m.opt.use_sh16 ? 128 : (x_up ? 257 : 128);
-            if (m.opt.use_sh16 && compact && lvl_edges[level_of(a.res_div)][sw->TH == 16 ? 1 : 0]) {      // straight-edge pixels served by the interior pass
-                ip.e16 = L.e16;
-                ip.etab = a.edge_tab;
-                ip.p6 = (a.styled && q.lut) ? m.p6 : nullptr;
-            }
-            // (impl 2, four pixels per thread: 10 % ahead at 512^2 in tools/interior_bench.hip, no difference in the generator
-            // step -- 159.7 vs 159.9 images/s -- so the one-pixel kernel stays; dbg bit 16777216 selects it)
-            if (!m.opt.use_sh16 && CH_ABL(m.opt.dbg & 16777216) && r >= 128) {
-                ip.impl = 2;
-                ip.fill_min = 128;
-            }
-            p.sp_list = (m.opt.use_sh16 && !compact) ? nullptr : L.list;      // f16x3: the lists request the compacting kernel
-            p.sp_cnt = L.cnt;
-            p.sp_work = sw->work;
-            p.sp_total = sw->total;
-            p.sp_work2 = sw->work2;
-            p.sp_total2 = sw->total2;
-            p.sp_work3 = sw->work3;
-            timed(3, 0.0, 0.0, sw->total, 0.0, xpp + opp + 5.0, 4.0 * 19 * 2 * a.C * B, npix, [&] {
-                // (the f16x3 LUT is stored pre-multiplied by the ACE output scale)
-                check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, m.opt.use_sh16 ? 1.f / a.out_scale : 1.f,
-                                 m.gtab, B, a.C, st), "ace_gtable");
-                if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f / a.out_scale, m.p6, B, a.C, st), "ace_p6table");
-                check(m.opt.use_sh16 ? ace_interior_sh16(ip, st) : ace_interior_f32(ip, st), "ace interior");
-            });
-            timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 0.0, sw->total, 32.0 * 64 * 2.0 * HID * 9, 4.0 * HID + xpp + opp,
-                  4.0 * 2.0 * a.C * HID * 9, npix, [&] {
-                      if (m.opt.use_sh16) check(conv_sh16_ace(p, st), "spade conv (tiles with boundary pixels)");
-                      else check(conv_ace_sparse(p, L.TH, st), "spade conv (boundary pixels)");
-                  });
-            if (m.opt.use_sh16) {      // second passes: return at once unless the recorded maximum left the f16 window (sh16.h)
-                ip.pass = 1;
-                check(ace_interior_sh16(ip, st), "ace interior (second pass)");
-                p.pass = 1;
-                check(conv_sh16_ace(p, st), "spade conv (second pass)");
-            }
-            return;
+        return p;
+    }
+    double dense_bytes(const AcePlan& p, const AceIO& io) const {
+        const double npix = (double)B * p.r * p.r, xin = npix * p.a->C / (io.x_up ? 4.0 : 1.0);
+        return 4.0 * (npix * HID + xin + npix * p.a->C + 2.0 * p.a->C * HID * 9);
+    }
+    // interior pixels: elementwise with the per-(sample, label) gamma/beta rows; the others: conv over the compacted
+    // boundary pixels (exact-f32 path) / over the tiles that hold a boundary pixel (f16x3 path)
+    void ace_sparse(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
+        const AceW& a = *pl.a;
+        const SparseLevel& L = *pl.SL;
+        const SparseWork* sw = pl.sw;
+        const int r = pl.r, x_up = io.x_up;
+        const bool compact = pl.compact;
+        const double npix = (double)B * r * r;
+        const double xpp = 4.0 * a.C / (x_up ? 4.0 : 1.0), opp = 4.0 * a.C;
+        ConvParams p = ace_conv_params(pl, q, io);
+        AceInteriorParams ip = interior_params(pl, io, L);
+        ip.out_scale = a.out_scale;
+        ip.out_amax = m.amax_slots + 2 * a.index;
+        ip.bf16 = m.opt.terms == 2;
+        ip.single = (m.opt.use_sh16 && m.opt.terms != 3 && !(m.opt.dbg & 268435456)) ? 1 : 0;      // (dbg bit: A/B)
+        ip.variant = m.opt.use_sh16 ? (compact ? 1 : 0) : (CH_ABL(m.opt.dbg & 65536) ? 1 : (CH_ABL(m.opt.dbg & 1048576) ? 2 : 0));
+        // blocks of 32 x 8 pixels; mostly-interior blocks write every pixel (the conv below overwrites the boundary pixels).
+        // Exact-f32 pass: filling pays only where x is read at full size (measured, tools/interior_bench.hip).
+        // dbg bit 2097152: the row-shaped kernels of the first version (A/B)
+        ip.impl = CH_ABL(m.opt.dbg & 2097152) ? 1 : 0;
+        ip.fill_min = m.opt.use_sh16 ? 128 : (x_up ? 257 : 128);
+        if (m.opt.use_sh16 && compact && lvl[pl.k].edges[sw->TH == 16 ? 1 : 0]) interior_edges(ip, pl, q, L);
+        // (impl 2, four pixels per thread: 10 % ahead at 512^2 in tools/interior_bench.hip, no difference in the generator
+        // step -- 159.7 vs 159.9 images/s -- so the one-pixel kernel stays; dbg bit 16777216 selects it)
+        if (!m.opt.use_sh16 && CH_ABL(m.opt.dbg & 16777216) && r >= 128) {
+            ip.impl = 2;
+            ip.fill_min = 128;
         }
-        if (!m.opt.use_sh16 && m.gb_small && !m.opt.batch_inv) {
-            // Tiny levels at small batches (one image at 16 x 16: 16 blocks of the fused kernel, 8 % of the CUs, 200 us): the SPADE conv as a
-            // PLAIN conv over the same packed image -- which splits K over blocks when its grid is small (conv_mfma.h launch_conv) -- into
-            // a scratch of gamma | beta sums, then ace_finish_f32 (style-LUT gathers, biases, modulation).  Same sums per element, the
-            // split-K slabs added in order: deterministic.
-            const int rowsP = ((a.C + 31) / 32) * 64;
-            const long long tiles = ((long long)B * r * r + 255) / 256;
-            if (((rowsP + 127) / 128) * tiles < 128 && (long long)rowsP * B * r * r <= m.gb_small_cap) {
-                ConvParams c = p;
-                c.out = m.gb_small;
-                c.Mrows = rowsP;
-                c.bias = nullptr;
-                c.res = nullptr;
-                c.act = ACT_NONE;
-                c.partial = m.splitk_ws;
-                c.partial_cap = m.splitk_cap;
-                c.dbg &= ~256;
-                timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 4.0 * (npix * HID + xin + npix * a.C + 2.0 * a.C * HID * 9), [&] {
-                    check(conv_plain3(c, st), "spade conv (plain, split-K)");
-                    check(ace_finish_f32(m.gb_small, rowsP, x, x_up, a.bias_g, a.bias_b, a.bn_a, a.bn_d, a.nv, noise + noff, (long long)nf, lab, q.lut,
-                                         static_cast<float*>(hout), B, a.C, r, r, act, st), "ace finish");
-                });
-                return;
-            }
+        p.sp_list = (m.opt.use_sh16 && !compact) ? nullptr : L.list;      // f16x3: the lists request the compacting kernel
+        p.sp_cnt = L.cnt;
+        p.sp_work = sw->work;
+        p.sp_total = sw->total;
+        p.sp_work2 = sw->work2;
+        p.sp_total2 = sw->total2;
+        p.sp_work3 = sw->work3;
+        timed(3, 0.0, 0.0, SpStat{sw->total, 0.0, xpp + opp + 5.0, 4.0 * 19 * 2 * a.C * B, npix}, [&] {
+            // (the f16x3 LUT is stored pre-multiplied by the ACE output scale)
+            check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, m.opt.use_sh16 ? 1.f / a.out_scale : 1.f,
+                             m.gtab, B, a.C, st), "ace_gtable");
+            if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f / a.out_scale, m.p6, B, a.C, st), "ace_p6table");
+            check(m.opt.use_sh16 ? ace_interior_sh16(ip, st) : ace_interior_f32(ip, st), "ace interior");
+        });
+        timed(1, dense_flops(pl), 0.0, SpStat{sw->total, 32.0 * 64 * 2.0 * HID * 9, 4.0 * HID + xpp + opp, 4.0 * 2.0 * a.C * HID * 9, npix}, [&] {
+            if (m.opt.use_sh16) check(conv_sh16_ace(p, st), "spade conv (tiles with boundary pixels)");
+            else check(conv_ace_sparse(p, L.TH, st), "spade conv (boundary pixels)");
+        });
+        if (m.opt.use_sh16) {      // second passes: return at once unless the recorded maximum left the f16 window (sh16.h)
+            ip.pass = 1;
+            check(ace_interior_sh16(ip, st), "ace interior (second pass)");
+            p.pass = 1;
+            check(conv_sh16_ace(p, st), "spade conv (second pass)");
         }
-        timed(1, 2.0 * 2 * a.C * HID * 9 * npix, 4.0 * (npix * HID + xin + npix * a.C + 2.0 * a.C * HID * 9), [&] {
+    }
+    // Tiny levels at small batches (one image at 16 x 16: 16 blocks of the fused kernel, 8 % of the CUs, 200 us): the SPADE conv as a
+    // PLAIN conv over the same packed image -- which splits K over blocks when its grid is small (conv_mfma.h launch_conv) -- into
+    // a scratch of gamma | beta sums, then ace_finish_f32 (style-LUT gathers, biases, modulation).  Same sums per element, the
+    // split-K slabs added in order: deterministic.
+    void ace_tiny(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
+        const AceW& a = *pl.a;
+        const int r = pl.r, rowsP = ((a.C + 31) / 32) * 64;
+        ConvParams c = ace_conv_params(pl, q, io);
+        c.out = m.gb_small;
+        c.Mrows = rowsP;
+        c.act = ACT_NONE;
+        c.partial = m.splitk_ws;
+        c.partial_cap = m.splitk_cap;
+        c.dbg &= ~256;
+        timed(1, dense_flops(pl), dense_bytes(pl, io), [&] {
+            check(conv_plain3(c, st), "spade conv (plain, split-K)");
+            check(ace_finish_f32(m.gb_small, rowsP, io.x, io.x_up, a.bias_g, a.bias_b, a.bn_a, a.bn_d, a.nv, io.noise, io.nf, pl.lab, q.lut,
+                                 io.out, B, a.C, r, r, io.act, st), "ace finish");
+        });
+    }
+    void ace_dense(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
+        ConvParams p = ace_conv_params(pl, q, io);
+        timed(1, dense_flops(pl), dense_bytes(pl, io), [&] {
             if (!m.opt.use_sh16) {
                 check(conv_ace(p, st), "spade conv");
                 return;
@@ -1912,17 +1835,11 @@ struct Runner {
             q.split = m.opt.wino4_split;
             next_flops_exec = 2.0 * w.Cout * w.Cin * 36.0 * npix / 16.0;
             // many GEMM rows on a small level: the input transform once, in its own pass, instead of in every row tile (conv_wino4v.h)
-            const bool vroute = m.opt.wino4v && wino4v_pays(w.Cout, r) && m.wino4v_fits(B, r, w.Cin / 4);
+            Wino4vPackParams vp;
+            const bool vroute = m.wino4v_route(wino4v_pays(w.Cout, r), in, B, r, w.Cin, w.Cin / 4, vp);
             timed(0, 2.0 * w.Cout * w.Cin * 9.0 * npix,
                   4.0 * (npix * w.Cin + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * w.Cin * 36.0), [&] {
                       if (vroute) {
-                          Wino4vPackParams vp{};
-                          vp.in = in;
-                          vp.v = m.vbuf;
-                          vp.B = B;
-                          vp.K = w.Cin;
-                          vp.H = vp.W = vp.pitch = r;
-                          vp.nks = w.Cin / 4;
                           check(wino4v_pack(vp, st), "conv input transform (winograd F(4x4,3x3))");
                           q.v = m.vbuf;
                           check(conv_wino4v_plain(q, st), "conv (winograd F(4x4,3x3), pre-transformed input)");
@@ -2013,9 +1930,10 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
     };
     for (int bo = 0; bo < Btot; bo += max_batch) {
         const int B = std::min(max_batch, Btot - bo);
-        Runner R(*this, st, B, S);
-        if (claim_pool) R.check(hipMemsetAsync(claim_pool, 0, (size_t)CLAIM_SLOTS * CLAIM_WORDS * sizeof(unsigned), st), "claim counters");
         const uint8_t* lab = labels + (size_t)bo * S * S;
+        Runner R(*this, st, B, S, lab);
+        const ChunkMode& mode = R.mode;
+        if (claim_pool) R.check(hipMemsetAsync(claim_pool, 0, (size_t)CLAIM_SLOTS * CLAIM_WORDS * sizeof(unsigned), st), "claim counters");
         const float* cd = codes + (size_t)bo * LABEL_NC * STYLE;
         const float* nz;
         if (noise) {
@@ -2026,34 +1944,24 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
         }
         for (int k = 1; k <= 5; ++k) R.check(label_downsample(lab, lab_r[k], B, S, S >> k, st), "label_downsample");
         if (opt.use_sh16) R.check(hipMemsetAsync(amax_slots, 0, 64 * sizeof(unsigned), st), "amax slots");
-        if (fcmu_batched && !opt.use_sh16) {
-            if (B * LABEL_NC > 64 || opt.batch_inv) {     // (smaller batches take the GEMV branch of ace_prepare, which projects per ACE)
-                // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout)
-                const bool grouped = lut_groups && lut_ngroups > 0;
-                R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, ((B * LABEL_NC + 31) / 32) * 32, LABEL_NC, 1.f,
-                                      nullptr, 0, 0, st, grouped ? 2 : 0), "fc_mu (all ACEs)");
-                if (grouped) R.luts_grouped();
-            }
-        } else if (fcmu_batched) {
+        if (mode.project_all) {     // (smaller batches take the GEMV branch of Runner::build_lut, which projects per ACE)
+            // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout)
+            R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, ((B * LABEL_NC + 31) / 32) * 32, LABEL_NC, 1.f,
+                                  nullptr, 0, 0, st, mode.grouped ? 2 : 0), "fc_mu (all ACEs)");
+            if (mode.grouped) R.luts_grouped();
+        } else if (fcmu_batched && opt.use_sh16) {
             const int npad_c = ((B * (LABEL_NC + 1) + 31) / 32) * 32;
             for (int pass = 0; pass < 2; ++pass)         // second pass: returns at once unless a projection left the f16 window
                 R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, npad_c, LABEL_NC + 1, SH16_ACT_SCALE,
                                       amax_slots, pass, opt.terms == 2, st), "fc_mu (all ACEs)");
         }
         // interactive-size jobs: everything that depends on labels / codes only runs ahead on the side stream
-        if (side && !prof_on && !(opt.dbg & 4096)) {
-            const bool ov = overlap_on && (long long)B * S * S > ahead_limit && R.luts_ready;
-            if (ov) {      // large job on an overlap handle: label tables of every ACE ahead on the CU-masked side stream, interior passes beside the convs
-                R.prepass(lab);
-                R.overlap = gtab_side != nullptr;
-                R.prepare_all_ahead(lab, cd, true);
-            } else if (ahead_full && (long long)B * S * S <= ahead_limit) R.prepare_all_ahead(lab, cd, true);
-            // large jobs: only the style LUT builds (small, latency-bound GEMMs) run ahead, in the tails of the conv kernels
-            // (exact-f32 path, B = 16 at 512^2: 147.2 -> 148.3 images/s)
-            else if ((fcmu_batched || !opt.use_sh16) && !(opt.dbg & 8192) && !R.luts_ready) R.prepare_all_ahead(lab, cd, false);
-        }
+        // (chunk_mode; large jobs run only the style LUT builds -- small, latency-bound GEMMs -- ahead, in the tails of the conv kernels: exact-f32
+        // path, B = 16 at 512^2: 147.2 -> 148.3 images/s)
+        if (mode.prepass) R.prepass();
+        if (mode.ahead != ChunkMode::NONE) R.prepare_all_ahead(cd);
         // large chunks: the label / code-only products of the ACEs from grouped launches, ahead of the first conv (no tap reads any of them)
-        R.prologue(lab);
+        if (mode.prologue) R.prologue();
 
         const int sw = S / 32;
         float* x = xa;
@@ -2070,7 +1978,7 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             int sc_up;
             bool fuse_s = false;
             if (b.learned) {
-                R.ace(b.ace_s, lab, cd, nz, nf, noff, xsrc, up, ACT_NONE, hs);
+                R.ace(b.ace_s, cd, nz, nf, noff, xsrc, up, ACT_NONE, hs);
                 noff += rr;
                 R.tap_sh16(b.name + ".hs", hs, b.fin, rr, b.ace_s);
                 // the 1x1 shortcut conv is folded into conv_1 (extra K chunks on a second input) unless a test taps its output
@@ -2086,12 +1994,12 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
                 shortcut = xsrc;
                 sc_up = up;
             }
-            R.ace(b.ace_0, lab, cd, nz, nf, noff, xsrc, up, ACT_LRELU, h0);
+            R.ace(b.ace_0, cd, nz, nf, noff, xsrc, up, ACT_LRELU, h0);
             noff += rr;
             R.tap_sh16(b.name + ".h0", h0, b.fin, rr, b.ace_0);
             R.conv(b.conv_0, h0, b.ace_0, dx, r, nullptr, 0);
             R.tap_c4(b.name + ".dx", dx, b.fmid, rr);
-            R.ace(b.ace_1, lab, cd, nz, nf, noff, dx, 0, ACT_LRELU, h1);
+            R.ace(b.ace_1, cd, nz, nf, noff, dx, 0, ACT_LRELU, h1);
             noff += rr;
             R.tap_sh16(b.name + ".h1", h1, b.fmid, rr, b.ace_1);
             R.conv(b.conv_1, h1, b.ace_1, y, r, shortcut, sc_up, fuse_s ? &b.conv_s : nullptr, fuse_s ? hs : nullptr, fuse_s ? &b.ace_s : nullptr);
@@ -2269,15 +2177,8 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
                 q.reflect = 1;
                 q.wpk_split = z14_wino4s;
                 q.split = opt.wino4_split;
-                if (opt.wino4v && wino4v_fits(B, h2, 64)) {          // 512 GEMM rows: the (reflected) input transform in its own pass
-                    Wino4vPackParams vp{};
-                    vp.in = hs;
-                    vp.v = vbuf;
-                    vp.B = B;
-                    vp.K = 256;
-                    vp.H = vp.W = vp.pitch = h2;
-                    vp.nks = 64;
-                    vp.reflect = 1;
+                Wino4vPackParams vp;
+                if (wino4v_route(true, hs, B, h2, 256, 64, vp, false, true)) {          // 512 GEMM rows: the (reflected) input transform in its own pass
                     ck(wino4v_pack(vp, st), "zenc conv5 input transform");
                     q.v = vbuf;
                     ck(conv_wino4v_plain(q, st), "zenc conv5 (winograd F(4x4,3x3), pre-transformed input)");
@@ -2318,6 +2219,82 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
     return "";
 }
 
-bool SeanModel::wino4v_fits(int Bn, int r, int nks) const { return vbuf && r % 32 == 0 && wino4v_bytes(Bn, r, r, nks) <= vbuf_bytes; }
+bool SeanModel::wino4v_route(bool pays, const float* in, int Bn, int r, int K, int nks, Wino4vPackParams& vp, bool padded, bool reflect) const {
+    if (!(opt.wino4v && pays && vbuf && r % 32 == 0 && wino4v_bytes(Bn, r, r, nks) <= vbuf_bytes)) return false;
+    vp = Wino4vPackParams{};
+    vp.in = in;
+    vp.v = vbuf;
+    vp.B = Bn;
+    vp.K = K;
+    vp.H = vp.W = r;
+    vp.nks = nks;
+    vp.pitch = padded ? wino_apitch(r) : r;
+    vp.xoff = padded ? WINO_AXOFF : 0;
+    vp.padded = padded ? 1 : 0;
+    vp.reflect = reflect ? 1 : 0;
+    return true;
+}
+
+// ---- routes and modes: host decisions only ----------------------------------------------------------------------------------------
+// The Winograd ACE routes need the level's quad lists and the task list of this row-tile count, sized at build time (they exist where
+// (max_size >> k) % 32 == 0; a smaller S can reach a 32-grid level that max_size does not have, e.g. max_size = 96, S = 64 -- ADVICE r04);
+// else the ACE takes the direct kernels and their [B][128][H][W] layout
+const SeanModel::WinoWork* SeanModel::wino_work(const AceW& a, int r) const {
+    if (!(opt.wino && !opt.use_sh16 && a.spade_wino && r >= 32 && r % 32 == 0)) return nullptr;
+    const WinoLevel& L = wq_level[level_of(a.res_div)];
+    if (!L.qlist) return nullptr;
+    for (const auto& w : L.works)
+        if (w.nrt == (a.C + 15) / 16) return &w;
+    return nullptr;
+}
+const SparseWork* SeanModel::sparse_work(const AceW& a, int r) const {
+    if (!opt.sparse || r < opt.sparse_min_r || r < 32) return nullptr;
+    const int k = level_of(a.res_div);
+    for (const auto& w : sp_work[k])
+        if (w.mtiles == (a.C + 31) / 32) return sp_level[k][w.TH == 16 ? 1 : 0].u5 ? &w : nullptr;
+    return nullptr;
+}
+AceRoute SeanModel::ace_route_shape(const AceW& a, int r) const {
+    if (wino_work(a, r)) {
+        // F(4x4,3x3) over every tile: the low-resolution levels, where nearly every tile holds a boundary pixel
+        const bool f4 = opt.wino >= 2 && a.spade_wino4 && r <= opt.wino4_ace_max_r && wino4_ace_supported(r, r, a.C) && (!a.styled || wsty4);
+        return f4 ? AceRoute::F4 : AceRoute::WinoQuads;
+    }
+    return sparse_work(a, r) ? AceRoute::Sparse : AceRoute::Dense;
+}
+AceRoute SeanModel::ace_route(const AceW& a, int r, int B) const {
+    const AceRoute s = ace_route_shape(a, r);
+    if (s == AceRoute::F4)      // (few tasks per CU -- single images -- : the gather kernel)
+        return (opt.wino4_force || opt.batch_inv || wino4_pays((long long)B * (r / 32) * (r / 32) * ((a.C + 15) / 16), num_cus)) ? s : AceRoute::WinoQuads;
+    if (s == AceRoute::Sparse && opt.use_sh16) {      // tile-skip mode: honoured by the wave-specialised kernel only (conv_sh16.h)
+        ConvParams t{};
+        t.C = a.C;
+        t.W = t.H = r;
+        t.B = B;
+        t.Cin = HID;
+        t.dbg = opt.dbg;
+        return sh16_ace_uses_ws(t) ? s : AceRoute::Dense;
+    }
+    if (s == AceRoute::Dense && !opt.use_sh16 && gb_small && !opt.batch_inv) {      // tiny levels at small batches (Runner::ace_tiny)
+        const int rowsP = ((a.C + 31) / 32) * 64;
+        const long long tiles = ((long long)B * r * r + 255) / 256;
+        if (((rowsP + 127) / 128) * tiles < 128 && (long long)rowsP * B * r * r <= gb_small_cap) return AceRoute::TinySplitK;
+    }
+    return s;
+}
+SeanModel::ChunkMode SeanModel::chunk_mode(int B, int S) const {
+    ChunkMode c;
+    const bool large = (long long)B * S * S > ahead_limit;
+    c.project_all = fcmu_batched && !opt.use_sh16 && (B * LABEL_NC > 64 || opt.batch_inv);
+    c.grouped = c.project_all && lut_groups && lut_ngroups > 0;
+    // interactive-size jobs: everything that depends on labels / codes only runs ahead on the side stream
+    const bool side_ok = side && !prof_on && !(opt.dbg & 4096);
+    c.prepass = side_ok && overlap_on && large && c.grouped;      // large job on an overlap handle
+    c.overlap = c.prepass && gtab_side;
+    if (c.prepass || (side_ok && ahead_full && !large)) c.ahead = ChunkMode::FULL;
+    else if (side_ok && (fcmu_batched || !opt.use_sh16) && !(opt.dbg & 8192) && !c.grouped) c.ahead = ChunkMode::LUTS;
+    c.prologue = pro_on && !prof_on && c.ahead != ChunkMode::FULL && large;
+    return c;
+}
 
 }  // namespace chk

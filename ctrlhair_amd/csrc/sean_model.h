@@ -12,6 +12,7 @@
 #include "net_common.h"
 
 namespace chk {
+struct Wino4vPackParams;      // conv_wino4v.h
 
 struct ConvW {
     float* wpk = nullptr;
@@ -80,6 +81,14 @@ inline int level_of(int res_div) {
     while ((1 << k) < res_div) ++k;
     return k;
 }
+
+enum class AceRoute {      // the route of one ACE (SeanModel::ace_route): decided once per chunk (sean_model.cpp AcePlan), read everywhere else
+    F4,          // SPADE conv as F(4x4,3x3) over every tile of a low-resolution level (conv_wino4.h)
+    WinoQuads,   // F(2x2,3x3) over the boundary quads, gather or tile mode (conv_wino.h), interior pixels from tables (ace_sparse.h)
+    Sparse,      // direct conv over the boundary pixels: exact-f32 compacted kernel / f16x3 wave-specialised kernel
+    TinySplitK,  // exact f32, tiny levels at small batches: plain split-K conv into gb_small + ace_finish_f32
+    Dense        // every pixel through the fused ACE conv
+};
 
 // Everything ch_set_option writes (ch_api.cpp holds the table of keys).  build() and the forward passes only read these.
 struct SeanOptions {
@@ -228,9 +237,23 @@ struct SeanModel {
     float* wsty4 = nullptr;                    // per-sample F(4x4,3x3) style images of the ACE being run (conv_wino4.h)
     float* vbuf = nullptr;                     // the pre-transformed input V of the layer being run (conv_wino4v.h)
     size_t vbuf_bytes = 0;
-    bool wino4v_fits(int Bn, int r, int nks) const;      // sean_model.cpp
+    // the V route of one F(4x4,3x3) layer (sean_model.cpp): taken when it `pays` (wino4v_pays) and V fits vbuf; then vp is the transform pass over `in`
+    // (padded: hidden planes of an ACE level, conv_wino.h WINO_AXOFF; reflect: reflection padding)
+    bool wino4v_route(bool pays, const float* in, int Bn, int r, int K, int nks, Wino4vPackParams& vp, bool padded = false, bool reflect = false) const;
+    const WinoWork* wino_work(const AceW& a, int r) const;        // task list of the ACE's row tiles on its Winograd level; nullptr: no Winograd route at r
+    const SparseWork* sparse_work(const AceW& a, int r) const;    // work list of the ACE's row tiles on its sparse level; nullptr: not served at r
+    AceRoute ace_route_shape(const AceW& a, int r) const;         // from shape, weights and options: F4 / WinoQuads / Sparse / Dense (build() sizes buffers by it)
+    AceRoute ace_route(const AceW& a, int r, int B) const;        // ... and the task count of the call: F4 may fall to WinoQuads, f16x3 Sparse to Dense, Dense to TinySplitK
+    // How one chunk of B samples at S pixels runs on this handle (decided once, by chunk_mode; generate() and the Runner read it)
+    struct ChunkMode {
+        bool project_all = false, grouped = false;      // exact f32, more than 64 (sample, label) columns: the style projections of every styled ACE from one launch; ... feeding ONE grouped LUT GEMM
+        enum Ahead { NONE, LUTS, FULL } ahead = NONE;      // run-ahead on the side stream: nothing / the style LUT builds / LUTs and label tables
+        bool prepass = false, overlap = false;      // overlap handle, large chunk: level geometry up front, label tables ahead on the CU-masked side stream; ... and interior passes on side_int
+        bool prologue = false;         // grouped launches of the label / code-only products ahead of the first conv (Runner::prologue)
+    };
+    ChunkMode chunk_mode(int B, int S) const;
     // ACE prologue (option "sean.prologue", Runner::prologue): per-ACE destinations of the grouped launches, sized by the route the ACE takes at
-    // (max_batch, max_size) -- F(4x4) route (32 / 64 pixels): its own padded hidden planes; gather route (128 pixels and more): its own gamma / beta
+    // (max_batch, max_size), SeanModel::ace_route_shape -- F(4x4) route (32 / 64 pixels): its own padded hidden planes; gather route (128 pixels and more): its own gamma / beta
     // table, column / row sums and F(2x2) style images.  nullptr: the ACE keeps its inline launches and the shared buffers above.
     bool pro_on = false;
     std::vector<float*> pro_actv, pro_gtab, pro_p6, pro_wsty;

@@ -1,5 +1,5 @@
-"""GPU tests of the ACE prologue (option sean.prologue, ctrlhair_amd/csrc/sean_model.cpp Runner::prologue): on handles beyond the run-ahead
-sizes the label / code-only products of the ACEs -- hidden planes of the F(4x4)-route ACEs, gamma / beta tables, column / row sums and style
+"""GPU tests of the ACE prologue (option sean.prologue, ctrlhair_amd/csrc/sean_model.cpp Runner::prologue, run where SeanModel::chunk_mode
+says so, over the routes of Runner::plan_aces): on handles beyond the run-ahead sizes the label / code-only products of the ACEs -- hidden planes of the F(4x4)-route ACEs, gamma / beta tables, column / row sums and style
 images of the gather-route ACEs -- come from grouped launches at the start of a chunk, into per-ACE buffers.  The prologue reorders launches
 and moves buffers; it changes no arithmetic, so every case asserts torch.equal(sean.prologue = 1, sean.prologue = 0).
 
