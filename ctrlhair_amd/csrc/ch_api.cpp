@@ -601,6 +601,37 @@ int ch_sweep_stats(ch_handle* h, const void* img, int kind, const uint8_t* label
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_sweep_stats: ") + hipGetErrorString(e));
 }
 
+// ---- PNG encoding (png_encode.hip) -----------------------------------------------------------------------------------------------
+namespace {
+bool png_dims_ok(int H, int W, int C) {
+    return (C == 1 || C == 3 || C == 4) && H >= 1 && W >= 1 && H <= 32768 && W <= 32768 && (int64_t)H * W <= (1 << 30);
+}
+}  // namespace
+
+int ch_png_chunk_bytes(void) { return chk::PNG_CHUNK; }
+
+size_t ch_png_zlib_bound(int H, int W, int C) { return png_dims_ok(H, W, C) ? chk::png_zlib_bound(H, W, C) : 0; }
+
+size_t ch_png_encode_workspace_bytes(int N, int H, int W, int C) {
+    return (N >= 1 && N <= 65535 && png_dims_ok(H, W, C)) ? chk::png_encode_workspace_bytes(N, H, W, C) : 0;
+}
+
+int ch_png_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes, void* workspace,
+                  size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!img || !out || !sizes || !workspace) return fail(h, CH_ERR_ARG, "ch_png_encode: null pointer");
+    if (C != 1 && C != 3 && C != 4) return fail(h, CH_ERR_ARG, "ch_png_encode: C must be 1, 3 or 4");
+    if (filter < -1 || filter > 4) return fail(h, CH_ERR_ARG, "ch_png_encode: filter must be -1 (adaptive) or 0..4");
+    if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, "ch_png_encode: N outside 1..65535");
+    if (!png_dims_ok(H, W, C)) return fail(h, CH_ERR_ARG, "ch_png_encode: image too small or too large (sides 1..32768, H * W <= 2^30)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, "ch_png_encode: workspace not 16-byte aligned");
+    if (workspace_bytes < chk::png_encode_workspace_bytes(N, H, W, C))
+        return fail(h, CH_ERR_ARG, "ch_png_encode: workspace smaller than ch_png_encode_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::png_encode(img, N, H, W, C, filter, out, sizes, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_png_encode: ") + hipGetErrorString(e));
+}
+
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {
     if (!h || !name) return CH_ERR_ARG;
     if (dev_ptr) h->sean.taps[name] = dev_ptr;

@@ -251,4 +251,11 @@ size_t style_medoid_workspace_bytes(const int64_t* seg_offsets, int R, int n_spl
 hipError_t style_medoid(const float* codes, const int64_t* seg_offsets, int R, int dim, int n_split, int* index, double* sums, float* mean,
                         void* ws, hipStream_t s);
 
+// png_encode.hip: N uint8 images [N,H,W,C] -> N complete zlib streams of their PNG-filtered bytes (row filters, chunk-wise deflate with
+// distance-1 matches and a dynamic Huffman code per chunk, gather + Adler-32).  See ch_png_encode in ctrlhair_hip.h.
+constexpr int PNG_CHUNK = 32768;              // == ch_png_chunk_bytes(): bytes of the filtered stream one workgroup deflates
+size_t png_zlib_bound(int H, int W, int C);
+size_t png_encode_workspace_bytes(int N, int H, int W, int C);
+hipError_t png_encode(const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes, void* ws, hipStream_t s);
+
 }  // namespace chk

@@ -16,7 +16,7 @@ On-disk formats are the reference's:
   rgb_stat_dict.pkl, color_var_stat_dict.pkl   the merged dicts;  hsv_stat_dict_ordered.pkl   uint8 [N,3] table of the colour
                                         sliders (script_get_rgb_hsv_label.py:70-90; load with hostutil.DistTranslation(root=<root>))
 
-    python -m ctrlhair_amd.dataset masks    <root> <dataset> [--batch 16]
+    python -m ctrlhair_amd.dataset masks    <root> <dataset> [--batch 16] [--png host|device]
     python -m ctrlhair_amd.dataset codes    <root> <dataset> [--batch 16]
     python -m ctrlhair_amd.dataset rgb      <root> <dataset> [--batch 16]     (no network weights: ctrlhair_amd.colorstats)
     python -m ctrlhair_amd.dataset colorvar <root> <dataset> [--batch 16]
@@ -51,6 +51,8 @@ On-disk formats are the reference's:
                                            candidates are sharded over ranks: ctrlhair_amd.directions)
     python -m ctrlhair_amd.dataset use-direction <out> <att> <index> <used-dir>
                                           (copy candidate <index> of that search into the used set under the next free name)
+    (masks, crop, uncrop and directions take --png host|device: 'device' encodes their PNG files with ch_png_encode,
+     ctrlhair_amd.pngenc, instead of downloading the pixels for Pillow; the pixels are the same, the file bytes are not)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -113,19 +115,36 @@ def write_label_png(path: str, label: np.ndarray) -> None:
 
 
 # ---- batched drivers (HairEditor on the HIP library) -----------------------------------------------------------------
+def _png_encoder(png: str, owner):
+    """None for png='host'; for 'device' the device encoder (pngenc.PngEncoder) on `owner`'s handle and device.  The option names who
+    writes PNG files: a file of another format (a .jpg name of the crop jobs) is Pillow's either way."""
+    from .pngenc import PngEncoder, check_png_mode
+    return PngEncoder(owner.handle, owner.device) if check_png_mode(png) == 'device' else None
+
+
+def _is_png(name: str) -> bool:
+    return name.lower().endswith('.png')
+
+
 def extract_masks(editor, img_dir: str, label_dir: str, batch: int = 16, rank: int = 0, world: int = 1,
-                  parse_size: int = 512) -> List[str]:
+                  parse_size: int = 512, png: str = 'host') -> List[str]:
     """BiSeNet-parse every image of `img_dir` (this rank's shard) and write `label_dir/<name>.png`.
-    Per image identical to FaceParsing.parsing_img + swap_parsing_label_to_celeba_mask (my_parsing_util.py:31-54)."""
+    Per image identical to FaceParsing.parsing_img + swap_parsing_label_to_celeba_mask (my_parsing_util.py:31-54).
+    png='device': the label maps of a batch are encoded on the device in one call (the same pixels in another file)."""
     import torch
     from PIL import Image
     os.makedirs(label_dir, exist_ok=True)
     fp = editor.face_parsing
+    encoder = _png_encoder(png, fp)
     done = []
     for names in batches(shard(list_images(img_dir), rank, world), batch):
         x = torch.cat([fp.normalise(np.asarray(Image.fromarray(read_rgb(os.path.join(img_dir, n)))
                                                .resize((parse_size, parse_size), Image.BILINEAR))) for n in names], dim=0)
         labels, _ = fp.parse_tensor(x)                       # uint8 [B,512,512], CelebAMask-HQ ids
+        if encoder is not None:
+            encoder.write([os.path.join(label_dir, os.path.splitext(n)[0] + '.png') for n in names], labels)
+            done += names
+            continue
         labels = labels.cpu().numpy()
         for n, lab in zip(names, labels):
             write_label_png(os.path.join(label_dir, os.path.splitext(n)[0] + '.png'), lab)
@@ -240,12 +259,13 @@ def find_landmarks(landmarks: Dict[str, np.ndarray], dataset: str, file_name: st
 
 
 def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = 256, rank: int = 0,
-               world: int = 1):
+               world: int = 1, png: str = 'host'):
     """dataset_scripts/script_crop.py:36-54 for this rank's shard of `src_dir`: align every photo that has landmarks
     (`aligner`: alignment.FaceAligner) and write it to `out_dir/<name>`.  Returns (done, skipped): the file names written and the
-    ones without a landmark entry, which are reported and left out."""
+    ones without a landmark entry, which are reported and left out.  png='device': .png names are encoded on the device."""
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
+    encoder = _png_encoder(png, aligner)
     done, skipped = [], []
     for n in shard(list_images(src_dir), rank, world):
         lm = find_landmarks(landmarks, dataset, n)
@@ -254,6 +274,10 @@ def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dic
             skipped.append(n)
             continue
         crop, _ = aligner.align(read_rgb(os.path.join(src_dir, n)), lm[:68], size)
+        if encoder is not None and _is_png(n):
+            encoder.write([os.path.join(out_dir, n)], crop[None])
+            done.append(n)
+            continue
         crop = crop.cpu().numpy() if hasattr(crop, 'cpu') else np.asarray(crop)
         Image.fromarray(crop).save(os.path.join(out_dir, n))
         done.append(n)
@@ -274,17 +298,19 @@ def label_weight(label_path: str, S: int) -> np.ndarray:
 
 
 def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = None,
-                 rank: int = 0, world: int = 1, label_dir: str = None, matte=None):
+                 rank: int = 0, world: int = 1, label_dir: str = None, matte=None, png: str = 'host'):
     """The inverse of crop_faces for this rank's shard of `photo_dir`: paste the edited crop `edit_dir/<name>` back into the photo
     `photo_dir/<name>` it was aligned from (same landmarks, same file names) and write the photo-sized result to `out_dir/<name>`.
     size: the crops' side (default: each edit's own).  label_dir: per-image weight from `label_dir/<stem>.png` (hair = 255); matte
     (True or a dict, alignment.matte_params; needs label_dir): that weight refined by a guided filter of the photo.  Returns
-    (done, skipped); a photo without landmarks, without an edit or (with label_dir) without a label map is reported and left out."""
+    (done, skipped); a photo without landmarks, without an edit or (with label_dir) without a label map is reported and left out.
+    png='device': .png names are encoded on the device (the photo-sized result is never downloaded)."""
     from PIL import Image
     from .alignment import align_plan
     if matte is not None and label_dir is None:
         raise ValueError('matte refines a weight map: it needs label_dir')
     os.makedirs(out_dir, exist_ok=True)
+    encoder = _png_encoder(png, aligner)
     done, skipped = [], []
     for n in shard(list_images(photo_dir), rank, world):
         lm = find_landmarks(landmarks, dataset, n)
@@ -306,7 +332,10 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
             out = aligner.paste_back(photo, edit, plan)[0]
         else:
             out = aligner.paste_back(photo, edit, plan, weight=label_weight(label, S), matte=matte)[0]
-        Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n))
+        if encoder is not None and _is_png(n):
+            encoder.write([os.path.join(out_dir, n)], out[None])
+        else:
+            Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n))
         done.append(n)
     return done, skipped
 
@@ -453,6 +482,7 @@ def _main_directions(argv):
                                                      'W ranks write up to W * K sheets')
     ap.add_argument('--list', default=None, help='file with the image names to use, one per line')
     ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
     args = ap.parse_args(argv)
     import torch
     from . import directions as DS
@@ -474,7 +504,7 @@ def _main_directions(argv):
     search = DS.DirectionSearch(pipe, imgs, noise_seed=args.noise_seed)
     recs = DS.find_directions(search, args.att, DS.load_used(args.used_dir), args.out, n=args.n,
                               values=np.linspace(-args.max_val, args.max_val, args.values), seed=args.seed, rank=rank, world=world,
-                              sheets=args.sheets, cell=args.cell)
+                              sheets=args.sheets, cell=args.cell, png=args.png)
     if dist is not None:
         dist.barrier()
     if rank == 0:
@@ -524,6 +554,7 @@ def main(argv=None):
     ap.add_argument('--img-size', type=int, default=256)
     ap.add_argument('--weights', default='reference', help="'reference' (the Google-Drive checkpoints under the reference's "
                                                            "paths) or 'procedural'")
+    ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
     args = ap.parse_args(argv)
     import torch
     from .hair_editor import HairEditor
@@ -551,7 +582,7 @@ def main(argv=None):
         return
     he = HairEditor(True, True, weights=args.weights, device=local, img_size=args.img_size, max_batch=args.batch)
     if args.job == 'masks':
-        n = len(extract_masks(he, os.path.join(base, 'images_256'), os.path.join(base, 'label'), args.batch, rank, world))
+        n = len(extract_masks(he, os.path.join(base, 'images_256'), os.path.join(base, 'label'), args.batch, rank, world, png=args.png))
     else:
         code_dir = os.path.join(args.root, 'hair_info_all_dataset', 'sean_code')
         n = len(encode_sean_codes(he, os.path.join(base, 'images_256'), os.path.join(base, 'label'), code_dir, args.dataset,
@@ -573,6 +604,7 @@ def _main_crop(argv):
     ap.add_argument('dataset')
     ap.add_argument('--landmarks', required=True, help='.npz or pickled dict: image name -> [68,2] pixel landmarks')
     ap.add_argument('--size', type=int, default=256)
+    ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
     args = ap.parse_args(argv)
     import torch
     from . import lib
@@ -581,7 +613,7 @@ def _main_crop(argv):
     torch.cuda.set_device(local)
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = crop_faces(aligner, args.src_dir, os.path.join(args.root, args.dataset, 'images_256'), args.dataset,
-                               load_landmarks(args.landmarks), args.size, rank, world)
+                               load_landmarks(args.landmarks), args.size, rank, world, png=args.png)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} without landmarks')
 
 
@@ -598,6 +630,7 @@ def _main_uncrop(argv):
     ap.add_argument('--matte', action='store_true', help='refine the hair region with a guided filter of the photo (needs --labels)')
     ap.add_argument('--matte-radius', type=int, default=None, help='matte window radius in photo pixels, 1..64 (default: 4 crop pixels)')
     ap.add_argument('--matte-eps', type=float, default=None, help='matte regularisation (default 1e-4)')
+    ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
     args = ap.parse_args(argv)
     matte = None
     if args.matte or args.matte_radius is not None or args.matte_eps is not None:
@@ -616,7 +649,7 @@ def _main_uncrop(argv):
     torch.cuda.set_device(local)
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = uncrop_faces(aligner, args.photos, args.edits, args.out, args.dataset, load_landmarks(args.landmarks), args.size,
-                                 rank, world, label_dir=args.labels, matte=matte)
+                                 rank, world, label_dir=args.labels, matte=matte, png=args.png)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
 
 

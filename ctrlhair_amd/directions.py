@@ -354,13 +354,17 @@ def parse_sheets(spec: str):
 
 
 def find_directions(search: DirectionSearch, att: str, existing: Sequence, out_dir: str, n: int = 300, values=None, seed: int = 0,
-                    rank: int = 0, world: int = 1, sheets: str = 'all', cell: Optional[int] = None) -> List[dict]:
+                    rank: int = 0, world: int = 1, sheets: str = 'all', cell: Optional[int] = None, png: str = 'host') -> List[dict]:
     """This rank's candidates (round-robin over 0..n-1) of a direction search: direction pickle, contact sheet and scores per
     candidate.  sheets: 'all', 'none', or 'top:K' -- score every candidate of the rank first, then render only the rank's K best
-    again into sheets (PNG encoding is host zlib and, at full size, the largest single cost per candidate).  Writes
+    again into sheets (PNG encoding is host zlib and, at full size, the largest single cost per candidate).  png: 'host' downloads
+    the sheet and writes it with Pillow (`write_png`); 'device' encodes it where it is (pngenc.PngEncoder) and downloads the
+    compressed bytes: the same pixels in another file.  Writes
     <out_dir>/scores.rank<r>of<world>.json and returns its records; `merge_scores(out_dir, world)` makes scores.json from the files of
     that world's ranks (files an earlier run with another world size left behind are not read)."""
     from .dataset import shard
+    from .pngenc import PngEncoder, check_png_mode
+    encoder = PngEncoder(search.handle, search.device) if check_png_mode(png) == 'device' else None
     mode, top = parse_sheets(sheets)
     values = np.linspace(-2.5, 2.5, 6) if values is None else np.asarray(values, dtype=np.float64)
     k = len(existing) + 1
@@ -377,7 +381,11 @@ def find_directions(search: DirectionSearch, att: str, existing: Sequence, out_d
             write_direction(os.path.join(dir_dir, '%d.pkl' % idx), d)
             rec = {'index': int(idx), **score(att, search.stats(images, masks), values, S, S)}
         if want_sheet:
-            write_png(os.path.join(img_dir, '%d.png' % idx), search.sheet(att, images, masks, cell=cell).numpy())
+            sheet = search.sheet(att, images, masks, cell=cell)
+            if encoder is None:
+                write_png(os.path.join(img_dir, '%d.png' % idx), sheet.numpy())
+            else:
+                encoder.write([os.path.join(img_dir, '%d.png' % idx)], sheet.canvas[None])
         return rec
 
     mine = shard(list(range(n)), rank, world)

@@ -324,6 +324,29 @@ int  ch_sheet_compose(ch_handle* h, const void* src, int kind, int n, int Hs, in
 int  ch_sweep_stats(ch_handle* h, const void* img, int kind, const uint8_t* labels, const int32_t* ref, int N, int H, int W, int lh,
                     int lw, int64_t* stats, ch_stream_t stream);
 
+/* ---- PNG encoding on the device: contact sheets, label maps, crops and paste-backs leave as compressed bytes -----------------------
+ * ch_png_encode turns N images img uint8 [N,H,W,C] (device pointer; C = 1 grey, 3 RGB, 4 RGBA) into N complete zlib streams
+ * (RFC 1950) of their PNG-filtered bytes (RFC 2083 section 6: per row the filter type byte and the filtered row, H * (1 + W * C)
+ * bytes): image n's stream starts at out + n * ch_png_zlib_bound(H, W, C) and is sizes[n] bytes long (out uint8, sizes int64 [N]:
+ * device pointers).  The caller wraps a stream into signature / IHDR / IDAT / IEND; nothing else is needed for a PNG file.
+ *   filter -1: per row the type 0..4 with the smallest sum of |int8(filtered byte)|, the lowest type on a tie, the row above row 0
+ *              being zero (libpng's heuristic); filter 0..4: that type for every row.
+ *   The filtered stream is cut into chunks of ch_png_chunk_bytes() bytes regardless of rows (the last may be short).  A chunk is
+ *   one deflate block of literals and (length 3..258, distance 1) matches under a dynamic Huffman code of its own (lengths limited
+ *   to 15 / 7 bits), followed by the empty stored block that realigns to a byte -- or one stored block where that is not smaller
+ *   (5 + len bytes).  A run never reaches back across a chunk start.  After the last chunk: an empty final block and the Adler-32.
+ *   sizes[n] <= ch_png_zlib_bound = 2 + sum over chunks (len + 10) + 2 + 4.
+ *   Integer arithmetic only; atomics are integer add and or: the bytes of an image are the same in every call and in every batch
+ *   (they do depend on ch_png_chunk_bytes()).  Pixels decode exactly; the bytes differ from zlib's for the same pixels.
+ * workspace: caller-owned device buffer (16-byte aligned) of ch_png_encode_workspace_bytes(N, H, W, C) bytes (0 for arguments the
+ * call would reject).  1 <= N <= 65535, 1 <= H, W <= 32768, H * W <= 2^30.  Enqueues three kernels on `stream` without synchronising
+ * or allocating. */
+int    ch_png_chunk_bytes(void);
+size_t ch_png_zlib_bound(int H, int W, int C);
+size_t ch_png_encode_workspace_bytes(int N, int H, int W, int C);
+int    ch_png_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes,
+                     void* workspace, size_t workspace_bytes, ch_stream_t stream);
+
 /* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
  * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image
  * edge extended 10 px, mask_adaptor.py:119-131), the pair's triangle mesh is deformed as rigidly as possible (libigl's per-element
