@@ -187,6 +187,8 @@ struct AceInteriorParams {
                                 // accesses), 2 = one pixel per thread writing whole 32-byte sectors (A/B measurements)
     int groups;                 // exact-f32 tile4 kernel: channel groups of 32 served by one block (option "sean.int_groups"): 0 = chosen by the
                                 // launcher (ace_interior_groups), n >= 1 = at most n; the kernel receives the number in use
+    int onepass;                // exact-f32 tile4 kernel (option "sean.int_onepass"): 1 = 128 key slots for a block's straight-edge codes and steps of 16
+                                // channels where a block holds more than 64 of them (one round up to 128 codes); 0 = 64 key slots, another round beyond
 };
 int ace_interior_groups(const AceInteriorParams& q);      // groups per block the tile4 launch of q uses (a divisor of ceil(C / 32))
 hipError_t ace_interior_f32(const AceInteriorParams& q, hipStream_t s);

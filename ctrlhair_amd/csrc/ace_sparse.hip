@@ -529,23 +529,39 @@ __global__ __launch_bounds__(256) void ace_interior_f32_tile_kernel(const AceInt
 #define ACE_T4_UNROLL 1      // channel-loop unroll of the four-pixel interior kernel: 1 = 68 VGPRs (seven blocks per CU), 4 = 97 (five): 4.0 vs 5.3 ms per step (profiles/r06_interior_ab.txt)
 #endif
 typedef float nt_f32x4 __attribute__((ext_vector_type(4)));      // (a 16-byte store the compiler keeps whole)
+typedef float t4_row16 __attribute__((ext_vector_type(4), aligned(8)));      // two {1 + gamma, beta} pairs of an LDS table row (rows are 8-byte aligned)
 // Four pixels of a row per thread, blocks of 128 x 8 pixels (W >= 128): 16-byte stores, 8- / 16-byte x loads, the four noise
 // values of a thread share their 32-byte sectors with the seven other rows of the block.
 // A block serves q.groups consecutive channel groups of its tile: what depends on the pixels only -- marks, noise, ownership, line fill,
 // the slots of the straight-edge codes -- is set up once per block (per round), the table rows and the channel loop run per group.
 // Table rows are interleaved {1 + gamma_c, beta_c} pairs (one 8-byte read per pixel and channel; the 1 + gamma is the same f32 addition the
 // channel loop used to do, moved to the table build), {bn_a, nv, bn_d} one 16-byte entry per channel (one broadcast read).
+//
+// Straight-edge rows and the width of a channel step.  The block's distinct codes are hashed into EK = 128 key slots and the occupied slots
+// are compacted to ranks; the row table is indexed by rank.  How many codes a block of 128 x 8 pixels holds follows the label map: on the
+// benchmark's 16 x 16-block maps a tile of the 128-pixel level is one row of 16 label blocks of 8 x 8 pixels -- 15 vertical borders with
+// 4 codes each and 16 blocks with 4 horizontal codes each, 112 on average and up to 122 (frame codes on top) -- while the 256- and
+// 512-pixel levels hold about 42 and 18.  The rows share one LDS pool in two layouts, chosen per block and round from the number of codes:
+//      nocc <= 64:         steps of 32 channels, row pitch 66 floats, 19 + 64 rows  (5016 + 16 896 bytes)
+//      64 < nocc <= 128:   steps of 16 channels, row pitch 34 floats, 19 + 128 rows (2584 + 17 408 bytes), twice as many steps
+// so a block with up to 128 codes serves all its pixels in ONE round with whole-line stores.  Codes that find no key slot wait for another
+// round, whose pixels are stored one by one into lines the first round has filled (q.onepass == 0: 64 key slots, the rule up to round 10).
+// VEC4: the row builds with 16-byte loads (C % 4 == 0 and 16-byte aligned tables, the launcher's choice); else one channel per thread.
+template <bool VEC4>
 __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const AceInteriorParams q) {      // (8 blocks per CU: <= 64 VGPR; it is a streaming kernel)
 #ifndef ACE_T4_ES_BITS
-#define ACE_T4_ES_BITS 6      // 64 slots.  32 (14 KB of LDS instead of 22: eight blocks per CU at 64 VGPRs) was measured: 5.6 vs 4.2 ms per step on the
-#endif                        // benchmark labels -- a 128 x 8 block of the 128-pixel level holds up to ~60 codes, so it takes a second round; 16: 9.1 ms
-    // RS: row pitch in floats.  8-byte reads bank on (address / 4) % 64 per half wave: with 2 * IN_CG + 2 the rows r and r + 1 sit one bank
-    // pair apart, so up to 32 different rows read by one half wave at the same channel do not collide.
-    constexpr int RS = 2 * IN_CG + 2, ES = 1 << ACE_T4_ES_BITS;      // ES: slots of the block's table of straight-edge rows
-    __shared__ __attribute__((aligned(16))) float gt[19 * RS];
-    __shared__ __attribute__((aligned(16))) float et[ES * RS];
+#define ACE_T4_ES_BITS 6      // 64 rows of 32 channels.  32 (14 KB of LDS instead of 22: eight blocks per CU at 64 VGPRs) was measured: 5.6 vs 4.2 ms
+#endif                        // per step on the benchmark labels (two rounds at 256 pixels, four at 128); 16: 9.1 ms
+    // Row pitch in floats: 2 * cg + 2 for steps of cg channels.  8-byte reads bank on (address / 4) % 64 per half wave: with 66 the rows r and
+    // r + 1 sit one bank pair apart, with 34 the rows 2 k sit at bank 4 k and the rows 2 k + 1 at bank 34 + 4 k -- either way up to 32
+    // consecutive rows read by one half wave at the same channel do not collide.
+    constexpr int ES = 1 << ACE_T4_ES_BITS, EK = 2 * ES;      // ES: rows of the wide layout, EK: key slots = rows of the narrow layout
+    constexpr int POOL = (19 + ES) * (2 * IN_CG + 2);         // (the narrow layout, (19 + EK) * (IN_CG + 2) floats, is the smaller one)
+    static_assert((19 + EK) * (IN_CG + 2) <= POOL && EK <= 128, "row pool; the two key ballots; ranks in a byte");
+    __shared__ __attribute__((aligned(16))) float pool[POOL];
     __shared__ __attribute__((aligned(16))) float4 pp[IN_CG];      // {bn_a, nv, bn_d, -}
-    __shared__ int ekey[ES], olist[ES], nocc;
+    __shared__ int ekey[EK], nocc;                                 // key slot: -1 or the code, after the compaction code | rank << 16
+    __shared__ uint8_t olist[EK];                                  // key slot of a rank
     const int HW = q.H * q.W, tpr = (q.W + 127) >> 7, tpc = (q.H + 7) >> 3;
     const int b = blockIdx.x / (tpr * tpc), r = blockIdx.x - b * (tpr * tpc), tyi = r / tpr;
     const int x = (r - tyi * tpr) * 128 + (threadIdx.x & 31) * 4, y = tyi * 8 + (threadIdx.x >> 5);
@@ -563,6 +579,7 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
         i0 = i1 = q0;
         i2 = i3 = q1;
     }
+    const unsigned jpack = (unsigned)j4.x | (unsigned)j4.y << 8 | (unsigned)j4.z << 16 | (unsigned)j4.w << 24;
     const bool m0 = i0 || e0, m1 = i1 || e1, m2 = i2 || e2, m3 = i3 || e3;      // pixels this pass owns
     const unsigned im = (i0 ? 1u : 0u) | (i1 ? 2u : 0u) | (i2 ? 4u : 0u) | (i3 ? 8u : 0u);      // (the interior ones)
     const int nmine = __syncthreads_count(m0) + __syncthreads_count(m1) + __syncthreads_count(m2) + __syncthreads_count(m3);
@@ -589,11 +606,13 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
     const int xW = q.W >> q.x_up, xHW = xW * (q.H >> q.x_up);
     const int ngrp = (q.C + IN_CG - 1) / IN_CG, G = q.groups > 0 ? q.groups : 1;
     const int gfirst = blockIdx.y * G, glast = gfirst + G < ngrp ? gfirst + G : ngrp;      // this block's channel groups
+    const int cfirst = gfirst * IN_CG, cend = glast * IN_CG < q.C ? glast * IN_CG : q.C;   // = its channels
     const float slope = q.act == ACT_NONE ? 1.f : (q.act == ACT_LRELU ? 0.2f : 0.f);
-    // Straight-edge pixels: the block's distinct codes go into a 64-slot table (open addressing on the code, LDS compare-and-swap); the
-    // rows -- E[code] + the three style sums -- are built once per block and channel group, cooperatively, and read like the interior
-    // rows.  Codes that find no slot (more than 64 distinct ones in 128 x 8 pixels) wait for another ROUND of the same code with a fresh
-    // table; a later round stores its pixels one by one.  The slots of a round hold for every channel group of that round.
+    const int ekb = q.onepass ? ACE_T4_ES_BITS + 1 : ACE_T4_ES_BITS, ekm = (1 << ekb) - 1;      // key slots in use
+    // Straight-edge pixels: the block's distinct codes go into the key table (open addressing on the code, LDS compare-and-swap); the
+    // rows -- E[code] + the three style sums -- are built once per block and channel step, cooperatively, and read like the interior
+    // rows.  Codes that find no slot (more than 128 distinct ones in 128 x 8 pixels) wait for another ROUND of the same code with a fresh
+    // table; a later round stores its pixels one by one.  The ranks of a round hold for every channel step of that round.
     // pend: the edge pixels without a row yet.
     unsigned k01 = 0, k23 = 0, pend = (e0 ? 1u : 0u) | (e1 ? 2u : 0u) | (e2 ? 4u : 0u) | (e3 ? 8u : 0u);      // codes of the four pixels (16 bits each)
     if (pend) {
@@ -601,88 +620,141 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
         k01 = k4.x; k23 = k4.y;
     }
     for (bool first = true;; first = false) {
-        int slot[4] = {-1, -1, -1, -1};
+        int slot[4] = {-1, -1, -1, -1};                      // key slot, then rank (= row of the block's table) of the four pixels
+        int cgb = 5;                                         // log2 of the channels per step: 32, or 16 with more than ES codes
         if (edges) {
-            if (threadIdx.x < ES) ekey[threadIdx.x] = -1;
+            if (threadIdx.x < EK) ekey[threadIdx.x] = -1;
             __syncthreads();
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 if (!(pend >> s & 1u)) continue;
                 const int code = (int)(((s & 2) ? k23 : k01) >> ((s & 1) * 16) & 0xFFFFu);
-                unsigned h = ((unsigned)code * 2654435761u) >> (32 - ACE_T4_ES_BITS);
-                for (int probe = 0; probe < ES; ++probe) {
+                unsigned h = ((unsigned)code * 2654435761u) >> (32 - ekb);
+                for (int probe = 0; probe <= ekm; ++probe) {
                     const int old = atomicCAS(&ekey[h], -1, code);
                     if (old == -1 || old == code) {
                         slot[s] = (int)h;
                         pend &= ~(1u << s);
                         break;
                     }
-                    h = (h + 1) & (ES - 1);
+                    h = (h + 1) & ekm;
                 }
             }
             __syncthreads();                                 // (the slots are final)
-            if (threadIdx.x < ES) {                          // the occupied slots, compacted (most blocks hold 0 ... 20 codes)
-                const bool occ = ekey[threadIdx.x] >= 0;
-                const unsigned long long om = __ballot(occ);
-                if (occ) olist[__popcll(om & ((1ull << threadIdx.x) - 1ull))] = threadIdx.x;
-                if (threadIdx.x == 0) nocc = __popcll(om);
+            if (threadIdx.x < EK) {                          // the occupied slots, compacted to ranks: both waves look at both halves of the keys
+                const int lane = threadIdx.x & 63;
+                const unsigned long long lo = __ballot(ekey[lane] >= 0), hi = __ballot(ekey[64 + lane] >= 0), below = (1ull << lane) - 1ull;
+                const bool up = threadIdx.x >= 64;
+                if (((up ? hi : lo) >> lane) & 1ull) {
+                    const int rk = up ? __popcll(lo) + __popcll(hi & below) : __popcll(lo & below);
+                    ekey[threadIdx.x] |= rk << 16;       // (stays >= 0 for the other wave's ballot)
+                    olist[rk] = (uint8_t)threadIdx.x;
+                }
+                if (threadIdx.x == 0) nocc = __popcll(lo) + __popcll(hi);
             }
+            __syncthreads();                                 // (ranks, olist and nocc are written)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if (slot[s] >= 0) slot[s] = ekey[slot[s]] >> 16;
+            if (__builtin_amdgcn_readfirstlane(nocc) > ES) cgb = 4;
         }
+        const int cg = 1 << cgb, RS = 2 * cg + 2;            // channels per step and row pitch of this round (block-uniform)
+        float* const gt = pool;                              // 19 (sample, label) rows, then the rows of the block's codes
+        float* const et = pool + 19 * RS;
         // this round's pixels: the first round takes the interior pixels, the edge pixels that found a slot and (fill) the line's others
         const unsigned wm = (slot[0] >= 0 ? 1u : 0u) | (slot[1] >= 0 ? 2u : 0u) | (slot[2] >= 0 ? 4u : 0u) | (slot[3] >= 0 ? 8u : 0u) | (first ? im : 0u);
         const bool work = first ? any : wm != 0;
         // a pixel's row of {1 + gamma, beta} pairs: the (sample, label) row of an interior pixel, the block-table row of a straight-edge pixel
-        const float *g0 = slot[0] >= 0 ? et + slot[0] * RS : gt + ((im & 1u) ? j4.x : 0) * RS, *g1 = slot[1] >= 0 ? et + slot[1] * RS : gt + ((im & 2u) ? j4.y : 0) * RS,
-                    *g2 = slot[2] >= 0 ? et + slot[2] * RS : gt + ((im & 4u) ? j4.z : 0) * RS, *g3 = slot[3] >= 0 ? et + slot[3] * RS : gt + ((im & 8u) ? j4.w : 0) * RS;
-        for (int gi = gfirst; gi < glast; ++gi) {
-            const int c0 = gi * IN_CG;
-            __syncthreads();                                 // (olist / nocc are written; the previous group's table reads are over)
-            // one thread = one channel of one row, gamma and beta together.  (tid is opaque to the compiler here: the addresses of the table
-            // build are otherwise hoisted out of the group loop and held in registers through the channel loop)
+        // (the four labels stay packed in one register between the rounds: jw is opaque to the compiler here)
+        unsigned jw = jpack;
+        asm volatile("" : "+v"(jw));
+        const float *g0 = slot[0] >= 0 ? et + slot[0] * RS : gt + ((im & 1u) ? (int)(jw & 255u) : 0) * RS, *g1 = slot[1] >= 0 ? et + slot[1] * RS : gt + ((im & 2u) ? (int)(jw >> 8 & 255u) : 0) * RS,
+                    *g2 = slot[2] >= 0 ? et + slot[2] * RS : gt + ((im & 4u) ? (int)(jw >> 16 & 255u) : 0) * RS, *g3 = slot[3] >= 0 ? et + slot[3] * RS : gt + ((im & 8u) ? (int)(jw >> 24) : 0) * RS;
+        for (int c0 = cfirst; c0 < cend; c0 += cg) {
+            if (c0 != cfirst) __syncthreads();               // (the previous step's table reads are over)
+            // (tid is opaque to the compiler here: the addresses of the table build are otherwise hoisted out of the step loop and held in
+            // registers through the channel loop)
             int tid = threadIdx.x;
             asm volatile("" : "+v"(tid));
-            for (int i = tid; i < 19 * IN_CG; i += 256) {
-                const int jj = i / IN_CG, cl = i % IN_CG, c = c0 + cl;
-                float2 v = make_float2(0.f, 0.f);
-                if (c < q.C) {
-                    const float* gp = q.gtab + ((long long)b * 19 + jj) * 2 * q.C + c;
-                    v = make_float2(gp[0], gp[q.C]);
+            const int nrows = edges ? 19 + __builtin_amdgcn_readfirstlane(nocc) : 19;      // the label rows, then the block's codes by rank
+            if constexpr (VEC4) {
+                // one thread = four adjacent channels of one row: 16-byte loads of gamma and beta, two 16-byte stores of {1 + gamma, beta} pairs
+                // (the sample's tables by a block-uniform base and a 32-bit offset: 19 * 12 C and ACE_EDGE_CODES * 2 C floats at the most)
+                const int qb = cgb - 2, qm = (1 << qb) - 1;
+                const float *gtab_b = q.gtab + (long long)b * 19 * 2 * q.C, *p6_b = q.p6 + (long long)b * 19 * 12 * q.C;
+                for (int i = tid; i < nrows << qb; i += 256) {
+                    const int row = i >> qb, cl = (i & qm) * 4, c = c0 + cl;
+                    float4 g = make_float4(0.f, 0.f, 0.f, 0.f), bt = g;
+                    if (c < q.C) {
+                        if (row < 19) {
+                            const float* gp = gtab_b + (unsigned)(row * 2 * q.C + c);
+                            g = *reinterpret_cast<const float4*>(gp);
+                            bt = *reinterpret_cast<const float4*>(gp + q.C);
+                        } else {
+                            const int code = ekey[olist[row - 19]] & 0xFFFF;
+                            const AceCode cd = ace_code_decode(code);
+                            // E[code], then the style sums t = 0, 1, 2 (line label 1 + t of A^s B^(5-s); frame codes: < 0 = the tap falls outside)
+                            auto sum4 = [&](int gb) {
+                                float4 v = *reinterpret_cast<const float4*>(q.etab + (unsigned)((code * 2 + gb) * q.C + c));
+                                if (q.p6) {
+#pragma unroll
+                                    for (int t = 0; t < 3; ++t) {
+                                        const int l = cd.line(1 + t);
+                                        if (l < 0) continue;
+                                        const float4 pv = *reinterpret_cast<const float4*>(p6_b + (unsigned)(((l * 6 + cd.o * 3 + t) * 2 + gb) * q.C + c));
+                                        v.x += pv.x; v.y += pv.y; v.z += pv.z; v.w += pv.w;
+                                    }
+                                }
+                                return v;
+                            };
+                            g = sum4(0);
+                            __builtin_amdgcn_sched_barrier(0);      // (gamma, then beta: both halves in flight together cost four more registers)
+                            bt = sum4(1);
+                        }
+                    }
+                    t4_row16* d = reinterpret_cast<t4_row16*>(gt + row * RS + 2 * cl);      // (et follows gt at the same pitch)
+                    d[0] = (t4_row16){1.f + g.x, bt.x, 1.f + g.y, bt.y};
+                    d[1] = (t4_row16){1.f + g.z, bt.z, 1.f + g.w, bt.w};
                 }
-                *reinterpret_cast<float2*>(gt + jj * RS + 2 * cl) = make_float2(1.f + v.x, v.y);
-            }
-            if (tid < IN_CG) {
-                const int c = c0 + tid;
-                pp[tid] = c < q.C ? make_float4(q.bn_a[c], q.nv[c], q.bn_d[c], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            if (edges) {
-                const int ne = nocc * IN_CG;
-                for (int i = tid; i < ne; i += 256) {
-                    const int sl = olist[i / IN_CG], cl = i % IN_CG, c = c0 + cl;
-                    const int code = ekey[sl];
+            } else {
+                // C % 4 != 0: one thread = one channel of one row, gamma and beta together
+                const int cm = cg - 1;
+                for (int i = tid; i < nrows << cgb; i += 256) {
+                    const int row = i >> cgb, cl = i & cm, c = c0 + cl;
                     float2 v = make_float2(0.f, 0.f);
                     if (c < q.C) {
-                        const float* ep = q.etab + (long long)code * 2 * q.C + c;
-                        v = make_float2(ep[0], ep[q.C]);
-                        if (q.p6) {
-                            const AceCode cd = ace_code_decode(code);
+                        if (row < 19) {
+                            const float* gp = q.gtab + ((long long)b * 19 + row) * 2 * q.C + c;
+                            v = make_float2(gp[0], gp[q.C]);
+                        } else {
+                            const int code = ekey[olist[row - 19]] & 0xFFFF;
+                            const float* ep = q.etab + (long long)code * 2 * q.C + c;
+                            v = make_float2(ep[0], ep[q.C]);
+                            if (q.p6) {
+                                const AceCode cd = ace_code_decode(code);
 #pragma unroll
-                            for (int t = 0; t < 3; ++t) {
-                                const int l = cd.line(1 + t);                // line label 1 + t of A^s B^(5-s); frame codes: < 0 = the tap falls outside
-                                if (l < 0) continue;
-                                const float* pq = q.p6 + (((long long)b * 19 + l) * 6 + cd.o * 3 + t) * 2 * q.C + c;
-                                v.x += pq[0];
-                                v.y += pq[q.C];
+                                for (int t = 0; t < 3; ++t) {
+                                    const int l = cd.line(1 + t);
+                                    if (l < 0) continue;
+                                    const float* pq = q.p6 + (((long long)b * 19 + l) * 6 + cd.o * 3 + t) * 2 * q.C + c;
+                                    v.x += pq[0];
+                                    v.y += pq[q.C];
+                                }
                             }
                         }
                     }
-                    *reinterpret_cast<float2*>(et + sl * RS + 2 * cl) = make_float2(1.f + v.x, v.y);
+                    *reinterpret_cast<float2*>(gt + row * RS + 2 * cl) = make_float2(1.f + v.x, v.y);
                 }
+            }
+            if (tid < cg) {
+                const int c = c0 + tid;
+                pp[tid] = c < q.C ? make_float4(q.bn_a[c], q.nv[c], q.bn_d[c], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
             __syncthreads();
             if (!work) continue;
             const float* __restrict__ xp = q.x + ((long long)b * q.C + c0) * xHW + (y >> q.x_up) * xW + (x >> q.x_up);
             float* __restrict__ op = reinterpret_cast<float*>(q.out) + ((long long)b * q.C + c0) * HW + pix;
-            const int cmax = q.C - c0 < IN_CG ? q.C - c0 : IN_CG;
+            const int cmax = cend - c0 < cg ? cend - c0 : cg;
             // x of channel c (optionally loaded ACE_T4_AHEAD iterations before its use: measured slower, see the macro)
             auto loadx = [&](int c) {
                 float4 xv;
@@ -786,7 +858,10 @@ hipError_t ace_interior_f32(const AceInteriorParams& q, hipStream_t s) {
         qq.groups = ace_interior_groups(q);
         const int ngrp = (q.C + IN_CG - 1) / IN_CG;
         dim3 gridt((unsigned)(q.B * ((q.W + 127) / 128) * ((q.H + 7) / 8)), (unsigned)((ngrp + qq.groups - 1) / qq.groups));
-        hipLaunchKernelGGL(ace_interior_f32_tile4_kernel, gridt, dim3(256), 0, s, qq);
+        // row builds with 16-byte loads: every table row starts at a multiple of C floats (and the build's 32-bit offsets hold ACE_EDGE_CODES * 2 C)
+        const bool vec4 = q.C % 4 == 0 && q.C <= (1 << 16) && ((reinterpret_cast<uintptr_t>(q.gtab) | reinterpret_cast<uintptr_t>(q.etab) | reinterpret_cast<uintptr_t>(q.p6)) & 15) == 0;
+        if (vec4) hipLaunchKernelGGL(ace_interior_f32_tile4_kernel<true>, gridt, dim3(256), 0, s, qq);
+        else hipLaunchKernelGGL(ace_interior_f32_tile4_kernel<false>, gridt, dim3(256), 0, s, qq);
         return hipGetLastError();
     }
     if (q.impl == 0 || q.impl == 2) {

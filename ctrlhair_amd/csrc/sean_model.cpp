@@ -1599,6 +1599,7 @@ struct Runner {
             // (tools/interior_bench.hip); level in the 100 ms step of round 3, measurable in this one
             ip.impl = r >= 128 ? 2 : 0;
             ip.groups = m.opt.int_groups;       // (tile4 kernel: channel groups per block, 0 = the launcher's rule; ace_sparse.hip)
+            ip.onepass = m.opt.int_onepass;     // (tile4 kernel: 128 key slots and the narrow channel step for code-dense blocks)
             if (wp.edges) {         // (P6 is built below)
                 if (!a.edge_tab || r < 128) check(hipErrorInvalidValue, "straight-edge marks on a level whose ACE has no table");
                 interior_edges(ip, p, q, *wp.S);

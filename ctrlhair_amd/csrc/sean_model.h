@@ -117,6 +117,9 @@ struct SeanOptions {
                                                //   >= 128 pixels whose in-image 5x5 window is uniform are served the same way (frame codes, ace_sparse.h); 0 = boundary conv
     int int_groups = 0;                        // option "sean.int_groups": channel groups of 32 per block of the four-pixel interior kernel (levels >= 128 pixels,
                                                //   exact-f32 Winograd path): 0 = chosen per launch (ace_interior_groups), n >= 1 = at most n (1 = one group per block)
+    int int_onepass = 1;                       // option "sean.int_onepass": 1 = a block of the four-pixel interior kernel hashes its straight-edge codes into 128 slots
+                                               //   and, holding more than 64, serves them in one round with steps of 16 channels (bit-identical results); 0 = 64
+                                               //   slots and a second round beyond them
     int batch_inv = 0;                         // option "sean.batch_invariant": 1 = every choice that follows the number of tasks of a call (F(4x4) vs F(2x2),
                                                //   split-K, sample-pair tiles at 16 pixels, the small-batch LUT / tiny-level routes) is made as for a large
                                                //   batch: sample i alone == sample i in any batch, bit for bit (exact-f32 path)

@@ -113,6 +113,10 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   straight-edge codes -- and then serves several groups of 32 channels.  0 = per launch, the largest divisor of the group count that
  *   leaves at least sixteen blocks per compute unit in the grid; n >= 1 = at most n groups per block (1 = one group per block, the
  *   decomposition before the group loop).  Bit-identical for every value.
+ * "sean.int_onepass" (default 1; any time; same kernel): 1 = a block hashes its distinct straight-edge codes into 128 key slots and, where
+ *   it holds more than 64 of them (label maps with many small regions: 16 x 16-block maps at the 128-pixel level), runs steps of 16
+ *   channels over a table of 128 rows, so up to 128 codes are served in one round with whole-line stores; beyond 128, further rounds.
+ *   0 = 64 key slots, steps of 32 channels, another round for every further 64 codes.  Bit-identical.
  * "sean.batch_invariant" (default 0; any time; exact-f32 path): by default several choices follow the number of tasks of a call, i.e. its
  *   batch size -- F(4x4,3x3) vs F(2x2,3x3) (wino4_pays), split-K of launches with few tasks, sample-pair tiles of the 16-pixel level, the
  *   GEMV / tiny-level routes of interactive batches -- so the same sample rendered alone and inside a batch differs by the rounding of two

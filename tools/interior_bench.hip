@@ -2,7 +2,9 @@
 // copy kernel of the same access pattern.  Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I ctrlhair_amd/csrc
 //   tools/interior_bench.hip -o tools/interior_bench.bin ; run on the GPU box.
 // `interior_bench.bin groups`: the four-pixel exact-f32 kernel (ace_interior_f32_tile4_kernel) at the nine launch shapes of the headline
-//   leg (B = 16, 512^2) with straight-edge marks on blocky labels, for 1, 2, 4, 8 channel groups per block and the launcher's rule.
+//   leg (B = 16, 512^2) with straight-edge marks on blocky labels, for 1, 2, 4, 8 channel groups per block and the launcher's rule, and
+//   at the launcher's rule with q.onepass = 0 (64 code slots per block and rounds) beside the default 1; per shape a census of the distinct
+//   straight-edge codes per block of 128 x 8 pixels, counted on the host from the device's own classification.
 #include "../ctrlhair_amd/csrc/ace_sparse.hip"
 #include <cstdio>
 #include <vector>
@@ -44,8 +46,9 @@ static int run_groups() {
                         {"256px ace_0", 256, 256, 1, 1}, {"256px ace_s", 256, 256, 1, 1}, {"256px ace_1", 128, 256, 0, 1},
                         {"512px ace_0", 128, 512, 1, 0}, {"512px ace_s", 128, 512, 1, 0}, {"512px ace_1", 64, 512, 0, 0}};
     const int B = 16;
-    double tot[5] = {0, 0, 0, 0, 0};
-    const int gsel[5] = {1, 2, 4, 8, 0};
+    constexpr int NK = 6;
+    double tot[NK] = {};
+    const int gsel[NK] = {1, 2, 4, 8, 0, 0}, osel[NK] = {1, 1, 1, 1, 1, 0};      // (groups, onepass) of a column
     for (const Cfg& c : cfgs) {
         const int C = c.C, H = c.H, W = c.H, HW = H * W, xh = H >> c.up, cell = H / 16;
         std::vector<uint8_t> lab((size_t)B * HW);
@@ -69,6 +72,26 @@ static int run_groups() {
         CK(hipMemcpy(u5.data(), d_u5, u5.size(), hipMemcpyDeviceToHost));
         size_t nint = 0, nedge = 0;
         for (uint8_t v : u5) { nint += v < 19; nedge += v == ACE_EDGE; }
+        {   // distinct codes per block of 128 x 8 pixels (the tile4 kernel's tile)
+            std::vector<uint16_t> e16(lab.size());
+            CK(hipMemcpy(e16.data(), d_e16, e16.size() * 2, hipMemcpyDeviceToHost));
+            std::vector<uint8_t> seen(ACE_EDGE_CODES);
+            size_t nt = 0, sum = 0, mx = 0, over64 = 0, over128 = 0;
+            for (int b = 0; b < B; ++b)
+                for (int ty = 0; ty < H; ty += 8)
+                    for (int tx = 0; tx < W; tx += 128) {
+                        std::fill(seen.begin(), seen.end(), 0);
+                        size_t n = 0;
+                        for (int y = ty; y < std::min(ty + 8, H); ++y)
+                            for (int x = tx; x < std::min(tx + 128, W); ++x) {
+                                const size_t p = ((size_t)b * H + y) * W + x;
+                                if (u5[p] == ACE_EDGE && !seen[e16[p]]) { seen[e16[p]] = 1; ++n; }
+                            }
+                        ++nt; sum += n; mx = std::max(mx, n); over64 += n > 64; over128 += n > 128;
+                    }
+            printf("%s census: distinct codes per 128 x 8 tile: mean %.1f max %zu, share of tiles above 64: %.3f, above 128: %.3f (%zu tiles)\n",
+                   c.name, (double)sum / nt, mx, (double)over64 / nt, (double)over128 / nt, nt);
+        }
         auto fill = [&](float** d, size_t n, float lo, float hi) {
             std::vector<float> h(n);
             for (auto& v : h) v = lo + (hi - lo) * (float)rand() / RAND_MAX;
@@ -85,8 +108,9 @@ static int run_groups() {
         std::vector<uint32_t> ref(nout), got(nout);
         hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
         printf("%s C=%3d H=%3d up=%d interior=%.3f straight-edge=%.3f |", c.name, C, H, c.up, (double)nint / u5.size(), (double)nedge / u5.size());
-        for (int k = 0; k < 5; ++k) {
+        for (int k = 0; k < NK; ++k) {
             q.groups = gsel[k];
+            q.onepass = osel[k];
             const int G = ace_interior_groups(q);
             CK(hipMemset(d_out, 0, nout * 4));
             CK(ace_interior_f32(q, 0));
@@ -103,14 +127,28 @@ static int run_groups() {
             std::sort(t + 1, t + 9);                       // (the first run warms up) median of eight
             const float med = 0.5f * (t[4] + t[5]);
             tot[k] += med;
-            printf(" groups=%d -> G=%d %7.1f us (min %.1f) diff=%zu |", gsel[k], G, med * 1e3, t[1] * 1e3, bad);
+            printf(" groups=%d onepass=%d -> G=%d %7.1f us (min %.1f) diff=%zu |", gsel[k], osel[k], G, med * 1e3, t[1] * 1e3, bad);
+        }
+        {   // the one-channel-per-thread row build (the launcher takes it for C % 4 != 0 or tables off 16-byte alignment) on the same operands
+            AceInteriorParams qq = q;
+            qq.groups = 0; qq.onepass = 1;
+            qq.groups = ace_interior_groups(qq);
+            const int ngrp = (C + IN_CG - 1) / IN_CG;
+            dim3 grid((unsigned)(B * ((W + 127) / 128) * ((H + 7) / 8)), (unsigned)((ngrp + qq.groups - 1) / qq.groups));
+            CK(hipMemset(d_out, 0, nout * 4));
+            hipLaunchKernelGGL(ace_interior_f32_tile4_kernel<false>, grid, dim3(256), 0, 0, qq);
+            CK(hipGetLastError());
+            CK(hipMemcpy(got.data(), d_out, nout * 4, hipMemcpyDeviceToHost));
+            size_t bad = 0;
+            for (size_t i = 0; i < nout; ++i) bad += got[i] != ref[i];
+            printf(" scalar row build diff=%zu |", bad);
         }
         printf("\n");
         hipFree(d_lab); hipFree(d_u5); hipFree(d_need); hipFree(d_e16); hipFree(d_list); hipFree(d_cnt); hipFree(d_x); hipFree(d_gtab);
         hipFree(d_par); hipFree(d_noise); hipFree(d_etab); hipFree(d_p6); hipFree(d_out);
     }
     printf("sum of the nine launches:");
-    for (int k = 0; k < 5; ++k) printf(" groups=%d %.3f ms |", gsel[k], tot[k]);
+    for (int k = 0; k < NK; ++k) printf(" groups=%d onepass=%d %.3f ms |", gsel[k], osel[k], tot[k]);
     printf("\n");
     return 0;
 }
