@@ -67,7 +67,7 @@ hipError_t onehot_conv3x3_sh16(const uint8_t* lab, const float* table, const flo
                                                                  // 1 = never, 2 = always (A/B, tools/onehot_bench.hip)
 // amax: device slot of a dynamically scaled tensor (sh16.h), null = static scale
 hipError_t sh16_decode(const void* in, float* out, int B, int C, long long HW, float scale, const unsigned* amax,
-                       hipStream_t s, int bf16 = 0);
+                       hipStream_t s, int bf16 = 0, int single = 0);
 hipError_t fc_mu(const float* codes, const float* Wt, const float* bias, float* mu_img, int B, int Npad, hipStream_t s,
                  float* mu_rows = nullptr, int sh16 = 0, int bs = 19, float scale = 1.f, unsigned* amax = nullptr,
                  int pass = 0, int bf16 = 0);

@@ -844,9 +844,10 @@ hipError_t onehot_conv3x3_sh16(const uint8_t* lab, const float* table, const flo
     return hipGetLastError();
 }
 
-// SH16 -> f32 NCHW (test taps only)
+// SH16 -> f32 NCHW (test taps only).  single: the single-term paths read the hi plane alone, so that is what the tap shows (their interior pass
+// does not even write the lo plane)
 __global__ void sh16_decode_kernel(const _Float16* __restrict__ in, float* __restrict__ out, int B, int C, long long HW,
-                                   float inv_scale, const unsigned* __restrict__ amax, int bf16) {
+                                   float inv_scale, const unsigned* __restrict__ amax, int bf16, int single) {
     if (amax) inv_scale /= sh16_dyn_extra(*amax);
     const long long n = (long long)B * C * HW;
     const int G = (C + 7) / 8;
@@ -855,13 +856,14 @@ __global__ void sh16_decode_kernel(const _Float16* __restrict__ in, float* __res
         const int c = (int)((i / HW) % C), b = (int)(i / (HW * C));
         const long long unit = (((long long)b * G + c / 8) * 2) * HW + p;
         if (bf16) out[i] = (float)__builtin_bit_cast(__bf16, in[unit * 8 + (c & 7)]) * inv_scale;
+        else if (single) out[i] = (float)in[unit * 8 + (c & 7)] * inv_scale;
         else out[i] = ((float)in[unit * 8 + (c & 7)] + (float)in[(unit + HW) * 8 + (c & 7)]) * inv_scale;
     }
 }
 hipError_t sh16_decode(const void* in, float* out, int B, int C, long long HW, float scale, const unsigned* amax,
-                       hipStream_t s, int bf16) {
+                       hipStream_t s, int bf16, int single) {
     hipLaunchKernelGGL(sh16_decode_kernel, dim3(4096), dim3(256), 0, s, static_cast<const _Float16*>(in), out, B, C, HW,
-                       1.f / scale, amax, bf16);
+                       1.f / scale, amax, bf16, single);
     return hipGetLastError();
 }
 

@@ -1082,7 +1082,8 @@ struct Runner {
         auto it = m.taps.find(name);
         if (it == m.taps.end() || !it->second) return;
         if (m.opt.use_sh16)
-            check(sh16_decode(src, it->second, B, C, (long long)hw, producer.out_scale, m.amax_slots + 2 * producer.index, st, m.opt.terms == 2), "tap decode");
+            check(sh16_decode(src, it->second, B, C, (long long)hw, producer.out_scale, m.amax_slots + 2 * producer.index, st, m.opt.terms == 2,
+                              m.opt.terms != 3), "tap decode");
         else check(hipMemcpyAsync(it->second, src, (size_t)B * C * hw * 4, hipMemcpyDeviceToDevice, st), "tap copy");
     }
     // f32 tensors between kernels are NCHW on the exact-f32 path and C4 ([B][C/4][HW][4]) on the f16x3 path

@@ -66,20 +66,42 @@ def one_hot(labels: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     return oh[:, :LABEL_NC].contiguous()
 
 
-def spade(sd, p, segmap):
-    """normalization.py:249-257 (SPADE.forward): relu(conv 19->128) then two 128->C convs."""
+def _conv3x3(x, w, b):
+    """F.conv2d(x, w, b, padding=1); b may be None.  In float64 with many input channels the same dense sum as nine shifted matrix products:
+    ATen's double conv is parallel over the samples only, which left the float64 references of a few samples on one core each.  fp32 is untouched
+    (bit for bit); a float64 reference moves by its own rounding, about 1e-16 (tests/test_stage_local_model.py holds the two forms to 1e-14)."""
+    if x.dtype != torch.float64 or w.shape[1] < 64:
+        return F.conv2d(x, w, b, padding=1)
+    B, C, H, W = x.shape
+    xp = F.pad(x, (1, 1, 1, 1))
+    out = torch.zeros(B, w.shape[0], H * W, dtype=x.dtype)
+    for t in range(9):
+        out += torch.matmul(w[:, :, t // 3, t % 3], xp[:, :, t // 3:t // 3 + H, t % 3:t % 3 + W].reshape(B, C, H * W))
+    out = out.reshape(B, -1, H, W)
+    return out if b is None else out + b.view(1, -1, 1, 1)
+
+
+def spade(sd, p, segmap, hooks=None):
+    """normalization.py:249-257 (SPADE.forward): relu(conv 19->128) then two 128->C convs.  hooks: see ace."""
     actv = F.relu(F.conv2d(segmap, sd[p + '.mlp_shared.0.weight'], sd[p + '.mlp_shared.0.bias'], padding=1))
-    gamma = F.conv2d(actv, sd[p + '.mlp_gamma.weight'], sd[p + '.mlp_gamma.bias'], padding=1)
-    beta = F.conv2d(actv, sd[p + '.mlp_beta.weight'], sd[p + '.mlp_beta.bias'], padding=1)
+    if hooks and 'actv' in hooks:
+        actv = hooks['actv'](actv)
+    gamma = _conv3x3(actv, sd[p + '.mlp_gamma.weight'], sd[p + '.mlp_gamma.bias'])
+    beta = _conv3x3(actv, sd[p + '.mlp_beta.weight'], sd[p + '.mlp_beta.bias'])
     return gamma, beta
 
 
-def ace(sd, p, x, seg, codes, noise_plane, styled, stats_out=None):
+def ace(sd, p, x, seg, codes, noise_plane, styled, stats_out=None, hooks=None, modulation=None):
     """normalization.py:108-189 (ACE.forward), batched 'else' branch semantics == UI_mode arithmetic
     applied to every sample (SURVEY.md 7 'UI_mode is batch-1 only').
 
     noise_plane: [B, W, H] -- the tensor randn(B, W, H, 1) of normalization.py:111 without its
     trailing 1; ``(n * noise_var).transpose(1, 3)`` gives added[b,c,h,w] = n[b,w,h] * noise_var[c].
+
+    hooks: {'actv' | 'mu' | 'modulation': callable} -- the callable's result takes the place of the SPADE hidden activation, of the
+    projected style codes [B,19,512] or of the final (gamma, beta) pair (tests/stage_local.py: operand rounding, planted faults).
+    modulation: a (gamma, beta) pair that a 'modulation' hook saw earlier for the same labels and codes; it is used as it is, and
+    the SPADE and style branches, which do not depend on x, are not evaluated again.
     """
     B, C, H, W = x.shape
     added = (noise_plane.reshape(B, W, H, 1) * sd[p + '.noise_var']).transpose(1, 3)
@@ -94,9 +116,13 @@ def ace(sd, p, x, seg, codes, noise_plane, styled, stats_out=None):
     # sync_batchnorm/batchnorm.py:52-55, eval: F.batch_norm with running stats, affine=False, eps 1e-5
     normalized = F.batch_norm(xin, sd[p + '.param_free_norm.running_mean'], sd[p + '.param_free_norm.running_var'],
                               None, None, False, 0.1, 1e-5)
+    if modulation is not None:
+        return normalized * (1 + modulation[0]) + modulation[1]
     segmap = F.interpolate(seg, size=(H, W), mode='nearest')          # normalization.py:115
-    gamma_spade, beta_spade = spade(sd, p + '.Spade', segmap)         # :175
+    gamma_spade, beta_spade = spade(sd, p + '.Spade', segmap, hooks)  # :175
     if not styled:                                                    # :183-187 (use_rgb False)
+        if hooks and 'modulation' in hooks:
+            gamma_spade, beta_spade = hooks['modulation'](gamma_spade, beta_spade)
         return normalized * (1 + gamma_spade) + beta_spade
     # :117-153 -- middle_avg[b,:,p] = relu(fc_mu_j(code[b,j])) for j = label(p) (only labels with >=1 px
     # at this resolution are ever written; all others stay zero -- and are never read back).
@@ -104,15 +130,19 @@ def ace(sd, p, x, seg, codes, noise_plane, styled, stats_out=None):
     mu = torch.zeros(B, LABEL_NC, STYLE_LEN, dtype=x.dtype)
     for j in range(LABEL_NC):
         mu[:, j] = F.relu(F.linear(codes[:, j], sd[f'{p}.fc_mu{j}.weight'], sd[f'{p}.fc_mu{j}.bias']))
+    if hooks and 'mu' in hooks:
+        mu = hooks['mu'](mu)
     middle_avg = torch.gather(mu, 1, lab.reshape(B, H * W, 1).expand(B, H * W, STYLE_LEN))
     middle_avg = middle_avg.reshape(B, H, W, STYLE_LEN).permute(0, 3, 1, 2).contiguous()
     middle_avg = middle_avg * segmap.sum(dim=1, keepdim=True)         # pixels of no class are never written (:127-129)
-    gamma_avg = F.conv2d(middle_avg, sd[p + '.conv_gamma.weight'], sd[p + '.conv_gamma.bias'], padding=1)  # :172
-    beta_avg = F.conv2d(middle_avg, sd[p + '.conv_beta.weight'], sd[p + '.conv_beta.bias'], padding=1)    # :173
+    gamma_avg = _conv3x3(middle_avg, sd[p + '.conv_gamma.weight'], sd[p + '.conv_gamma.bias'])  # :172
+    beta_avg = _conv3x3(middle_avg, sd[p + '.conv_beta.weight'], sd[p + '.conv_beta.bias'])    # :173
     ga = torch.sigmoid(sd[p + '.blending_gamma'])                     # :177-178
     ba = torch.sigmoid(sd[p + '.blending_beta'])
     gamma_final = ga * gamma_avg + (1 - ga) * gamma_spade             # :180-181
     beta_final = ba * beta_avg + (1 - ba) * beta_spade
+    if hooks and 'modulation' in hooks:
+        gamma_final, beta_final = hooks['modulation'](gamma_final, beta_final)
     return normalized * (1 + gamma_final) + beta_final                # :182
 
 
