@@ -616,20 +616,41 @@ size_t ch_png_encode_workspace_bytes(int N, int H, int W, int C) {
     return (N >= 1 && N <= 65535 && png_dims_ok(H, W, C)) ? chk::png_encode_workspace_bytes(N, H, W, C) : 0;
 }
 
+namespace {
+// ch_png_encode and ch_png_encode_dist: `fn` names the entry point in the messages
+int png_encode_checked(const char* fn, ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist,
+                       uint8_t* out, int64_t* sizes, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    const std::string f = std::string(fn) + ": ";
+    if (!img || !out || !sizes || !workspace) return fail(h, CH_ERR_ARG, f + "null pointer");
+    if (C != 1 && C != 3 && C != 4) return fail(h, CH_ERR_ARG, f + "C must be 1, 3 or 4");
+    if (filter < -1 || filter > 4) return fail(h, CH_ERR_ARG, f + "filter must be -1 (adaptive) or 0..4");
+    if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, f + "N outside 1..65535");
+    if (!png_dims_ok(H, W, C)) return fail(h, CH_ERR_ARG, f + "image too small or too large (sides 1..32768, H * W <= 2^30)");
+    if (ndist < 0 || ndist > 3) return fail(h, CH_ERR_ARG, f + "ndist outside 0..3");
+    if (ndist > 0 && !dist) return fail(h, CH_ERR_ARG, f + "dist is null with ndist > 0");
+    for (int k = 0; k < ndist; ++k) {
+        if (dist[k] < 2 || dist[k] > 32767) return fail(h, CH_ERR_ARG, f + "distance outside 2..32767 (distance 1 is always present)");
+        for (int j = 0; j < k; ++j)
+            if (dist[j] == dist[k]) return fail(h, CH_ERR_ARG, f + "duplicate distance");
+    }
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
+    if (workspace_bytes < chk::png_encode_workspace_bytes(N, H, W, C))
+        return fail(h, CH_ERR_ARG, f + "workspace smaller than ch_png_encode_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::png_encode_dist(img, N, H, W, C, filter, dist, ndist, out, sizes, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, f + hipGetErrorString(e));
+}
+}  // namespace
+
 int ch_png_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes, void* workspace,
                   size_t workspace_bytes, ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!img || !out || !sizes || !workspace) return fail(h, CH_ERR_ARG, "ch_png_encode: null pointer");
-    if (C != 1 && C != 3 && C != 4) return fail(h, CH_ERR_ARG, "ch_png_encode: C must be 1, 3 or 4");
-    if (filter < -1 || filter > 4) return fail(h, CH_ERR_ARG, "ch_png_encode: filter must be -1 (adaptive) or 0..4");
-    if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, "ch_png_encode: N outside 1..65535");
-    if (!png_dims_ok(H, W, C)) return fail(h, CH_ERR_ARG, "ch_png_encode: image too small or too large (sides 1..32768, H * W <= 2^30)");
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, "ch_png_encode: workspace not 16-byte aligned");
-    if (workspace_bytes < chk::png_encode_workspace_bytes(N, H, W, C))
-        return fail(h, CH_ERR_ARG, "ch_png_encode: workspace smaller than ch_png_encode_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::png_encode(img, N, H, W, C, filter, out, sizes, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_png_encode: ") + hipGetErrorString(e));
+    return png_encode_checked("ch_png_encode", h, img, N, H, W, C, filter, nullptr, 0, out, sizes, workspace, workspace_bytes, stream);
+}
+
+int ch_png_encode_dist(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist, uint8_t* out,
+                       int64_t* sizes, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    return png_encode_checked("ch_png_encode_dist", h, img, N, H, W, C, filter, dist, ndist, out, sizes, workspace, workspace_bytes, stream);
 }
 
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {

@@ -257,5 +257,8 @@ constexpr int PNG_CHUNK = 32768;              // == ch_png_chunk_bytes(): bytes 
 size_t png_zlib_bound(int H, int W, int C);
 size_t png_encode_workspace_bytes(int N, int H, int W, int C);
 hipError_t png_encode(const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes, void* ws, hipStream_t s);
+// the same with matches at ndist (0..3) further distances dist[] (host values, 2..32767, distinct); ndist = 0 is png_encode
+hipError_t png_encode_dist(const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist, uint8_t* out,
+                           int64_t* sizes, void* ws, hipStream_t s);
 
 }  // namespace chk

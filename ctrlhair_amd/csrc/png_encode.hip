@@ -3,6 +3,8 @@
 //   png_filter_kernel    the PNG row filters (RFC 2083 section 6): type byte + filtered row, H * (1 + W * C) bytes per image
 //   png_deflate_kernel   one workgroup per PNG_CHUNK bytes of that stream: distance-1 run matching, a dynamic Huffman code per chunk,
 //                        or a stored block where that is not smaller; every chunk starts and ends on a byte
+//   png_deflate_dist_kernel   the same with matches at up to three further distances the caller gives (ch_png_encode_dist): a position
+//                        goes to the distance whose interval of x[i] == x[i - d] around it is longest -- the rule stands above the kernel
 //   png_gather_kernel    scans the chunk sizes, packs the chunks behind the zlib header, sums the Adler-32 pairs, appends the trailer
 // Determinism: the only atomics are integer add (histograms, counts, checksum sums) and integer or (bits into LDS words); both commute
 // and associate exactly, every other value is a pure function of the chunk's bytes, and a chunk never looks outside itself.  The bytes
@@ -25,9 +27,9 @@ constexpr int SLOT = PNG_CHUNK + 16;                     // bytes a chunk may ta
 constexpr uint32_t ADLER_MOD = 65521;
 constexpr int NLL = 286, NCL = 19;                       // literal/length and code-length alphabets
 constexpr int LL_PAD = 288;
-constexpr int CLSEQ_MAX = 2 * NT;                        // code-length symbols of one header (at most 287), two per thread
+constexpr int CLSEQ_MAX = 2 * NT;                        // code-length symbols of one header (at most 286 + 30), two per thread
 static_assert(SEG * NT == PNG_CHUNK && SEG % 16 == 0 && SEG < 258, "a thread's segment: 16-byte groups, shorter than one full match");
-static_assert(NLL + 1 <= CLSEQ_MAX, "header sequence fits");
+static_assert(NLL + 30 <= CLSEQ_MAX, "header sequence fits");
 
 struct Layout {                                          // workspace sections, every one 256-byte aligned
     size_t fpad, nchunks, filt, slots, csize, cadler, total;
@@ -258,6 +260,41 @@ __device__ void huff_build(const uint32_t* freq, int n, int maxbits, uint8_t* le
 
 __device__ __forceinline__ int cl_extra_bits(int sym) { return sym == 16 ? 2 : sym == 17 ? 3 : sym == 18 ? 7 : 0; }
 
+// The header's code-length sequence (RFC 1951 3.2.7), run-length coded with the symbols 16 / 17 / 18 as zlib does: `total` lengths
+// len_at(0..total-1), the literal/length lengths followed by the distance lengths.  One thread calls; returns the number of symbols.
+template <class F>
+__device__ __forceinline__ int cl_sequence(int total, F len_at, uint8_t* seq_sym, uint8_t* seq_ext) {
+    int ns = 0, i = 0;
+    while (i < total) {
+        const int v = len_at(i);
+        int r = 1;
+        while (i + r < total && len_at(i + r) == v) ++r;
+        i += r;
+        if (v == 0) {
+            while (r >= 11) {
+                const int t = r < 138 ? r : 138;
+                seq_sym[ns] = 18, seq_ext[ns++] = (uint8_t)(t - 11);
+                r -= t;
+            }
+            if (r >= 3) {
+                seq_sym[ns] = 17, seq_ext[ns++] = (uint8_t)(r - 3);
+                r = 0;
+            }
+            while (r-- > 0) seq_sym[ns] = 0, seq_ext[ns++] = 0;
+        } else {
+            seq_sym[ns] = (uint8_t)v, seq_ext[ns++] = 0;
+            --r;
+            while (r >= 3) {
+                const int t = r < 6 ? r : 6;
+                seq_sym[ns] = 16, seq_ext[ns++] = (uint8_t)(t - 3);
+                r -= t;
+            }
+            while (r-- > 0) seq_sym[ns] = (uint8_t)v, seq_ext[ns++] = 0;
+        }
+    }
+    return ns;
+}
+
 }  // namespace
 
 // ---- row filters -----------------------------------------------------------------------------------------------------------------------
@@ -429,7 +466,375 @@ __device__ __forceinline__ int walk(DeflateShared& sh, int a, int b, int len, in
     return bits;
 }
 
+template <int P>
+struct Pass {
+    static constexpr int value = P;
+};
+
+// What follows the literal/length code of a chunk, for both deflate kernels (every thread calls): the header with its code-length
+// code, the body or the stored form, the copy to the chunk's slot.  ndc distance lengths dlen_at(0..ndc-1) follow the literal/length
+// lengths in the header; walk(Pass<1>, -) returns the bits of the thread's tokens, walk(Pass<2>, writer) writes them.
+template <class DLen, class Walk>
+__device__ __forceinline__ void finish_chunk(DeflateShared& sh, int len, int ndc, DLen dlen_at, Walk walk, uint8_t* __restrict__ slot,
+                                             int* __restrict__ csize, uint32_t* __restrict__ cadler) {
+    const int tid = threadIdx.x;
+    // the header's code-length sequence (RFC 1951 3.2.7): nlit literal/length lengths and the ndc distance lengths, run-length coded
+    if (tid == 0) {
+        int nlit = NLL;
+        while (nlit > 257 && sh.ll_len[nlit - 1] == 0) --nlit;
+        sh.nlit = nlit;
+        const uint8_t* ll = sh.ll_len;
+        const int ns = cl_sequence(nlit + ndc, [ll, nlit, dlen_at](int i) -> int { return i < nlit ? ll[i] : dlen_at(i - nlit); },
+                                   sh.seq_sym, sh.seq_ext);
+        sh.nseq = ns;
+        for (int k = 0; k < ns; ++k) sh.cl_hist[sh.seq_sym[k]] += 1;
+    }
+    huff_build(sh.cl_hist, NCL, 7, sh.cl_len, sh.cl_code, sh.hs);
+
+    if (tid == 0) {                                                                 // the fixed part of the header
+        const uint8_t order[NCL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+        int ncl = NCL;
+        while (ncl > 4 && sh.cl_len[order[ncl - 1]] == 0) --ncl;
+        BitWriter bw;
+        bw.begin(sh.out, 0);
+        bw.put(0u | (2u << 1), 3);                                                  // BFINAL 0, BTYPE 10
+        bw.put((uint32_t)(sh.nlit - 257), 5);
+        bw.put((uint32_t)(ndc - 1), 5);                                             // HDIST
+        bw.put((uint32_t)(ncl - 4), 4);
+        for (int k = 0; k < ncl; ++k) bw.put(sh.cl_len[order[k]], 3);
+        bw.end();
+        sh.hdr_fixed = 17 + 3 * ncl;
+    }
+    __syncthreads();
+    int total = 0;
+    {
+        const int nseq = sh.nseq;
+        int bits = 0;
+        for (int k = 2 * tid; k < 2 * tid + 2 && k < nseq; ++k) bits += sh.cl_len[sh.seq_sym[k]] + cl_extra_bits(sh.seq_sym[k]);
+        const int off = scan_add_excl(bits, sh.scan, &total);
+        BitWriter bw;
+        bw.begin(sh.out, sh.hdr_fixed + off);
+        for (int k = 2 * tid; k < 2 * tid + 2 && k < nseq; ++k) {
+            const int sym = sh.seq_sym[k];
+            bw.put(sh.cl_code[sym], sh.cl_len[sym]);
+            if (sym >= 16) bw.put(sh.seq_ext[k], cl_extra_bits(sym));
+        }
+        bw.end();
+    }
+    const int hdr_bits = sh.hdr_fixed + total;
+
+    const int mybits = walk(Pass<1>{}, nullptr);
+    int body = 0;
+    const int off = scan_add_excl(mybits, sh.scan, &body);
+    const int block_bits = hdr_bits + body + sh.ll_len[256];
+    const int coded_bytes = (block_bits + 3 + 7) / 8 + 4;                           // + the empty stored block that realigns: 000, pad, 00 00 FF FF
+    int nbytes;
+    if (coded_bytes < 5 + len) {                                                    // (uniform)
+        nbytes = coded_bytes;
+        BitWriter bw;
+        bw.begin(sh.out, hdr_bits + off);
+        walk(Pass<2>{}, &bw);
+        bw.end();
+        if (tid == 0) {
+            BitWriter e;
+            e.begin(sh.out, hdr_bits + body);
+            e.put(sh.ll_code[256], sh.ll_len[256]);
+            e.end();
+            const int p = coded_bytes - 2;                                          // the bytes FF FF
+            atomicOr(&sh.out[p >> 2], 0xFFu << (8 * (p & 3)));
+            atomicOr(&sh.out[(p + 1) >> 2], 0xFFu << (8 * ((p + 1) & 3)));
+        }
+    } else {
+        nbytes = 5 + len;
+        __syncthreads();                                                            // the header bits in out are dead: overwrite them
+        const uint8_t* d = reinterpret_cast<const uint8_t*>(sh.data);
+        uint8_t* o = reinterpret_cast<uint8_t*>(sh.out);
+        if (tid == 0) {
+            o[0] = 0;                                                               // BFINAL 0, BTYPE 00
+            o[1] = (uint8_t)(len & 255), o[2] = (uint8_t)(len >> 8);                // (len = 32768 fits 16 bits)
+            o[3] = (uint8_t)(~len & 255), o[4] = (uint8_t)((~len >> 8) & 255);
+        }
+        for (int i = tid; i < len; i += NT) o[5 + i] = (uint8_t)ld(d, i);
+    }
+    __syncthreads();
+    uint4* dst = reinterpret_cast<uint4*>(slot);
+    const uint4* o4 = reinterpret_cast<const uint4*>(sh.out);
+    for (int i = tid; i < (nbytes + 15) / 16; i += NT) dst[i] = o4[i];              // nbytes <= 5 + PNG_CHUNK <= SLOT
+    if (tid == 0) {
+        *csize = nbytes;
+        cadler[0] = sh.s1 % ADLER_MOD;
+        cadler[1] = sh.s2 % ADLER_MOD;
+    }
+}
+
+// ---- the same with caller-given match distances ------------------------------------------------------------------------------------------
+// Distances d[0] = 1, d[1..NK-1] the caller's, in priority order.  eq_d[i] = (i >= d and x[i] == x[i - d]); the maximal true intervals of
+// eq_d are the match intervals of d.  Position i belongs to the distance whose interval containing i is longest (a tie goes to the
+// earlier distance); if that interval is shorter than 3, i is a literal.  A class run is a maximal run of positions of one distance; it
+// lies inside one interval of that distance, so every byte of it repeats the byte d before it.  A class run of R positions from p is
+// coded as floor(R / 258) matches (258, d) at p + 258 k and then the remainder, one match if it is >= 3, else literals.  All of it is a
+// pure function of the chunk's bytes and the list.  Per distance a thread holds eq_d of its segment as a 128-bit mask; the interval that
+// enters and the one that leaves the segment come from the two scans of the distance-1 kernel, distance after distance through the same LDS
+// arrays, the results kept in registers; a second pair of scans does the same for class runs.  The class of a position is recomputed
+// from the masks in every walk, piece by piece (a piece: positions between two interval boundaries of any distance -- one class).
+typedef unsigned __int128 u128;
+constexpr int LIT = -1;
+constexpr int NDSYM = 30;                                                           // distance alphabet
+
+struct PngDistances {
+    int d[4];                                                                       // d[0] = 1
+};
+
+struct DeflateDistShared : DeflateShared {
+    uint32_t d_hist[32];
+    uint8_t d_len[32];
+    uint16_t d_code[32];
+    int8_t cfirst[NT], clast[NT];                                                   // class of a segment's first and last position
+};
+
+__device__ __forceinline__ int ctz128(u128 m) {
+    const uint64_t lo = (uint64_t)m, hi = (uint64_t)(m >> 64);
+    return lo ? __builtin_ctzll(lo) : hi ? 64 + __builtin_ctzll(hi) : 128;
+}
+__device__ __forceinline__ int clz128(u128 m) {
+    const uint64_t lo = (uint64_t)m, hi = (uint64_t)(m >> 64);
+    return hi ? __builtin_clzll(hi) : lo ? 64 + __builtin_clzll(lo) : 128;
+}
+
+// distance 1..32768 -> (symbol 0..29, extra bits, extra value)   (RFC 1951 section 3.2.5)
+__device__ __forceinline__ void distance_code(int dist, int& sym, int& nextra, int& extra) {
+    const int t = dist - 1;
+    if (t < 4) {
+        sym = t, nextra = 0, extra = 0;
+    } else {
+        const int nb = 30 - __clz(t);                                               // floor(log2 t) - 1
+        sym = 2 * nb + 2 + ((t >> nb) & 1);
+        nextra = nb;
+        extra = t & ((1 << nb) - 1);
+    }
+}
+
+template <int NK>
+struct Segment {                                                                    // what a thread knows of its bytes [a, b)
+    u128 eq[NK];                                                                    // bit j: eq_d[a + j]   (0 from b on)
+    int enter[NK], leave[NK];                                                       // start of the interval that enters at a, end of the one that leaves at b - 1; -1: none
+    int dsym[NK], dnx[NK], dx[NK];                                                  // the distances' codes
+    int a, b;
+    int cprev, cnext;                                                               // class of a - 1 and of b (LIT outside the chunk)
+    int cstart, cend;                                                               // the class run entering at a starts here, the one leaving at b - 1 ends here
+};
+
+// the piece that holds position i (a <= i < b): its class; nx = the first position behind it (i < nx <= b)
+template <int NK>
+__device__ __forceinline__ int piece(const Segment<NK>& g, int i, int& nx) {
+    const int j = i - g.a;                                                          // 0..127
+    int best = LIT, blen = 2, next = g.b;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const u128 m = g.eq[k] >> j;
+        if ((uint64_t)m & 1) {
+            const int up = ctz128(~m);                                              // true bits from j upwards: 1..128 - j
+            const int down = clz128(~(g.eq[k] << (127 - j)));                       // and from j downwards: 1..j + 1
+            const int hi = i + up - 1, lo = i - down + 1;
+            const int e = (hi == g.b - 1 && g.leave[k] >= 0) ? g.leave[k] : hi;
+            const int s = (lo == g.a && g.enter[k] >= 0) ? g.enter[k] : lo;
+            if (e - s + 1 > blen) blen = e - s + 1, best = k;                       // (strictly longer: a tie stays with the earlier distance)
+            next = hi + 1 < next ? hi + 1 : next;
+        } else {
+            const int z = i + ctz128(m);                                            // the next true bit, or >= b
+            next = z < next ? z : next;
+        }
+    }
+    nx = next > i ? next : i + 1;
+    return best;
+}
+
+// the tokens that start in [a, b): PASS 0 counts symbols, PASS 1 returns their bits, PASS 2 writes them
+template <int PASS, int NK>
+__device__ __forceinline__ int walk_dist(DeflateDistShared& sh, const Segment<NK>& g, BitWriter* bw) {
+    const uint8_t* d = reinterpret_cast<const uint8_t*>(sh.data);
+    int bits = 0;
+    auto literal = [&](int q) {
+        const int v = ld(d, q);
+        if (PASS == 0) atomicAdd(&sh.hist[v], 1u);
+        else if (PASS == 1) bits += sh.ll_len[v];
+        else bw->put(sh.ll_code[v], sh.ll_len[v]);
+    };
+    auto match = [&](int n, int c) {
+        int lsym, lnx, lx, dsym = 0, dnx = 0, dx = 0;
+        length_code(n, lsym, lnx, lx);
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+            if (c == k) dsym = g.dsym[k], dnx = g.dnx[k], dx = g.dx[k];
+        if (PASS == 0) {
+            atomicAdd(&sh.hist[lsym], 1u);
+            atomicAdd(&sh.d_hist[dsym], 1u);
+        } else if (PASS == 1) {
+            bits += sh.ll_len[lsym] + lnx + sh.d_len[dsym] + dnx;
+        } else {
+            bw->put(sh.ll_code[lsym], sh.ll_len[lsym]);
+            if (lnx) bw->put((uint32_t)lx, lnx);
+            bw->put(sh.d_code[dsym], sh.d_len[dsym]);
+            if (dnx) bw->put((uint32_t)dx, dnx);
+        }
+    };
+    int i = g.a, nx = g.a, c = LIT;
+    if (i < g.b) c = piece(g, i, nx);
+    while (i < g.b) {
+        if (c == LIT) {
+            for (int q = i; q < nx; ++q) literal(q);
+            i = nx;
+            if (i < g.b) c = piece(g, i, nx);
+            continue;
+        }
+        const int lo = i, c0 = c;                                                   // the part [lo, hi] of a class run of c0
+        do {
+            i = nx;
+            if (i < g.b) c = piece(g, i, nx);
+        } while (i < g.b && c == c0);
+        const int hi = i - 1;
+        const int p = (lo == g.a && g.cprev == c0) ? g.cstart : lo;
+        const int e = (i == g.b && g.cnext == c0) ? g.cend : hi;
+        const int R = e - p + 1, full = R / 258, rem = R - full * 258, pr = p + 258 * full;
+        // full matches start at p + 258 k, k < full; a segment is shorter than 258: at most one of them starts in [lo, hi]
+        const int k = (lo - p + 257) / 258;
+        if (k < full && p + 258 * k <= hi) match(258, c0);
+        if (rem >= 3) {
+            if (pr >= lo && pr <= hi) match(rem, c0);
+        } else {
+            for (int q = pr > lo ? pr : lo; q <= hi; ++q) literal(q);               // (at most two; pr + rem - 1 = e >= hi)
+        }
+    }
+    return bits;
+}
+
 }  // namespace
+
+template <int NK>
+__global__ __launch_bounds__(NT) void png_deflate_dist_kernel(const uint8_t* __restrict__ filt, size_t fpad, size_t F, size_t nchunks,
+                                                              PngDistances D, uint8_t* __restrict__ slots, int* __restrict__ csize,
+                                                              uint32_t* __restrict__ cadler) {
+    __shared__ DeflateDistShared sh;
+    const int tid = threadIdx.x;
+    const size_t chunk = blockIdx.x, n = blockIdx.y;
+    const size_t begin = chunk * PNG_CHUNK;
+    const int len = (int)(F - begin < (size_t)PNG_CHUNK ? F - begin : (size_t)PNG_CHUNK);      // 1..PNG_CHUNK
+    const uint8_t* src = filt + n * fpad + begin;                                   // 16-byte aligned; fpad rounds the image up to 16
+    uint8_t* d = reinterpret_cast<uint8_t*>(sh.data);
+
+    for (int i = tid * 16; i < len; i += NT * 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(src + i);
+        uint32_t* p = sh.data + ((i >> 7) * SEGP + (i & (SEG - 1))) / 4;
+        p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
+    }
+    for (int i = tid; i < SLOT / 4; i += NT) sh.out[i] = 0;
+    for (int i = tid; i < LL_PAD; i += NT) sh.hist[i] = 0;
+    if (tid < 32) sh.cl_hist[tid] = 0, sh.d_hist[tid] = 0;
+    if (tid == 0) sh.s1 = 0, sh.s2 = 0;
+    __syncthreads();
+
+    Segment<NK> g;
+    const int a = tid * SEG, b = a + SEG < len ? a + SEG : len;                     // a >= len: an idle thread (a short last chunk)
+    g.a = a, g.b = b;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        g.eq[k] = 0;
+        distance_code(D.d[k], g.dsym[k], g.dnx[k], g.dx[k]);
+    }
+    // the eq masks and the Adler-32 sums of the segment
+    {
+        uint32_t s1 = 0, s2 = 0;                                                    // s2 = sum (b - i) d[i] <= 255 * 128 * 129 / 2
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            uint64_t part[NK];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) part[k] = 0;
+            for (int j = 0; j < 64; ++j) {
+                const int i = a + 64 * w + j;
+                if (i < b) {
+                    const int v = ld(d, i);
+                    s1 += (uint32_t)v;
+                    s2 += (uint32_t)(b - i) * (uint32_t)v;
+#pragma unroll
+                    for (int k = 0; k < NK; ++k)
+                        if (i >= D.d[k] && ld(d, i - D.d[k]) == v) part[k] |= 1ull << j;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NK; ++k) g.eq[k] |= (u128)part[k] << (64 * w);
+        }
+        if (a < b) {
+            // Adler-32 of the image: A = 1 + sum d, B = F + sum (F - pos) d; (F - pos) = (b - i) + (F - begin - b)
+            const uint32_t after = (uint32_t)((F - begin - (size_t)b) % ADLER_MOD);
+            const uint32_t t2 = (uint32_t)(((uint64_t)after * s1 + s2) % ADLER_MOD);
+            atomicAdd(&sh.s1, s1);                                                  // <= 255 * 32768: no overflow
+            atomicAdd(&sh.s2, t2);                                                  // <= 256 * 65520
+        }
+    }
+    // per distance: the interval that enters the segment and the one that leaves it
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int dk = D.d[k];
+        const bool busy = a < b;
+        const bool prevbit = busy && a > 0 && a - 1 >= dk && ld(d, a - 1) == ld(d, a - 1 - dk);
+        const bool nextbit = busy && b < len && b >= dk && ld(d, b) == ld(d, b - dk);
+        const u128 m = g.eq[k];
+        const u128 starts = m & ~((m << 1) | (u128)(prevbit ? 1 : 0));
+        const u128 ends = m & ~((m >> 1) | (nextbit ? (u128)1 << (b - 1 - a) : (u128)0));
+        const int last_start = starts ? a + 127 - clz128(starts) : -1;
+        const int first_end = ends ? a + ctz128(ends) : INT_MAX;
+        const int smax = scan_max_incl(last_start, sh.scan);
+        const int emin = scan_min_incl_rev(first_end, sh.scan);
+        // a thread needs its predecessor's inclusive maximum and its successor's inclusive minimum: pass them through LDS
+        sh.smax_all[tid] = smax;
+        sh.emin_all[tid] = emin;
+        __syncthreads();
+        g.enter[k] = (busy && ((uint64_t)m & 1) && prevbit) ? sh.smax_all[tid - 1] : -1;            // (prevbit: tid > 0)
+        g.leave[k] = (busy && nextbit && ((uint64_t)(m >> (b - 1 - a)) & 1)) ? sh.emin_all[tid + 1] : -1;   // (nextbit: b < len, tid < NT - 1)
+    }
+    // class runs: the neighbours' classes, then the same two scans
+    {
+        int nx;
+        sh.cfirst[tid] = (int8_t)(a < b ? piece(g, a, nx) : LIT);
+        sh.clast[tid] = (int8_t)(a < b ? piece(g, b - 1, nx) : LIT);
+        __syncthreads();
+        g.cprev = tid > 0 ? sh.clast[tid - 1] : LIT;
+        g.cnext = tid < NT - 1 ? sh.cfirst[tid + 1] : LIT;
+        int last_start = -1, first_end = INT_MAX, pc = g.cprev;
+        for (int i = a; i < b; i = nx) {
+            const int c = piece(g, i, nx);
+            if (c != pc) {
+                if (c != LIT) last_start = i;
+                if (pc != LIT && i > a && first_end == INT_MAX) first_end = i - 1;
+            }
+            pc = c;
+        }
+        if (a < b && pc != LIT && pc != g.cnext && first_end == INT_MAX) first_end = b - 1;
+        const int smax = scan_max_incl(last_start, sh.scan);
+        const int emin = scan_min_incl_rev(first_end, sh.scan);
+        sh.smax_all[tid] = smax;
+        sh.emin_all[tid] = emin;
+        __syncthreads();
+        g.cstart = tid > 0 ? sh.smax_all[tid - 1] : 0;
+        g.cend = tid < NT - 1 ? sh.emin_all[tid + 1] : len - 1;
+    }
+
+    if (tid == 0) atomicAdd(&sh.hist[256], 1u);                                     // end of block
+    walk_dist<0>(sh, g, nullptr);
+    huff_build(sh.hist, NLL, 15, sh.ll_len, sh.ll_code, sh.hs);
+    // the distance code: a real length-limited code over the used symbols (at most NK); one used symbol, or none, gets one bit
+    huff_build(sh.d_hist, NDSYM, 15, sh.d_len, sh.d_code, sh.hs);
+    int ndc = NDSYM;
+    while (ndc > 1 && sh.d_len[ndc - 1] == 0) --ndc;
+    const bool none = ndc == 1 && sh.d_len[0] == 0;                                 // no match at all: symbol 0 with one bit, as in png_deflate_kernel
+    __syncthreads();
+    if (none && tid == 0) sh.d_len[0] = 1;
+    const uint8_t* dl = sh.d_len;
+    finish_chunk(
+        sh, len, ndc, [dl](int i) -> int { return dl[i]; },
+        [&](auto pass, BitWriter* bw) -> int { return walk_dist<decltype(pass)::value>(sh, g, bw); },
+        slots + (n * nchunks + chunk) * SLOT, csize + n * nchunks + chunk, cadler + 2 * (n * nchunks + chunk));
+}
 
 __global__ __launch_bounds__(NT) void png_deflate_kernel(const uint8_t* __restrict__ filt, size_t fpad, size_t F, size_t nchunks,
                                                          uint8_t* __restrict__ slots, int* __restrict__ csize,
@@ -490,120 +895,11 @@ __global__ __launch_bounds__(NT) void png_deflate_kernel(const uint8_t* __restri
     if (tid == 0) atomicAdd(&sh.hist[256], 1u);                                     // end of block
     walk<0>(sh, a, b, len, cstart, cend, nullptr);
     huff_build(sh.hist, NLL, 15, sh.ll_len, sh.ll_code, sh.hs);
-
-    // the header's code-length sequence (RFC 1951 3.2.7): nlit literal/length lengths and the one distance length, run-length coded
-    if (tid == 0) {
-        int nlit = NLL;
-        while (nlit > 257 && sh.ll_len[nlit - 1] == 0) --nlit;
-        sh.nlit = nlit;
-        const int total = nlit + 1;
-        int ns = 0, i = 0;
-        while (i < total) {
-            const int v = i < nlit ? sh.ll_len[i] : 1;
-            int r = 1;
-            while (i + r < total && (i + r < nlit ? sh.ll_len[i + r] : 1) == v) ++r;
-            i += r;
-            if (v == 0) {
-                while (r >= 11) {
-                    const int t = r < 138 ? r : 138;
-                    sh.seq_sym[ns] = 18, sh.seq_ext[ns++] = (uint8_t)(t - 11);
-                    r -= t;
-                }
-                if (r >= 3) {
-                    sh.seq_sym[ns] = 17, sh.seq_ext[ns++] = (uint8_t)(r - 3);
-                    r = 0;
-                }
-                while (r-- > 0) sh.seq_sym[ns] = 0, sh.seq_ext[ns++] = 0;
-            } else {
-                sh.seq_sym[ns] = (uint8_t)v, sh.seq_ext[ns++] = 0;
-                --r;
-                while (r >= 3) {
-                    const int t = r < 6 ? r : 6;
-                    sh.seq_sym[ns] = 16, sh.seq_ext[ns++] = (uint8_t)(t - 3);
-                    r -= t;
-                }
-                while (r-- > 0) sh.seq_sym[ns] = (uint8_t)v, sh.seq_ext[ns++] = 0;
-            }
-        }
-        sh.nseq = ns;
-        for (int k = 0; k < ns; ++k) sh.cl_hist[sh.seq_sym[k]] += 1;
-    }
-    huff_build(sh.cl_hist, NCL, 7, sh.cl_len, sh.cl_code, sh.hs);
-
-    if (tid == 0) {                                                                 // the fixed part of the header
-        const uint8_t order[NCL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        int ncl = NCL;
-        while (ncl > 4 && sh.cl_len[order[ncl - 1]] == 0) --ncl;
-        BitWriter bw;
-        bw.begin(sh.out, 0);
-        bw.put(0u | (2u << 1), 3);                                                  // BFINAL 0, BTYPE 10
-        bw.put((uint32_t)(sh.nlit - 257), 5);
-        bw.put(0, 5);                                                               // one distance code
-        bw.put((uint32_t)(ncl - 4), 4);
-        for (int k = 0; k < ncl; ++k) bw.put(sh.cl_len[order[k]], 3);
-        bw.end();
-        sh.hdr_fixed = 17 + 3 * ncl;
-    }
-    __syncthreads();
-    int total = 0;
-    {
-        const int nseq = sh.nseq;
-        int bits = 0;
-        for (int k = 2 * tid; k < 2 * tid + 2 && k < nseq; ++k) bits += sh.cl_len[sh.seq_sym[k]] + cl_extra_bits(sh.seq_sym[k]);
-        const int off = scan_add_excl(bits, sh.scan, &total);
-        BitWriter bw;
-        bw.begin(sh.out, sh.hdr_fixed + off);
-        for (int k = 2 * tid; k < 2 * tid + 2 && k < nseq; ++k) {
-            const int sym = sh.seq_sym[k];
-            bw.put(sh.cl_code[sym], sh.cl_len[sym]);
-            if (sym >= 16) bw.put(sh.seq_ext[k], cl_extra_bits(sym));
-        }
-        bw.end();
-    }
-    const int hdr_bits = sh.hdr_fixed + total;
-
-    const int mybits = walk<1>(sh, a, b, len, cstart, cend, nullptr);
-    int body = 0;
-    const int off = scan_add_excl(mybits, sh.scan, &body);
-    const int block_bits = hdr_bits + body + sh.ll_len[256];
-    const int coded_bytes = (block_bits + 3 + 7) / 8 + 4;                           // + the empty stored block that realigns: 000, pad, 00 00 FF FF
-    int nbytes;
-    if (coded_bytes < 5 + len) {                                                    // (uniform)
-        nbytes = coded_bytes;
-        BitWriter bw;
-        bw.begin(sh.out, hdr_bits + off);
-        walk<2>(sh, a, b, len, cstart, cend, &bw);
-        bw.end();
-        if (tid == 0) {
-            BitWriter e;
-            e.begin(sh.out, hdr_bits + body);
-            e.put(sh.ll_code[256], sh.ll_len[256]);
-            e.end();
-            const int p = coded_bytes - 2;                                          // the bytes FF FF
-            atomicOr(&sh.out[p >> 2], 0xFFu << (8 * (p & 3)));
-            atomicOr(&sh.out[(p + 1) >> 2], 0xFFu << (8 * ((p + 1) & 3)));
-        }
-    } else {
-        nbytes = 5 + len;
-        __syncthreads();                                                            // the header bits in out are dead: overwrite them
-        uint8_t* o = reinterpret_cast<uint8_t*>(sh.out);
-        if (tid == 0) {
-            o[0] = 0;                                                               // BFINAL 0, BTYPE 00
-            o[1] = (uint8_t)(len & 255), o[2] = (uint8_t)(len >> 8);                // (len = 32768 fits 16 bits)
-            o[3] = (uint8_t)(~len & 255), o[4] = (uint8_t)((~len >> 8) & 255);
-        }
-        for (int i = tid; i < len; i += NT) o[5 + i] = (uint8_t)ld(d, i);
-    }
-    __syncthreads();
-    const size_t ci = n * nchunks + chunk;
-    uint4* dst = reinterpret_cast<uint4*>(slots + ci * SLOT);
-    const uint4* o4 = reinterpret_cast<const uint4*>(sh.out);
-    for (int i = tid; i < (nbytes + 15) / 16; i += NT) dst[i] = o4[i];              // nbytes <= 5 + PNG_CHUNK <= SLOT
-    if (tid == 0) {
-        csize[ci] = nbytes;
-        cadler[2 * ci] = sh.s1 % ADLER_MOD;
-        cadler[2 * ci + 1] = sh.s2 % ADLER_MOD;
-    }
+    // only distance symbol 0 exists: one distance length, 1
+    finish_chunk(
+        sh, len, 1, [](int) -> int { return 1; },
+        [&](auto pass, BitWriter* bw) -> int { return walk<decltype(pass)::value>(sh, a, b, len, cstart, cend, bw); },
+        slots + (n * nchunks + chunk) * SLOT, csize + n * nchunks + chunk, cadler + 2 * (n * nchunks + chunk));
 }
 
 // ---- gather -----------------------------------------------------------------------------------------------------------------------------
@@ -682,7 +978,9 @@ size_t png_zlib_bound(int H, int W, int C) {
 
 size_t png_encode_workspace_bytes(int N, int H, int W, int C) { return layout(N, H, W, C).total; }
 
-hipError_t png_encode(const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes, void* ws, hipStream_t s) {
+// dist: ndist (0..3) host values, checked by the caller; ndist = 0 launches the distance-1 kernel, whose bytes are those of every release
+hipError_t png_encode_dist(const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist, uint8_t* out,
+                           int64_t* sizes, void* ws, hipStream_t s) {
     const Layout L = layout(N, H, W, C);
     const size_t F = (size_t)H * (1 + (size_t)W * C);
     uint8_t* base = static_cast<uint8_t*>(ws);
@@ -693,13 +991,26 @@ hipError_t png_encode(const uint8_t* img, int N, int H, int W, int C, int filter
     hipLaunchKernelGGL(png_filter_kernel, dim3(H, N), dim3(NT), 0, s, img, H, W, C, filter, filt, L.fpad);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(png_deflate_kernel, dim3((unsigned)L.nchunks, N), dim3(NT), 0, s, filt, L.fpad, F, L.nchunks, slots, csize, cadler);
+    const dim3 grid((unsigned)L.nchunks, N);
+    PngDistances D = {{1, 0, 0, 0}};
+    for (int k = 0; k < ndist; ++k) D.d[1 + k] = dist[k];
+    switch (ndist) {
+        case 0: hipLaunchKernelGGL(png_deflate_kernel, grid, dim3(NT), 0, s, filt, L.fpad, F, L.nchunks, slots, csize, cadler); break;
+        case 1: hipLaunchKernelGGL(png_deflate_dist_kernel<2>, grid, dim3(NT), 0, s, filt, L.fpad, F, L.nchunks, D, slots, csize, cadler); break;
+        case 2: hipLaunchKernelGGL(png_deflate_dist_kernel<3>, grid, dim3(NT), 0, s, filt, L.fpad, F, L.nchunks, D, slots, csize, cadler); break;
+        case 3: hipLaunchKernelGGL(png_deflate_dist_kernel<4>, grid, dim3(NT), 0, s, filt, L.fpad, F, L.nchunks, D, slots, csize, cadler); break;
+        default: return hipErrorInvalidValue;
+    }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const unsigned gb = (unsigned)(L.nchunks < 64 ? L.nchunks : 64);
     hipLaunchKernelGGL(png_gather_kernel, dim3(gb, N), dim3(NT), 0, s, slots, csize, cadler, L.nchunks, F, png_zlib_bound(H, W, C), out,
                        reinterpret_cast<long long*>(sizes));
     return hipGetLastError();
+}
+
+hipError_t png_encode(const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes, void* ws, hipStream_t s) {
+    return png_encode_dist(img, N, H, W, C, filter, nullptr, 0, out, sizes, ws, s);
 }
 
 }  // namespace chk

@@ -44,6 +44,7 @@ On-disk formats are the reference's:
     python -m ctrlhair_amd.dataset directions <img_dir> --att shape|texture [--weights procedural|<checkpoint root>] [--used-dir DIR]
                                           [--out DIR] [--n 300] [--images 10] [--values 6] [--max-val 2.5] [--seed 0] [--noise-seed 0]
                                           [--size 256|512] [--cell PX] [--sheets all|top:K|none] [--list FILE] [--batch 16]
+                                          [--png host|device] [--png-stride]
                                           (shape_branch/ and color_texture_branch/script_find_direction.py: random candidate directions
                                            orthogonal to the ones in <used-dir>, each swept over the first --images images of <img_dir> (or
                                            the names in --list) at --values slider values; writes <out>/<att>_dir_<k+1>/<i>.pkl,
@@ -52,7 +53,8 @@ On-disk formats are the reference's:
     python -m ctrlhair_amd.dataset use-direction <out> <att> <index> <used-dir>
                                           (copy candidate <index> of that search into the used set under the next free name)
     (masks, crop, uncrop and directions take --png host|device: 'device' encodes their PNG files with ch_png_encode,
-     ctrlhair_amd.pngenc, instead of downloading the pixels for Pillow; the pixels are the same, the file bytes are not)
+     ctrlhair_amd.pngenc, instead of downloading the pixels for Pillow; the pixels are the same, the file bytes are not;
+     directions --png device --png-stride: the encoder also matches at the sheet's column pitch (ch_png_encode_dist): smaller sheets)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -483,7 +485,11 @@ def _main_directions(argv):
     ap.add_argument('--list', default=None, help='file with the image names to use, one per line')
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
+    ap.add_argument('--png-stride', action='store_true', help='with --png device: also match at the sheet\'s column pitch, (cell + margin) * 3 bytes, where the columns of a row '
+                                                              'repeat each other (ch_png_encode_dist): same pixels, smaller files.  Off by default')
     args = ap.parse_args(argv)
+    if args.png_stride and args.png != 'device':
+        ap.error('--png-stride needs --png device')
     import torch
     from . import directions as DS
     from .pipeline import EditPipeline
@@ -504,7 +510,7 @@ def _main_directions(argv):
     search = DS.DirectionSearch(pipe, imgs, noise_seed=args.noise_seed)
     recs = DS.find_directions(search, args.att, DS.load_used(args.used_dir), args.out, n=args.n,
                               values=np.linspace(-args.max_val, args.max_val, args.values), seed=args.seed, rank=rank, world=world,
-                              sheets=args.sheets, cell=args.cell, png=args.png)
+                              sheets=args.sheets, cell=args.cell, png=args.png, png_stride=args.png_stride)
     if dist is not None:
         dist.barrier()
     if rank == 0:

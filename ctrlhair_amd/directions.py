@@ -81,6 +81,14 @@ def _image_kind(t: torch.Tensor, what: str) -> int:
     raise ValueError(f'{what}: expected float32 [n,3,H,W] or uint8 [n,H,W,3], got {t.dtype} {tuple(t.shape)}')
 
 
+def sheet_png_distances(cols: int, W: int, margin: int) -> tuple:
+    """The match distances to give the PNG encoder for a sheet of `cols` columns of W pixels, `margin` apart: the column pitch in bytes,
+    (W + margin) * 3, at which the renders of one row repeat each other outside the edited region.  Empty for a one-column sheet and
+    for a pitch beyond deflate's window (32767)."""
+    pitch = (int(W) + int(margin)) * 3
+    return (pitch,) if cols > 1 and pitch <= 32767 else ()
+
+
 class ContactSheet:
     """util/canvas_grid.py Canvas on the device: uint8 [rows * H, cols * W + margin * (cols - 1), 3], filled with 255."""
 
@@ -133,6 +141,10 @@ class ContactSheet:
 
     def numpy(self) -> np.ndarray:
         return U.to_host(self.canvas)
+
+    def png_distances(self) -> tuple:
+        """`distances` for pngenc.PngEncoder on this sheet's canvas: the column pitch in bytes (sheet_png_distances)."""
+        return sheet_png_distances(self.cols, self.W, self.margin)
 
 
 class SweepStats:
@@ -354,16 +366,20 @@ def parse_sheets(spec: str):
 
 
 def find_directions(search: DirectionSearch, att: str, existing: Sequence, out_dir: str, n: int = 300, values=None, seed: int = 0,
-                    rank: int = 0, world: int = 1, sheets: str = 'all', cell: Optional[int] = None, png: str = 'host') -> List[dict]:
+                    rank: int = 0, world: int = 1, sheets: str = 'all', cell: Optional[int] = None, png: str = 'host',
+                    png_stride: bool = False) -> List[dict]:
     """This rank's candidates (round-robin over 0..n-1) of a direction search: direction pickle, contact sheet and scores per
     candidate.  sheets: 'all', 'none', or 'top:K' -- score every candidate of the rank first, then render only the rank's K best
     again into sheets (PNG encoding is host zlib and, at full size, the largest single cost per candidate).  png: 'host' downloads
     the sheet and writes it with Pillow (`write_png`); 'device' encodes it where it is (pngenc.PngEncoder) and downloads the
-    compressed bytes: the same pixels in another file.  Writes
+    compressed bytes: the same pixels in another file.  png_stride (with png='device' only): the encoder also matches at the
+    sheet's column pitch (`ContactSheet.png_distances`), where the columns of a row repeat each other: a smaller file.  Writes
     <out_dir>/scores.rank<r>of<world>.json and returns its records; `merge_scores(out_dir, world)` makes scores.json from the files of
     that world's ranks (files an earlier run with another world size left behind are not read)."""
     from .dataset import shard
     from .pngenc import PngEncoder, check_png_mode
+    if png_stride and check_png_mode(png) != 'device':
+        raise ValueError("png_stride needs png='device': Pillow's writer takes no match distances")
     encoder = PngEncoder(search.handle, search.device) if check_png_mode(png) == 'device' else None
     mode, top = parse_sheets(sheets)
     values = np.linspace(-2.5, 2.5, 6) if values is None else np.asarray(values, dtype=np.float64)
@@ -385,7 +401,8 @@ def find_directions(search: DirectionSearch, att: str, existing: Sequence, out_d
             if encoder is None:
                 write_png(os.path.join(img_dir, '%d.png' % idx), sheet.numpy())
             else:
-                encoder.write([os.path.join(img_dir, '%d.png' % idx)], sheet.canvas[None])
+                kw = {'distances': sheet.png_distances()} if png_stride else {}
+                encoder.write([os.path.join(img_dir, '%d.png' % idx)], sheet.canvas[None], **kw)
         return rec
 
     mine = shard(list(range(n)), rank, world)

@@ -9,7 +9,12 @@ signature, IHDR, the stream cut into IDAT chunks, IEND -- and PNG's CRC-32, whic
 
 Pixels decode exactly; the file bytes are NOT those of Pillow or of any zlib level (another deflate of the same filtered bytes), and they
 depend on ch_png_chunk_bytes().
+
+distances=(...) on streams / encode / write: up to three byte distances at which the image repeats itself -- the column pitch of a
+contact sheet (ContactSheet.png_distances), a tile period, a row stride.  ch_png_encode_dist then also codes matches at those distances
+(the deflate stage alone sees distance 1 only); the pixels are the same, the file is smaller where the layout repeats.
 """
+import ctypes
 import struct
 import zlib
 from typing import List, Sequence
@@ -21,12 +26,31 @@ PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
 COLOUR_TYPE = {1: 0, 3: 2, 4: 6}          # channels -> PNG colour type (grey, RGB, RGBA), bit depth 8
 IDAT_MAX = 1 << 20                        # bytes of zlib stream per IDAT chunk (any split is valid; libpng's default writes far smaller ones)
 PNG_MODES = ('host', 'device')
+MAX_DISTANCES = 3                         # caller-given match distances of ch_png_encode_dist
 
 
 def check_png_mode(png: str) -> str:
     if png not in PNG_MODES:
         raise ValueError(f"png must be 'host' or 'device', got {png!r}")
     return png
+
+
+def check_distances(distances: Sequence[int]) -> tuple:
+    """The further match distances of ch_png_encode_dist as a tuple of ints, checked as the library checks them: at most three, each in
+    2..32767 (distance 1 is always present), pairwise distinct."""
+    try:
+        dist = tuple(distances)
+    except TypeError:
+        raise ValueError(f'PngEncoder: distances must be a sequence of at most three ints, got {distances!r}') from None
+    if len(dist) > MAX_DISTANCES:
+        raise ValueError(f'PngEncoder: at most {MAX_DISTANCES} distances, got {len(dist)}')
+    for d in dist:
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or not 2 <= int(d) <= 32767:
+            raise ValueError(f'PngEncoder: every distance must be an int in 2..32767 (distance 1 is always present), got {d!r}')
+    dist = tuple(int(d) for d in dist)
+    if len(set(dist)) != len(dist):
+        raise ValueError(f'PngEncoder: distances must be pairwise distinct, got {dist}')
+    return dist
 
 
 def adler32_combine(a1: int, a2: int, len2: int) -> int:
@@ -59,7 +83,7 @@ def wrap_png(zlib_stream: bytes, H: int, W: int, C: int) -> bytes:
 
 
 class PngEncoder:
-    """ch_png_encode on one ch_handle.  No CPU fallback: the constructor needs the library and a GPU."""
+    """ch_png_encode / ch_png_encode_dist on one ch_handle.  No CPU fallback: the constructor needs the library and a GPU."""
 
     def __init__(self, handle, device):
         import torch
@@ -76,8 +100,10 @@ class PngEncoder:
             setattr(self, name, buf)
         return buf
 
-    def streams(self, images, filter: int = -1) -> List[bytes]:
-        """uint8 device tensor [N,H,W,C] or [N,H,W] -> the N zlib streams (bytes).  Two downloads: the lengths, then the bytes."""
+    def streams(self, images, filter: int = -1, distances: Sequence[int] = ()) -> List[bytes]:
+        """uint8 device tensor [N,H,W,C] or [N,H,W] -> the N zlib streams (bytes).  Two downloads: the lengths, then the bytes.
+        distances: up to three further match distances in bytes of the filtered stream (check_distances; ch_png_encode_dist); empty:
+        ch_png_encode, distance-1 runs only."""
         import torch
         if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8 or images.dim() not in (3, 4):
             raise ValueError('PngEncoder: images must be a uint8 tensor [N,H,W,C] or [N,H,W]')
@@ -88,6 +114,7 @@ class PngEncoder:
             raise ValueError(f'PngEncoder: C must be 1, 3 or 4, got {C}')
         if not -1 <= int(filter) <= 4:
             raise ValueError(f'PngEncoder: filter must be -1 (adaptive) or 0..4, got {filter}')
+        dist = check_distances(distances)
         if N == 0:
             return []
         lib = self.handle.lib
@@ -96,8 +123,13 @@ class PngEncoder:
             raise ValueError(f'PngEncoder: ch_png_encode rejects N={N}, H={H}, W={W} (sides 1..32768, H * W <= 2^30, N <= 65535)')
         ws, out = self._grown('_ws', need, device=self.device), self._grown('_out', N * bound, device=self.device)
         sizes = torch.empty(N, dtype=torch.int64, device=self.device)
-        self.handle.call('ch_png_encode', x.data_ptr(), N, H, W, C, int(filter), out.data_ptr(), sizes.data_ptr(), ws.data_ptr(),
-                         ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if dist:
+            self.handle.call('ch_png_encode_dist', x.data_ptr(), N, H, W, C, int(filter), (ctypes.c_int * len(dist))(*dist), len(dist),
+                             out.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        else:
+            self.handle.call('ch_png_encode', x.data_ptr(), N, H, W, C, int(filter), out.data_ptr(), sizes.data_ptr(), ws.data_ptr(),
+                             ws.numel(), stream)
         lens = [int(v) for v in sizes.cpu()]                                   # download 1 (synchronises)
         if any(v < 8 or v > bound for v in lens):
             raise RuntimeError(f'ch_png_encode returned stream lengths {lens} outside 8..{bound}')
@@ -109,17 +141,17 @@ class PngEncoder:
         offs = np.concatenate([[0], np.cumsum(lens)])
         return [raw[offs[n]:offs[n + 1]] for n in range(N)]
 
-    def encode(self, images, filter: int = -1) -> List[bytes]:
+    def encode(self, images, filter: int = -1, distances: Sequence[int] = ()) -> List[bytes]:
         """uint8 device tensor [N,H,W,C] or [N,H,W] -> N whole PNG files (bytes)."""
         H, W = int(images.shape[1]), int(images.shape[2])
         C = int(images.shape[3]) if images.dim() == 4 else 1
-        return [wrap_png(z, H, W, C) for z in self.streams(images, filter)]
+        return [wrap_png(z, H, W, C) for z in self.streams(images, filter, distances)]
 
-    def write(self, paths: Sequence[str], images, filter: int = -1) -> None:
+    def write(self, paths: Sequence[str], images, filter: int = -1, distances: Sequence[int] = ()) -> None:
         """Encode images [N,...] and write file n to paths[n]."""
         paths = list(paths)
         if len(paths) != int(images.shape[0]):
             raise ValueError(f'PngEncoder.write: {len(paths)} paths for {int(images.shape[0])} images')
-        for path, png in zip(paths, self.encode(images, filter)):
+        for path, png in zip(paths, self.encode(images, filter, distances)):
             with open(path, 'wb') as f:
                 f.write(png)

@@ -344,12 +344,25 @@ int  ch_sweep_stats(ch_handle* h, const void* img, int kind, const uint8_t* labe
  *   (they do depend on ch_png_chunk_bytes()).  Pixels decode exactly; the bytes differ from zlib's for the same pixels.
  * workspace: caller-owned device buffer (16-byte aligned) of ch_png_encode_workspace_bytes(N, H, W, C) bytes (0 for arguments the
  * call would reject).  1 <= N <= 65535, 1 <= H, W <= 32768, H * W <= 2^30.  Enqueues three kernels on `stream` without synchronising
- * or allocating. */
+ * or allocating.
+ * ch_png_encode_dist is the same call with matches at ndist (0..3) further distances dist[0..ndist) (a HOST array read at the call;
+ * every value in 2..32767, pairwise distinct): a layout period the caller knows -- the byte pitch of a contact sheet's columns, a
+ * tile period, a row stride.  ndist = 0 gives the bytes of ch_png_encode exactly.  With D = (1, dist[0], ...) in that order:
+ *   eq_d[i] = (i >= d and x[i] == x[i - d]) over the chunk's bytes x; the maximal true intervals of eq_d are the match intervals of
+ *   d.  Position i belongs to the distance whose interval containing i is longest, the earlier in D on a tie; if that interval is
+ *   shorter than 3, i is a literal.  A class run -- a maximal run of positions of one distance, R long, from p -- is coded as
+ *   floor(R / 258) matches (258, d) at p + 258 k and then the remainder, one match if it is >= 3, else literals.  No match reaches
+ *   before its chunk.  Distance symbols and extra bits follow RFC 1951 3.2.5; the used distance symbols (at most 4) get a Huffman
+ *   code of their own, one bit where only one is used.
+ * The bound, the workspace, the chunk size and the determinism are those of ch_png_encode: the bytes are a pure function of the
+ * chunk's bytes and the list. */
 int    ch_png_chunk_bytes(void);
 size_t ch_png_zlib_bound(int H, int W, int C);
 size_t ch_png_encode_workspace_bytes(int N, int H, int W, int C);
 int    ch_png_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, uint8_t* out, int64_t* sizes,
                      void* workspace, size_t workspace_bytes, ch_stream_t stream);
+int    ch_png_encode_dist(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist,
+                          uint8_t* out, int64_t* sizes, void* workspace, size_t workspace_bytes, ch_stream_t stream);
 
 /* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
  * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image
