@@ -13,6 +13,7 @@
 #include "aux_models.h"
 #include "sean_model.h"
 #include "kernels.h"
+#include "png_inflate_core.h"
 
 struct ch_handle {
     int device = 0;
@@ -651,6 +652,32 @@ int ch_png_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, 
 int ch_png_encode_dist(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist, uint8_t* out,
                        int64_t* sizes, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
     return png_encode_checked("ch_png_encode_dist", h, img, N, H, W, C, filter, dist, ndist, out, sizes, workspace, workspace_bytes, stream);
+}
+
+// ---- PNG decoding (png_decode.hip, png_inflate_core.h) ---------------------------------------------------------------------------------
+size_t ch_png_decode_workspace_bytes(int N, int H, int W, int C) {
+    return (N >= 1 && N <= 65535 && png_dims_ok(H, W, C)) ? chk::png_decode_workspace_bytes(N, H, W, C) : 0;
+}
+
+int ch_png_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, int N, int H, int W, int C, uint8_t* img, int32_t* status,
+                  void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    namespace pi = chk::pnginf;
+    static_assert(CH_PNG_DEC_OK == pi::OK && CH_PNG_DEC_BAD_HEADER == pi::BAD_HEADER && CH_PNG_DEC_BAD_BLOCK == pi::BAD_BLOCK &&
+                      CH_PNG_DEC_BAD_CODE == pi::BAD_CODE && CH_PNG_DEC_BAD_SYMBOL == pi::BAD_SYMBOL &&
+                      CH_PNG_DEC_BAD_DISTANCE == pi::BAD_DISTANCE && CH_PNG_DEC_INPUT_END == pi::INPUT_END && CH_PNG_DEC_SIZE == pi::SIZE &&
+                      CH_PNG_DEC_ADLER == pi::ADLER && CH_PNG_DEC_BAD_FILTER == pi::BAD_FILTER,
+                  "status codes of the header and of png_inflate_core.h");
+    if (!h) return CH_ERR_ARG;
+    const std::string f = "ch_png_decode: ";
+    if (!streams || !offsets || !img || !status || !workspace) return fail(h, CH_ERR_ARG, f + "null pointer");
+    if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, f + "N outside 1..65535");
+    if (!png_dims_ok(H, W, C)) return fail(h, CH_ERR_ARG, f + "C must be 1, 3 or 4, sides 1..32768, H * W <= 2^30");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
+    if (workspace_bytes < chk::png_decode_workspace_bytes(N, H, W, C))
+        return fail(h, CH_ERR_ARG, f + "workspace smaller than ch_png_decode_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::png_decode(streams, offsets, N, H, W, C, img, status, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, f + hipGetErrorString(e));
 }
 
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {

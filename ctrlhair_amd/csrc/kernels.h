@@ -261,4 +261,10 @@ hipError_t png_encode(const uint8_t* img, int N, int H, int W, int C, int filter
 hipError_t png_encode_dist(const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist, uint8_t* out,
                            int64_t* sizes, void* ws, hipStream_t s);
 
+// png_decode.hip: N zlib streams (stream n = streams[offsets[n], offsets[n + 1]), device) -> uint8 images [N,H,W,C]: inflate (one wave per
+// stream, png_inflate_core.h) into the workspace, then the PNG row filters undone.  status[n]: pnginf::Status.  See ch_png_decode.
+size_t png_decode_workspace_bytes(int N, int H, int W, int C);
+hipError_t png_decode(const uint8_t* streams, const int64_t* offsets, int N, int H, int W, int C, uint8_t* img, int32_t* status, void* ws,
+                      hipStream_t s);
+
 }  // namespace chk

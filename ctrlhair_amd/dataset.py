@@ -124,6 +124,13 @@ def _png_encoder(png: str, owner):
     return PngEncoder(owner.handle, owner.device) if check_png_mode(png) == 'device' else None
 
 
+def _png_decoder(decode: str, owner):
+    """None for decode='host'; for 'device' the device decoder (pngdec.PngDecoder) on `owner`'s handle and device.  The option names
+    who decodes the PNG files a job reads; whatever the device does not decode is Pillow's, file by file (PngDecoder.fallbacks)."""
+    from .pngdec import PngDecoder, check_decode_mode
+    return PngDecoder(owner.handle, owner.device) if check_decode_mode(decode) == 'device' else None
+
+
 def _is_png(name: str) -> bool:
     return name.lower().endswith('.png')
 
@@ -180,17 +187,21 @@ COLOR_JOBS = {'rgb': 'rgb_stat', 'colorvar': 'color_var_stat'}      # job -> hai
 
 
 def hair_color_stats(stats, img_dir: str, label_dir: str, out_root: str, dataset: str, jobs: Sequence[str] = ('rgb',),
-                     batch: int = 16, rank: int = 0, world: int = 1) -> Dict[str, Dict[str, object]]:
+                     batch: int = 16, rank: int = 0, world: int = 1, decode: str = 'host') -> Dict[str, Dict[str, object]]:
     """Hair colour labels of every (image, label) pair of this rank's shard (script_get_rgb_hsv_label.py:49-67,
     script_get_color_var_label.py:48-90): eroded hair mask and exact sums on the device (`stats`: colorstats.HairColorStats),
     statistics finished on the host, one pickle per image under `out_root/hair_info_all_dataset/<job dir>/`.  Returns
     {job: {key: value}}; the colorvar job has no entry (and writes no file) for images with <= 5 hair pixels.
     Images must be square: the reference resizes the label map to `hair_img.shape[:2]` as cv2's (w, h), which swaps the
-    axes of a non-square image."""
+    axes of a non-square image.
+    decode='device': the image and label files of a batch are read as bytes and decoded on the device (pngdec.PngDecoder; the same
+    pixels, so the same pickles byte for byte); the pixels are never on the host."""
+    import torch
     from . import colorstats as CS
     unknown = [j for j in jobs if j not in COLOR_JOBS]
     if unknown:
         raise ValueError(f'unknown colour job(s) {unknown}; expected {sorted(COLOR_JOBS)}')
+    decoder = _png_decoder(decode, stats)
     dirs = {j: os.path.join(out_root, 'hair_info_all_dataset', COLOR_JOBS[j]) for j in jobs}
     for d in dirs.values():
         os.makedirs(d, exist_ok=True)
@@ -198,7 +209,7 @@ def hair_color_stats(stats, img_dir: str, label_dir: str, out_root: str, dataset
 
     def flush(group):
         names, imgs, labs = zip(*group)
-        sums = stats.sums(np.stack(imgs), np.stack(labs))
+        sums = stats.sums(*((np.stack(imgs), np.stack(labs)) if decoder is None else (torch.stack(imgs), torch.stack(labs))))
         for n, sm in zip(names, sums):
             key = code_key(dataset, n)
             for j in jobs:
@@ -211,12 +222,15 @@ def hair_color_stats(stats, img_dir: str, label_dir: str, out_root: str, dataset
 
     for names in batches(shard(list_images(img_dir), rank, world), batch):
         group = []
-        for n in names:
-            img = read_rgb(os.path.join(img_dir, n))
+        if decoder is not None:
+            dev_imgs = decoder.read_rgb([os.path.join(img_dir, n) for n in names])
+            dev_labs = decoder.read_gray([os.path.join(label_dir, os.path.splitext(n)[0] + '.png') for n in names])
+        for k, n in enumerate(names):
+            img = read_rgb(os.path.join(img_dir, n)) if decoder is None else dev_imgs[k]
             if img.shape[0] != img.shape[1]:
                 raise ValueError(f'{n}: image is {img.shape[1]}x{img.shape[0]}; the colour statistics need square images '
                                  f'(the reference\'s resize swaps (h, w) for cv2\'s dsize)')
-            lab = read_gray(os.path.join(label_dir, os.path.splitext(n)[0] + '.png'))
+            lab = read_gray(os.path.join(label_dir, os.path.splitext(n)[0] + '.png')) if decoder is None else dev_labs[k]
             if group and (group[-1][1].shape != img.shape or group[-1][2].shape != lab.shape):
                 flush(group)             # one device batch per run of equal sizes
                 group = []
@@ -561,7 +575,10 @@ def main(argv=None):
     ap.add_argument('--weights', default='reference', help="'reference' (the Google-Drive checkpoints under the reference's "
                                                            "paths) or 'procedural'")
     ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
+    ap.add_argument('--decode', choices=('host', 'device'), default='host', help='rgb / colorvar: who decodes the PNG files read: Pillow on the host (default) or ch_png_decode on the device (same pixels, same pickles)')
     args = ap.parse_args(argv)
+    if args.decode != 'host' and args.job not in COLOR_JOBS:
+        ap.error('--decode device is for the rgb and colorvar jobs')
     import torch
     from .hair_editor import HairEditor
     rank, world, local = _dist_env()
@@ -577,7 +594,7 @@ def main(argv=None):
         from .colorstats import HairColorStats
         stats = HairColorStats(lib.Handle(local), torch.device('cuda', local))
         res = hair_color_stats(stats, os.path.join(base, 'images_256'), os.path.join(base, 'label'), args.root, args.dataset,
-                               (args.job,), args.batch, rank, world)
+                               (args.job,), args.batch, rank, world, decode=args.decode)
         if dist is not None:
             dist.barrier()
         if rank == 0:

@@ -364,6 +364,46 @@ int    ch_png_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int 
 int    ch_png_encode_dist(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int filter, const int* dist, int ndist,
                           uint8_t* out, int64_t* sizes, void* workspace, size_t workspace_bytes, ch_stream_t stream);
 
+/* ---- PNG decoding on the device: crops and label maps arrive as compressed bytes ------------------------------------------------------
+ * ch_png_decode turns N zlib streams into N images img uint8 [N,H,W,C] (device pointer; C = 1 grey, 3 RGB, 4 RGBA; bit depth 8, not
+ * interlaced).  Stream n is the bytes streams[offsets[n] .. offsets[n + 1]) (streams uint8, offsets int64 [N + 1]: device pointers): one
+ * complete zlib stream (RFC 1950), the concatenated IDAT payloads of one PNG file.  It is inflated (RFC 1951: stored, fixed and dynamic
+ * blocks) to H * (1 + W * C) bytes in the workspace, and the five row filters are undone (RFC 2083 section 6; Average is
+ * floor((a + b) / 2), Paeth with the tie order a, b, c).  The container (signature, chunks, CRC-32) is the caller's: pngdec.parse_png.
+ * status[n] (int32 [N], device): CH_PNG_DEC_OK, or
+ *   BAD_HEADER    CM != 8, CINFO > 7, FCHECK fails, or FDICT is set
+ *   BAD_BLOCK     BTYPE 3, or a stored block's LEN != ~NLEN
+ *   BAD_CODE      HLIT > 286 or HDIST > 30; repeat code 16 without a predecessor or a repeat past HLIT + HDIST; an over-subscribed
+ *                 code; an incomplete code other than one single code of length 1 or a distance code without any code; no
+ *                 end-of-block code
+ *   BAD_SYMBOL    length symbol 286 / 287, distance symbol 30 / 31, or bits that are no code of an incomplete code (a distance
+ *                 symbol wanted from an empty distance code)
+ *   BAD_DISTANCE  a distance beyond the bytes produced so far (or beyond 32768)
+ *   INPUT_END     the stream ends inside a block or before the end of the Adler-32
+ *   SIZE          the stream inflates to more or fewer than H * (1 + W * C) bytes
+ *   ADLER         Adler-32 mismatch
+ *   BAD_FILTER    a row's filter type byte is greater than 4
+ * and the pixels of that image are unspecified.  What is accepted is what stock zlib's inflate accepts: CINFO is not enforced as a
+ * window size, bytes behind the Adler-32 are ignored, an empty stored block may stand anywhere.
+ * For every byte sequence: the work for image n reads no stream byte outside [offsets[n], offsets[n + 1]), writes nothing outside image
+ * n's slice of img, of status and of the workspace, and terminates.
+ * workspace: caller-owned device buffer (16-byte aligned) of ch_png_decode_workspace_bytes(N, H, W, C) bytes (0 for arguments the call
+ * would reject).  1 <= N <= 65535, 1 <= H, W <= 32768, H * W <= 2^30.  Enqueues two kernels on `stream` without synchronising or
+ * allocating.  Integer arithmetic only, no atomics: image n is the same in every batch and every call. */
+#define CH_PNG_DEC_OK 0
+#define CH_PNG_DEC_BAD_HEADER 1
+#define CH_PNG_DEC_BAD_BLOCK 2
+#define CH_PNG_DEC_BAD_CODE 3
+#define CH_PNG_DEC_BAD_SYMBOL 4
+#define CH_PNG_DEC_BAD_DISTANCE 5
+#define CH_PNG_DEC_INPUT_END 6
+#define CH_PNG_DEC_SIZE 7
+#define CH_PNG_DEC_ADLER 8
+#define CH_PNG_DEC_BAD_FILTER 9
+size_t ch_png_decode_workspace_bytes(int N, int H, int W, int C);
+int    ch_png_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, int N, int H, int W, int C, uint8_t* img,
+                     int32_t* status, void* workspace, size_t workspace_bytes, ch_stream_t stream);
+
 /* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
  * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image
  * edge extended 10 px, mask_adaptor.py:119-131), the pair's triangle mesh is deformed as rigidly as possible (libigl's per-element
