@@ -773,6 +773,8 @@ const OptRow OPTION_TABLE[] = {
     {"sean.frame", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(frame)},                  // with sean.edge, exact-f32 Winograd path: 1 = frame pixels with a uniform in-image window from table rows too (default), 0 = boundary conv
     {"sean.int_groups", NEVER, CLAMP, 0, MAXI, SEAN_FIELD(int_groups)},      // channel groups per block of the four-pixel interior pass: 0 = chosen per launch (default), n >= 1 = at most n
     {"sean.int_onepass", NEVER, BOOL, 0, 0, SEAN_FIELD(int_onepass)},        // four-pixel interior pass: 1 = 128 code slots per block, one round up to 128 codes (default), 0 = 64 slots and rounds
+    // exact-f32 path: 1 = 64-row wave tiles of the 1x1 GEMM kernel, transposed fc_mu reduction, one-thread-per-(row, label) style pack (default), 0 = round 11's kernels
+    {"sean.pw_wide", NEVER, BOOL, 0, 0, SEAN_FIELD(pw_wide)},
     {"sean.batch_invariant", NEVER, BOOL, 0, 0, SEAN_FIELD(batch_inv)},      // exact-f32 path: 1 = kernel choices independent of the batch size of a call (default 0)
     {"sean.wino4v", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(wino4v)},                // 1 = pre-transformed-input route of the F(4x4,3x3) layers with many GEMM rows (conv_wino4v.h; default), 0 = off
     // plain F(4x4,3x3) convs on the position-split kernel (conv_wino4_split.h): 0 = never, 1 = wherever supported, < 0 = per shape (default)

@@ -118,18 +118,40 @@ static hipError_t launch_pw(PwParams p, hipStream_t s) {
     hipLaunchKernelGGL(pw_conv_kernel<RT>, dim3(grid), dim3(512), Cfg::LDS_BYTES, s, p);
     return hipGetLastError();
 }
+template <int RP>
+static hipError_t launch_pw_wide(PwParams p, hipStream_t s) {
+    using Cfg = PwWideCfg<RP>;
+    static bool d0[64] = {};
+    hipError_t e = wino_attr(pw_conv_wide_kernel<RP>, Cfg::LDS_BYTES, d0);
+    if (e != hipSuccess) return e;
+    const int nrt = (p.Cout + 31) / 32;
+    p.nrg = (nrt + Cfg::RTB - 1) / Cfg::RTB;
+    p.npt = p.HW / Cfg::PXB;
+    p.ntasks = p.B * p.npt * p.nrg;
+    p.nst = p.Cin / 16;
+    const int grid = p.ntasks < wino_num_cus() ? p.ntasks : wino_num_cus();
+    hipLaunchKernelGGL(pw_conv_wide_kernel<RP>, dim3(grid), dim3(512), Cfg::LDS_BYTES, s, p);
+    return hipGetLastError();
+}
 hipError_t conv_pw(PwParams p, hipStream_t s) {
     if (!pw_supported(p.Cin, p.Cout, p.HW)) return hipErrorInvalidValue;
     p.groups = nullptr;
     p.ngroups = 0;
+    const int rp = pw_wide_rule(p.wide, p.Cout, p.HW);
+    if (rp) return rp == 2 ? launch_pw_wide<2>(p, s) : launch_pw_wide<1>(p, s);
     return (p.Cout + 31) / 32 >= 4 ? launch_pw<4>(p, s) : launch_pw<2>(p, s);
 }
-// several GEMMs (same Cin, same Cout, own operands and pixel counts) as ONE persistent launch of the RT = 4 kernel (conv_pw.h)
+// several GEMMs (same Cin, same Cout, own operands and pixel counts) as ONE persistent launch of the RT = 4 kernel, or (p.wide, more than
+// 64 rows; every group's HW % 256 == 0: the caller's word) of the wide kernel with the same four row tiles per block (conv_pw.h).
+// ntasks counts tiles of 128 pixels x row groups either way.
 hipError_t conv_pw_grouped(PwParams p, int ntasks, hipStream_t s) {
     using Cfg = PwCfg<4>;
+    using Wide = PwWideCfg<2>;
     if (p.Cin % 16 || p.Cout < 1 || !p.groups || p.ngroups < 1 || ntasks < 1) return hipErrorInvalidValue;      // (rows beyond Cout: zero rows of the packed operand, masked at the store)
-    static bool d0[64] = {};
-    hipError_t e = wino_attr(pw_conv_kernel<4>, Cfg::LDS_BYTES, d0);
+    const bool wide = p.wide && p.Cout > 64;
+    if (wide && ntasks % (Wide::PXB / 128)) return hipErrorInvalidValue;
+    static bool d0[64] = {}, d1[64] = {};
+    hipError_t e = wide ? wino_attr(pw_conv_wide_kernel<2>, Wide::LDS_BYTES, d1) : wino_attr(pw_conv_kernel<4>, Cfg::LDS_BYTES, d0);
     if (e != hipSuccess) return e;
     p.in = p.wpk = nullptr;
     p.out = nullptr;
@@ -137,10 +159,11 @@ hipError_t conv_pw_grouped(PwParams p, int ntasks, hipStream_t s) {
     p.HW = 0;
     p.nrg = ((p.Cout + 31) / 32 + 3) / 4;
     p.npt = 0;
-    p.ntasks = ntasks;
+    p.ntasks = wide ? ntasks / (Wide::PXB / 128) : ntasks;
     p.nst = p.Cin / 16;
-    const int grid = ntasks < wino_num_cus() ? ntasks : wino_num_cus();
-    hipLaunchKernelGGL(pw_conv_kernel<4>, dim3(grid), dim3(512), Cfg::LDS_BYTES, s, p);
+    const int grid = p.ntasks < wino_num_cus() ? p.ntasks : wino_num_cus();
+    if (wide) hipLaunchKernelGGL(pw_conv_wide_kernel<2>, dim3(grid), dim3(512), Wide::LDS_BYTES, s, p);
+    else hipLaunchKernelGGL(pw_conv_kernel<4>, dim3(grid), dim3(512), Cfg::LDS_BYTES, s, p);
     return hipGetLastError();
 }
 

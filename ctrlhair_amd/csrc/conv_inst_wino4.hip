@@ -65,6 +65,12 @@ hipError_t conv_wino4_ace(Wino4AceParams p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// a0 b0 + a1 b1 + a2 b2 of the style-image transform G g G^T, with its roundings spelled out: fma(a2, b2, fma(a0, b0, a1 * b1)) is what
+// hipcc made of the plain sum in the per-unit kernel (coefficients in registers); with the coefficients as literals (per-row kernel) it
+// contracts the other product first.  Both kernels must give the same words.
+__device__ __forceinline__ float wino4_dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
+    return __builtin_fmaf(a2, b2, __builtin_fmaf(a0, b0, a1 * b1));
+}
 // one thread = one 16-byte unit (idx, lane) of a style image: fragments a = 4 idx .. 4 idx + 3 = 36 m + xi of GEMM row 16 m + (lane & 15),
 // input "channel" = label j = 4 s + (lane >> 4) (j >= 19, and the sixth image s = 5: zeros)
 __global__ __launch_bounds__(256) void wino4_style_pack_kernel(const float* __restrict__ lut, float* __restrict__ wsty, int B, int C, int nrt) {
@@ -91,17 +97,59 @@ __global__ __launch_bounds__(256) void wino4_style_pack_kernel(const float* __re
             const int xi = 4 * idx + e - 36 * m, ii = xi / 6, jj = xi % 6;
             float r[3];
 #pragma unroll
-            for (int q = 0; q < 3; ++q) r[q] = Gm[ii][0] * g[0][q] + Gm[ii][1] * g[1][q] + Gm[ii][2] * g[2][q];
-            u[e] = r[0] * Gm[jj][0] + r[1] * Gm[jj][1] + r[2] * Gm[jj][2];
+            for (int q = 0; q < 3; ++q) r[q] = wino4_dot3(Gm[ii][0], g[0][q], Gm[ii][1], g[1][q], Gm[ii][2], g[2][q]);
+            u[e] = wino4_dot3(r[0], Gm[jj][0], r[1], Gm[jj][1], r[2], Gm[jj][2]);
         }
         o = make_float4(u[0], u[1], u[2], u[3]);
     }
     reinterpret_cast<float4*>(wsty)[i] = o;
 }
-hipError_t wino4_style_pack(const float* lut, float* wsty, int B, int C, hipStream_t s) {
+// one thread = one (GEMM row 32 rt + 16 m + (lane & 15), label j = 4 s + (lane >> 4)): its nine LUT values once, all 36 G g G^T values
+// (each from the expression of the kernel above: the same words), nine 16-byte stores (units 9 m .. 9 m + 8 of its lane: a wave's store
+// is a contiguous KB).  The units that are zero whatever B and C (s = 5; s = 4 with lane >= 48, i.e. j >= 19) are not written: their
+// place in a [6][1152]-unit image depends on neither, and the buffer is zeroed once before its first use (sean_model.cpp).
+__global__ __launch_bounds__(256) void wino4_style_pack_rows_kernel(const float* __restrict__ lut, float* __restrict__ wsty, int B, int C, int nrt) {
+    const long long n = (long long)B * nrt * 5 * 128;
+    const long long i = blockIdx.x * 256LL + threadIdx.x;
+    if (i >= n) return;
+    const int lane = (int)(i & 63), m = (int)((i >> 6) & 1), s = (int)((i >> 7) % 5);
+    const int rt = (int)((i / 640) % nrt), b = (int)(i / (640LL * nrt));
+    const int j = 4 * s + (lane >> 4);
+    if (j >= 19) return;
+    float4* dst = reinterpret_cast<float4*>(wsty) + (((long long)b * nrt + rt) * 6 + s) * 1152 + 9 * m * 64 + lane;
+    int ch, beta;
+    wino4_ace_row(rt * 32 + m * 16 + (lane & 15), ch, beta);
+    if (ch >= C) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dst[k * 64] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float* P = lut + ((long long)(b * 19 + j) * 9) * 2 * C + beta * C + ch;
+    float g[3][3];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) g[t / 3][t % 3] = P[(long long)t * 2 * C];
+    const float Gm[6][3] = {{0.25f, 0.f, 0.f}, {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
+                            {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0.f, 0.f, 1.f}};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        float u[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int xi = 4 * k + e, ii = xi / 6, jj = xi % 6;
+            float r[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) r[q] = wino4_dot3(Gm[ii][0], g[0][q], Gm[ii][1], g[1][q], Gm[ii][2], g[2][q]);
+            u[e] = wino4_dot3(r[0], Gm[jj][0], r[1], Gm[jj][1], r[2], Gm[jj][2]);
+        }
+        dst[k * 64] = make_float4(u[0], u[1], u[2], u[3]);
+    }
+}
+// rows: 1 = wino4_style_pack_rows_kernel (wsty was zeroed once by the caller), 0 = one thread per 16-byte unit
+hipError_t wino4_style_pack(const float* lut, float* wsty, int B, int C, hipStream_t s, int rows) {
     const int nrt = (C + 15) / 16;
-    const long long n = (long long)B * nrt * 6 * 1152;
-    hipLaunchKernelGGL(wino4_style_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lut, wsty, B, C, nrt);
+    const long long n = rows ? (long long)B * nrt * 5 * 128 : (long long)B * nrt * 6 * 1152;
+    if (rows) hipLaunchKernelGGL(wino4_style_pack_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lut, wsty, B, C, nrt);
+    else hipLaunchKernelGGL(wino4_style_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, lut, wsty, B, C, nrt);
     return hipGetLastError();
 }
 

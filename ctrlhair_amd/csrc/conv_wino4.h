@@ -737,6 +737,6 @@ hipError_t conv_wino4_plain(Wino4Params p, hipStream_t s);      // conv_inst_win
 inline bool wino4_ace_supported(int H, int W, int C) { return H % wino4::TS == 0 && W % wino4::TS == 0 && C % 2 == 0; }
 hipError_t conv_wino4_ace(Wino4AceParams p, hipStream_t s);
 // wsty[b][rt][6][ADW] <- F(4x4,3x3) transform (G P G^T, f32) of the style LUT lut[(b*19 + j)][tap][gamma|beta][C]; rows as wino4_ace_row
-hipError_t wino4_style_pack(const float* lut, float* wsty, int B, int C, hipStream_t s);
+hipError_t wino4_style_pack(const float* lut, float* wsty, int B, int C, hipStream_t s, int rows = 0);      // rows = 1: one thread per (row, label); needs wsty zeroed once
 
 }  // namespace chk

@@ -886,8 +886,13 @@ hipError_t c4_decode(const float* in, float* out, int B, int C, long long HW, hi
 // Weight-bandwidth bound (19 x 1 MB per ACE).  One wave per 4 output features; lanes split the 512-long dot
 // product (8 floats each, two float4 loads), wave shuffle reduction, up to FCMU_BT samples per pass.
 // Output is written as the [512][Npad] "image" the LUT GEMM (1x1 conv, NHWC epilogue) consumes: column b*19+j.
+// TR: the wave's 32 partial sums (4 features x 8 samples) go through ONE transposed butterfly instead of 32 independent ones: at
+// offset 32 the lanes below 32 keep values 0..15 and send 16..31 (the upper lanes the reverse), then 8, 4, 2, 1 values per lane at
+// offsets 16 .. 2, and a plain exchange at offset 1: 32 shuffles instead of 192.  Every sum still adds lane l and lane l ^ off in the
+// order 32, 16, .., 1 (the same additions, commuted: the same bits); lane l ends with value l >> 1 and the even lanes store.
 constexpr int FCMU_BT = 8;
 
+template <bool TR>
 __device__ __forceinline__ void fc_mu_body(const float* __restrict__ codes, const float* __restrict__ Wt,
                                            const float* __restrict__ bias, float* __restrict__ mu_img, int B, int Npad,
                                            float* __restrict__ mu_rows, int sh16, int bs, float scale,
@@ -923,62 +928,100 @@ __device__ __forceinline__ void fc_mu_body(const float* __restrict__ codes, cons
                 c1 = cr[1];
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                part[i][t] = w[i][0].x * c0.x + w[i][0].y * c0.y + w[i][0].z * c0.z + w[i][0].w * c0.w +
-                             w[i][1].x * c1.x + w[i][1].y * c1.y + w[i][1].z * c1.z + w[i][1].w * c1.w;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int t = 0; t < FCMU_BT; ++t) {
-                float v = part[i][t];
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-                part[i][t] = v;
+            for (int i = 0; i < 4; ++i) {
+                // the roundings of the eight-term sum spelled out (one product, seven fused multiply-adds in order: what hipcc made of the
+                // plain sum before the reduction was templated; left to the compiler, the two instantiations contract different products first)
+                float d = w[i][0].x * c0.x;
+                d = __builtin_fmaf(w[i][0].y, c0.y, d);
+                d = __builtin_fmaf(w[i][0].z, c0.z, d);
+                d = __builtin_fmaf(w[i][0].w, c0.w, d);
+                d = __builtin_fmaf(w[i][1].x, c1.x, d);
+                d = __builtin_fmaf(w[i][1].y, c1.y, d);
+                d = __builtin_fmaf(w[i][1].z, c1.z, d);
+                part[i][t] = __builtin_fmaf(w[i][1].w, c1.w, d);
             }
-        if (lane == 0) {
+        }
+        // one result: feature o0 + i of sample bb + t, in all five output layouts
+        auto emit = [&](int i, int t, float sum) {
+            const float v = sum + bias[j * 512 + o0 + i];
+            const float r = v > 0.f ? v : 0.f;
+            const int o = o0 + i, n = (bb + t) * bs + j;      // bs = 19, or 20 with a zero column per sample
+            if (bs > 19 && j == 0) {   // (re)write the zero column: the image pitch Npad changes with the batch
+                const int nz = (bb + t) * bs + 19;
+                if (mu_rows) mu_rows[(long long)nz * 512 + o] = 0.f;
+                else if (sh16 == 1) {
+                    _Float16* mh = reinterpret_cast<_Float16*>(mu_img);
+                    mh[(((long long)(o >> 3) * 2 + 0) * Npad + nz) * 8 + (o & 7)] = (_Float16)0.f;
+                    mh[(((long long)(o >> 3) * 2 + 1) * Npad + nz) * 8 + (o & 7)] = (_Float16)0.f;
+                }
+            }
+            if (mu_rows) mu_rows[(long long)n * 512 + o] = r;   // [N][512] for the GEMV path
+            else if (sh16 == 2)   // A-fragment order of the grouped LUT build (conv_pw.h pack_pw_A: row n, input channel o)
+                mu_img[((long long)(n >> 5) * 32 + (o >> 4)) * 512 + ((n & 31) + 32 * (o & 1)) * 8 + ((o & 15) >> 1)] = r;
+            else if (sh16) {   // split-operand image [512/8][hi|lo][Npad][8] for the f16x3 LUT GEMM
+                _Float16* mh = reinterpret_cast<_Float16*>(mu_img);
+                _Float16 h, l;
+                sh16_split_any(r, scale, bf16, h, l);
+                vmax = fmaxf(vmax, r * scale);
+                mh[(((long long)(o >> 3) * 2 + 0) * Npad + n) * 8 + (o & 7)] = h;
+                mh[(((long long)(o >> 3) * 2 + 1) * Npad + n) * 8 + (o & 7)] = l;
+            } else mu_img[(long long)o * Npad + n] = r;
+        };
+        if constexpr (TR) {
+            float q16[16], q8[8], q4[4], q2[2];
+            const bool u5 = lane & 32, u4 = lane & 16, u3 = lane & 8, u2 = lane & 4, u1 = lane & 2;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {      // value v = 8 i + t
+                const float lo = part[v >> 3][v & 7], hi = part[(v + 16) >> 3][v & 7];
+                q16[v] = (u5 ? hi : lo) + __shfl_xor(u5 ? lo : hi, 32, 64);
+            }
+#pragma unroll
+            for (int v = 0; v < 8; ++v) q8[v] = (u4 ? q16[v + 8] : q16[v]) + __shfl_xor(u4 ? q16[v] : q16[v + 8], 16, 64);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) q4[v] = (u3 ? q8[v + 4] : q8[v]) + __shfl_xor(u3 ? q8[v] : q8[v + 4], 8, 64);
+#pragma unroll
+            for (int v = 0; v < 2; ++v) q2[v] = (u2 ? q4[v + 2] : q4[v]) + __shfl_xor(u2 ? q4[v] : q4[v + 2], 4, 64);
+            float q1 = (u1 ? q2[1] : q2[0]) + __shfl_xor(u1 ? q2[0] : q2[1], 2, 64);
+            q1 += __shfl_xor(q1, 1, 64);
+            const int v = lane >> 1;
+            if (!(lane & 1) && bb + (v & 7) < B) emit(v >> 3, v & 7, q1);
+        } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int t = 0; t < FCMU_BT; ++t)
-                    if (bb + t < B) {
-                        const float v = part[i][t] + bias[j * 512 + o0 + i];
-                        const float r = v > 0.f ? v : 0.f;
-                        const int o = o0 + i, n = (bb + t) * bs + j;      // bs = 19, or 20 with a zero column per sample
-                        if (bs > 19 && j == 0) {   // (re)write the zero column: the image pitch Npad changes with the batch
-                            const int nz = (bb + t) * bs + 19;
-                            if (mu_rows) mu_rows[(long long)nz * 512 + o] = 0.f;
-                            else if (sh16 == 1) {
-                                _Float16* mh = reinterpret_cast<_Float16*>(mu_img);
-                                mh[(((long long)(o >> 3) * 2 + 0) * Npad + nz) * 8 + (o & 7)] = (_Float16)0.f;
-                                mh[(((long long)(o >> 3) * 2 + 1) * Npad + nz) * 8 + (o & 7)] = (_Float16)0.f;
-                            }
-                        }
-                        if (mu_rows) mu_rows[(long long)n * 512 + o] = r;   // [N][512] for the GEMV path
-                        else if (sh16 == 2)   // A-fragment order of the grouped LUT build (conv_pw.h pack_pw_A: row n, input channel o)
-                            mu_img[((long long)(n >> 5) * 32 + (o >> 4)) * 512 + ((n & 31) + 32 * (o & 1)) * 8 + ((o & 15) >> 1)] = r;
-                        else if (sh16) {   // split-operand image [512/8][hi|lo][Npad][8] for the f16x3 LUT GEMM
-                            _Float16* mh = reinterpret_cast<_Float16*>(mu_img);
-                            _Float16 h, l;
-                            sh16_split_any(r, scale, bf16, h, l);
-                            vmax = fmaxf(vmax, r * scale);
-                            mh[(((long long)(o >> 3) * 2 + 0) * Npad + n) * 8 + (o & 7)] = h;
-                            mh[(((long long)(o >> 3) * 2 + 1) * Npad + n) * 8 + (o & 7)] = l;
-                        } else mu_img[(long long)o * Npad + n] = r;
-                    }
+                for (int t = 0; t < FCMU_BT; ++t) {
+                    float v = part[i][t];
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+                    part[i][t] = v;
+                }
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int t = 0; t < FCMU_BT; ++t)
+                        if (bb + t < B) emit(i, t, part[i][t]);
+            }
         }
+    }
+    if constexpr (TR) {      // the results sit in the even lanes: their maximum, as lane 0 found it before
+        if (sh16 == 1 && amax && pass == 0)
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
     }
     if (sh16 == 1 && amax && pass == 0 && lane == 0) sh16_slot_max(amax, vmax);
 }
+template <bool TR>
 __global__ __launch_bounds__(256) void fc_mu_kernel(const float* __restrict__ codes, const float* __restrict__ Wt,
                                                     const float* __restrict__ bias, float* __restrict__ mu_img, int B,
                                                     int Npad, float* __restrict__ mu_rows, int sh16, int bs, float scale,
                                                     unsigned* __restrict__ amax, int pass, int bf16) {
-    fc_mu_body(codes, Wt, bias, mu_img, B, Npad, mu_rows, sh16, bs, scale, amax, pass, bf16, blockIdx.x, blockIdx.y);
+    fc_mu_body<TR>(codes, Wt, bias, mu_img, B, Npad, mu_rows, sh16, bs, scale, amax, pass, bf16, blockIdx.x, blockIdx.y);
 }
 // All styled ACE layers of the generator in ONE launch (blockIdx.z = ACE index; a null weight pointer = unstyled layer): 15
 // launches of 608 blocks streaming 20 MB each ran at 0.9 TB/s, latency bound.  SH16 output into mu_base + a * mu_stride, slot
 // 2a + 1 of amax_slots (sean_model.cpp); the second pass works as in fc_mu_kernel.
+template <bool TR>
 __global__ __launch_bounds__(256) void fc_mu_batched_kernel(const float* __restrict__ codes, const float* const* __restrict__ Wts,
                                                             const float* const* __restrict__ biases, float* __restrict__ mu_base,
                                                             long long mu_stride, int B, int Npad, int bs, float scale,
@@ -986,21 +1029,21 @@ __global__ __launch_bounds__(256) void fc_mu_batched_kernel(const float* __restr
     const int a = blockIdx.z;
     const float* Wt = Wts[a];
     if (!Wt) return;
-    fc_mu_body(codes, Wt, biases[a], mu_base + a * mu_stride, B, Npad, nullptr, sh16, bs, scale, sh16 == 1 ? amax_slots + 2 * a + 1 : nullptr, pass,
+    fc_mu_body<TR>(codes, Wt, biases[a], mu_base + a * mu_stride, B, Npad, nullptr, sh16, bs, scale, sh16 == 1 ? amax_slots + 2 * a + 1 : nullptr, pass,
                bf16, blockIdx.x, blockIdx.y);
 }
 // sh16 = 0: f32 images [512][Npad] (exact-f32 path; no scale protocol, one pass); sh16 = 2: f32 in the A-fragment order of conv_pw.h
 hipError_t fc_mu_batched(const float* codes, const float* const* Wts, const float* const* biases, float* mu_base,
                          long long mu_stride, int n_aces, int B, int Npad, int bs, float scale, unsigned* amax_slots, int pass,
-                         int bf16, hipStream_t s, int sh16) {
-    hipLaunchKernelGGL(fc_mu_batched_kernel, dim3(512 / 16, 19, n_aces), dim3(256), 0, s, codes, Wts, biases, mu_base, mu_stride, B,
+                         int bf16, hipStream_t s, int sh16, int transposed) {
+    hipLaunchKernelGGL(transposed ? fc_mu_batched_kernel<true> : fc_mu_batched_kernel<false>, dim3(512 / 16, 19, n_aces), dim3(256), 0, s, codes, Wts, biases, mu_base, mu_stride, B,
                        Npad, bs, scale, amax_slots, pass, bf16, sh16);
     return hipGetLastError();
 }
 
 hipError_t fc_mu(const float* codes, const float* Wt, const float* bias, float* mu_img, int B, int Npad,
-                 hipStream_t s, float* mu_rows, int sh16, int bs, float scale, unsigned* amax, int pass, int bf16) {
-    hipLaunchKernelGGL(fc_mu_kernel, dim3(512 / 16, 19), dim3(256), 0, s, codes, Wt, bias, mu_img, B, Npad, mu_rows, sh16, bs,
+                 hipStream_t s, float* mu_rows, int sh16, int bs, float scale, unsigned* amax, int pass, int bf16, int transposed) {
+    hipLaunchKernelGGL(transposed ? fc_mu_kernel<true> : fc_mu_kernel<false>, dim3(512 / 16, 19), dim3(256), 0, s, codes, Wt, bias, mu_img, B, Npad, mu_rows, sh16, bs,
                        scale, amax, pass, bf16);
     return hipGetLastError();
 }

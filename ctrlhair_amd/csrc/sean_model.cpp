@@ -722,6 +722,7 @@ struct SeanBuild {
     // exact-f32 path: the group table of the one grouped GEMM launch that builds every style LUT of a chunk (Runner::luts_grouped)
     void style_lut_groups() {
         m.lut_groups = nullptr;
+        m.lut_groups_wide = false;
         m.lut_ngroups = m.lut_group_tiles = 0;
         m.lut_group_rows = 0.0;
         if (!(m.fcmu_batched && !opt.use_sh16 && opt.lut_grouped)) return;
@@ -749,6 +750,8 @@ struct SeanBuild {
             m.lut_groups = B.dalloc(g.size() * sizeof(PwGroup));
             if (m.lut_groups) (void)hipMemcpy(m.lut_groups, g.data(), g.size() * sizeof(PwGroup), hipMemcpyHostToDevice);
             m.lut_ngroups = (int)g.size();
+            m.lut_groups_wide = true;
+            for (const PwGroup& e : g) m.lut_groups_wide = m.lut_groups_wide && e.HW % 256 == 0;
         }
     }
 
@@ -793,6 +796,7 @@ struct SeanBuild {
             m.patchbuf = B.falloc((size_t)m.patch_cap_chunks * (HID + 20) * 1024);
         }
         if (wsty4_max) m.wsty4 = B.falloc(wsty4_max);
+        m.wsty4_floats = m.wsty4 ? wsty4_max : 0;
         wino4v_buffer();
         for (int k = 0; k < 6; ++k)
             if (m.wq_level[k].qlist) {
@@ -1285,7 +1289,7 @@ struct Runner {
         auto tm = [&](auto launch) { prof ? timed(2, fl, by, launch) : launch(); };
         if (a.lut_rows && N <= 64 && !m.opt.batch_inv) {
             // interactive batch sizes: P[n][row] = sum_k W[row][k] mu[n][k] as a batched GEMV (weight-bandwidth bound)
-            check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, m.mu_img, 0, bs), "fc_mu");
+            check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, m.mu_img, 0, bs, 1.f, nullptr, 0, 0, m.opt.pw_wide), "fc_mu");
             tm([&] { check(lut_gemv_mfma(m.mu_img, a.lut_rows, lut_buf, N, 18 * a.C, s), "lut gemv"); });
             return q;
         }
@@ -1306,7 +1310,7 @@ struct Runner {
                 p.in = m.mu_all + (size_t)a.index * m.mu_stride;
             } else {
                 for (int pass = 0; pass < 2; ++pass)     // second pass: returns at once unless the first one left the f16 window
-                    check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 1, bs, SH16_ACT_SCALE, mu_slot, pass, m.opt.terms == 2), "fc_mu");
+                    check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 1, bs, SH16_ACT_SCALE, mu_slot, pass, m.opt.terms == 2, m.opt.pw_wide), "fc_mu");
             }
             p.act = ACT_NONE;
             p.terms = m.opt.terms;
@@ -1321,7 +1325,7 @@ struct Runner {
             q.lut_ns = 4;
         } else {
             if (m.fcmu_batched && (N > 64 || m.opt.batch_inv)) p.in = m.mu_all + (size_t)a.index * m.mu_stride;      // projected at the start of the chunk (generate())
-            else check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s), "fc_mu");
+            else check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 0, 19, 1.f, nullptr, 0, 0, m.opt.pw_wide), "fc_mu");
             p.npix_valid = N;
             tm([&] { check(conv_nhwc1x1(p, s), "lut gemm"); });
         }
@@ -1403,6 +1407,7 @@ struct Runner {
         q.Cout = N;
         q.groups = static_cast<const PwGroup*>(m.lut_groups);
         q.ngroups = m.lut_ngroups;
+        q.wide = m.opt.pw_wide && m.lut_groups_wide;
         const int nrg = ((N + 31) / 32 + 3) / 4;
         timed(2, 2.0 * m.lut_group_rows * STYLE * N, 4.0 * (m.lut_group_rows * STYLE + m.lut_group_rows * N + (double)m.lut_ngroups * STYLE * N),
               [&] { check(conv_pw_grouped(q, m.lut_group_tiles * nrg, st), "style LUTs (grouped GEMM)"); });
@@ -1577,7 +1582,14 @@ struct Runner {
         Wino4vPackParams vp;
         const bool vroute = m.wino4v_route(wino4v_pays(2 * a.C, r), q.actv, B, r, p.kout, nks, vp, true);
         timed(1, dense_flops(p), 4.0 * (npix * p.kout + npix * a.C / (io.x_up ? 4.0 : 1.0) + npix * a.C), [&] {
-            if (w.wsty) check(wino4_style_pack(q.lut, m.wsty4, B, a.C, st), "wino4_style_pack");
+            if (w.wsty) {
+                const int rows = m.opt.pw_wide ? 1 : 0;
+                if (rows && m.pad_state[m.wsty4] != 1) {      // the units that are zero at every B and C: once (conv_inst_wino4.hip)
+                    check(hipMemsetAsync(m.wsty4, 0, m.wsty4_floats * sizeof(float), st), "wino4 style images: zero units");
+                    m.pad_state[m.wsty4] = 1;
+                }
+                check(wino4_style_pack(q.lut, m.wsty4, B, a.C, st, rows), "wino4_style_pack");
+            }
             if (vroute) {
                 check(wino4v_pack(vp, st), "hidden activation transform (winograd F(4x4,3x3))");
                 w.v = m.vbuf;
@@ -1884,6 +1896,7 @@ struct Runner {
             q.Cin = w.Cin;
             q.Cout = w.Cout;
             q.HW = r * r;
+            q.wide = m.opt.pw_wide;
             timed(0, 2.0 * w.Cout * w.Cin * npix, 4.0 * (npix * w.Cin + npix * w.Cout + (double)w.Cout * w.Cin),
                   [&] { check(conv_pw(q, st), "conv 1x1"); });
             return;
@@ -1949,13 +1962,13 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
         if (mode.project_all) {     // (smaller batches take the GEMV branch of Runner::build_lut, which projects per ACE)
             // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout)
             R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, ((B * LABEL_NC + 31) / 32) * 32, LABEL_NC, 1.f,
-                                  nullptr, 0, 0, st, mode.grouped ? 2 : 0), "fc_mu (all ACEs)");
+                                  nullptr, 0, 0, st, mode.grouped ? 2 : 0, opt.pw_wide), "fc_mu (all ACEs)");
             if (mode.grouped) R.luts_grouped();
         } else if (fcmu_batched && opt.use_sh16) {
             const int npad_c = ((B * (LABEL_NC + 1) + 31) / 32) * 32;
             for (int pass = 0; pass < 2; ++pass)         // second pass: returns at once unless a projection left the f16 window
                 R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, npad_c, LABEL_NC + 1, SH16_ACT_SCALE,
-                                      amax_slots, pass, opt.terms == 2, st), "fc_mu (all ACEs)");
+                                      amax_slots, pass, opt.terms == 2, st, 1, opt.pw_wide), "fc_mu (all ACEs)");
         }
         // interactive-size jobs: everything that depends on labels / codes only runs ahead on the side stream
         // (chunk_mode; large jobs run only the style LUT builds -- small, latency-bound GEMMs -- ahead, in the tails of the conv kernels: exact-f32
@@ -2123,6 +2136,7 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
                     q.Cin = cnt[ph] * 128;
                     q.Cout = 256;
                     q.HW = (int)hw4;
+                    q.wide = opt.pw_wide;
                     ck(conv_pw(q, st), "zenc convT (phase GEMM)");
                 }
                 ck(instnorm_act_d2s(tph, z10.bias, hs, B, 256, h4, h4, 1e-5f, ACT_LRELU, st), "zenc in4 (depth-to-space)");

@@ -98,6 +98,9 @@ struct SeanOptions {
                                                //   1 = F(2x2,3x3) everywhere (conv_wino.h); 2 = the ResBlock convs from 32 x 32 pixels as
                                                //   F(4x4,3x3) (conv_wino4.h), the rest F(2x2,3x3); 0 = direct evaluation (conv_mfma.h)
     int lut_grouped = 1;                       // option "sean.lut_grouped": exact-f32 path, style LUTs of all styled ACEs from one grouped GEMM launch
+    int pw_wide = 1;                           // option "sean.pw_wide": exact-f32 path, 1 = 64-row wave tiles of the 1x1 GEMM kernel where its launcher takes them
+                                               // (conv_pw.h pw_wide_rule; the grouped style-LUT launch when every group has 18 C % 256 == 0), the transposed wave
+                                               // reduction of fc_mu and the one-thread-per-(row, label) F(4x4) style pack; 0 = the kernels of round 11.  Same bits.
     int prologue = 1;                          // option "sean.prologue": exact-f32 Winograd path, handles beyond the run-ahead sizes: what the ACEs build from
                                                //   labels, codes and weights alone comes from a few grouped launches at the start of a chunk, into per-ACE
                                                //   buffers (SeanModel::pro_on); 0 = every ACE launches its own, inline
@@ -207,6 +210,7 @@ struct SeanModel {
     // exact-f32 path, more than 64 (sample, label) columns: the style LUTs of all styled ACEs from ONE grouped GEMM launch at the
     // start of a chunk (conv_pw.h: operands swapped -- the projected codes are the A operand, packed by fc_mu_batched) into lut_ahead
     void* lut_groups = nullptr;                 // device array of PwGroup
+    bool lut_groups_wide = false;               // every group of lut_groups has 18 C % 256 == 0: the grouped launch may take the wide tiles (sean.pw_wide)
     int lut_ngroups = 0, lut_group_tiles = 0;   // total pixel tiles (tasks = tiles x row groups of the call's batch)
     double lut_group_rows = 0.0;                // sum of 18 C over the groups (profiling figures)
     bool ahead_full = false;                   // handle sized for the full run-ahead mode (else: style LUTs only)
@@ -238,6 +242,7 @@ struct SeanModel {
     int patch_cap_chunks = 0;
     float* wsty = nullptr;
     float* wsty4 = nullptr;                    // per-sample F(4x4,3x3) style images of the ACE being run (conv_wino4.h)
+    size_t wsty4_floats = 0;                   // its size; pad_state[wsty4] == 1: zeroed since it was allocated (wino4_style_pack, rows = 1)
     float* vbuf = nullptr;                     // the pre-transformed input V of the layer being run (conv_wino4v.h)
     size_t vbuf_bytes = 0;
     // the V route of one F(4x4,3x3) layer (sean_model.cpp): taken when it `pays` (wino4v_pays) and V fits vbuf; then vp is the transform pass over `in`

@@ -139,6 +139,11 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   SLOWER than the serial order at every setting on MI355X: kept as an option, not used.
  * "sean.lut_grouped" (default 1; exact-f32 path, calls with more than 64 (sample, label) columns): the style LUTs of all styled ACEs
  *   of a chunk come from ONE grouped GEMM launch at its start (csrc/conv_pw.h); 0 = one launch of the generic 1x1 kernel per ACE.
+ * "sean.pw_wide" (default 1; any time; exact-f32 path): 1 = the 1x1 GEMM kernel (csrc/conv_pw.h) with wave tiles of 64 rows x 64 pixels
+ *   (pw_conv_wide_kernel) for the learned shortcuts with at least 64 output channels and a multiple of 256 pixels per plane, for the
+ *   Zencoder's phase GEMMs and for the grouped style-LUT launch of "sean.lut_grouped" (when every styled ACE has 18 C % 256 == 0);
+ *   fc_mu reduces a wave's 32 partial sums through one transposed butterfly; the F(4x4,3x3) style images are packed by one thread per
+ *   (GEMM row, label), their constant zero units written once per handle.  0 = the kernels of round 11.  Bit-identical results.
  * "sean.prologue" (default 1; before ch_finalize; exact-f32 Winograd path, handles beyond the run-ahead sizes of "sean.ahead"): what the ACEs
  *   of a chunk build from labels, codes and weights alone -- level geometry, hidden planes of the 32 / 64-pixel ACEs, gamma / beta tables,
  *   column / row sums and F(2x2) style images of the ACEs from 128 pixels -- comes from a few grouped launches at the start of the chunk,

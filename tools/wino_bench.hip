@@ -6,6 +6,7 @@
 #include "../ctrlhair_amd/csrc/conv_inst_wino.hip"
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -52,10 +53,39 @@ __global__ void ref_pw_kernel(const float* in, const float* w, float* out, int B
 static unsigned* g_claim = nullptr;      // "dyn" runs: 64 launches x 1024 words (eight counters each), zeroed before every timed series
 static int g_claim_i = 0;
 static unsigned* next_claim() { return g_claim ? g_claim + 1024 * (g_claim_i++ % 64) : nullptr; }
-static int run_pw() {      // the four learned shortcuts of the ngf = 64 generator at 512^2, B = 16 (+ two small shapes)
+// one launch per call of `go`, timed REP times after two warm-ups: min / median / max in ms
+struct Spread { float mn, med, mx; };
+template <class F>
+static Spread time_launches(F go) {
+    constexpr int REP = 9;
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    float t[REP];
+    for (int i = 0; i < 2; ++i) CK(go());
+    for (int i = 0; i < REP; ++i) {
+        CK(hipEventRecord(e0, 0));
+        CK(go());
+        CK(hipEventRecord(e1, 0));
+        CK(hipEventSynchronize(e1));
+        CK(hipEventElapsedTime(&t[i], e0, e1));
+    }
+    CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
+    std::sort(t, t + REP);
+    return {t[0], t[REP / 2], t[REP - 1]};
+}
+static size_t diff_words(const std::vector<float>& a, const std::vector<float>& b) {
+    size_t n = 0;
+    for (size_t i = 0; i < a.size(); ++i) n += memcmp(&a[i], &b[i], 4) != 0;
+    return n;
+}
+// the four learned shortcuts of the ngf = 64 generator at 512^2, B = 16 (+ two small shapes): pw_conv_kernel ("old", PwParams::wide = 0)
+// against the 64-row wave tiles ("wide", wide = 1), word for word; then the grouped
+// style-LUT launch of that generator (304 (sample, label) rows, Cin = 512, the 15 styled ACEs' 18 C "pixel" counts)
+static int run_pw() {
     struct S1 { int B, Cin, Cout, H; };
     const S1 all[] = {{2, 32, 48, 32}, {1, 64, 32, 16}, {16, 1024, 512, 64}, {16, 512, 256, 128}, {16, 256, 128, 256}, {16, 128, 64, 512}};
-    double tot = 0;
+    double tot[2] = {0, 0};
+    int bad = 0;
     for (const S1& c : all) {
         const int HW = c.H * c.H;
         const size_t nin = (size_t)c.B * c.Cin * HW, nout = (size_t)c.B * c.Cout * HW;
@@ -72,33 +102,100 @@ static int run_pw() {      // the four learned shortcuts of the ngf = 64 generat
         CK(hipMemcpy(d_in, hin.data(), nin * 4, hipMemcpyHostToDevice));
         CK(hipMemcpy(d_w, hw.data(), hw.size() * 4, hipMemcpyHostToDevice));
         CK(hipMemcpy(d_pk, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
-        CK(hipMemset(d_out, 0xFF, nout * 4));
         PwParams p{};
         p.in = d_in; p.wpk = d_pk; p.out = d_out; p.B = c.B; p.Cin = c.Cin; p.Cout = c.Cout; p.HW = HW;
-        if (g_claim) CK(hipMemset(g_claim, 0, 64 * 1024 * 4));
-        g_claim_i = 0;
-        CK(conv_pw(p, 0));
         hipLaunchKernelGGL(ref_pw_kernel, dim3(4096), dim3(256), 0, 0, d_in, d_w, d_ref, c.B, c.Cin, c.Cout, HW);
-        CK(hipDeviceSynchronize());
-        std::vector<float> ho(nout), hr(nout);
-        CK(hipMemcpy(ho.data(), d_out, nout * 4, hipMemcpyDeviceToHost));
+        std::vector<float> ho[2] = {std::vector<float>(nout), std::vector<float>(nout)}, hr(nout);
+        for (int v = 0; v < 2; ++v) {
+            p.wide = v;
+            CK(hipMemset(d_out, 0xFF, nout * 4));
+            CK(conv_pw(p, 0));
+            CK(hipDeviceSynchronize());
+            CK(hipMemcpy(ho[v].data(), d_out, nout * 4, hipMemcpyDeviceToHost));
+        }
         CK(hipMemcpy(hr.data(), d_ref, nout * 4, hipMemcpyDeviceToHost));
         double maxd = 0;
-        for (size_t i = 0; i < nout; ++i) { const double d = fabs((double)ho[i] - hr[i]); if (!(d <= maxd)) maxd = d; }
-        hipEvent_t e0, e1;
-        CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-        CK(hipEventRecord(e0, 0));
-        for (int i = 0; i < 5; ++i) CK(conv_pw(p, 0));
-        CK(hipEventRecord(e1, 0));
-        CK(hipEventSynchronize(e1));
-        float ms; CK(hipEventElapsedTime(&ms, e0, e1)); ms /= 5;
+        for (size_t i = 0; i < nout; ++i) { const double d = fabs((double)ho[0][i] - hr[i]); if (!(d <= maxd)) maxd = d; }
+        const size_t nd = diff_words(ho[0], ho[1]);
+        const int rp = pw_wide_rule(1, c.Cout, HW);
         const double fl = 2.0 * c.B * HW * (double)c.Cout * c.Cin;
-        printf("1x1  B%2d %4d->%4d %3d^2  maxdiff %.3e %s  %8.3f ms  %6.1f TF/s\n", c.B, c.Cin, c.Cout, c.H, maxd, maxd <= 2e-5 ? "OK  " : "FAIL", ms, fl / ms * 1e-9);
-        if (c.B == 16) tot += ms;
+        Spread t[2];
+        for (int v = 0; v < 2; ++v) {
+            p.wide = v;
+            t[v] = time_launches([&] { return conv_pw(p, 0); });
+        }
+        printf("1x1  B%2d %4d->%4d %3d^2  maxdiff %.3e %s  old %.3f [%.3f..%.3f] ms %6.1f TF/s | wide(%s) %.3f [%.3f..%.3f] ms %6.1f TF/s  diff=%zu\n", c.B, c.Cin,
+               c.Cout, c.H, maxd, maxd <= 2e-5 ? "OK  " : "FAIL", t[0].med, t[0].mn, t[0].mx, fl / t[0].med * 1e-9, rp == 2 ? "128x256" : rp == 1 ? "64x512" : "same kernel",
+               t[1].med, t[1].mn, t[1].mx, fl / t[1].med * 1e-9, nd);
+        fflush(stdout);
+        bad += nd != 0 || !(maxd <= 2e-5);
+        if (c.B == 16) { tot[0] += t[0].med; tot[1] += t[1].med; }
         hipFree(d_in); hipFree(d_w); hipFree(d_pk); hipFree(d_out); hipFree(d_ref);
     }
-    printf("sum over the four shortcut convs of one step: %.2f ms\n", tot);
-    return 0;
+    printf("sum over the four shortcut convs of one step: old %.2f ms, wide %.2f ms\n", tot[0], tot[1]);
+    {   // grouped style-LUT launch
+        const int N = 304, Cin = 512, Cs[15] = {1024, 1024, 1024, 1024, 1024, 1024, 1024, 512, 1024, 512, 256, 512, 256, 128, 256};
+        size_t rows = 0;
+        for (int C : Cs) rows += 18 * (size_t)C;
+        unsigned seed = 4242u;
+        std::vector<float> hin(rows * Cin), hmu((size_t)N * Cin);
+        for (auto& v : hin) v = frand(seed) / sqrtf((float)Cin);
+        for (auto& v : hmu) { const float f = frand(seed); v = f > 0.f ? f : 0.f; }
+        const float* mp = hmu.data();
+        std::vector<float> pk = pack_pw_A(N, Cin, [&](int row, int ci) { return mp[(size_t)row * Cin + ci]; });
+        float *d_in, *d_pk, *d_out;
+        PwGroup* d_g;
+        CK(hipMalloc(&d_in, hin.size() * 4)); CK(hipMalloc(&d_pk, pk.size() * 4)); CK(hipMalloc(&d_out, rows * N * 4)); CK(hipMalloc(&d_g, 15 * sizeof(PwGroup)));
+        CK(hipMemcpy(d_in, hin.data(), hin.size() * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(d_pk, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
+        std::vector<PwGroup> g(15);
+        size_t r0 = 0;
+        int tiles = 0;
+        for (int i = 0; i < 15; ++i) {
+            g[i].in = d_in + r0 * Cin;      // [Cin][HW] of the group
+            g[i].wpk = d_pk;
+            g[i].out = d_out + r0 * N;      // [N][HW]
+            g[i].HW = 18 * Cs[i];
+            g[i].start = tiles;
+            tiles += g[i].HW / 128;
+            r0 += g[i].HW;
+        }
+        CK(hipMemcpy(d_g, g.data(), 15 * sizeof(PwGroup), hipMemcpyHostToDevice));
+        PwParams p{};
+        p.Cin = Cin; p.Cout = N; p.groups = d_g; p.ngroups = 15;
+        const int ntasks = tiles * (((N + 31) / 32 + 3) / 4);
+        std::vector<float> ho[2] = {std::vector<float>(rows * N), std::vector<float>(rows * N)};
+        Spread t[2];
+        for (int v = 0; v < 2; ++v) {
+            p.wide = v;
+            CK(hipMemset(d_out, 0xFF, rows * N * 4));
+            CK(conv_pw_grouped(p, ntasks, 0));
+            CK(hipDeviceSynchronize());
+            CK(hipMemcpy(ho[v].data(), d_out, rows * N * 4, hipMemcpyDeviceToHost));
+            t[v] = time_launches([&] { return conv_pw_grouped(p, ntasks, 0); });
+        }
+        // spot check against a double sum (group 13: C = 128)
+        double maxd = 0;
+        {
+            size_t rb = 0;
+            for (int i = 0; i < 13; ++i) rb += g[i].HW;
+            const int HW = g[13].HW;
+            for (int n = 0; n < N; n += 7)
+                for (int px = 0; px < HW; px += 61) {
+                    double acc = 0;
+                    for (int ci = 0; ci < Cin; ++ci) acc += (double)hmu[(size_t)n * Cin + ci] * hin[rb * Cin + (size_t)ci * HW + px];
+                    const double d = fabs(acc - ho[0][rb * N + (size_t)n * HW + px]);
+                    if (!(d <= maxd)) maxd = d;
+                }
+        }
+        const size_t nd = diff_words(ho[0], ho[1]);
+        const double fl = 2.0 * rows * (double)Cin * N;
+        printf("LUT  grouped 304 rows x %zu, Cin 512  maxdiff %.3e %s  old %.3f [%.3f..%.3f] ms %6.1f TF/s | wide(128x256) %.3f [%.3f..%.3f] ms %6.1f TF/s  diff=%zu\n", rows, maxd,
+               maxd <= 2e-5 ? "OK  " : "FAIL", t[0].med, t[0].mn, t[0].mx, fl / t[0].med * 1e-9, t[1].med, t[1].mn, t[1].mx, fl / t[1].med * 1e-9, nd);
+        bad += nd != 0 || !(maxd <= 2e-5);
+        hipFree(d_in); hipFree(d_pk); hipFree(d_out); hipFree(d_g);
+    }
+    return bad ? 1 : 0;
 }
 
 int main(int argc, char** argv) {
