@@ -193,12 +193,12 @@ std::string ShapeModel::build(const TensorStore& ts, int mb) {
             const std::string p = d + ".layers." + std::to_string(2 * l + 1);
             const auto wv = B.vec(p + ".conv.weight", (size_t)co * ci * 9);
             const auto gam = B.vec(p + ".norm.gamma", co), bet = B.vec(p + ".norm.beta", co);
-            if (use_sh16 && l >= 1) {          // f16x3 path: only the bias of the f32 layer object is used
+            if (use_sh16 && l >= 1) {          // f16x3 path: the layer carries its f16x3 image only
                 const float* wp = wv.data();
                 auto getw = [&](int row, int c, int t) { return wp[((size_t)row * ci + c) * 9 + t]; };
                 const auto kexp = sh16_row_exponents(co, ci, 3, getw);
-                dec_sh[w][l] = B.upload(pack_A_sh16(co, ci, 3, getw, kexp));
-                dec_ws[w][l] = B.upload(sh16_wscale(kexp));
+                dec[w][l].sh_wpk = B.upload(pack_A_sh16(co, ci, 3, getw, kexp));
+                dec[w][l].sh_wscale = B.upload(sh16_wscale(kexp));
                 dec[w][l].bias = B.upload(B.vec(p + ".conv.bias", co));
                 dec[w][l].Cout = co;
                 dec[w][l].Cin = ci;
@@ -316,22 +316,8 @@ std::string ShapeModel::run_encoder(int w, const float* in, float* code, int B, 
         float s_in = ENC_IN_SCALE;
         for (int l = 0; l < ENC_S2D; ++l) {
             const ConvLayer& L = enc_s2d[w][l];
-            ConvParams p{};
-            p.in = x;
-            p.wpk = L.sh_wpk;
-            p.wscale = L.sh_wscale;
-            p.in_scale_inv = 1.f / s_in;
-            p.out = wc;
-            p.B = B;
-            p.Cin = L.Cin;
-            p.s2d_cr = L.s2d_cr;
-            p.s2d_phase0 = L.s2d_phase0;
             size /= 2;
-            p.H = size;
-            p.W = size;
-            p.Mrows = L.Cout;
-            p.bias = L.bias;
-            p.act = ACT_NONE;
+            ConvParams p = sh16_conv_params(L, x, wc, B, size, size, s_in);
             p.partial = wk;
             p.partial_cap = splitk_cap;
             ck(conv_sh16_s2d(p, L.KS, st), "shape enc conv (f16x3)");
@@ -418,19 +404,7 @@ std::string ShapeModel::run_decoder(int w, const float* code, int code_dim, floa
         ck(layernorm_act_conv(wc, 0, wb, 1, dec_ln_scale[w][0], dec_ln[w][0].gamma, dec_ln[w][0].beta, wl, B,
                               dec[w][0].Cout, size * size, 1e-5f, ACT_LRELU, st), "shape dec ln0");
         for (int l = 1; l < 7; ++l) {
-            ConvParams p{};
-            p.in = wb;
-            p.wpk = dec_sh[w][l];
-            p.wscale = dec_ws[w][l];
-            p.in_scale_inv = 1.f / dec_ln_scale[w][l - 1];
-            p.out = wc;
-            p.B = B;
-            p.Cin = dec[w][l].Cin;
-            p.H = 2 * size;
-            p.W = 2 * size;
-            p.Mrows = dec[w][l].Cout;
-            p.bias = dec[w][l].bias;
-            p.act = ACT_NONE;
+            ConvParams p = sh16_conv_params(dec[w][l], wb, wc, B, 2 * size, 2 * size, dec_ln_scale[w][l - 1]);
             p.in_mode = IN_UP2_NEAREST;
             p.partial = wk;
             p.partial_cap = splitk_cap;
@@ -440,21 +414,7 @@ std::string ShapeModel::run_decoder(int w, const float* code, int code_dim, floa
                                   dec[w][l].Cout, size * size, 1e-5f, ACT_LRELU, st), "shape dec ln");
         }
         {   // output conv (32 -> 1 / 18 rows, padded): C4 logits
-            const ConvLayer& L = dec_out_sh[w];
-            ConvParams p{};
-            p.in = wb;
-            p.wpk = L.sh_wpk;
-            p.wscale = L.sh_wscale;
-            p.in_scale_inv = 1.f / dec_ln_scale[w][6];
-            p.out = logit;
-            p.B = B;
-            p.Cin = 32;
-            p.H = size;
-            p.W = size;
-            p.Mrows = L.Cout;
-            p.bias = L.bias;
-            p.act = ACT_NONE;
-            ck(conv_sh16_plain(p, 3, st), "shape dec out (f16x3)");
+            ck(conv_sh16_plain(sh16_conv_params(dec_out_sh[w], wb, logit, B, size, size, dec_ln_scale[w][6]), 3, st), "shape dec out (f16x3)");
         }
         return ck.err;
     }
@@ -647,35 +607,18 @@ std::string BiSeNetModel::parse_sh16(const float* img, uint8_t* labels, float* l
                   h32 = H / 32, w32 = W / 32;
         // one conv on the f16x3 kernels over the C4 input (stride 2: conv_sh16.h S2D)
         auto conv = [&](const ConvLayer& L, T in, T out, int hin, int win, int act, const float* res, int in_mode, const char* what) {
-            ConvParams p{};
-            p.in = in.p;
-            p.out = out.p;
-            p.B = B;
-            p.Cin = L.Cin;
+            const bool s2d = L.stride == 2;      // space-to-depth form: output at half the input size
+            ConvParams p = sh16_conv_params(L, in.p, out.p, B, s2d ? hin / 2 : conv_out_size(L, hin, in_mode), s2d ? win / 2 : conv_out_size(L, win, in_mode),
+                                            SH16_ACT_SCALE);
             p.in_mode = in_mode;
-            p.H = conv_out_size(L, hin, in_mode);
-            p.W = conv_out_size(L, win, in_mode);
-            p.Mrows = L.Cout;
-            p.bias = L.bias;
             p.act = act;
             p.res = res;
             p.out_amax = out.amax;
             p.partial = splitk_ws;
             p.partial_cap = splitk_cap;
-            p.wpk = L.sh_wpk;
-            p.wscale = L.sh_wscale;
-            p.in_scale_inv = 1.f / SH16_ACT_SCALE;
             p.in_amax = in.amax;
             p.in_c4 = 1;
-            if (L.stride == 2) {           // space-to-depth form: output at half the input size
-                p.H = hin / 2;
-                p.W = win / 2;
-                p.s2d_cr = L.s2d_cr;
-                p.s2d_phase0 = L.s2d_phase0;
-                ck(conv_sh16_s2d_c4(p, L.KS, st), what);
-            } else {
-                ck(conv_sh16_plain_c4(p, L.KS, st), what);
-            }
+            ck(s2d ? conv_sh16_s2d_c4(p, L.KS, st) : conv_sh16_plain_c4(p, L.KS, st), what);
         };
         ck(stem7x7(img + (size_t)bo * 3 * H * W, stem_w, stem_b, b0, B, H, W, st), "stem");
         T x = mk(b1);

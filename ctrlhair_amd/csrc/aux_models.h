@@ -39,11 +39,10 @@ struct ShapeModel {
     float *dec_in_w[2] = {}, *dec_in_b[2] = {};
     ConvLayer dec[2][7], dec_out[2];
     LnW dec_ln[2][7];
-    // decoder layers 1..6 on the f16x3 split-operand kernels (conv_sh16.h): packed weights, per-row inverse scales, and the
-    // power-of-two SH16 scale of each LayerNorm output (from the bound sqrt(C*HW) * max|gamma| + max|beta|: cannot saturate)
+    // decoder layers 1..6 on the f16x3 split-operand kernels (conv_sh16.h): dec[w][l] carries sh_wpk / sh_wscale instead of the exact-f32 images;
+    // dec_ln_scale: the power-of-two SH16 scale of each LayerNorm output (from the bound sqrt(C*HW) * max|gamma| + max|beta|: cannot saturate)
     bool use_sh16 = true;
     int wino = 1;                   // option "aux.wino": exact-f32 kernels, 3x3 stride-1 convs as Winograd F(2x2,3x3) where the tiles fit (net_common.h run_conv)
-    float *dec_sh[2][7] = {}, *dec_ws[2][7] = {};
     float dec_ln_scale[2][7] = {};
     // encoder layers (k4 s2 convs, 128^2 .. 2^2 outputs) in the space-to-depth form of the f16x3 kernels (conv_sh16.h S2D):
     // SH16 inputs (scale 2^14: one-hot and sin / cos channels), LayerNorm outputs SH16 with their static scales

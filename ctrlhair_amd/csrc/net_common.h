@@ -1,5 +1,8 @@
 // net_common.h -- shared host-side helpers of the model files: host tensor store, weight upload, MFMA operand
-// packing, a generic conv layer (conv_mfma_kernel launcher wrapper) and small-op launch helpers.
+// packing, and the plain convs of every net: ONE layer type (ConvLayer: each weight image a route may read), ONE route
+// decision of the exact-f32 path (ConvRoute / conv_route: F(4x4,3x3) with or without the pre-transformed input, F(2x2,3x3),
+// 1x1 GEMM, direct kernel), ONE launcher (run_conv) and its profile figures (conv_figures), and ONE filler of the f16x3
+// ConvParams (sh16_conv_params).  The SEAN generator, the Zencoder, the shape nets and BiSeNet all launch through these.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,7 +15,10 @@
 #include <vector>
 
 #include "conv_mfma.h"
+#include "conv_pw.h"
+#include "conv_sh16.h"
 #include "conv_wino.h"
+#include "conv_wino4v.h"
 
 namespace chk {
 
@@ -168,16 +174,21 @@ inline std::vector<float> sh16_wscale(const std::vector<int>& kexp) {
     return v;
 }
 
-// ---- generic conv layer on the MFMA kernel ------------------------------------------------------------------
+// ---- the plain conv layer: every weight image a route may read (a handle uploads only those its path and options can reach) ----
 struct ConvLayer {
-    float* wpk = nullptr;
+    float* wpk = nullptr;           // exact-f32 direct kernel (conv_mfma.h): pack_A image
     float* bias = nullptr;
     int Cout = 0, Cin = 0, KS = 0, stride = 1, pad = 0;
-    float* sh_wpk = nullptr;       // f16x3 packing (make_conv_sh16 / make_conv_s2d): split-operand A fragments + per-row inverse scales
-    float* sh_wscale = nullptr;
+    float* sh_wpk = nullptr;        // f16x3 kernels (conv_sh16.h): split-operand A fragments (pack_A_sh16) ...
+    float* sh_wscale = nullptr;     // ... and the per-row inverse scales 2^-k (sh16.h)
     int s2d_cr = 0, s2d_phase0 = 0; // make_conv_s2d: real (padded) input channels and first phase of the space-to-depth form
-    float* wino = nullptr;          // 3x3 stride-1 pad-1 layers of the exact-f32 path: Winograd F(2x2,3x3) A images (conv_wino.h) ...
-    float* zero = nullptr;          // ... and a few zero words (source of out-of-image patch elements)
+    float* wino = nullptr;          // 3x3 stride-1 pad-1, exact f32: Winograd F(2x2,3x3) image U = G g G^T (conv_wino.h) ...
+    float* zero = nullptr;          // ... and a few zero words (source of out-of-image patch elements) where the caller has no zero page
+    float* wino4 = nullptr;         // the same conv as F(4x4,3x3) (conv_wino4.h) ...
+    float* wino4s = nullptr;        // ... and those values in the split kernel's fragment order (conv_wino4_split.h)
+    float* pw = nullptr;            // 1x1, exact f32: pack_pw_A image of the GEMM kernel (conv_pw.h)
+    int d2s = 0;                    // 1 = GEMM row 4 c + (2 py + px) holds phase (py, px) of channel c: depth-to-space store (a stride-2
+                                    //   ConvTranspose2d as four phase convs of the input grid; F(2x2,3x3) only)
 };
 
 // w: [Cout][Cin][KS][KS] (already folded: BN / spectral norm / flips), bias may be empty
@@ -262,6 +273,7 @@ inline ConvLayer make_conv_s2d(Builder& B, const std::vector<float>& w, const st
     return L;
 }
 
+// ---- one call of a plain conv: its epilogue, its input view and the environment the routes read ---------------------------------
 struct ConvOpts {
     int pad_mode = PAD_ZERO;
     int in_mode = IN_DIRECT;
@@ -271,7 +283,19 @@ struct ConvOpts {
     int res_after_act = 0;
     float* partial = nullptr;      // split-K scratch (optional): enables split-K for few-tile / long-K layers
     long long partial_cap = 0;
-    int no_wino = 0;               // 1 = keep a 3x3 stride-1 layer on the direct kernel (A/B tests)
+    int no_wino = 0;               // 1 = keep the layer on the direct kernel (A/B tests)
+    // the handle's side: options, device and shared buffers (defaults: what a net without them runs with)
+    int wino = 1;                  // Winograd level: 0 = direct kernels only, 1 = F(2x2,3x3) and the 1x1 GEMM, 2 = also F(4x4,3x3)
+    int wino4_force = 0;           // F(4x4,3x3) wherever the shape allows, whatever the task count
+    int batch_inv = 0;             // every choice that follows the task count is made as for a large batch (no sample-pair tiles)
+    int wino4_split = -1;          // Wino4Params::split
+    int v_pays = -1;               // the V route of an F(4x4,3x3) call: -1 = where wino4v_pays says so, 1 = wherever V fits, 0 = never
+    int pw_wide = 0;               // PwParams::wide
+    int num_cus = 256;
+    float* vbuf = nullptr;         // the pre-transformed input V (conv_wino4v.h) and its size; null: no V route
+    size_t vbuf_bytes = 0;
+    const float* zero = nullptr;   // zero page; null: the layer's own zero words
+    unsigned* claim = nullptr;     // claim slot of an F(2x2,3x3) launch (dynamic task claiming), or null
 };
 
 inline int conv_out_size(const ConvLayer& L, int in, int in_mode) {
@@ -279,37 +303,83 @@ inline int conv_out_size(const ConvLayer& L, int in, int in_mode) {
     return (l + 2 * L.pad - L.KS) / L.stride + 1;
 }
 
-// in: [B][Cin][Hin][Win] -> out: [B][Cout][Ho][Wo]
-inline hipError_t run_conv(const ConvLayer& L, const float* in, float* out, int B, int Hin, int Win,
-                           const ConvOpts& o, hipStream_t st) {
-    {   // Winograd F(2x2,3x3) route (exact f32: the same sums in another association, conv_wino.h): 3x3 stride-1 pad-1 layers whose
-        // output fits the kernel's tiles of 32 x 16 pixels (16 x 16 images: pairs of samples), direct or nearest-x2 input view
-        const int H = conv_out_size(L, Hin, o.in_mode), W = conv_out_size(L, Win, o.in_mode);
-        const bool up = o.in_mode == IN_UP2_NEAREST, refl = o.pad_mode == PAD_REFLECT;
-        const bool tiles = wino_supported(H, W, L.Cin) || (!up && !refl && !o.res_up && wino_supported_pair16(B, H, W, L.Cin));
-        if (L.wino && L.zero && !o.no_wino && L.KS == 3 && L.stride == 1 && L.pad == 1 && (o.in_mode == IN_DIRECT || up) && !(up && refl) &&
-            !o.res_after_act && tiles) {
-            WinoParams q{};
-            q.in = in;
-            q.wpk = L.wino;
-            q.out = out;
-            q.B = B;
-            q.Cin = L.Cin;
-            q.Cout = L.Cout;
-            q.H = H;
-            q.W = W;
-            q.bias = L.bias;
-            q.res = o.res;
-            q.res_up = o.res_up;
-            q.act = o.act;
-            q.reflect = refl ? 1 : 0;
-            q.in_up = up ? 1 : 0;
-            q.zero = L.zero;
-            q.partial = o.partial;             // (few tasks, long k-loop: conv_wino_plain splits K)
-            q.partial_cap = o.partial_cap;
-            return conv_wino_plain(q, st);
-        }
+// few tiles of the direct kernels (64 rows x 512 pixels) for the device: such a layer prefers split-K and takes no fused 1x1 operand
+inline bool conv_few_tiles(int Cout, long long npix) { return ((Cout + 63) / 64) * ((npix + 511) / 512) < 192; }
+
+// The V route of one F(4x4,3x3) layer (conv_wino4v.h): taken when it `pays` and V fits the buffer; then vp is the transform pass over `in`
+// (padded: hidden planes of an ACE level, conv_wino.h WINO_AXOFF; reflect: reflection padding)
+inline bool wino4v_plan(bool pays, float* vbuf, size_t vbuf_bytes, const float* in, int Bn, int H, int W, int K, int nks, Wino4vPackParams& vp,
+                        bool padded = false, bool reflect = false) {
+    if (!(pays && vbuf && H % 32 == 0 && W % 32 == 0 && wino4v_bytes(Bn, H, W, nks) <= vbuf_bytes)) return false;
+    vp = Wino4vPackParams{};
+    vp.in = in;
+    vp.v = vbuf;
+    vp.B = Bn;
+    vp.K = K;
+    vp.H = H;
+    vp.W = W;
+    vp.nks = nks;
+    vp.pitch = padded ? wino_apitch(W) : W;
+    vp.xoff = padded ? WINO_AXOFF : 0;
+    vp.padded = padded ? 1 : 0;
+    vp.reflect = reflect ? 1 : 0;
+    return true;
+}
+
+enum class ConvRoute {     // the route of one exact-f32 plain conv call (conv_route): decided once, read by the launcher and the profile figures
+    F4V,         // F(4x4,3x3) over the input pre-transformed by one extra pass (conv_wino4v.h)
+    F4,          // F(4x4,3x3) (conv_wino4.h; the launcher may take the split kernel, conv_wino4_split.h)
+    F2,          // F(2x2,3x3) (conv_wino.h)
+    Pw,          // 1x1 GEMM kernel (conv_pw.h): no bias, no residual
+    Direct       // conv_mfma.h
+};
+
+// From the layer's images, the call's shape (H x W: OUTPUT size) and `o`.  Launches nothing.  A route needs its image: a layer without an
+// F(4x4) image (every layer of the aux nets) never takes F(4x4), one without a direct image (the Zencoder's phase convs) must not fall to Direct.
+inline ConvRoute conv_route(const ConvLayer& L, int B, int H, int W, const ConvOpts& o) {
+    const bool up = o.in_mode == IN_UP2_NEAREST, refl = o.pad_mode == PAD_REFLECT;
+    const bool k3 = L.KS == 3 && L.stride == 1 && L.pad == 1 && !o.res_after_act && o.wino && !o.no_wino;
+    // F(2x2): tiles of 32 x 16 pixels over the direct or nearest-x2 view; 16 x 16 images as pairs of samples (direct input, zero padding, residual of
+    // the same size -- so never with an up-sampled residual at 16 pixels --, and only where the batch may decide)
+    const bool tiles = wino_supported(H, W, L.Cin) || (!up && !refl && !o.res_up && !o.batch_inv && !L.d2s && wino_supported_pair16(B, H, W, L.Cin));
+    const bool f2 = k3 && L.wino && (o.zero || L.zero) && (o.in_mode == IN_DIRECT || up) && !(up && refl) && tiles;
+    if (k3 && o.wino >= 2 && L.wino4 && o.in_mode == IN_DIRECT && !L.d2s && wino4_supported(H, W, L.Cin) &&
+        (!f2 || o.wino4_force || o.batch_inv || wino4_pays((long long)B * (H / 32) * (W / 32) * ((L.Cout + 31) / 32), o.num_cus))) {
+        // many GEMM rows on a small level: the input transform once, in its own pass, instead of in every row tile
+        const bool pays = o.v_pays < 0 ? wino4v_pays(L.Cout, H) : o.v_pays != 0;
+        Wino4vPackParams vp;
+        return wino4v_plan(pays, o.vbuf, o.vbuf_bytes, nullptr, B, H, W, L.Cin, L.Cin / 4, vp) ? ConvRoute::F4V : ConvRoute::F4;
     }
+    if (f2) return ConvRoute::F2;
+    if (o.wino && !o.no_wino && L.pw && L.KS == 1 && L.stride == 1 && o.in_mode == IN_DIRECT && !o.res && !L.bias && o.act == ACT_NONE &&
+        pw_supported(L.Cin, L.Cout, H * W))
+        return ConvRoute::Pw;
+    return ConvRoute::Direct;
+}
+
+// What a profile records for the call (SeanModel::prof, kind 0): FLOPs of the dense evaluation, FLOPs the matrix cores run on this route
+// (< 0: the same) and algorithmic bytes.  Cin2: channels of a fused 1x1 second operand (Direct only)
+struct ConvFigures { double flops, flops_exec, bytes; };
+inline ConvFigures conv_figures(ConvRoute rt, const ConvLayer& w, double npix, bool res, int Cin2 = 0) {
+    const double k2 = w.KS * w.KS, cin2 = Cin2;
+    switch (rt) {
+        case ConvRoute::F4V:
+        case ConvRoute::F4:      // 36 MFMA products per 4 x 4 tile and channel instead of 144
+            return {2.0 * w.Cout * w.Cin * 9.0 * npix, 2.0 * w.Cout * w.Cin * 36.0 * npix / 16.0,
+                    4.0 * (npix * w.Cin + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * w.Cin * 36.0)};
+        case ConvRoute::F2:      // 16 MFMA products per quad and channel instead of 36
+            return {2.0 * w.Cout * w.Cin * 9.0 * npix, 2.0 * w.Cout * w.Cin * 16.0 * npix / 4.0,
+                    4.0 * (npix * w.Cin + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * w.Cin * 16.0)};
+        case ConvRoute::Pw:
+            return {2.0 * w.Cout * w.Cin * npix, -1.0, 4.0 * (npix * w.Cin + npix * w.Cout + (double)w.Cout * w.Cin)};
+        default:
+            return {2.0 * w.Cout * (w.Cin * k2 + cin2) * npix, -1.0,
+                    4.0 * (npix * (w.Cin + cin2) + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * (w.Cin * k2 + cin2))};
+    }
+}
+
+// the direct kernel's operands (conv_mfma.h); in: [B][Cin][Hin][Win]
+inline ConvParams conv_direct_params(const ConvLayer& L, const float* in, float* out, int B, int Hin, int Win, const ConvOpts& o) {
     ConvParams p{};
     p.in = in;
     p.wpk = L.wpk;
@@ -331,10 +401,96 @@ inline hipError_t run_conv(const ConvLayer& L, const float* in, float* out, int 
     p.act = o.act;
     p.partial = o.partial;
     p.partial_cap = o.partial_cap;
+    return p;
+}
+
+// The launcher: in [B][Cin][Hin][Win] -> out [B][Cout][Ho][Wo] on route `rt` (= conv_route of the same call).  The three Winograd / GEMM parameter
+// structs take their common operands from one list; the V route launches its transform pass first.
+inline hipError_t run_conv(ConvRoute rt, const ConvLayer& L, const float* in, float* out, int B, int Hin, int Win, const ConvOpts& o, hipStream_t st) {
+    const int H = conv_out_size(L, Hin, o.in_mode), W = conv_out_size(L, Win, o.in_mode);
+    auto common = [&](auto& q, const float* image) {
+        q.in = in;
+        q.wpk = image;
+        q.out = out;
+        q.B = B;
+        q.Cin = L.Cin;
+        q.Cout = L.Cout;
+    };
+    auto epilogue = [&](auto& q) {
+        q.H = H;
+        q.W = W;
+        q.bias = L.bias;
+        q.res = o.res;
+        q.res_up = o.res_up;
+        q.act = o.act;
+        q.reflect = o.pad_mode == PAD_REFLECT ? 1 : 0;
+    };
+    switch (rt) {
+        case ConvRoute::F4V:
+        case ConvRoute::F4: {
+            Wino4Params q{};
+            common(q, L.wino4);
+            epilogue(q);
+            q.wpk_split = L.wino4s;
+            q.split = o.wino4_split;
+            if (rt == ConvRoute::F4) return conv_wino4_plain(q, st);
+            Wino4vPackParams vp;
+            if (!wino4v_plan(true, o.vbuf, o.vbuf_bytes, in, B, H, W, L.Cin, L.Cin / 4, vp, false, q.reflect != 0)) return hipErrorInvalidValue;
+            const hipError_t e = wino4v_pack(vp, st);
+            if (e != hipSuccess) return e;
+            q.v = o.vbuf;
+            return conv_wino4v_plain(q, st);
+        }
+        case ConvRoute::F2: {
+            WinoParams q{};
+            common(q, L.wino);
+            epilogue(q);
+            q.in_up = o.in_mode == IN_UP2_NEAREST ? 1 : 0;
+            q.d2s = L.d2s;
+            q.zero = o.zero ? o.zero : L.zero;
+            q.claim = o.claim;
+            q.partial = o.partial;             // (few tasks, long k-loop: conv_wino_plain splits K)
+            q.partial_cap = o.partial_cap;
+            return conv_wino_plain(q, st);
+        }
+        case ConvRoute::Pw: {
+            PwParams q{};
+            common(q, L.pw);
+            q.HW = H * W;
+            q.wide = o.pw_wide;
+            return conv_pw(q, st);
+        }
+        default: break;
+    }
+    if (!L.wpk) return hipErrorInvalidValue;
+    const ConvParams p = conv_direct_params(L, in, out, B, Hin, Win, o);
     if (L.stride == 2) return conv_plain_s2(p, L.KS, st);
     if (L.KS == 3) return conv_plain3(p, st);
     if (L.KS == 1) return conv_plain1(p, st);
     return hipErrorInvalidValue;
+}
+inline hipError_t run_conv(const ConvLayer& L, const float* in, float* out, int B, int Hin, int Win, const ConvOpts& o, hipStream_t st) {
+    return run_conv(conv_route(L, B, conv_out_size(L, Hin, o.in_mode), conv_out_size(L, Win, o.in_mode), o), L, in, out, B, Hin, Win, o, st);
+}
+
+// The f16x3 ConvParams (conv_sh16.h) of layer L: everything the layer determines, the operands and the OUTPUT size H x W; s_in = first-pass SH16
+// scale of the input.  The caller adds what is its own: input mode, activation, residual, amax slots, C4 flag, split-K scratch.
+inline ConvParams sh16_conv_params(const ConvLayer& L, const float* in, float* out, int B, int H, int W, float s_in) {
+    ConvParams p{};
+    p.in = in;
+    p.wpk = L.sh_wpk;
+    p.wscale = L.sh_wscale;
+    p.in_scale_inv = 1.f / s_in;
+    p.out = out;
+    p.B = B;
+    p.Cin = L.Cin;
+    p.s2d_cr = L.s2d_cr;
+    p.s2d_phase0 = L.s2d_phase0;
+    p.H = H;
+    p.W = W;
+    p.Mrows = L.Cout;
+    p.bias = L.bias;
+    return p;
 }
 
 }  // namespace chk

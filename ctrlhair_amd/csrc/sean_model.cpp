@@ -155,12 +155,12 @@ struct SeanBuild {
         r.cout = cout; r.cin = cin; r.ks = ks;
         return r;
     }
-    void sn_pack(const SN& r, const std::string& p, bool bias, const std::vector<int>* kexp, ConvW& cw) {
+    void sn_pack(const SN& r, const std::string& p, bool bias, const std::vector<int>* kexp, ConvLayer& cw) {
         if (!r.w) return;
         auto getw = sn_get(r);
         if (opt.use_sh16) {
-            cw.wpk = B.upload(pack_A_sh16(r.cout, r.cin, r.ks, getw, *kexp, opt.terms == 2));
-            cw.wscale = B.upload(sh16_wscale(*kexp));
+            cw.sh_wpk = B.upload(pack_A_sh16(r.cout, r.cin, r.ks, getw, *kexp, opt.terms == 2));
+            cw.sh_wscale = B.upload(sh16_wscale(*kexp));
         } else {
             cw.wpk = B.upload(pack_A(r.cout, r.cin, r.ks, r.ks == 3 ? CK_KS3 : CK_KS1, getw));
             if (opt.wino && r.ks == 3 && r.cin % 8 == 0) cw.wino = B.upload(pack_wino_A(r.cout, r.cin, getw));
@@ -173,6 +173,7 @@ struct SeanBuild {
         cw.Cout = r.cout;
         cw.Cin = r.cin;
         cw.KS = r.ks;
+        cw.pad = r.ks / 2;
         if (bias) {
             auto bb = B.get(p + ".bias", r.cout);
             if (bb) cw.bias = B.upload(std::vector<float>(bb->f32(), bb->f32() + r.cout));
@@ -513,10 +514,23 @@ struct SeanBuild {
             for (int co = 0; co < 256; ++co)
                 for (int ci = 0; ci < 128; ++ci)
                     for (int t = 0; t < 9; ++t) w[((size_t)co * 128 + ci) * 9 + t] = wt[((size_t)ci * 256 + co) * 9 + (8 - t)];
-            m.z10 = make_conv(B, w, B.vec("Zencoder.model.10.bias", 256), 256, 128, 3, 1, 1, false);      // (its Winograd form is z10_wino: four phase convs)
+            m.z10 = make_conv(B, w, B.vec("Zencoder.model.10.bias", 256), 256, 128, 3, 1, 1, false);      // (its Winograd form is the layer z10_wino: four phase convs)
         }
         plain("Zencoder.model.14", 512, 256, 1, m.z14);
-        m.z14_wino = m.z10_wino = m.z14_wino4 = m.z14_wino4s = nullptr;
+        auto form = [&](int cout, int cin, int ks) {      // another conv that computes the ConvTranspose: z10's bias, its own images
+            ConvLayer L;
+            L.Cout = cout;
+            L.Cin = cin;
+            L.KS = ks;
+            L.pad = ks / 2;
+            L.bias = m.z10.bias;
+            return L;
+        };
+        m.z10_wino = form(1024, 128, 3);
+        m.z10_wino.d2s = 1;
+        m.z10_d2s = form(1024, 128, 2);
+        static const int cnt[4] = {1, 2, 2, 4};
+        for (int ph = 0; ph < 4; ++ph) m.z10_pw[ph] = form(256, cnt[ph] * 128, 1);
         if (!opt.use_sh16 && opt.wino) zencoder_wino();
         if (opt.use_sh16) zencoder_sh16();
         if (!B.err.empty()) return B.err;
@@ -528,18 +542,18 @@ struct SeanBuild {
         auto w14 = B.vec("Zencoder.model.14.weight", (size_t)512 * 256 * 9);
         const float* wp = w14.data();
         auto g14 = [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; };
-        m.z14_wino = B.upload(pack_wino_A(512, 256, g14));
+        m.z14.wino = B.upload(pack_wino_A(512, 256, g14));
         // "sean.wino" = 2: the same conv as F(4x4,3x3) (conv_wino4.h, reflection instantiation) where the half-resolution grid is a multiple of 32
-        if (opt.wino >= 2) m.z14_wino4 = B.upload(pack_wino4_A(512, 256, g14));
+        if (opt.wino >= 2) m.z14.wino4 = B.upload(pack_wino4_A(512, 256, g14));
         if (opt.wino >= 2 && opt.wino4_split > 0)      // (512 GEMM rows: the V route by default; the split kernel only on request)
-            m.z14_wino4s = B.upload(pack_wino4_A(512, 256, g14, true));
+            m.z14.wino4s = B.upload(pack_wino4_A(512, 256, g14, true));
         // ConvTranspose2d(128, 256, k3, s2, p1, op1) (architecture.py:167-170) as four phase convs of the INPUT grid:
         //   out[2y+py][2x+px] = sum over dy, dx in {0, 1} of x[y+dy][x+dx] * Wt[ci][co][py+1-2dy][px+1-2dx]   (taps outside 0..2 absent)
         // each a 3x3 kernel with non-zero taps at offsets 0 / +1 only; as Winograd F(2x2,3x3) that is 4 products per output pixel,
         // against 9 of the plain conv over the zero-inserted view (three quarters of them on inserted zeros).  Row = 4 co + phase.
         auto wt10 = B.vec("Zencoder.model.10.weight", (size_t)128 * 256 * 9);
         const float* w10 = wt10.data();
-        m.z10_wino = B.upload(pack_wino_A(1024, 128, [&](int row, int ci, int t) {
+        m.z10_wino.wino = B.upload(pack_wino_A(1024, 128, [&](int row, int ci, int t) {
             const int co = row >> 2, py = (row >> 1) & 1, px = row & 1, dy = t / 3 - 1, dx = t % 3 - 1;
             if (dy < 0 || dx < 0) return 0.f;
             const int ky = py + 1 - 2 * dy, kx = px + 1 - 2 * dx;
@@ -552,7 +566,7 @@ struct SeanBuild {
         static const int first[4] = {1, 0, 1, 0}, cnt[4] = {1, 2, 2, 4}, sdy[4] = {0, 0, 1, 1}, sdx[4] = {1, 0, 0, 1};
         for (int ph = 0; ph < 4; ++ph) {
             const int py = ph >> 1, px = ph & 1;
-            m.z10_pw[ph] = B.upload(pack_pw_A(256, cnt[ph] * 128, [&](int co, int ci) {
+            m.z10_pw[ph].pw = B.upload(pack_pw_A(256, cnt[ph] * 128, [&](int co, int ci) {
                 const int sh = first[ph] + ci / 128, c = ci % 128;
                 const int ky = py + 1 - 2 * sdy[sh], kx = px + 1 - 2 * sdx[sh];
                 return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)c * 256 + co) * 9 + ky * 3 + kx] : 0.f;
@@ -565,15 +579,15 @@ struct SeanBuild {
         const float* wp = w14.data();
         auto g14 = [&](int row, int ci, int t) { return wp[((size_t)row * 256 + ci) * 9 + t]; };
         const auto k14 = sh16_row_exponents(512, 256, 3, g14);
-        m.z14_sh = B.upload(pack_A_sh16(512, 256, 3, g14, k14));
-        m.z14_ws = B.upload(sh16_wscale(k14));
+        m.z14.sh_wpk = B.upload(pack_A_sh16(512, 256, 3, g14, k14));
+        m.z14.sh_wscale = B.upload(sh16_wscale(k14));
         // the ConvTranspose too (a 3x3 conv over the zero-inserted view, flipped taps as above)
         auto wt10 = B.vec("Zencoder.model.10.weight", (size_t)128 * 256 * 9);
         const float* w10 = wt10.data();
         auto g10 = [&](int row, int ci, int t) { return w10[((size_t)ci * 256 + row) * 9 + (8 - t)]; };
         const auto k10 = sh16_row_exponents(256, 128, 3, g10);
-        m.z10_sh = B.upload(pack_A_sh16(256, 128, 3, g10, k10));
-        m.z10_ws = B.upload(sh16_wscale(k10));
+        m.z10.sh_wpk = B.upload(pack_A_sh16(256, 128, 3, g10, k10));
+        m.z10.sh_wscale = B.upload(sh16_wscale(k10));
         {   // depth-to-space form of the same ConvTranspose: out[2y+py][2x+px] += x[y+dy][x+dx] * Wt[ci][co][py+1-2dy][px+1-2dx]
             auto gd = [&](int row, int ci, int t) {
                 const int ph = row / 256, co = row % 256;
@@ -581,8 +595,8 @@ struct SeanBuild {
                 return (ky >= 0 && ky < 3 && kx >= 0 && kx < 3) ? w10[((size_t)ci * 256 + co) * 9 + ky * 3 + kx] : 0.f;
             };
             const auto kd = sh16_row_exponents(1024, 128, 2, gd);
-            m.z10_d2s = B.upload(pack_A_sh16(1024, 128, 2, gd, kd));
-            m.z10_d2s_ws = B.upload(sh16_wscale(kd));
+            m.z10_d2s.sh_wpk = B.upload(pack_A_sh16(1024, 128, 2, gd, kd));
+            m.z10_d2s.sh_wscale = B.upload(sh16_wscale(kd));
         }
         // and the two stride-2 convs (space-to-depth form)
         m.z4_s2d = make_conv_s2d(B, B.vec("Zencoder.model.4.weight", (size_t)64 * 32 * 9), B.vec("Zencoder.model.4.bias", 64), 64, 32, 3);
@@ -832,7 +846,7 @@ struct SeanBuild {
             return (r < 32 || r % 32 || r > 64) ? 0 : r;
         };
         for (const auto& b : m.blocks)
-            for (const ConvW* c : {&b.conv_0, &b.conv_1})
+            for (const ConvLayer* c : {&b.conv_0, &b.conv_1})
                 if (const int r = level_r(b.res_div))
                     if (c->wino4 && wino4v_pays(c->Cout, r)) need = std::max(need, wino4v_bytes(mb, r, r, c->Cin / 4));
         for_each_ace(m.blocks, [&](const AceW& a) {
@@ -840,7 +854,7 @@ struct SeanBuild {
                 if (m.ace_route_shape(a, r) == AceRoute::F4 && wino4v_pays(2 * a.C, r)) need = std::max(need, wino4v_bytes(mb, r, r, 38));
         });
         // the Zencoder's 256 -> 512 conv on the half-resolution grid: 9 bytes x 256 channels x (ms / 2)^2 per sample -- up to 2.5 GB only
-        if (m.z14_wino4 && (ms / 2) % 32 == 0 && wino4v_bytes(mb, ms / 2, ms / 2, 64) <= ((size_t)5 << 29)) need = std::max(need, wino4v_bytes(mb, ms / 2, ms / 2, 64));
+        if (m.z14.wino4 && (ms / 2) % 32 == 0 && wino4v_bytes(mb, ms / 2, ms / 2, 64) <= ((size_t)5 << 29)) need = std::max(need, wino4v_bytes(mb, ms / 2, ms / 2, 64));
         if (need) {
             m.vbuf = static_cast<float*>(B.dalloc(need));
             m.vbuf_bytes = need;
@@ -1791,121 +1805,167 @@ struct Runner {
     }
 
     // fuse: optional (weights, input) of a 1x1 conv added into this 3x3 conv's accumulators (f16x3 path, W >= 32, no split-K)
-    bool can_fuse_1x1(const ConvW& w, int r) const {
-        return !(m.opt.dbg & 32) && w.KS == 3 && r >= 32 &&
-               !(((w.Cout + 63) / 64) * (((long long)B * r * r + 511) / 512) < 192);
+    bool can_fuse_1x1(const ConvLayer& w, int r) const {
+        return !(m.opt.dbg & 32) && w.KS == 3 && r >= 32 && !conv_few_tiles(w.Cout, (long long)B * r * r);
     }
-    bool use_wino(const ConvW& w, int r) const {
-        return m.opt.wino && !m.opt.use_sh16 && w.wino && w.KS == 3 && (wino_supported(r, r, w.Cin) || (!m.opt.batch_inv && wino_supported_pair16(B, r, r, w.Cin)));
+    // one plain conv call of this chunk as the routes see it (net_common.h): the handle's environment, the residual, split-K scratch
+    ConvOpts conv_opts(const float* res, int res_up) const {
+        ConvOpts o = m.conv_env();
+        o.res = res;
+        o.res_up = res_up;
+        o.partial = m.opt.batch_inv ? nullptr : m.splitk_ws;      // (split-K follows the task count, i.e. the batch)
+        o.partial_cap = m.splitk_cap;
+        return o;
     }
-    // `prod` / `prod2`: the ACEs that wrote `in` / `in2` (their slots hold the scale in effect)
-    void conv(const ConvW& w, const float* in, const AceW& prod, float* out, int r, const float* res, int res_up,
-              const ConvW* w2 = nullptr, const float* in2 = nullptr, const AceW* prod2 = nullptr) {
-        ConvParams p{};
+    ConvRoute route(const ConvLayer& w, int r, const ConvOpts& o) const { return m.opt.use_sh16 ? ConvRoute::Direct : conv_route(w, B, r, r, o); }
+    bool use_wino(const ConvLayer& w, int r) const { return route(w, r, conv_opts(nullptr, 0)) != ConvRoute::Direct; }
+    // `prod` / `prod2`: the ACEs that wrote `in` / `in2` (their slots hold the scale in effect).  The generator's own: the fused second operand
+    // w2 / in2 (direct kernels only), the amax slots, timed()
+    void conv(const ConvLayer& w, const float* in, const AceW& prod, float* out, int r, const float* res, int res_up,
+              const ConvLayer* w2 = nullptr, const float* in2 = nullptr, const AceW* prod2 = nullptr) {
+        ConvOpts o = conv_opts(res, res_up);
+        const ConvRoute rt = w2 ? ConvRoute::Direct : route(w, r, o);
+        const ConvFigures f = conv_figures(rt, w, (double)B * r * r, res != nullptr, w2 ? w2->Cin : 0);
+        next_flops_exec = f.flops_exec;
+        if (rt != ConvRoute::Direct) {
+            if (rt == ConvRoute::F2) o.claim = next_claim();
+            timed(0, f.flops, f.bytes, [&] { check(run_conv(rt, w, in, out, B, r, r, o, st), "conv (winograd / 1x1 GEMM)"); });
+            return;
+        }
+        ConvParams p = conv_direct_params(w, in, out, B, r, r, o);
         if (w2) {
             p.in2 = in2;
-            p.wpk2 = w2->wpk;
+            p.wpk2 = m.opt.use_sh16 ? w2->sh_wpk : w2->wpk;
             p.Cin2 = w2->Cin;
             p.in2_amax = m.amax_slots + 2 * prod2->index;
         }
         p.in_amax = m.amax_slots + 2 * prod.index;
-        p.in = in;
-        p.wpk = w.wpk;
-        p.out = out;
-        p.B = B;
-        p.Cin = w.Cin;
-        p.H = r;
-        p.W = r;
-        p.Mrows = w.Cout;
-        p.bias = w.bias;
-        p.res = res;
-        p.res_up = res_up;
-        p.act = ACT_NONE;
-        p.pad = -1;
         p.dbg = m.opt.dbg;
         p.terms = m.opt.terms;
-        p.wscale = w.wscale;                       // shared with w2's rows when a 1x1 operand is fused (build())
+        if (m.opt.use_sh16) p.wpk = w.sh_wpk;
+        p.wscale = w.sh_wscale;                    // shared with w2's rows when a 1x1 operand is fused (build())
         p.in_scale_inv = 1.f / prod.out_scale;     // inputs are ACE outputs (a fused second operand: see sh16_in_scale_inv)
-        p.partial = m.opt.batch_inv ? nullptr : m.splitk_ws;      // (split-K follows the grid size, i.e. the batch)
-        p.partial_cap = m.splitk_cap;
-        p.mtiles_hint_small = (((w.Cout + 63) / 64) * (((long long)B * r * r + 511) / 512) < 192) ? 1 : 0;
-        const double npix = (double)B * r * r, k2 = w.KS * w.KS, cin2 = w2 ? w2->Cin : 0;
-        if (m.opt.wino >= 2 && !m.opt.use_sh16 && w.wino4 && w.KS == 3 && !w2 && wino4_supported(r, r, w.Cin) &&
-            (!use_wino(w, r) || m.opt.wino4_force || m.opt.batch_inv || wino4_pays((long long)B * (r / 32) * (r / 32) * ((w.Cout + 31) / 32), m.num_cus))) {
-            // Winograd F(4x4,3x3) on the exact-f32 matrix cores: 36 MFMA products per 4 x 4 tile and channel instead of 144
-            Wino4Params q{};
-            q.in = in;
-            q.wpk = w.wino4;
-            q.out = out;
-            q.B = B;
-            q.Cin = w.Cin;
-            q.Cout = w.Cout;
-            q.H = r;
-            q.W = r;
-            q.bias = w.bias;
-            q.res = res;
-            q.res_up = res_up;
-            q.wpk_split = w.wino4s;
-            q.split = m.opt.wino4_split;
-            next_flops_exec = 2.0 * w.Cout * w.Cin * 36.0 * npix / 16.0;
-            // many GEMM rows on a small level: the input transform once, in its own pass, instead of in every row tile (conv_wino4v.h)
-            Wino4vPackParams vp;
-            const bool vroute = m.wino4v_route(wino4v_pays(w.Cout, r), in, B, r, w.Cin, w.Cin / 4, vp);
-            timed(0, 2.0 * w.Cout * w.Cin * 9.0 * npix,
-                  4.0 * (npix * w.Cin + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * w.Cin * 36.0), [&] {
-                      if (vroute) {
-                          check(wino4v_pack(vp, st), "conv input transform (winograd F(4x4,3x3))");
-                          q.v = m.vbuf;
-                          check(conv_wino4v_plain(q, st), "conv (winograd F(4x4,3x3), pre-transformed input)");
-                      } else
-                          check(conv_wino4_plain(q, st), "conv (winograd F(4x4,3x3))");
-                  });
-            return;
+        p.mtiles_hint_small = conv_few_tiles(w.Cout, (long long)B * r * r) ? 1 : 0;
+        timed(0, f.flops, f.bytes, [&] {
+            if (m.opt.use_sh16) check(conv_sh16_plain(p, w.KS, st), "conv");
+            else check(w.KS == 3 ? conv_plain3(p, st) : conv_plain1(p, st), "conv");
+        });
+    }
+};
+
+// ---- encode(): one chunk of the Zencoder (architecture.py:158-207), stage by stage --------------------------------------------------
+// Buffers: stem -> hs; f16x3 kernels (f16path): h0 -> dx -> h1 -> hs -> dx -> hs -> h1 -> h0; exact f32: hs -> dx -> h1 -> hs -> h0.
+struct ZencRunner {
+    SeanModel& m;
+    const int B, S;
+    hipStream_t st;
+    const int h2 = S / 2, h4 = S / 4;
+    const bool f16path = m.opt.use_sh16 && h4 * h4 >= 4096;      // every conv after the stem on the f16x3 kernels
+    ConvOpts env = zenc_env(m);
+    static ConvOpts zenc_env(const SeanModel& m) {      // the Zencoder's routes follow its images alone (build() packs them by sean.wino)
+        ConvOpts o = m.conv_env();
+        o.wino = 2;
+        return o;
+    }
+    std::string err;
+    void ck(hipError_t e, const char* what) {
+        if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
+    }
+    // the f16x3 conv of layer L over an instance-normalised input of hw_in pixels (bounded by sqrt(HW): static scale), output side H
+    ConvParams sh16(const ConvLayer& L, const float* in, float* out, int hw_in, int H) const {
+        return sh16_conv_params(L, in, out, B, H, H, instnorm_sh16_scale(hw_in));
+    }
+    void stem(const float* x) {
+        ck(conv3x3_c3_reflect(x, m.z1_w, m.z1.bias, m.hs, B, 32, S, S, st), "zenc conv1");
+        if (f16path) ck(instnorm_act(m.hs, B * 32, S * S, 1e-5f, ACT_LRELU, st, m.h0, 32, m.splitk_ws), "zenc in1");
+        else ck(instnorm_act(m.hs, B * 32, S * S, 1e-5f, ACT_LRELU, st), "zenc in1");
+    }
+    // the two stride-2 convs, each followed by its InstanceNorm + lrelu (f16x3: space-to-depth form, SH16 -> C4 -> SH16)
+    void down() {
+        if (f16path) {
+            ck(conv_sh16_s2d(sh16(m.z4_s2d, m.h0, m.dx, S * S, h2), m.z4_s2d.KS, st), "zenc conv2 (f16x3)");
+            ck(instnorm_c4_to_sh16(m.dx, B, 64, h2 * h2, 1e-5f, ACT_LRELU, m.h1, st, m.splitk_ws), "zenc in2");
+            ck(conv_sh16_s2d(sh16(m.z7_s2d, m.h1, m.hs, h2 * h2, h4), m.z7_s2d.KS, st), "zenc conv3 (f16x3)");
+            ck(instnorm_c4_to_sh16(m.hs, B, 128, h4 * h4, 1e-5f, ACT_LRELU, m.dx, st, m.splitk_ws), "zenc in3");
+        } else {
+            ck(run_conv(m.z4, m.hs, m.dx, B, S, S, env, st), "zenc conv2");
+            ck(instnorm_act(m.dx, B * 64, h2 * h2, 1e-5f, ACT_LRELU, st), "zenc in2");
+            ck(run_conv(m.z7, m.dx, m.h1, B, h2, h2, env, st), "zenc conv3");
+            ck(instnorm_act(m.h1, B * 128, h4 * h4, 1e-5f, ACT_LRELU, st), "zenc in3");
         }
-        if (use_wino(w, r) && !w2 && !(r == 16 && res_up)) {      // (16 x 16 sample pairs: residual at the same size only)
-            // Winograd F(2x2,3x3) on the exact-f32 matrix cores: 16 MFMA products per quad and channel instead of 36
-            WinoParams q{};
-            q.in = in;
-            q.wpk = w.wino;
-            q.out = out;
+    }
+    // exact f32, enough pixel tiles to fill the device: four phase GEMMs over shifted views (the V buffer is free until conv5's transform pass);
+    // the InstanceNorm + lrelu that follows reads the phase planes and writes the depth-to-space plane
+    bool convt_phase_gemms() {
+        const long long hw4 = (long long)h4 * h4;
+        if (!(m.z10_pw[3].pw && !m.opt.use_sh16 && !m.opt.batch_inv && pw_supported(128, 256, (int)hw4) && (h4 & 3) == 0 && (long long)B * hw4 >= 16384 && m.vbuf &&
+              (size_t)B * (512 + 4 * 256) * hw4 * sizeof(float) <= m.vbuf_bytes))
+            return false;
+        float *xs = m.vbuf, *tph = m.vbuf + (size_t)B * 512 * hw4;
+        ck(convt_shift4(m.h1, xs, B, 128, h4, h4, st), "zenc convT shifted views");
+        static const int first[4] = {1, 0, 1, 0};
+        for (int ph = 0; ph < 4; ++ph) {
+            const ConvLayer& L = m.z10_pw[ph];
+            PwParams q{};
+            q.in = xs + (size_t)first[ph] * 128 * hw4;
+            q.in_bs = 512 * hw4;
+            q.wpk = L.pw;
+            q.out = tph + (size_t)ph * B * 256 * hw4;
             q.B = B;
-            q.Cin = w.Cin;
-            q.Cout = w.Cout;
-            q.H = r;
-            q.W = r;
-            q.bias = w.bias;
-            q.res = res;
-            q.res_up = res_up;
-            q.act = ACT_NONE;
-            q.zero = m.zero_page;
-            q.claim = next_claim();
-            q.partial = m.opt.batch_inv ? nullptr : m.splitk_ws;               // (launches with far fewer tasks than CUs split K: conv_wino_plain)
-            q.partial_cap = m.splitk_cap;
-            next_flops_exec = 2.0 * w.Cout * w.Cin * 16.0 * npix / 4.0;
-            timed(0, 2.0 * w.Cout * w.Cin * 9.0 * npix,
-                  4.0 * (npix * w.Cin + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * w.Cin * 16.0),
-                  [&] { check(conv_wino_plain(q, st), "conv (winograd)"); });
-            return;
-        }
-        if (m.opt.wino && !m.opt.use_sh16 && w.pw && w.KS == 1 && !w2 && !res && !w.bias && pw_supported(w.Cin, w.Cout, r * r)) {
-            PwParams q{};         // the learned shortcut conv_s: dedicated 1x1 kernel (conv_pw.h)
-            q.in = in;
-            q.wpk = w.pw;
-            q.out = out;
-            q.B = B;
-            q.Cin = w.Cin;
-            q.Cout = w.Cout;
-            q.HW = r * r;
+            q.Cin = L.Cin;
+            q.Cout = L.Cout;
+            q.HW = (int)hw4;
             q.wide = m.opt.pw_wide;
-            timed(0, 2.0 * w.Cout * w.Cin * npix, 4.0 * (npix * w.Cin + npix * w.Cout + (double)w.Cout * w.Cin),
-                  [&] { check(conv_pw(q, st), "conv 1x1"); });
+            ck(conv_pw(q, st), "zenc convT (phase GEMM)");
+        }
+        ck(instnorm_act_d2s(tph, m.z10.bias, m.hs, B, 256, h4, h4, 1e-5f, ACT_LRELU, st), "zenc in4 (depth-to-space)");
+        return true;
+    }
+    // the ConvTranspose and the InstanceNorm + lrelu that follows it
+    void conv_transpose() {
+        if (f16path) {
+            if (m.opt.dbg & 16384) {         // the earlier form, kept for comparison: 3x3 conv over the zero-inserted x2 view
+                ConvParams t = sh16(m.z10, m.dx, m.hs, h4 * h4, h2);
+                t.in_mode = IN_UP2_ZEROINS;
+                ck(conv_sh16_plain(t, 3, st), "zenc convT (f16x3)");
+            } else                           // 2x2-tap conv at the input resolution, depth-to-space store
+                ck(conv_sh16_d2s(sh16(m.z10_d2s, m.dx, m.hs, h4 * h4, h4), st), "zenc convT (f16x3, depth-to-space)");
+            ck(instnorm_c4_to_sh16(m.hs, B, 256, h2 * h2, 1e-5f, ACT_LRELU, m.h1, st, m.splitk_ws), "zenc in4");
             return;
         }
-        timed(0, 2.0 * w.Cout * (w.Cin * k2 + cin2) * npix,
-              4.0 * (npix * (w.Cin + cin2) + npix * w.Cout * (res ? 2.0 : 1.0) + (double)w.Cout * (w.Cin * k2 + cin2)), [&] {
-                  if (m.opt.use_sh16) check(conv_sh16_plain(p, w.KS, st), "conv");
-                  else check(w.KS == 3 ? conv_plain3(p, st) : conv_plain1(p, st), "conv");
-              });
+        if (convt_phase_gemms()) return;
+        if (conv_route(m.z10_wino, B, h4, h4, env) == ConvRoute::F2)
+            ck(run_conv(ConvRoute::F2, m.z10_wino, m.h1, m.hs, B, h4, h4, env, st), "zenc convT (winograd phase convs)");
+        else {
+            ConvOpts zins = env;
+            zins.in_mode = IN_UP2_ZEROINS;
+            ck(run_conv(m.z10, m.h1, m.hs, B, h4, h4, zins, st), "zenc convT");
+        }
+        if (m.opt.use_sh16) ck(instnorm_act(m.hs, B * 256, h2 * h2, 1e-5f, ACT_LRELU, st, m.h1, 256), "zenc in4");
+        else ck(instnorm_act(m.hs, B * 256, h2 * h2, 1e-5f, ACT_LRELU, st), "zenc in4");
+    }
+    // the reflection-padded 256 -> 512 conv with tanh (91 % of the Zencoder FLOPs)
+    void conv5() {
+        if (m.opt.use_sh16) {
+            ConvParams p = sh16(m.z14, m.h1, m.h0, h2 * h2, h2);
+            p.act = ACT_TANH;
+            p.pad_mode = PAD_REFLECT;
+            ck(conv_sh16_plain(p, 3, st), "zenc conv5 (f16x3)");
+            return;
+        }
+        ConvOpts last = env;
+        last.pad_mode = PAD_REFLECT;
+        last.act = ACT_TANH;
+        if (last.v_pays) last.v_pays = 1;      // 512 GEMM rows: the (reflected) input transform in its own pass at every size V fits
+        ck(run_conv(m.z14, m.hs, m.h0, B, h2, h2, last, st), "zenc conv5");
+    }
+    void means(const uint8_t* labels, float* codes) {
+        ck(region_mean(m.h0, labels, codes, B, STYLE, h2, h2, S, st, m.opt.use_sh16 ? 1 : 0), "region_mean");
+        auto it = m.taps.find("zenc.feat");
+        if (it != m.taps.end() && it->second) {
+            if (m.opt.use_sh16) ck(c4_decode(m.h0, it->second, B, STYLE, (long long)h2 * h2, st), "tap");
+            else ck(hipMemcpyAsync(it->second, m.h0, (size_t)B * STYLE * h2 * h2 * 4, hipMemcpyDeviceToDevice, st), "tap");
+        }
     }
 };
 
@@ -2039,216 +2099,32 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
     if (phase == 2 && (enc_pending_B != Btot || enc_pending_S != S)) return "split encode: no matching ch_sean_encode_features call";
     if (phase == 2) enc_pending_B = 0;
     for (int bo = 0; bo < Btot; bo += max_batch) {
-        const int B = std::min(max_batch, Btot - bo);
-        std::string err;
-        auto ck = [&](hipError_t e, const char* what) {
-            if (e != hipSuccess && err.empty()) err = std::string(what) + ": " + hipGetErrorString(e);
-        };
-        const float* x = img + (size_t)bo * 3 * S * S;
-        ConvOpts refl;
-        refl.pad_mode = PAD_REFLECT;
-        ConvOpts zero;
-        ConvOpts zins;
-        zins.in_mode = IN_UP2_ZEROINS;
-        ConvOpts last = refl;
-        last.act = ACT_TANH;
-        const int h2 = S / 2, h4 = S / 4;
-        const bool f16path = opt.use_sh16 && h4 * h4 >= 4096;
-        bool in4_done = false;       // the ConvTranspose route already applied the InstanceNorm + lrelu that follows it
+        ZencRunner R{*this, std::min(max_batch, Btot - bo), S, st};
         if (phase != 2) {
-        ck(conv3x3_c3_reflect(x, z1_w, z1.bias, hs, B, 32, S, S, st), "zenc conv1");
-        if (f16path) {
-            // every conv after the stem on the f16x3 kernels: InstanceNorm + lrelu -> SH16 -> stride-2 conv (space-to-depth
-            // form) -> C4, twice; then the ConvTranspose (f16x3 conv over the zero-inserted view) and the reflection-padded
-            // 3x3 conv with tanh.  Instance-norm outputs are bounded by sqrt(HW): static scales (instnorm_sh16_scale).
-            auto s2d = [&](const ConvLayer& L, const float* in, float* out, int hin, const char* what) {
-                ConvParams q{};
-                q.in = in;
-                q.wpk = L.sh_wpk;
-                q.wscale = L.sh_wscale;
-                q.in_scale_inv = 1.f / instnorm_sh16_scale(hin * hin);
-                q.out = out;
-                q.B = B;
-                q.Cin = L.Cin;
-                q.s2d_cr = L.s2d_cr;
-                q.s2d_phase0 = L.s2d_phase0;
-                q.H = hin / 2;
-                q.W = hin / 2;
-                q.Mrows = L.Cout;
-                q.bias = L.bias;
-                q.act = ACT_NONE;
-                ck(conv_sh16_s2d(q, L.KS, st), what);
-            };
-            ck(instnorm_act(hs, B * 32, S * S, 1e-5f, ACT_LRELU, st, h0, 32, splitk_ws), "zenc in1");
-            s2d(z4_s2d, h0, dx, S, "zenc conv2 (f16x3)");
-            ck(instnorm_c4_to_sh16(dx, B, 64, h2 * h2, 1e-5f, ACT_LRELU, h1, st, splitk_ws), "zenc in2");
-            s2d(z7_s2d, h1, hs, h2, "zenc conv3 (f16x3)");
-            ck(instnorm_c4_to_sh16(hs, B, 128, h4 * h4, 1e-5f, ACT_LRELU, dx, st, splitk_ws), "zenc in3");
-        } else {
-            ck(instnorm_act(hs, B * 32, S * S, 1e-5f, ACT_LRELU, st), "zenc in1");
-            ck(run_conv(z4, hs, dx, B, S, S, zero, st), "zenc conv2");
-            ck(instnorm_act(dx, B * 64, h2 * h2, 1e-5f, ACT_LRELU, st), "zenc in2");
-            ck(run_conv(z7, dx, h1, B, h2, h2, zero, st), "zenc conv3");
+            R.stem(img + (size_t)bo * 3 * S * S);
+            R.down();
+            R.conv_transpose();
+            R.conv5();
         }
-        if (f16path) {
-            ConvParams t{};
-            t.in = dx;
-            t.out = hs;
-            t.B = B;
-            t.Cin = 128;
-            t.bias = z10.bias;
-            t.in_scale_inv = 1.f / instnorm_sh16_scale(h4 * h4);
-            t.act = ACT_NONE;
-            if (opt.dbg & 16384) {           // the earlier form, kept for comparison: 3x3 conv over the zero-inserted x2 view
-                t.wpk = z10_sh;
-                t.wscale = z10_ws;
-                t.H = h2;
-                t.W = h2;
-                t.Mrows = 256;
-                t.in_mode = IN_UP2_ZEROINS;
-                ck(conv_sh16_plain(t, 3, st), "zenc convT (f16x3)");
-            } else {                     // 2x2-tap conv at the input resolution, depth-to-space store
-                t.wpk = z10_d2s;
-                t.wscale = z10_d2s_ws;
-                t.H = h4;
-                t.W = h4;
-                t.Mrows = 1024;
-                ck(conv_sh16_d2s(t, st), "zenc convT (f16x3, depth-to-space)");
-            }
-            ck(instnorm_c4_to_sh16(hs, B, 256, h2 * h2, 1e-5f, ACT_LRELU, h1, st, splitk_ws), "zenc in4");
-        } else {
-            ck(instnorm_act(h1, B * 128, h4 * h4, 1e-5f, ACT_LRELU, st), "zenc in3");
-            const long long hw4 = (long long)h4 * h4;
-            if (z10_pw[3] && !opt.use_sh16 && !opt.batch_inv && pw_supported(128, 256, (int)hw4) && (h4 & 3) == 0 && (long long)B * hw4 >= 16384 && vbuf &&
-                (size_t)B * (512 + 4 * 256) * hw4 * sizeof(float) <= vbuf_bytes) {
-                // four phase GEMMs over the shifted views (enough pixel tiles to fill the device; the V buffer is free until conv5's transform pass);
-                // the InstanceNorm + lrelu that follows reads the phase planes and writes the depth-to-space plane
-                float *xs = vbuf, *tph = vbuf + (size_t)B * 512 * hw4;
-                ck(convt_shift4(h1, xs, B, 128, h4, h4, st), "zenc convT shifted views");
-                static const int first[4] = {1, 0, 1, 0}, cnt[4] = {1, 2, 2, 4};
-                for (int ph = 0; ph < 4; ++ph) {
-                    PwParams q{};
-                    q.in = xs + (size_t)first[ph] * 128 * hw4;
-                    q.in_bs = 512 * hw4;
-                    q.wpk = z10_pw[ph];
-                    q.out = tph + (size_t)ph * B * 256 * hw4;
-                    q.B = B;
-                    q.Cin = cnt[ph] * 128;
-                    q.Cout = 256;
-                    q.HW = (int)hw4;
-                    q.wide = opt.pw_wide;
-                    ck(conv_pw(q, st), "zenc convT (phase GEMM)");
-                }
-                ck(instnorm_act_d2s(tph, z10.bias, hs, B, 256, h4, h4, 1e-5f, ACT_LRELU, st), "zenc in4 (depth-to-space)");
-                in4_done = true;
-            } else if (z10_wino && !opt.use_sh16 && wino_supported(h4, h4, 128)) {
-                WinoParams q{};
-                q.in = h1;
-                q.wpk = z10_wino;
-                q.out = hs;
-                q.B = B;
-                q.Cin = 128;
-                q.Cout = 1024;
-                q.H = h4;
-                q.W = h4;
-                q.bias = z10.bias;
-                q.act = ACT_NONE;
-                q.d2s = 1;
-                q.zero = zero_page;
-                ck(conv_wino_plain(q, st), "zenc convT (winograd phase convs)");
-            } else
-                ck(run_conv(z10, h1, hs, B, h4, h4, zins, st), "zenc convT");
-            if (opt.use_sh16) ck(instnorm_act(hs, B * 256, h2 * h2, 1e-5f, ACT_LRELU, st, h1, 256), "zenc in4");
-        }
-        if (opt.use_sh16) {
-            ConvParams p{};
-            p.in = h1;
-            p.wpk = z14_sh;
-            p.out = h0;
-            p.B = B;
-            p.Cin = 256;
-            p.H = h2;
-            p.W = h2;
-            p.Mrows = 512;
-            p.bias = z14.bias;
-            p.wscale = z14_ws;
-            p.in_scale_inv = 1.f / instnorm_sh16_scale(h2 * h2);
-            p.act = ACT_TANH;
-            p.pad_mode = PAD_REFLECT;
-            ck(conv_sh16_plain(p, 3, st), "zenc conv5 (f16x3)");
-        } else {
-            if (!in4_done) ck(instnorm_act(hs, B * 256, h2 * h2, 1e-5f, ACT_LRELU, st), "zenc in4");
-            if (z14_wino4 && wino4_supported(h2, h2, 256) && (opt.wino4_force || opt.batch_inv || wino4_pays((long long)B * (h2 / 32) * (h2 / 32) * 16, num_cus))) {
-                Wino4Params q{};
-                q.in = hs;
-                q.wpk = z14_wino4;
-                q.out = h0;
-                q.B = B;
-                q.Cin = 256;
-                q.Cout = 512;
-                q.H = h2;
-                q.W = h2;
-                q.bias = z14.bias;
-                q.act = ACT_TANH;
-                q.reflect = 1;
-                q.wpk_split = z14_wino4s;
-                q.split = opt.wino4_split;
-                Wino4vPackParams vp;
-                if (wino4v_route(true, hs, B, h2, 256, 64, vp, false, true)) {          // 512 GEMM rows: the (reflected) input transform in its own pass
-                    ck(wino4v_pack(vp, st), "zenc conv5 input transform");
-                    q.v = vbuf;
-                    ck(conv_wino4v_plain(q, st), "zenc conv5 (winograd F(4x4,3x3), pre-transformed input)");
-                } else
-                    ck(conv_wino4_plain(q, st), "zenc conv5 (winograd F(4x4,3x3))");
-            } else if (z14_wino && wino_supported(h2, h2, 256)) {
-                WinoParams q{};
-                q.in = hs;
-                q.wpk = z14_wino;
-                q.out = h0;
-                q.B = B;
-                q.Cin = 256;
-                q.Cout = 512;
-                q.H = h2;
-                q.W = h2;
-                q.bias = z14.bias;
-                q.act = ACT_TANH;
-                q.reflect = 1;
-                q.zero = zero_page;
-                ck(conv_wino_plain(q, st), "zenc conv5 (winograd)");
-            } else
-                ck(run_conv(z14, hs, h0, B, h2, h2, last, st), "zenc conv5");
-        }
-        }   // phase != 2
-        if (phase == 1) {
-            if (!err.empty()) return err;
-            continue;
-        }
-        ck(region_mean(h0, labels + (size_t)bo * S * S, codes_out + (size_t)bo * LABEL_NC * STYLE, B, STYLE, h2, h2, S, st,
-                       opt.use_sh16 ? 1 : 0), "region_mean");
-        auto it = taps.find("zenc.feat");
-        if (it != taps.end() && it->second) {
-            if (opt.use_sh16) ck(c4_decode(h0, it->second, B, STYLE, (long long)h2 * h2, st), "tap");
-            else ck(hipMemcpyAsync(it->second, h0, (size_t)B * STYLE * h2 * h2 * 4, hipMemcpyDeviceToDevice, st), "tap");
-        }
-        if (!err.empty()) return err;
+        if (phase != 1) R.means(labels + (size_t)bo * S * S, codes_out + (size_t)bo * LABEL_NC * STYLE);
+        if (!R.err.empty()) return R.err;
     }
     return "";
 }
 
-bool SeanModel::wino4v_route(bool pays, const float* in, int Bn, int r, int K, int nks, Wino4vPackParams& vp, bool padded, bool reflect) const {
-    if (!(opt.wino4v && pays && vbuf && r % 32 == 0 && wino4v_bytes(Bn, r, r, nks) <= vbuf_bytes)) return false;
-    vp = Wino4vPackParams{};
-    vp.in = in;
-    vp.v = vbuf;
-    vp.B = Bn;
-    vp.K = K;
-    vp.H = vp.W = r;
-    vp.nks = nks;
-    vp.pitch = padded ? wino_apitch(r) : r;
-    vp.xoff = padded ? WINO_AXOFF : 0;
-    vp.padded = padded ? 1 : 0;
-    vp.reflect = reflect ? 1 : 0;
-    return true;
+ConvOpts SeanModel::conv_env() const {
+    ConvOpts o;
+    o.wino = opt.wino;
+    o.wino4_force = opt.wino4_force;
+    o.batch_inv = opt.batch_inv;
+    o.wino4_split = opt.wino4_split;
+    o.v_pays = opt.wino4v ? -1 : 0;
+    o.pw_wide = opt.pw_wide;
+    o.num_cus = num_cus;
+    o.vbuf = vbuf;
+    o.vbuf_bytes = vbuf_bytes;
+    o.zero = zero_page;
+    return o;
 }
 
 // ---- routes and modes: host decisions only ----------------------------------------------------------------------------------------

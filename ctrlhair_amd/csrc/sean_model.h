@@ -1,5 +1,7 @@
 // sean_model.h -- host side of the SEAN generator path: weight folding/packing at load, workspace arena,
 // and the launch sequence of one batched forward.  No torch types; plain HIP runtime.
+// Plain convs (ResBlock convs, 1x1 shortcut, Zencoder) are net_common.h ConvLayers, routed by conv_route and launched by run_conv
+// with SeanModel::conv_env(); the ACEs have their own routes (AceRoute).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,19 +14,6 @@
 #include "net_common.h"
 
 namespace chk {
-struct Wino4vPackParams;      // conv_wino4v.h
-
-struct ConvW {
-    float* wpk = nullptr;
-    float* bias = nullptr;
-    float* wscale = nullptr;                    // f16x3 path: per-row 2^-k undoing the weight scaling (sh16.h)
-    float* wino = nullptr;                      // exact-f32 path, 3x3: Winograd F(2x2,3x3) image U = G g G^T (conv_wino.h)
-    float* wino4 = nullptr;                     // exact-f32 path, 3x3, sean.wino = 2: Winograd F(4x4,3x3) image (conv_wino4.h)
-    float* wino4s = nullptr;                    // ... and the same values in the split kernel's fragment order (conv_wino4_split.h), see SeanOptions::wino4_split
-    float* pw = nullptr;                        // exact-f32 path, 1x1: pack_pw_A image (conv_pw.h)
-    int Cout = 0, Cin = 0, KS = 0;
-};
-
 struct AceW {
     std::string name;
     int C = 0, res_div = 1, index = 0;
@@ -52,7 +41,7 @@ struct BlockW {
     std::string name;
     int fin = 0, fout = 0, fmid = 0, res_div = 1;
     bool up_before = false, styled = false, learned = false;
-    ConvW conv_0, conv_1, conv_s;
+    ConvLayer conv_0, conv_1, conv_s;          // (f16x3 handles: sh_wpk / sh_wscale, like every ConvLayer; exact-f32 handles: wpk and the Winograd / GEMM images)
     AceW ace_0, ace_1, ace_s;
 };
 
@@ -171,16 +160,14 @@ struct SeanModel {
     float* img_w4 = nullptr;                           // the same, [ngf/4][tap][co][4] (conv_img_c4_kernel's scalar loads)
     bool has_zencoder = false;
     float* z1_w = nullptr;                             // Zencoder stem weights, unpacked (direct VALU conv)
-    ConvLayer z1, z4, z7, z10, z14;                    // architecture.py:158-176
-    float *z14_sh = nullptr, *z10_sh = nullptr;        // z14 / the ConvTranspose packed for the f16x3 kernel
-    float* z10_wino = nullptr;                         // exact-f32 path: the ConvTranspose as four Winograd phase convs of the input grid (rows 4 co + phase)
-    float* z10_pw[4] = {};                             // option "sean.convt_gemm": the same ConvTranspose as four phase GEMMs over shifted views (conv_pw.h; phase = 2 py + px)
-    float* z14_wino = nullptr;                         // exact-f32 path: z14 as Winograd A images (conv_wino.h, reflection padding)
-    float* z14_wino4s = nullptr;                       // (the F(4x4,3x3) image in the split kernel's fragment order, conv_wino4_split.h)
-    float* z14_wino4 = nullptr;                        // ... and as F(4x4,3x3) images (conv_wino4.h), sean.wino = 2
-    float *z14_ws = nullptr, *z10_ws = nullptr;        // their per-row inverse weight scales
-    float *z10_d2s = nullptr, *z10_d2s_ws = nullptr;   // the ConvTranspose in its 2x2-tap depth-to-space form (rows = phase * 256 + co)
+    // architecture.py:158-176.  Each layer carries the images of every route it can take: z10 (the ConvTranspose as a 3x3 conv over the zero-inserted view)
+    // direct + f16x3; z14 direct, F(2x2), F(4x4) (sean.wino = 2), its split order (sean.wino4_split = 1) + f16x3
+    ConvLayer z1, z4, z7, z10, z14;
     ConvLayer z4_s2d, z7_s2d;                          // the two stride-2 convs in the space-to-depth form (conv_sh16.h S2D)
+    // the forms of the ConvTranspose that are different convs (bias: z10's):
+    ConvLayer z10_wino;                                // exact f32: four Winograd phase convs of the input grid (1024 rows = 4 co + phase, depth-to-space store)
+    ConvLayer z10_d2s;                                 // f16x3: 2x2 taps at the input resolution, depth-to-space store (1024 rows = phase * 256 + co)
+    ConvLayer z10_pw[4];                               // option "sean.convt_gemm": four phase GEMMs over shifted views (conv_pw.h; phase = 2 py + px)
 
     // ---- workspace ----
     float* gb_small = nullptr;                  // exact-f32 path: gamma | beta sums of a tiny ACE level whose SPADE conv runs as a plain split-K conv (ace())
@@ -245,9 +232,12 @@ struct SeanModel {
     size_t wsty4_floats = 0;                   // its size; pad_state[wsty4] == 1: zeroed since it was allocated (wino4_style_pack, rows = 1)
     float* vbuf = nullptr;                     // the pre-transformed input V of the layer being run (conv_wino4v.h)
     size_t vbuf_bytes = 0;
-    // the V route of one F(4x4,3x3) layer (sean_model.cpp): taken when it `pays` (wino4v_pays) and V fits vbuf; then vp is the transform pass over `in`
-    // (padded: hidden planes of an ACE level, conv_wino.h WINO_AXOFF; reflect: reflection padding)
-    bool wino4v_route(bool pays, const float* in, int Bn, int r, int K, int nks, Wino4vPackParams& vp, bool padded = false, bool reflect = false) const;
+    // the V route of an ACE's F(4x4,3x3) conv (net_common.h wino4v_plan; padded: the hidden planes of an ACE level; the plain convs: conv_route)
+    bool wino4v_route(bool pays, const float* in, int Bn, int r, int K, int nks, Wino4vPackParams& vp, bool padded = false) const {
+        return wino4v_plan(opt.wino4v && pays, vbuf, vbuf_bytes, in, Bn, r, r, K, nks, vp, padded);
+    }
+    // what the plain-conv routes read of this handle (net_common.h conv_route / run_conv); the caller adds the call's epilogue, split-K scratch and claim slot
+    ConvOpts conv_env() const;
     const WinoWork* wino_work(const AceW& a, int r) const;        // task list of the ACE's row tiles on its Winograd level; nullptr: no Winograd route at r
     const SparseWork* sparse_work(const AceW& a, int r) const;    // work list of the ACE's row tiles on its sparse level; nullptr: not served at r
     AceRoute ace_route_shape(const AceW& a, int r) const;         // from shape, weights and options: F4 / WinoQuads / Sparse / Dense (build() sizes buffers by it)

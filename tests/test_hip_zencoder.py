@@ -119,3 +119,60 @@ def test_convtranspose_as_phase_gemms(hip_lib):
     assert df > 0, 'both handles took the same route'
     on.handle.close()
     off.handle.close()
+
+
+def _encode_with_tap(g, img, lab, slots):
+    S = img.shape[-1]
+    feat = torch.zeros(slots, 512, S // 2, S // 2, device=g.device)
+    g.handle.sean_set_tap('zenc.feat', feat.data_ptr())
+    codes = g.encode(torch.from_numpy(img).to(g.device), torch.from_numpy(lab).to(g.device))
+    torch.cuda.synchronize()
+    g.handle.sean_set_tap('zenc.feat', None)
+    return feat.cpu().numpy(), codes.cpu().numpy()
+
+
+def test_exact_f32_direct_fallbacks_at_96(hip_lib):
+    """Exact-f32 Zencoder at S = 96: the half- and quarter-resolution grids are 48 and 24 pixels, which no Winograd kernel takes (F(2x2,3x3)
+    wants rows % 16 == 0 and columns % 32 == 0, conv_wino.h wino_supported; F(4x4,3x3) wants both % 32 == 0, conv_wino4.h wino4_supported; the
+    phase GEMMs want 16384 input pixels per chunk).  So the 256 -> 512 conv runs on the direct kernel with reflection padding and tanh and the
+    ConvTranspose on the direct kernel over the zero-inserted view.  B = 3 on a max_batch = 2 handle crosses a chunk boundary."""
+    from ctrlhair_amd import procedural as P
+    from ctrlhair_amd.sean.generator import SeanGenerator
+    from oracle import sean_oracle as O
+    sd = P.sean_state_dict(0, 16)
+    B, S = 3, 96
+    g = SeanGenerator(0, f16x3=0).load_state_dict(sd, max_batch=2, max_size=S)
+    lab, img = P.blocky_labels(B, S, grid=8, seed=49), P.synthetic_images(B, S, seed=50)
+    taps = {}
+    ref = O.zencoder_forward(O.to_torch(sd), img, lab, taps=taps).numpy()
+    feat, codes = _encode_with_tap(g, img, lab, 2)
+    g.handle.close()
+    # the tap holds the last chunk (sample 2 -> slot 0)
+    df, dc = float(np.abs(feat[0] - taps['zenc.feat'][2].detach().numpy()).max()), float(np.abs(codes - ref).max())
+    print(f'S = 96 exact f32 vs oracle: feature map {df:.3e}, codes {dc:.3e}')
+    assert np.isfinite(codes).all() and df <= TOL and dc <= TOL
+
+
+def test_exact_f32_without_winograd(hip_lib):
+    """An exact-f32 handle with sean.wino = 0 packs no Winograd or GEMM image: every Zencoder conv runs on the direct kernel.  Against the oracle at
+    TOL, and against a default handle on the same inputs at the bound test_convtranspose_as_phase_gemms sets between two routes of the same map;
+    the maps must differ somewhere, or both handles took one route."""
+    from ctrlhair_amd import procedural as P
+    from ctrlhair_amd.sean.generator import SeanGenerator
+    from oracle import sean_oracle as O
+    sd = P.sean_state_dict(0, 16)
+    B, S = 2, 64
+    lab, img = P.blocky_labels(B, S, grid=8, seed=59), P.synthetic_images(B, S, seed=60)
+    taps = {}
+    ref = O.zencoder_forward(O.to_torch(sd), img, lab, taps=taps).numpy()
+    out = {}
+    for name, options in (('direct', {'sean.wino': 0}), ('default', {})):
+        g = SeanGenerator(0, f16x3=0, options=options).load_state_dict(sd, max_batch=B, max_size=S)
+        out[name] = _encode_with_tap(g, img, lab, B)
+        g.handle.close()
+    feat, codes = out['direct']
+    do, dc = float(np.abs(feat - taps['zenc.feat'].detach().numpy()).max()), float(np.abs(codes - ref).max())
+    df = float(np.abs(feat - out['default'][0]).max())
+    print(f'sean.wino = 0 vs oracle: feature map {do:.3e}, codes {dc:.3e}; vs the default handle: feature map {df:.3e}')
+    assert np.isfinite(feat).all() and do <= TOL and dc <= TOL and df <= 2e-5
+    assert df > 0, 'both handles took the same route'
