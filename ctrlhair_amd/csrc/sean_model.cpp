@@ -133,7 +133,21 @@ struct SeanBuild {
             m.blocks.push_back(bw);
         }
         m.n_aces = ace_index;
-        return "";
+        return level_facts();
+    }
+    // what every ACE of a resolution level shares, read off the ACEs -- the block table cannot make them disagree, and here that is checked
+    std::string level_facts() {
+        for (int k = 0; k < 6; ++k) m.levels[k] = SeanModel::Level{ms >> k};
+        std::string err;
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            SeanModel::Level& L = m.levels[level_of(a.res_div)];
+            const bool etab = a.edge_tab != nullptr;
+            if (L.used && (L.styled != a.styled || L.edge_tab != etab)) err = "the ACEs of one resolution level disagree (styled / straight-edge table) at " + a.name;
+            L.used = true;
+            L.styled = a.styled;
+            L.edge_tab = etab;
+        });
+        return err;
     }
 
     SN sn_read(const std::string& p, int cout, int cin, int ks) {
@@ -330,7 +344,7 @@ struct SeanBuild {
         // 128 pixels and more (res_div <= 4), from the hidden vectors of the windows AAB / ABB (double, host) and the column / row sums
         // of the gamma / beta weights, contracted on the device in double (ace_edge_table).  vbg / vbb (blended biases) are added.
         a.edge_tab = nullptr;
-        if (!(opt.edge && (opt.use_sh16 ? opt.sparse : opt.wino) && a.res_div <= 4)) return;
+        if (!m.level_marks(level_of(a.res_div), SeanModel::NOMINAL_SIZE / a.res_div, 0, false).edges) return;
         s.edge_hv.assign((size_t)2 * ACE_EDGE_HV * HID, 0.0);
         s.edge_W6.assign((size_t)2 * HID * 6 * C, 0.0);
         std::vector<double>&hv = s.edge_hv, &W6 = s.edge_W6;
@@ -680,10 +694,8 @@ struct SeanBuild {
     size_t npad() const { return (((size_t)mb * (LABEL_NC + 1) + 31) / 32) * 32; }     // f16x3 path: 20 columns per sample (19 = zero column)
     std::string arena() {
         const size_t MB = mb, S = ms;
-        for (int k = 1; k <= 5; ++k) {   // res_div 2^k
-            const size_t r = S >> k;
-            m.lab_r[k] = static_cast<uint8_t*>(B.dalloc(MB * r * r));
-        }
+        for (int k = 1; k <= 5; ++k)     // res_div 2^k
+            m.levels[k].lab = static_cast<uint8_t*>(B.dalloc(MB * m.levels[k].r * m.levels[k].r));
         size_t nf = m.noise_floats(ms);
         m.noise_ws = static_cast<float*>(B.dalloc(MB * nf * 4));
         m.mu_img = static_cast<float*>(B.dalloc((size_t)STYLE * npad() * 4));
@@ -704,7 +716,7 @@ struct SeanBuild {
             midmax = std::max(midmax, MB * S * S * (opt.use_sh16 ? 64 : 16));
         }
         m.lut = static_cast<float*>(B.dalloc(lutmax * 4));
-        m.actv = static_cast<float*>(B.dalloc(MB * S * S * HID * 4));      // (direct kernels; the Winograd ACE levels own padded buffers, actv_lvl)
+        m.actv = static_cast<float*>(B.dalloc(MB * S * S * HID * 4));      // (direct kernels; the Winograd ACE levels own padded buffers, Level::actv)
         m.h0 = static_cast<float*>(B.dalloc(h0max * 4));
         m.hs = static_cast<float*>(B.dalloc(h0max * 4));
         m.dx = static_cast<float*>(B.dalloc(midmax * 4));
@@ -771,20 +783,15 @@ struct SeanBuild {
 
     // ---- Winograd ACE path: boundary-quad lists per level, task lists per (level, row tiles), per-sample style images ------
     std::string wino_levels() {
-        for (int k = 0; k < 6; ++k) {
-            m.wq_level[k] = SeanModel::WinoLevel();
-            m.actv_lvl[k] = nullptr;
-        }
         m.pad_state.clear();
         m.wsty = m.wsty4 = nullptr;
         if (!(opt.wino && !opt.use_sh16)) return "";
         size_t wsty_max = 0, wsty4_max = 0;
-        int lvl_planes[6] = {0, 0, 0, 0, 0, 0};        // planes of the level's padded hidden-activation buffer: what its ACEs write (AcePlan::kout)
         for_each_ace(m.blocks, [&](const AceW& a) {
             if (!a.spade_wino) return;
-            const int k = level_of(a.res_div), r = ms >> k;
+            const int r = m.levels[level_of(a.res_div)].r;
             if (r < 32 || r % 32) return;
-            SeanModel::WinoLevel& L = m.wq_level[k];
+            SeanModel::WinoLevel& L = m.levels[level_of(a.res_div)].wq;
             if (!L.qlist) wino_level_lists(L, r);
             const int nrt = (a.C + 15) / 16;
             bool have = false;
@@ -796,7 +803,6 @@ struct SeanBuild {
                 w.total = static_cast<int*>(B.dalloc(8 * sizeof(int)));
                 L.works.push_back(w);
             }
-            lvl_planes[k] = std::max(lvl_planes[k], a.styled ? HID + 20 : HID);       // (up_3 is unstyled: 128 planes, no one-hot planes)
             if (a.styled) wsty_max = std::max(wsty_max, (size_t)mb * nrt * 5 * 2048);
             if (a.styled && a.spade_wino4) wsty4_max = std::max(wsty4_max, (size_t)mb * nrt * 6 * wino4::ADW);
         });
@@ -812,11 +818,8 @@ struct SeanBuild {
         if (wsty4_max) m.wsty4 = B.falloc(wsty4_max);
         m.wsty4_floats = m.wsty4 ? wsty4_max : 0;
         wino4v_buffer();
-        for (int k = 0; k < 6; ++k)
-            if (m.wq_level[k].qlist) {
-                const size_t r = (size_t)ms >> k;
-                m.actv_lvl[k] = B.falloc((size_t)mb * r * wino_apitch((int)r) * lvl_planes[k]);
-            }
+        for (SeanModel::Level& V : m.levels)      // the planes its ACEs write (AcePlan::kout; up_3 is unstyled: 128 planes, no one-hot planes)
+            if (V.wq.qlist) V.actv = B.falloc((size_t)mb * V.r * wino_apitch(V.r) * (V.styled ? HID + 20 : HID));
         return "";
     }
     void wino_level_lists(SeanModel::WinoLevel& L, int r) {
@@ -842,7 +845,7 @@ struct SeanBuild {
         if (!(opt.wino >= 2 && opt.wino4v)) return;
         size_t need = 0;
         auto level_r = [&](int res_div) {       // the level's size when it can take the route at max_size, else 0
-            const int r = ms >> level_of(res_div);
+            const int r = m.levels[level_of(res_div)].r;
             return (r < 32 || r % 32 || r > 64) ? 0 : r;
         };
         for (const auto& b : m.blocks)
@@ -866,31 +869,28 @@ struct SeanBuild {
         m.prof_stats_cap = 16384;
         m.prof_stats_used = 0;
         m.prof_stats = static_cast<int*>(B.dalloc((size_t)m.prof_stats_cap * 4 * sizeof(int)));
-        for (int k = 0; k < 6; ++k) {
-            m.sp_level[k][0] = m.sp_level[k][1] = SparseLevel();
-            m.sp_work[k].clear();
-        }
         m.gtab = m.gtab_side = nullptr;
         if (!opt.sparse) return "";
         int cmax = 0;
         for_each_ace(m.blocks, [&](const AceW& a) {
-            const int k = level_of(a.res_div), r = ms >> k;
+            const int k = level_of(a.res_div), r = m.levels[k].r;
             if (r < opt.sparse_min_r || r < 32) return;
             const int mt = (a.C + 31) / 32;
             // f16x3 path: tile-skip mode of the wave-specialised kernel, whose tiles are 32 x 16
             const int th = opt.use_sh16 ? 16 : opt.sparse_tile_h(mt, r);
-            SparseLevel& L = m.sp_level[k][th == 16 ? 1 : 0];
+            const int ti = th == 16 ? 1 : 0;
+            SparseLevel& L = m.levels[k].sp[ti];
             if (!L.u5) {
                 L.TH = th;
                 L.cap_tiles = mb * ((r + 31) / 32) * ((r + L.TH - 1) / L.TH);
                 L.u5 = static_cast<uint8_t*>(B.dalloc((size_t)mb * r * r));
-                L.e16 = (opt.edge && (opt.use_sh16 || opt.wino) && r >= 128) ? static_cast<uint16_t*>(B.dalloc((size_t)mb * r * r * sizeof(uint16_t))) : nullptr;
+                L.e16 = m.level_marks(k, r, ti, false).edges ? static_cast<uint16_t*>(B.dalloc((size_t)mb * r * r * sizeof(uint16_t))) : nullptr;
                 L.need = static_cast<uint8_t*>(B.dalloc((size_t)mb * r * r));
                 L.list = static_cast<uint16_t*>(B.dalloc((size_t)L.cap_tiles * 32 * L.TH * sizeof(uint16_t)));
                 L.cnt = static_cast<int*>(B.dalloc((size_t)L.cap_tiles * sizeof(int)));
             }
             bool have = false;
-            for (const auto& w : m.sp_work[k]) have = have || w.mtiles == mt;
+            for (const auto& w : m.levels[k].sp_work) have = have || w.mtiles == mt;
             if (!have) {
                 SparseWork w;
                 w.mtiles = mt;
@@ -905,13 +905,13 @@ struct SeanBuild {
                     if (mt >= 4 && !(opt.dbg & 67108864))
                         w.work3 = static_cast<unsigned*>(B.dalloc((size_t)L.cap_tiles * ((mt + 3) / 4) * sizeof(unsigned)));
                 }
-                m.sp_work[k].push_back(w);
+                m.levels[k].sp_work.push_back(w);
             }
             cmax = std::max(cmax, a.C);
         });
         if (cmax) m.gtab = B.falloc((size_t)mb * LABEL_NC * 2 * cmax);
         if (cmax && m.overlap_on) m.gtab_side = B.falloc((size_t)mb * LABEL_NC * 2 * cmax);
-        m.p6 = (cmax && opt.edge && (opt.use_sh16 || opt.wino)) ? B.falloc((size_t)mb * LABEL_NC * 6 * 2 * cmax) : nullptr;      // (straight-edge pixels: ace_sparse.h)
+        m.p6 = (cmax && m.level_marks(0, SeanModel::NOMINAL_SIZE, 0, false).edges) ? B.falloc((size_t)mb * LABEL_NC * 6 * 2 * cmax) : nullptr;      // (straight-edge pixels: ace_sparse.h)
         return "";
     }
 
@@ -933,7 +933,7 @@ struct SeanBuild {
             return B.falloc(floats);
         };
         for_each_ace(m.blocks, [&](const AceW& a) {
-            const int r = ms >> level_of(a.res_div);
+            const int r = m.levels[level_of(a.res_div)].r;
             if (!m.wino_work(a, r)) return;
             if (m.ace_route_shape(a, r) == AceRoute::F4) {
                 m.pro_actv[a.index] = alloc((size_t)mb * r * wino_apitch(r) * (a.styled ? HID + 20 : HID));
@@ -1011,31 +1011,49 @@ void SeanModel::destroy() {
 
 namespace {
 
-// What an ACE needs that depends on the label map and the style codes only -- never on the activations flowing
-// through the generator: the SPADE hidden activations (label table) and the style LUT (fc_mu + LUT GEMM / GEMV).
+// The operands of an ACE that depend on the label map and the style codes only -- never on the activations flowing through the generator:
+// the SPADE hidden activations (label table) and the view of its style LUT (fc_mu + LUT GEMM / GEMV)
 struct AcePrep {
     const float* actv = nullptr;
     const float* lut = nullptr;
     int lut_rs = 1, lut_ns = 0, lut_bs = LABEL_NC;
 };
-// One ACE of one chunk: its route and what that route works on, decided once (Runner::plan_aces) and read by everything else
+// What a chunk launches for one resolution level ahead of the level's ACEs: decided by Runner::plan_aces, launched by Runner::prepare
+struct LevelPlan {
+    bool classify[2] = {};                          // the SparseLevels classified [tiles of 32 x 8 | 32 x 16] (the direct exact-f32 route can need both) ...
+    SeanModel::LevelMarks marks[2];                 // ... and the marks their interior maps carry (u5 == 253 + e16; frame marks)
+    const SparseLevel* S = nullptr;                 // Winograd route: the classified level its quad lists and interior passes read (nullptr: every quad is a boundary quad)
+    bool quads = false, gather = false;             // Winograd route: boundary-quad lists; ... with per-sample gather lists and chunk bases
+    bool grouped = false;                           // ... the geometry joins the prologue's group instead of direct launches
+    unsigned wino_lists = 0, sparse_lists = 0;      // the row-tile counts that need a Winograd task list / a sparse work list: bit i = entry i of Level::wq.works / Level::sp_work
+    const uint8_t* hidden_u5 = nullptr;             // the interior map the level's hidden-activation passes may read (the rule: Runner::plan_aces)
+};
+// One ACE of one chunk: its route, what that route works on and where its operands come from, decided once (Runner::plan_aces) and read by everything else
 struct AcePlan {
     const AceW* a = nullptr;
     AceRoute route = AceRoute::Dense;
     int r = 0, k = 0;                                    // level size of this call, level index
     const uint8_t* lab = nullptr;                        // the level's label map
-    const SeanModel::WinoLevel* L = nullptr;             // WinoQuads: quad lists of the level ...
-    const SeanModel::WinoWork* W = nullptr;              // ... and the task list of the ACE's row tiles
+    const SeanModel::WinoWork* W = nullptr;              // Winograd routes: the task list of the ACE's row tiles on its level (Level::wq)
     const SeanModel::WinoLevel* patch = nullptr;         // ... the level, when its pre-gathered patches may serve this ACE
     const SparseWork* sw = nullptr;                      // direct routes: work list to prepare (f16x3: also where the route then fell to Dense)
-    const SparseLevel* SL = nullptr;                     // Sparse: the classified level
+    int ti = -1;                                         // the classified SparseLevel this ACE's route reads: index into Level::sp / LevelPlan::classify (-1: none) ...
+    SeanModel::LevelMarks marks;                         // ... and the marks of that classification
     bool compact = false;                                // Sparse, f16x3: pixel-level compaction inside the wave-specialised kernel
     const uint8_t* need = nullptr;                       // inline label-table kernel: the pixels / tiles the conv will read (nullptr: all)
     const int* tile_cnt = nullptr;
+    const uint8_t* hidden_u5 = nullptr;                  // WinoQuads, sean.hidden_wq: LevelPlan::hidden_u5
     float* abuf = nullptr;                               // hidden activations of an inline launch: actv, or the level's padded planes
     int kout = HID;                                      // ... planes of the padded layout (one-hot planes behind the hidden channels)
-    const float *pre_actv = nullptr, *pre_gtab = nullptr, *pre_p6 = nullptr, *pre_wsty = nullptr;      // what the prologue built for this ACE (F4: hidden planes)
-    AcePrep ahead;                                       // operands built ahead of the ACE: by the side stream, or the LUT by the grouped GEMM
+    // where the operands come from: built inline before the ACE, ahead on the side stream, or by a grouped launch at the start of the chunk
+    // (hidden planes: the prologue's HiddenGroup; LUT: the grouped GEMM)
+    enum Src { NONE, INLINE, AHEAD, GROUP } hidden = INLINE, lut_src = NONE;      // (NONE: an unstyled ACE has no LUT)
+    float* lut_buf = nullptr;                            // styled: where its LUT is built ...
+    bool lut_gemv = false;                               // ... by the GEMV (else the GEMM) when it is built per ACE
+    bool join = false;                                   // the ACE waits for its event of the side stream
+    AcePrep q;                                           // the operands as the ACE kernels read them
+    float *gtab = nullptr, *p6 = nullptr, *wsty = nullptr;            // interior tables and F(2x2) style images: the shared buffers, or this ACE's own ...
+    bool pre_tables = false, pre_wsty = false;           // ... filled by the prologue's groups (else inline)
     bool wino() const { return route == AceRoute::F4 || route == AceRoute::WinoQuads; }      // padded layout, Winograd ACE kernels
 };
 struct AceIO { const float* noise; long long nf; const float* x; int x_up, act; float* out; };      // the operands every ACE parameter struct carries under the same names
@@ -1122,190 +1140,199 @@ struct Runner {
         if (!m.claim_pool || claim_next >= SeanModel::CLAIM_SLOTS) return nullptr;
         return m.claim_pool + (size_t)SeanModel::CLAIM_WORDS * claim_next++;
     }
-    // exact SPADE-interior reduction: the level's classification and the work list of (level, row tiles), once per chunk
-    // What this chunk has launched for a level so far.  A level is classified on its first visit (in for_each_ace order) and the ACE that makes
-    // that visit decides whether the interior map carries straight-edge marks; lists and task lists follow lazily, where the first ACE needs them.
-    struct LevelState {
-        bool done[2] = {}, edges[2] = {};      // [tiles of 32 x 8 | 32 x 16]: classified; with straight-edge marks (u5 == 253 + e16; Winograd path with sean.frame: frame marks too)
-        bool wq_done = false;                  // boundary-quad lists
-        std::vector<int> work_done, wwork_done;      // task lists built: row-tile counts of the sparse / the Winograd route
-        int geo_slot = -1;                     // the level's slot in the prologue's geometry group
-    } lvl[6];
-    void sparse_prepare(const AcePlan& p) {
-        const SparseWork& w = *p.sw;
-        const int r = p.r, mt = w.mtiles, ti = w.TH == 16 ? 1 : 0;
-        LevelState& ls = lvl[p.k];
-        const SparseLevel& L = m.sp_level[p.k][ti];
-        const int ntiles = B * ((r + 31) / 32) * ((r + L.TH - 1) / L.TH);
-        // f16x3 / f16 / bf16 path, pixel-level compaction: the interior pass knows the straight-edge pixels (ace_interior_sh16_tile_kernel)
-        const bool want = m.opt.use_sh16 && m.opt.edge && L.e16 && r >= 128 && p.a->edge_tab && (!p.a->styled || m.p6) && w.mode >= 2;
-        if (!ls.done[ti] || ls.edges[ti] != want) {
-            // (a level classified WITH straight-edge marks for the Winograd ACEs and then needed by the direct sparse kernels of the
-            //  exact-f32 path, which do not know them: classified again without, and the quad lists of the level with it -- not
-            //  expected to happen: every ACE of a level takes the same route)
-            check(ace_classify(p.lab, L.u5, L.need, L.list, L.cnt, B, r, r, L.TH, st, want ? L.e16 : nullptr), "ace_classify");
-            const bool again = ls.done[ti];
-            ls.done[ti] = true;
-            ls.edges[ti] = want;
-            if (again) {
-                ls.wq_done = false;
-                ls.wwork_done.clear();
-                ls.work_done.clear();
-            }
-        }
-        bool done = false;
-        for (int d : ls.work_done) done = done || d == mt;
-        if (!done) {
-            check(ace_worklist(L.cnt, ntiles, mt, w.work, w.total, st, w.mode, 32 * L.TH, w.work2, w.total2, w.work3), "ace_worklist");
-            ls.work_done.push_back(mt);
-        }
-    }
-    // Winograd ACE path: classification of the level (when the interior reduction serves it), boundary-quad lists, task list
-    // (edges: the level's interior map carries straight-edge marks -- and, with option sean.frame, frame marks)
-    struct WinoPrep { const SparseLevel* S = nullptr; bool edges = false; };
-    WinoPrep wino_prepare(const AcePlan& p) {
-        WinoPrep o;
-        const AceW& a = *p.a;
-        const int k = p.k, r = p.r, nrt = p.W->nrt;
-        const SeanModel::WinoLevel& L = *p.L;
-        LevelState& ls = lvl[k];
-        if (m.opt.sparse && r >= m.opt.sparse_min_r) {
-            for (int ti = 1; ti >= 0 && !o.S; --ti)
-                if (m.sp_level[k][ti].u5) {
-                    const SparseLevel& S = m.sp_level[k][ti];
-                    if (!ls.done[ti]) {
-                        // straight-edge pixels (ace_sparse.h): marked on the levels whose interior pass knows them (128 pixels and more) when
-                        // the ACE carries its table -- every ACE of such a level does (res_div <= 4), checked in ace()
-                        const bool edges = m.opt.edge && S.e16 && r >= 128 && a.edge_tab && (!a.styled || m.p6) && !m.overlap_on;      // (overlap mode: quad_only interior pass)
-                        // frame pixels (option sean.frame): marked with them; only this path's interior pass (tile4 kernel) knows their codes
-                        check(ace_classify(p.lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, edges ? S.e16 : nullptr, edges && m.opt.frame), "ace_classify");
-                        ls.done[ti] = true;
-                        ls.edges[ti] = edges;
-                    }
-                    o.S = &S;
-                    o.edges = ls.edges[ti];
-                }
-        }
-        const int ntiles = B * (r / 32) * (r / L.TH);
-        // the prologue collects the lists of gather-mode levels into one group (geo) instead of launching them level by level
-        const bool collect = geo && L.gq && L.TH == 16 && geo->nl < WinoGeoGroup::MAX_L;
-        if (!ls.wq_done) {
-            if (collect) {
-                ls.geo_slot = geo->nl;
-                WinoGeoGroup::Level& g = geo->l[geo->nl++];
-                g.u5 = o.S ? o.S->u5 : nullptr;
-                g.qlist = L.qlist;
-                g.qcnt = L.qcnt;
-                g.pcnt = L.pcnt;
-                g.qoff = L.qoff;
-                g.gq = L.gq;
-                g.gq_n = L.gq_n;
-                g.chunk_base = L.chunk_base;
-                g.patch_mode = L.patch_mode;
-                g.gq_cap = L.gq_cap;
-                g.cap_chunks = m.patchbuf ? m.patch_cap_chunks : 0;
-                g.H = g.W = r;
-            } else {
-                check(wino_quad_lists(o.S ? o.S->u5 : nullptr, L.qlist, L.qcnt, L.pcnt, B, r, r, L.TH, st), "wino_quad_lists");
-                if (L.gq) check(wino_gather_lists(L.qlist, L.qcnt, L.qoff, L.gq, L.gq_n, L.gq_cap, B, r, r, st), "wino_gather_lists");
-                if (L.gq && L.chunk_base) check(wino_chunk_base(L.gq_n, B, m.patchbuf ? m.patch_cap_chunks : 0, L.chunk_base, L.patch_mode, st), "wino_chunk_base");
-            }
-            ls.wq_done = true;
-        }
-        bool done = false;
-        for (int d : ls.wwork_done) done = done || d == nrt;
-        if (!done) {
-            if (geo && ls.geo_slot >= 0 && geo->nw < WinoGeoGroup::MAX_W) {
-                WinoGeoGroup::Work& w = geo->w[geo->nw++];
-                w.level = ls.geo_slot;
-                w.nrt = nrt;
-                w.work = p.W->work;
-                w.total = p.W->total;
-            } else {
-                // (a level collected by the prologue whose group has no room for this list: the group is launched first, prologue())
-                if (geo && ls.geo_slot >= 0) geo_flush();
-                if (L.gq) check(wino_gather_worklist(L.gq_n, L.pcnt, B, ntiles / B, nrt, p.W->work, p.W->total, st), "wino_gather_worklist");
-                else check(wino_ace_worklist(L.qcnt, L.pcnt, ntiles, nrt, p.W->work, p.W->total, st), "wino_ace_worklist");
-            }
-            ls.wwork_done.push_back(nrt);
-        }
-        return o;
-    }
-    // the geometry group of the prologue (set only while prologue() runs; each level's slot in it: LevelState::geo_slot)
+    // What this chunk has launched for a level so far -- bits only: what is launched at all is the LevelPlan's decision
+    struct Launched {
+        bool cls[2] = {}, quads = false;            // classification [tiles of 32 x 8 | 32 x 16]; boundary-quad lists
+        unsigned wino_lists = 0, sparse_lists = 0;  // task / work lists, bits as in LevelPlan
+        int geo_slot = -1;                          // the level's slot in the prologue's geometry group (set only while prologue() runs: geo)
+    } launched[6];
     WinoGeoGroup* geo = nullptr;
+    // The one prepare step: launches what the level plan lists for the route of this ACE and the chunk has not launched yet -- the classification
+    // the ACE reads, the level's quad lists, the list of the ACE's row tiles.  Called for the first ACE that needs each piece on the inline path
+    // (ace()), for every gather-route ACE up front by prepass() and prologue(); nothing is decided here.
+    void prepare(const AcePlan& p) {
+        const LevelPlan& lp = lplans[p.k];
+        const SeanModel::Level& V = m.levels[p.k];
+        Launched& ld = launched[p.k];
+        const int r = p.r;
+        if (p.ti >= 0 && lp.classify[p.ti] && !ld.cls[p.ti]) {
+            const SparseLevel& S = V.sp[p.ti];
+            const SeanModel::LevelMarks mk = lp.marks[p.ti];
+            check(ace_classify(p.lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, mk.edges ? S.e16 : nullptr, mk.frame), "ace_classify");
+            ld.cls[p.ti] = true;
+        }
+        if (p.route == AceRoute::WinoQuads) {
+            const SeanModel::WinoLevel& L = V.wq;
+            if (lp.quads && !ld.quads) {
+                // the level's geometry: arguments of the grouped and of the direct launches alike (tile0: the grouped launcher's)
+                const WinoGeoGroup::Level g{lp.S ? lp.S->u5 : nullptr, L.qlist, L.qcnt, L.pcnt, L.qoff, L.gq, L.gq_n, L.chunk_base, L.patch_mode,
+                                            L.gq_cap, m.patchbuf ? m.patch_cap_chunks : 0, r, r, 0};
+                if (lp.grouped && geo && geo->nl < WinoGeoGroup::MAX_L) {
+                    ld.geo_slot = geo->nl;
+                    geo->l[geo->nl++] = g;
+                } else {
+                    check(wino_quad_lists(g.u5, g.qlist, g.qcnt, g.pcnt, B, r, r, L.TH, st), "wino_quad_lists");
+                    if (lp.gather) check(wino_gather_lists(g.qlist, g.qcnt, g.qoff, g.gq, g.gq_n, g.gq_cap, B, r, r, st), "wino_gather_lists");
+                    if (lp.gather && g.chunk_base) check(wino_chunk_base(g.gq_n, B, g.cap_chunks, g.chunk_base, g.patch_mode, st), "wino_chunk_base");
+                }
+                ld.quads = true;
+            }
+            const unsigned bit = 1u << (p.W - L.works.data());
+            if ((lp.wino_lists & bit) && !(ld.wino_lists & bit)) {
+                if (geo && ld.geo_slot >= 0 && geo->nw < WinoGeoGroup::MAX_W) {
+                    geo->w[geo->nw++] = WinoGeoGroup::Work{ld.geo_slot, p.W->nrt, p.W->work, p.W->total};
+                } else {
+                    // (a level collected by the prologue whose group has no room for this list: the group is launched first)
+                    if (geo && ld.geo_slot >= 0) geo_flush();
+                    const int tiles = (r / 32) * (r / L.TH);
+                    if (lp.gather) check(wino_gather_worklist(L.gq_n, L.pcnt, B, tiles, p.W->nrt, p.W->work, p.W->total, st), "wino_gather_worklist");
+                    else check(wino_ace_worklist(L.qcnt, L.pcnt, B * tiles, p.W->nrt, p.W->work, p.W->total, st), "wino_ace_worklist");
+                }
+                ld.wino_lists |= bit;
+            }
+        }
+        if (p.sw) {
+            const SparseWork& w = *p.sw;
+            const SparseLevel& S = V.sp[p.ti];
+            const unsigned bit = 1u << (p.sw - V.sp_work.data());
+            if ((lp.sparse_lists & bit) && !(ld.sparse_lists & bit)) {
+                const int ntiles = B * ((r + 31) / 32) * ((r + S.TH - 1) / S.TH);
+                check(ace_worklist(S.cnt, ntiles, w.mtiles, w.work, w.total, st, w.mode, 32 * S.TH, w.work2, w.total2, w.work3), "ace_worklist");
+                ld.sparse_lists |= bit;
+            }
+        }
+    }
     void geo_flush() {
         if (!geo) return;
         if (geo->nl) check(wino_geometry_grouped(*geo, st), "level geometry (grouped)");
         geo->nl = geo->nw = 0;
-        for (LevelState& s : lvl) s.geo_slot = -1;
+        for (Launched& l : launched) l.geo_slot = -1;
     }
-    // the interior map of an ACE's level once its classification has run in this chunk (else nullptr)
-    const uint8_t* level_u5(const AcePlan& p) const {
-        if (!m.opt.sparse || p.r < m.opt.sparse_min_r) return nullptr;
-        for (int ti = 1; ti >= 0; --ti)
-            if (m.sp_level[p.k][ti].u5 && lvl[p.k].done[ti]) return m.sp_level[p.k][ti].u5;
-        return nullptr;
-    }
-    // The plan of the chunk: every ACE's route at (B, S) and the lists, buffers and maps that route works on.  Decides only -- launches nothing.
+    // The plan of the chunk: every ACE's route at (B, S), the lists, buffers and maps that route works on, where its operands come from, and what
+    // is launched for its level first.  Decides only -- makes no HIP call, launches nothing; an inconsistency ends generate() here (err).
+    //
+    // The interior map a hidden-activation pass may read (LevelPlan::hidden_u5; with it the pass writes only the pixels a boundary quad's patch
+    // reads): non-null only where the level's classification precedes the pass on the same stream or is joined to it by an event -- the inline
+    // path (prepare() runs first in ace()), the prologue, and the prepass (classified on the main stream before the fork event of the side
+    // stream).  In full run-ahead mode without prepass the hidden passes run on the side stream with no ordering to the classification, which
+    // the main stream launches later: the map is null and they write every pixel.
     std::vector<AcePlan> plans;
+    LevelPlan lplans[6];
     void plan_aces(const uint8_t* labfull) {
+        const bool full = mode.ahead == SeanModel::ChunkMode::FULL;
+        int n_hidden = 0, n_tables = 0, n_wsty = 0;      // members of the prologue's groups so far
         plans.assign(m.n_aces, AcePlan());
         for_each_ace(m.blocks, [&](const AceW& a) {
             AcePlan& p = plans[a.index];
             p.a = &a;
             p.k = level_of(a.res_div);
             p.r = S / a.res_div;
-            p.lab = a.res_div == 1 ? labfull : m.lab_r[p.k];
+            const SeanModel::Level& V = m.levels[p.k];
+            LevelPlan& lp = lplans[p.k];
+            p.lab = a.res_div == 1 ? labfull : V.lab;
             p.route = m.ace_route(a, p.r, B);
-            p.abuf = (p.wino() && m.actv_lvl[p.k]) ? m.actv_lvl[p.k] : m.actv;
+            p.abuf = (p.wino() && V.actv) ? V.actv : m.actv;
             p.kout = a.styled ? HID + 20 : HID;
-            p.ahead.lut_ns = 18 * a.C;
+            p.gtab = m.gtab;
+            auto classified = [&](int ti) {       // this ACE reads SparseLevel ti: classified once per chunk, with the level's marks
+                const SeanModel::LevelMarks mk = m.level_marks(p.k, p.r, ti);
+                if (lp.classify[ti] && (lp.marks[ti].edges != mk.edges || lp.marks[ti].frame != mk.frame) && err.empty())
+                    err = "level plan: the ACEs of one level disagree on the straight-edge marks at " + a.name;
+                lp.classify[ti] = true;
+                lp.marks[ti] = p.marks = mk;
+                p.ti = ti;
+            };
             if (p.wino()) {
-                p.L = &m.wq_level[p.k];
                 p.W = m.wino_work(a, p.r);
-                // (pre-gathered patches: gather mode, not run-ahead -- the ahead buffers are per ACE -- and not beside an interior pass)
-                if (p.route == AceRoute::WinoQuads && p.L->gq && mode.ahead != SeanModel::ChunkMode::FULL && m.patchbuf && !mode.overlap) p.patch = p.L;
-                return;
+                if (p.route == AceRoute::WinoQuads) {
+                    // (pre-gathered patches: gather mode, not run-ahead -- the ahead buffers are per ACE -- and not beside an interior pass)
+                    if (V.wq.gq && !full && m.patchbuf && !mode.overlap) p.patch = &V.wq;
+                    // the interior reduction serves the level: the 32 x 16 classification if the handle has it, else the 32 x 8 one
+                    if (m.opt.sparse && p.r >= m.opt.sparse_min_r && (V.sp[1].u5 || V.sp[0].u5)) {
+                        classified(V.sp[1].u5 ? 1 : 0);
+                        lp.S = &V.sp[p.ti];
+                    }
+                    lp.quads = true;
+                    lp.gather = V.wq.gq != nullptr;
+                    lp.grouped = mode.prologue && lp.gather && V.wq.TH == 16;      // (while the group has room: prepare())
+                    lp.wino_lists |= 1u << (p.W - V.wq.works.data());
+                    lp.hidden_u5 = (lp.S && !(full && !mode.prepass)) ? lp.S->u5 : nullptr;      // (the rule above)
+                    p.hidden_u5 = m.opt.hidden_wq ? lp.hidden_u5 : nullptr;
+                }
+            } else if ((p.sw = m.sparse_work(a, p.r))) {
+                // exact SPADE-interior reduction (ace_sparse.h).  f16x3 path: tile-skip mode, honoured by the wave-specialised kernel only
+                // (conv_sh16.h) -- the lists of an ACE that kernel does not serve are still built
+                classified(p.sw->TH == 16 ? 1 : 0);
+                lp.sparse_lists |= 1u << (p.sw - V.sp_work.data());
+                if (p.route == AceRoute::Sparse) {
+                    p.compact = m.opt.use_sh16 && p.sw->mode >= 2;
+                    // the label-table kernel only writes the hidden activations the conv will read -- not in full run-ahead mode (label tables
+                    // ahead of the classification: every pixel)
+                    // (exact-f32 path: skipping pixels of the NCHW planes made the kernel slower at every granularity tried -- it is bound by
+                    // its LDS table reads, not by the writes; the map stays available behind sean.dbg bit 131072)
+                    if (!full && (m.opt.use_sh16 ? p.compact : (m.opt.dbg & 131072) != 0)) p.need = V.sp[p.ti].need;
+                    if (!full && m.opt.use_sh16 && !p.compact) p.tile_cnt = V.sp[p.ti].cnt;
+                }
             }
-            // exact SPADE-interior reduction (ace_sparse.h).  f16x3 path: tile-skip mode, honoured by the wave-specialised kernel only
-            // (conv_sh16.h) -- the lists of an ACE that kernel does not serve are still built
-            p.sw = m.sparse_work(a, p.r);
-            if (p.route != AceRoute::Sparse) return;
-            p.SL = &m.sp_level[p.k][p.sw->TH == 16 ? 1 : 0];
-            p.compact = m.opt.use_sh16 && p.sw->mode >= 2;
-            if (mode.ahead == SeanModel::ChunkMode::FULL) return;      // (label tables ahead of the classification: every pixel)
-            // the label-table kernel only writes the hidden activations the conv will read
-            // (exact-f32 path: skipping pixels of the NCHW planes made the kernel slower at every granularity tried -- it is bound by
-            // its LDS table reads, not by the writes; the map stays available behind sean.dbg bit 131072)
-            if (m.opt.use_sh16 ? p.compact : (m.opt.dbg & 131072) != 0) p.need = p.SL->need;
-            if (m.opt.use_sh16 && !p.compact) p.tile_cnt = p.SL->cnt;
+            // (every ACE of a level takes the Winograd routes or the direct ones: they read one interior map)
+            if (lp.quads && lp.sparse_lists && err.empty()) err = "level plan: Winograd-route and direct-route ACEs on one level at " + a.name;
+            // ---- operand sources ----
+            // style LUT: the chunk's grouped GEMM, built ahead on the side stream (joined in ace()), or built inline before the ACE
+            p.q.lut_ns = 18 * a.C;
+            if (a.styled) {
+                p.lut_src = mode.grouped ? AcePlan::GROUP : ((full || mode.ahead == SeanModel::ChunkMode::LUTS) ? AcePlan::AHEAD : AcePlan::INLINE);
+                p.lut_buf = p.lut_src == AcePlan::INLINE ? m.lut : m.lut_ahead[a.index];
+                p.q.lut = p.lut_buf;
+                // built per ACE (build_lut): by a batched GEMV at interactive batch sizes, else a GEMM; on the f16x3 path one extra all-zero column per
+                // sample (mu = 0 -> LUT = 0) that taps outside the image point at, and the GEMM writes C4
+                p.q.lut_bs = (m.opt.use_sh16 && p.lut_src != AcePlan::GROUP) ? LABEL_NC + 1 : LABEL_NC;
+                p.lut_gemv = p.lut_src != AcePlan::GROUP && a.lut_rows && B * p.q.lut_bs <= 64 && !m.opt.batch_inv;
+                if (m.opt.use_sh16 && p.lut_src != AcePlan::GROUP && !p.lut_gemv) {
+                    p.q.lut_rs = ((B * p.q.lut_bs + 31) / 32) * 32;
+                    p.q.lut_ns = 4;
+                }
+            }
+            // hidden planes: ahead on the side stream, from the prologue's group (F(4x4) route, its own buffer), or inline
+            const bool pro_hidden = mode.prologue && p.route == AceRoute::F4 && m.pro_actv[a.index] && n_hidden < HiddenGroup::MAX;
+            p.hidden = full ? AcePlan::AHEAD : (pro_hidden ? AcePlan::GROUP : AcePlan::INLINE);
+            p.q.actv = full ? m.actv_ahead[a.index] : (pro_hidden ? m.pro_actv[a.index] : p.abuf);
+            n_hidden += pro_hidden;
+            p.join = full || p.lut_src == AcePlan::AHEAD;
+            // gamma / beta table, column / row sums, F(2x2) style images: the prologue's (gather route; they read the style LUT, so styled ACEs
+            // join only with the grouped LUT GEMM of the chunk) or the shared buffers, filled inline
+            const bool with_lut = a.styled && p.q.lut;
+            const bool p6 = p.marks.edges && with_lut;
+            if (mode.prologue && p.route == AceRoute::WinoQuads && (!a.styled || (mode.grouped && p.q.lut))) {
+                p.pre_tables = lp.S && m.pro_gtab[a.index] && (!p6 || m.pro_p6[a.index]) && n_tables < AceTableGroup::MAX;
+                p.pre_wsty = a.styled && m.pro_wsty[a.index] && n_wsty < StylePackGroup::MAX;
+                n_tables += p.pre_tables;
+                n_wsty += p.pre_wsty;
+            }
+            if (p.pre_tables) p.gtab = m.pro_gtab[a.index];
+            p.p6 = p6 ? (p.pre_tables ? m.pro_p6[a.index] : m.p6) : nullptr;
+            p.wsty = with_lut ? (p.pre_wsty ? m.pro_wsty[a.index] : m.wsty) : nullptr;
         });
     }
     // classification, quad lists and task lists of every Winograd ACE level up front (labels only): the label tables that run ahead need the interior maps
     void prepass() {
         for (const AcePlan& p : plans)
-            if (p.route == AceRoute::WinoQuads) (void)wino_prepare(p);
+            if (p.route == AceRoute::WinoQuads) prepare(p);
     }
 
-    // The style LUT of one ACE (fc_mu + LUT GEMM / GEMV) into lut_buf, on stream s; prof: the GEMM is a timed launch of the main stream.
-    // An unstyled ACE has none: only the default view comes back.
-    AcePrep build_lut(const AcePlan& pl, const float* codes, hipStream_t s, float* lut_buf, float* splitk, bool prof) {
+    // The style LUT of one styled ACE (fc_mu + LUT GEMM / GEMV) into pl.lut_buf, on stream s; prof: the GEMM is a timed launch of the main stream.
+    // (the view the consumers read: AcePlan::q, plan_aces)
+    void build_lut(const AcePlan& pl, const float* codes, hipStream_t s, float* splitk, bool prof) {
         const AceW& a = *pl.a;
-        AcePrep q;
-        q.lut_ns = 18 * a.C;
-        if (!a.styled) return q;
-        q.lut = lut_buf;
-        // f16x3 path: one extra all-zero column per sample (mu = 0 -> LUT = 0) that taps outside the image point at
-        const int bs = m.opt.use_sh16 ? LABEL_NC + 1 : LABEL_NC;
+        float* lut_buf = pl.lut_buf;
+        const int bs = pl.q.lut_bs;
         const int N = B * bs, npad = ((N + 31) / 32) * 32;
-        q.lut_bs = bs;
         const double fl = 2.0 * 18 * a.C * STYLE * N, by = 4.0 * (18.0 * a.C * STYLE + (double)STYLE * N + 18.0 * a.C * N);
         auto tm = [&](auto launch) { prof ? timed(2, fl, by, launch) : launch(); };
-        if (a.lut_rows && N <= 64 && !m.opt.batch_inv) {
+        if (pl.lut_gemv) {
             // interactive batch sizes: P[n][row] = sum_k W[row][k] mu[n][k] as a batched GEMV (weight-bandwidth bound)
             check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, m.mu_img, 0, bs, 1.f, nullptr, 0, 0, m.opt.pw_wide), "fc_mu");
             tm([&] { check(lut_gemv_mfma(m.mu_img, a.lut_rows, lut_buf, N, 18 * a.C, s), "lut gemv"); });
-            return q;
+            return;
         }
         // LUT GEMM: 1x1 conv over the [npad/32 x 32] "image" of (sample, label) columns
         ConvParams p{};
@@ -1335,15 +1362,12 @@ struct Runner {
             p.partial = splitk;                // K = 512 in 32 chunks on few tiles (C <= 512): split-K fills the chip
             p.partial_cap = m.splitk_cap;
             tm([&] { check(conv_sh16_plain(p, 1, s), "lut gemm"); });
-            q.lut_rs = npad;
-            q.lut_ns = 4;
         } else {
             if (m.fcmu_batched && (N > 64 || m.opt.batch_inv)) p.in = m.mu_all + (size_t)a.index * m.mu_stride;      // projected at the start of the chunk (generate())
             else check(fc_mu(codes, a.fcmu_w, a.fcmu_b, m.mu_img, B, npad, s, nullptr, 0, 19, 1.f, nullptr, 0, 0, m.opt.pw_wide), "fc_mu");
             p.npix_valid = N;
             tm([&] { check(conv_nhwc1x1(p, s), "lut gemm"); });
         }
-        return q;
     }
     // the zero columns left and right of the image in a padded hidden buffer: the label-table kernels never write them, so they are cleared
     // whenever the buffer changes its geometry (first use, another image size) -- per-pixel pad stores cost 200 us per 512^2 launch
@@ -1370,9 +1394,9 @@ struct Runner {
         else if (pl.wino()) {
             // Winograd ACE path: hidden activations (+ the one-hot planes of a styled ACE, which feed the style k-steps) in one
             // persistent pass into the padded planes the ACE kernels read (conv_wino.h WINO_AXOFF), whole 64-byte groups of pixels
-            // that a boundary quad's patch touches only (sean.hidden_wq = 0, F(4x4) levels, level not classified yet: every pixel)
+            // that a boundary quad's patch touches only (sean.hidden_wq = 0, F(4x4) levels, no interior map this pass may read: every pixel)
             zero_pads(actv_buf, r, kout, s);
-            const uint8_t* u5 = (pl.route == AceRoute::WinoQuads && m.opt.hidden_wq) ? level_u5(pl) : nullptr;
+            const uint8_t* u5 = pl.hidden_u5;
             const SeanModel::WinoLevel* PL = pl.patch;
             const bool pm = PL && PL->gq && PL->patch_mode && m.patchbuf;
             if (pm && mode.prologue && PL->chunk_base) {
@@ -1395,16 +1419,14 @@ struct Runner {
     // stream, into per-ACE buffers, while the main stream walks the dependent chain of convs; an event per ACE joins them.
     // mode.ahead == LUTS (large jobs): only the style LUT builds run ahead; the label-table kernels stay inline.
     void prepare_all_ahead(const float* codes) {
-        const bool full = mode.ahead == SeanModel::ChunkMode::FULL;
         check(hipEventRecord(m.ev_fork, st), "fork");
         check(hipStreamWaitEvent(m.side, m.ev_fork, 0), "fork wait");
-        for (AcePlan& p : plans) {
+        for (const AcePlan& p : plans) {
             const AceW& a = *p.a;
-            if (!full && !a.styled) continue;
+            if (!p.join) continue;
             // (grouped LUT build: the launch on the main stream built it)
-            if (!(mode.grouped && a.styled)) p.ahead = build_lut(p, codes, m.side, m.lut_ahead[a.index], m.splitk_side, false);
-            p.ahead.actv = m.actv_ahead[a.index];
-            if (full) build_hidden(p, m.side, m.actv_ahead[a.index]);
+            if (p.lut_src == AcePlan::AHEAD) build_lut(p, codes, m.side, m.splitk_side, false);
+            if (p.hidden == AcePlan::AHEAD) build_hidden(p, m.side, m.actv_ahead[a.index]);
             check(hipEventRecord(m.ev_join[a.index], m.side), "join record");
         }
     }
@@ -1425,8 +1447,6 @@ struct Runner {
         const int nrg = ((N + 31) / 32 + 3) / 4;
         timed(2, 2.0 * m.lut_group_rows * STYLE * N, 4.0 * (m.lut_group_rows * STYLE + m.lut_group_rows * N + (double)m.lut_ngroups * STYLE * N),
               [&] { check(conv_pw_grouped(q, m.lut_group_tiles * nrg, st), "style LUTs (grouped GEMM)"); });
-        for (AcePlan& p : plans)
-            if (p.a->styled) p.ahead.lut = m.lut_ahead[p.a->index];      // (the view: AcePrep's defaults, lut_ns from the plan)
     }
 
     // ACE prologue (SeanModel::pro_on; large chunks of the exact-f32 Winograd path): what the ACEs of the chunk build from labels, codes and
@@ -1437,9 +1457,9 @@ struct Runner {
     //   * the padded hidden planes of every F(4x4)-route ACE (spade_hidden_wq_grouped);
     //   * gtab and P6 of every gather-route ACE (ace_tables_grouped) and its F(2x2) style images (wino_style_pack_grouped) -- these read the
     //     style LUTs, so they need the grouped LUT GEMM of the chunk (mode.grouped); without it only unstyled ACEs join.
-    // The groups are filled here, per call: the set of ACEs, their level sizes and label pointers follow B and S.  AcePlan::pre_* != nullptr
-    // tells the ACE functions that the product is in place; every other ACE keeps its inline launches.  The level geometry of the gather-route
-    // ACEs (classification, quad lists, task lists: wino_prepare) runs here too, since gtab / P6 depend on what it decides (edges).
+    // The groups are filled here, per call, from the plan, which names their members (AcePlan::hidden == GROUP, pre_tables, pre_wsty: the set of
+    // ACEs, their level sizes and label pointers follow B and S); every other ACE keeps its inline launches.  The level geometry of the gather-route
+    // ACEs (classification, quad lists, task lists: prepare()) runs here too, ahead of the tables that follow its marks.
     // With the prologue on, the gather-mode levels also take their hidden activations -- planes or pre-gathered patches, a device flag decides
     // -- from one launch per ACE (spade_hidden_level) instead of two of which one returns at once.  Runs where mode.prologue says so.
     void prologue() {
@@ -1452,52 +1472,19 @@ struct Runner {
         tg.lut_rs = 1;
         tg.lut_bs = LABEL_NC;
         tg.lut_mul = 1.f;
-        for (AcePlan& p : plans) {
+        for (const AcePlan& p : plans) {
             const AceW& a = *p.a;
             const int r = p.r;
-            if (p.route == AceRoute::F4) {
+            if (p.hidden == AcePlan::GROUP) {
                 float* buf = m.pro_actv[a.index];
-                if (!buf || hg.n >= HiddenGroup::MAX) continue;
                 zero_pads(buf, r, p.kout, st);
-                HiddenGroup::Entry& e = hg.e[hg.n++];
-                e.lab = p.lab;
-                e.u5 = nullptr;                              // (F(4x4) levels: every pixel is read)
-                e.table = a.actv_table;
-                e.bias = a.actv_bias;
-                e.out = buf;
-                e.H = e.W = r;
-                e.kout = p.kout;
-                e.onehot = a.styled ? 1 : 0;
-                e.pitch = wino_apitch(r);
-                e.xoff = WINO_AXOFF;
-                p.pre_actv = buf;
-                continue;
+                // (lab, u5 = nullptr: F(4x4) levels, every pixel is read; table, bias, out, H, W, kout, onehot, pitch, xoff; the rest is the launcher's)
+                hg.e[hg.n++] = HiddenGroup::Entry{p.lab, nullptr, a.actv_table, a.actv_bias, buf, r, r, p.kout, a.styled ? 1 : 0, wino_apitch(r), WINO_AXOFF};
             }
             if (p.route != AceRoute::WinoQuads) continue;
-            const WinoPrep wp = wino_prepare(p);      // (lists and task lists: into the geometry group)
-            if (a.styled && !mode.grouped) continue;
-            const float* lut = a.styled ? p.ahead.lut : nullptr;
-            if (a.styled && !lut) continue;
-            const bool p6 = wp.edges && a.styled;
-            if (wp.S && m.pro_gtab[a.index] && (!p6 || m.pro_p6[a.index]) && tg.n < AceTableGroup::MAX) {
-                AceTableGroup::Entry& e = tg.e[tg.n++];
-                e.bias_g = a.bias_g;
-                e.bias_b = a.bias_b;
-                e.gconst = a.gconst;
-                e.lut = lut;
-                e.gtab = m.pro_gtab[a.index];
-                e.p6 = p6 ? m.pro_p6[a.index] : nullptr;
-                e.C = a.C;
-                p.pre_gtab = e.gtab;
-                p.pre_p6 = e.p6;
-            }
-            if (a.styled && m.pro_wsty[a.index] && sg.n < StylePackGroup::MAX) {
-                StylePackGroup::Entry& e = sg.e[sg.n++];
-                e.lut = lut;
-                e.wsty = m.pro_wsty[a.index];
-                e.C = a.C;
-                p.pre_wsty = e.wsty;
-            }
+            prepare(p);      // (lists and task lists: into the geometry group)
+            if (p.pre_tables) tg.e[tg.n++] = AceTableGroup::Entry{a.bias_g, a.bias_b, a.gconst, p.q.lut, p.gtab, p.p6, a.C};
+            if (p.pre_wsty) sg.e[sg.n++] = StylePackGroup::Entry{p.q.lut, p.wsty, a.C};
         }
         geo_flush();
         geo = nullptr;
@@ -1511,35 +1498,19 @@ struct Runner {
     void ace(const AceW& a, const float* codes, const float* noise, size_t nf, size_t noff, const float* x, int x_up, int act, float* hout) {
         const AcePlan& p = plans[a.index];
         const AceIO io{noise + noff, (long long)nf, x, x_up, act, hout};
-        const WinoPrep wp = p.route == AceRoute::WinoQuads ? wino_prepare(p) : WinoPrep();
-        if (p.sw) sparse_prepare(p);
-        const AcePrep q = operands(p, codes);
+        prepare(p);
+        // the operands (AcePlan::q) that are not in place yet: the LUT and the hidden planes the plan wants built inline, then the join with the side
+        // stream for what was built ahead
+        if (p.lut_src == AcePlan::INLINE) build_lut(p, codes, st, m.splitk_ws, true);
+        if (p.hidden == AcePlan::INLINE) build_hidden(p, st, p.abuf);
+        if (p.join) check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
         switch (p.route) {
-            case AceRoute::F4: return ace_f4(p, q, io);
-            case AceRoute::WinoQuads: return ace_wino(p, wp, q, io);
-            case AceRoute::Sparse: return ace_sparse(p, q, io);
-            case AceRoute::TinySplitK: return ace_tiny(p, q, io);
-            case AceRoute::Dense: return ace_dense(p, q, io);
+            case AceRoute::F4: return ace_f4(p, io);
+            case AceRoute::WinoQuads: return ace_wino(p, io);
+            case AceRoute::Sparse: return ace_sparse(p, io);
+            case AceRoute::TinySplitK: return ace_tiny(p, io);
+            case AceRoute::Dense: return ace_dense(p, io);
         }
-    }
-    // The operands of this ACE: hidden planes and LUT view.  Full run-ahead: both wait on the side stream.  Else the hidden activations are built
-    // here (unless the prologue wrote them), and the style LUT is the chunk's grouped one, the one built ahead (joined here), or built here first.
-    AcePrep operands(const AcePlan& p, const float* codes) {
-        const AceW& a = *p.a;
-        AcePrep q;
-        if (mode.ahead == SeanModel::ChunkMode::FULL) {
-            q = p.ahead;
-            check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
-        } else {
-            const bool lut_made = a.styled && (mode.grouped || mode.ahead == SeanModel::ChunkMode::LUTS);
-            if (!lut_made) q = build_lut(p, codes, st, m.lut, m.splitk_ws, true);
-            if (!p.pre_actv) build_hidden(p, st, p.abuf);      // label table inline
-            if (lut_made) q = p.ahead;
-            q.actv = p.abuf;
-            if (lut_made && !mode.grouped) check(hipStreamWaitEvent(st, m.ev_join[a.index], 0), "join wait");
-        }
-        if (p.pre_actv) q.actv = p.pre_actv;
-        return q;
     }
     // the same-named modulation operands of any ACE parameter struct (the interior pass takes its biases through gtab)
     template <class P>
@@ -1569,20 +1540,21 @@ struct Runner {
         fill_mod(ip, p, io);
         ip.u5 = L.u5;
         ip.cnt = L.cnt;
-        ip.gtab = m.gtab;
+        ip.gtab = p.gtab;
+        if (p.marks.edges) {      // straight-edge pixels served by the interior pass: table row of the code + three column / row sums of the style LUT
+            ip.e16 = L.e16;
+            ip.etab = p.a->edge_tab;
+            ip.p6 = p.p6;
+        }
         return ip;
-    }
-    void interior_edges(AceInteriorParams& ip, const AcePlan& p, const AcePrep& q, const SparseLevel& L) {
-        ip.e16 = L.e16;      // straight-edge pixels served by the interior pass: table row of the code + three column / row sums of the style LUT
-        ip.etab = p.a->edge_tab;
-        ip.p6 = (p.a->styled && q.lut) ? m.p6 : nullptr;
     }
     double dense_flops(const AcePlan& p) const { return 2.0 * 2 * p.a->C * HID * 9 * ((double)B * p.r * p.r); }
 
     // F(4x4,3x3) over every tile of a low-resolution level (conv_wino4.h): nearly every tile holds a boundary pixel there -- no classification,
     // no interior pass, hidden activations at every pixel
-    void ace_f4(const AcePlan& p, const AcePrep& q, const AceIO& io) {
+    void ace_f4(const AcePlan& p, const AceIO& io) {
         const AceW& a = *p.a;
+        const AcePrep& q = p.q;
         const int r = p.r;
         const double npix = (double)B * r * r;
         Wino4AceParams w{};
@@ -1612,25 +1584,23 @@ struct Runner {
                 check(conv_wino4_ace(w, st), "spade conv (winograd F(4x4,3x3), every tile)");
         });
     }
-    // F(2x2,3x3) over the boundary quads of the level (gather or tile mode, conv_wino.h); where the interior reduction serves the level (wp.S),
-    // the interior pixels first, from tables
-    void ace_wino(const AcePlan& p, const WinoPrep& wp, const AcePrep& q, const AceIO& io) {
+    // F(2x2,3x3) over the boundary quads of the level (gather or tile mode, conv_wino.h); where the interior reduction serves the level
+    // (LevelPlan::S), the interior pixels first, from tables
+    void ace_wino(const AcePlan& p, const AceIO& io) {
         const AceW& a = *p.a;
+        const AcePrep& q = p.q;
+        const SparseLevel* S = lplans[p.k].S;
         const int r = p.r, x_up = io.x_up;
         const double npix = (double)B * r * r;
         const double xpp = 4.0 * a.C / (x_up ? 4.0 : 1.0), opp = 4.0 * a.C;
         const int ktot = p.kout;
-        if (wp.S) {
-            AceInteriorParams ip = interior_params(p, io, *wp.S);
+        if (S) {
+            AceInteriorParams ip = interior_params(p, io, *S);      // (P6 is built below)
             // four pixels per thread (16-byte stores) from 128 pixels of width: 530 -> 420 us on the up-sampled 512^2 launches
             // (tools/interior_bench.hip); level in the 100 ms step of round 3, measurable in this one
             ip.impl = r >= 128 ? 2 : 0;
             ip.groups = m.opt.int_groups;       // (tile4 kernel: channel groups per block, 0 = the launcher's rule; ace_sparse.hip)
             ip.onepass = m.opt.int_onepass;     // (tile4 kernel: 128 key slots and the narrow channel step for code-dense blocks)
-            if (wp.edges) {         // (P6 is built below)
-                if (!a.edge_tab || r < 128) check(hipErrorInvalidValue, "straight-edge marks on a level whose ACE has no table");
-                interior_edges(ip, p, q, *wp.S);
-            }
             // (tile4 kernel, r >= 128: 0 = whole 128-byte lines that hold an interior pixel, ace_sparse.hip; sean.dbg bit 134217728: the
             //  block rule of rounds 3-5 for A/B)
             ip.fill_min = (x_up && r < 128) ? 257 : ((r >= 128 && !(m.opt.dbg & 134217728)) ? 0 : 128);
@@ -1646,28 +1616,21 @@ struct Runner {
                 check(ace_interior_f32(ip, m.side_int), "ace interior");
                 check(hipEventRecord(m.ev_int[a.index], m.side_int), "interior done");
             } else {
-                // tables from the prologue: only when it built exactly what this pass reads (P6 follows the level's straight-edge marks)
-                const bool pre = p.pre_gtab && (ip.p6 != nullptr) == (p.pre_p6 != nullptr);
-                if (pre) {
-                    ip.gtab = p.pre_gtab;
-                    ip.p6 = p.pre_p6;
-                }
                 timed(3, 0.0, 0.0, SpStat{p.W->total + 4, 0.0, xpp + opp + 5.0, 4.0 * 19 * 2 * a.C * B, npix}, [&] {
-                    if (!pre) {
-                        check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.gtab, B, a.C, st), "ace_gtable");
-                        if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, m.p6, B, a.C, st), "ace_p6table");
+                    if (!p.pre_tables) {      // (else: the prologue filled this ACE's own)
+                        check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, p.gtab, B, a.C, st), "ace_gtable");
+                        if (p.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f, p.p6, B, a.C, st), "ace_p6table");
                     }
                     check(ace_interior_f32(ip, st), "ace interior");
                 });
             }
         }
-        const SeanModel::WinoLevel& L = *p.L;
+        const SeanModel::WinoLevel& L = m.levels[p.k].wq;
         WinoAceParams w{};
         fill_mod(w, p, io);
         w.actv = q.actv;
         w.wpk = a.spade_wino;
-        const float* pre_wsty = (a.styled && q.lut) ? p.pre_wsty : nullptr;      // style images from the prologue
-        w.wsty = (a.styled && q.lut) ? (pre_wsty ? pre_wsty : m.wsty) : nullptr;
+        w.wsty = p.wsty;      // (style images: the shared buffer, packed below, or the prologue's)
         w.patch = p.patch ? m.patchbuf : nullptr;
         w.chunk_base = L.chunk_base;
         w.patch_mode = L.patch_mode;
@@ -1683,14 +1646,15 @@ struct Runner {
         w.claim = w.gq ? next_claim() : nullptr;
         // executed FLOPs = wave tasks x (32 rows x 16 quads x 16 positions x K) x 2; dense = the direct conv over every pixel
         timed(1, dense_flops(p), 0.0, SpStat{p.W->total + 4, 2.0 * 32 * 16 * 16 * ktot, 4.0 * ktot + xpp + opp, 4.0 * 2.0 * a.C * ktot * 16, npix}, [&] {
-            if (w.wsty && !pre_wsty) check(wino_style_pack(q.lut, m.wsty, B, a.C, st), "wino_style_pack");
+            if (p.wsty && !p.pre_wsty) check(wino_style_pack(q.lut, p.wsty, B, a.C, st), "wino_style_pack");
             check(conv_wino_ace(w, st), "spade conv (winograd, boundary quads)");
         });
-        if (mode.overlap && wp.S) check(hipStreamWaitEvent(st, m.ev_int[a.index], 0), "interior done wait");
+        if (mode.overlap && S) check(hipStreamWaitEvent(st, m.ev_int[a.index], 0), "interior done wait");
     }
     // the fused ACE conv of the direct routes (conv_mfma.h / conv_sh16.h): every pixel, or the work list the Sparse route adds
-    ConvParams ace_conv_params(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
+    ConvParams ace_conv_params(const AcePlan& pl, const AceIO& io) {
         const AceW& a = *pl.a;
+        const AcePrep& q = pl.q;
         ConvParams p{};
         fill_mod(p, pl, io);
         p.in = q.actv;
@@ -1719,15 +1683,16 @@ struct Runner {
     }
     // interior pixels: elementwise with the per-(sample, label) gamma/beta rows; the others: conv over the compacted
     // boundary pixels (exact-f32 path) / over the tiles that hold a boundary pixel (f16x3 path)
-    void ace_sparse(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
+    void ace_sparse(const AcePlan& pl, const AceIO& io) {
         const AceW& a = *pl.a;
-        const SparseLevel& L = *pl.SL;
+        const AcePrep& q = pl.q;
+        const SparseLevel& L = m.levels[pl.k].sp[pl.ti];
         const SparseWork* sw = pl.sw;
         const int r = pl.r, x_up = io.x_up;
         const bool compact = pl.compact;
         const double npix = (double)B * r * r;
         const double xpp = 4.0 * a.C / (x_up ? 4.0 : 1.0), opp = 4.0 * a.C;
-        ConvParams p = ace_conv_params(pl, q, io);
+        ConvParams p = ace_conv_params(pl, io);
         AceInteriorParams ip = interior_params(pl, io, L);
         ip.out_scale = a.out_scale;
         ip.out_amax = m.amax_slots + 2 * a.index;
@@ -1739,7 +1704,6 @@ struct Runner {
         // dbg bit 2097152: the row-shaped kernels of the first version (A/B)
         ip.impl = CH_ABL(m.opt.dbg & 2097152) ? 1 : 0;
         ip.fill_min = m.opt.use_sh16 ? 128 : (x_up ? 257 : 128);
-        if (m.opt.use_sh16 && compact && lvl[pl.k].edges[sw->TH == 16 ? 1 : 0]) interior_edges(ip, pl, q, L);
         // (impl 2, four pixels per thread: 10 % ahead at 512^2 in tools/interior_bench.hip, no difference in the generator
         // step -- 159.7 vs 159.9 images/s -- so the one-pixel kernel stays; dbg bit 16777216 selects it)
         if (!m.opt.use_sh16 && CH_ABL(m.opt.dbg & 16777216) && r >= 128) {
@@ -1757,7 +1721,7 @@ struct Runner {
             // (the f16x3 LUT is stored pre-multiplied by the ACE output scale)
             check(ace_gtable(a.bias_g, a.bias_b, a.gconst, q.lut, q.lut_rs, q.lut_ns, q.lut_bs, m.opt.use_sh16 ? 1.f / a.out_scale : 1.f,
                              m.gtab, B, a.C, st), "ace_gtable");
-            if (ip.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f / a.out_scale, m.p6, B, a.C, st), "ace_p6table");
+            if (pl.p6) check(ace_p6table(q.lut, q.lut_rs, q.lut_ns, q.lut_bs, 1.f / a.out_scale, pl.p6, B, a.C, st), "ace_p6table");
             check(m.opt.use_sh16 ? ace_interior_sh16(ip, st) : ace_interior_f32(ip, st), "ace interior");
         });
         timed(1, dense_flops(pl), 0.0, SpStat{sw->total, 32.0 * 64 * 2.0 * HID * 9, 4.0 * HID + xpp + opp, 4.0 * 2.0 * a.C * HID * 9, npix}, [&] {
@@ -1775,10 +1739,11 @@ struct Runner {
     // PLAIN conv over the same packed image -- which splits K over blocks when its grid is small (conv_mfma.h launch_conv) -- into
     // a scratch of gamma | beta sums, then ace_finish_f32 (style-LUT gathers, biases, modulation).  Same sums per element, the
     // split-K slabs added in order: deterministic.
-    void ace_tiny(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
+    void ace_tiny(const AcePlan& pl, const AceIO& io) {
         const AceW& a = *pl.a;
+        const AcePrep& q = pl.q;
         const int r = pl.r, rowsP = ((a.C + 31) / 32) * 64;
-        ConvParams c = ace_conv_params(pl, q, io);
+        ConvParams c = ace_conv_params(pl, io);
         c.out = m.gb_small;
         c.Mrows = rowsP;
         c.act = ACT_NONE;
@@ -1791,8 +1756,8 @@ struct Runner {
                                  io.out, B, a.C, r, r, io.act, st), "ace finish");
         });
     }
-    void ace_dense(const AcePlan& pl, const AcePrep& q, const AceIO& io) {
-        ConvParams p = ace_conv_params(pl, q, io);
+    void ace_dense(const AcePlan& pl, const AceIO& io) {
+        ConvParams p = ace_conv_params(pl, io);
         timed(1, dense_flops(pl), dense_bytes(pl, io), [&] {
             if (!m.opt.use_sh16) {
                 check(conv_ace(p, st), "spade conv");
@@ -2007,6 +1972,7 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
         const int B = std::min(max_batch, Btot - bo);
         const uint8_t* lab = labels + (size_t)bo * S * S;
         Runner R(*this, st, B, S, lab);
+        if (!R.err.empty()) return join(R.err);      // (the plan: nothing has been launched)
         const ChunkMode& mode = R.mode;
         if (claim_pool) R.check(hipMemsetAsync(claim_pool, 0, (size_t)CLAIM_SLOTS * CLAIM_WORDS * sizeof(unsigned), st), "claim counters");
         const float* cd = codes + (size_t)bo * LABEL_NC * STYLE;
@@ -2017,7 +1983,7 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             R.check(gen_noise(noise_ws, (long long)B * nf, chunk_seed(seed, bo), st), "gen_noise");
             nz = noise_ws;
         }
-        for (int k = 1; k <= 5; ++k) R.check(label_downsample(lab, lab_r[k], B, S, S >> k, st), "label_downsample");
+        for (int k = 1; k <= 5; ++k) R.check(label_downsample(lab, levels[k].lab, B, S, S >> k, st), "label_downsample");
         if (opt.use_sh16) R.check(hipMemsetAsync(amax_slots, 0, 64 * sizeof(unsigned), st), "amax slots");
         if (mode.project_all) {     // (smaller batches take the GEMV branch of Runner::build_lut, which projects per ACE)
             // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout)
@@ -2041,7 +2007,7 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
         const int sw = S / 32;
         float* x = xa;
         float* y = xb;
-        R.check(onehot_conv3x3(lab_r[5], fc_table, fc_bias, x, B, sw, sw, 16 * ngf, 0, st, opt.use_sh16 ? 1 : 0), "fc");
+        R.check(onehot_conv3x3(levels[5].lab, fc_table, fc_bias, x, B, sw, sw, 16 * ngf, 0, st, opt.use_sh16 ? 1 : 0), "fc");
         R.tap_c4("fc", x, 16 * ngf, (size_t)sw * sw);
         size_t noff = 0;
         for (const auto& b : blocks) {
@@ -2133,7 +2099,7 @@ ConvOpts SeanModel::conv_env() const {
 // else the ACE takes the direct kernels and their [B][128][H][W] layout
 const SeanModel::WinoWork* SeanModel::wino_work(const AceW& a, int r) const {
     if (!(opt.wino && !opt.use_sh16 && a.spade_wino && r >= 32 && r % 32 == 0)) return nullptr;
-    const WinoLevel& L = wq_level[level_of(a.res_div)];
+    const WinoLevel& L = levels[level_of(a.res_div)].wq;
     if (!L.qlist) return nullptr;
     for (const auto& w : L.works)
         if (w.nrt == (a.C + 15) / 16) return &w;
@@ -2141,10 +2107,27 @@ const SeanModel::WinoWork* SeanModel::wino_work(const AceW& a, int r) const {
 }
 const SparseWork* SeanModel::sparse_work(const AceW& a, int r) const {
     if (!opt.sparse || r < opt.sparse_min_r || r < 32) return nullptr;
-    const int k = level_of(a.res_div);
-    for (const auto& w : sp_work[k])
-        if (w.mtiles == (a.C + 31) / 32) return sp_level[k][w.TH == 16 ? 1 : 0].u5 ? &w : nullptr;
+    const Level& L = levels[level_of(a.res_div)];
+    for (const auto& w : L.sp_work)
+        if (w.mtiles == (a.C + 31) / 32) return L.sp[w.TH == 16 ? 1 : 0].u5 ? &w : nullptr;
     return nullptr;
+}
+SeanModel::LevelMarks SeanModel::level_marks(int k, int r, int ti, bool built) const {
+    const Level& L = levels[k];
+    // the interior passes that know the codes: the tile4 kernel of the exact-f32 Winograd path and the compacting f16 kernels, from 128 pixels
+    bool e = opt.edge && (opt.use_sh16 ? opt.sparse : opt.wino) && r >= 128;
+    if (e && built) {
+        // ... on a classified level with a code plane whose ACEs carry the table rows and, styled ACEs, have room for their column / row sums
+        e = opt.sparse && L.sp[ti].e16 && L.edge_tab && (!L.styled || p6);
+        // f16 paths: work lists of the compacting kernel (sean.sh16_compact: mode >= 2).  Exact f32: the level takes the Winograd route at r,
+        // and not on an overlap handle (quad_only interior pass)
+        if (opt.use_sh16) e = e && !L.sp_work.empty() && L.sp_work[0].mode >= 2;
+        else e = e && L.wq.qlist && r % 32 == 0 && !overlap_on;
+    }
+    LevelMarks mk;
+    mk.edges = e;
+    mk.frame = e && !opt.use_sh16 && opt.frame;      // frame pixels: only the tile4 kernel knows their codes
+    return mk;
 }
 AceRoute SeanModel::ace_route_shape(const AceW& a, int r) const {
     if (wino_work(a, r)) {

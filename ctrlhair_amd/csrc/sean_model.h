@@ -174,7 +174,6 @@ struct SeanModel {
     long long gb_small_cap = 0;
     float* splitk_ws = nullptr;
     long long splitk_cap = 0;
-    uint8_t* lab_r[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // res_div 32,16,8,4,2 (index by log2) ; [0] unused
     unsigned* amax_slots = nullptr;            // f16x3 path: recorded maxima of the dynamically scaled SH16 tensors (sh16.h)
     float* zero_page = nullptr;                // 256 bytes of zeros
     float *noise_ws = nullptr, *mu_img = nullptr, *lut = nullptr, *actv = nullptr;
@@ -211,7 +210,7 @@ struct SeanModel {
     unsigned* claim_pool = nullptr;            // dynamic task claiming: CLAIM_SLOTS launches x CLAIM_WORDS words (8 counters + mailboxes), zeroed per chunk
     static constexpr int CLAIM_SLOTS = 96, CLAIM_WORDS = 1024;
 
-    // ---- Winograd levels ----
+    // ---- levels ----
     // Winograd ACE path (conv_wino.h wino_ace_kernel): per resolution level the boundary quads of every 32 x 16 tile and one task
     // list per distinct row-tile count; per-sample style images of the ACE being run
     struct WinoWork { int nrt = 0; unsigned* work = nullptr; int* total = nullptr; };
@@ -222,8 +221,25 @@ struct SeanModel {
         int* chunk_base = nullptr;        // [33] first chunk of 64 quads of every sample (patch source of the gather kernel, conv_wino.h)
         int* patch_mode = nullptr;        // device flag: 1 = this chunk's patches come pre-gathered from SeanModel::patchbuf
     };
-    WinoLevel wq_level[6];
-    float* actv_lvl[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // per Winograd ACE level: hidden activations in the padded layout (conv_wino.h WINO_AXOFF)
+    // One resolution level (index = log2(res_div)): the facts build() fixes for every ACE of the level -- it returns an error if they disagree --
+    // and the buffers the level's ACEs share.  The Runner's per-chunk LevelPlan (sean_model.cpp) decides what a call launches on them.
+    struct Level {
+        int r = 0;                                 // the level's size at max_size
+        bool used = false, styled = false, edge_tab = false;      // an ACE runs here; its ACEs are styled; ... carry AceW::edge_tab
+        uint8_t* lab = nullptr;                    // down-sampled label map (levels 1-5; level 0 reads the caller's)
+        WinoLevel wq;                              // Winograd ACE routes: quad lists and one task list per distinct row-tile count (16-channel tiles)
+        float* actv = nullptr;                     // ... hidden activations in the padded layout (conv_wino.h WINO_AXOFF)
+        // exact SPADE-interior reduction (ace_sparse.h): classification buffers and one work list per distinct number of 64-row tiles
+        SparseLevel sp[2];                         // [0: tiles of 32 x 8 | 1: tiles of 32 x 16]
+        std::vector<SparseWork> sp_work;
+    };
+    Level levels[6];
+    // The one statement of "the classification of level k carries straight-edge marks (u5 == 253 + e16) and frame marks": r = the level's size,
+    // ti = the SparseLevel classified.  built = true: a call asks (r of the call; the buffers and the level's route are part of the answer).
+    // built = false: build() asks what to allocate (e16: r of max_size; edge_tab: r at NOMINAL_SIZE; p6: level 0 at NOMINAL_SIZE) -- options and size only.
+    struct LevelMarks { bool edges = false, frame = false; };
+    static constexpr int NOMINAL_SIZE = 512;
+    LevelMarks level_marks(int k, int r, int ti, bool built = true) const;
     std::map<const float*, long long> pad_state;   // geometry (size, planes) a padded buffer's zero columns were last cleared for
     float* patchbuf = nullptr;                 // pre-gathered hidden-activation patches of the ACE being run (few, scattered boundary quads)
     int patch_cap_chunks = 0;
@@ -257,12 +273,8 @@ struct SeanModel {
     std::vector<float*> pro_actv, pro_gtab, pro_p6, pro_wsty;
     size_t pro_bytes = 0;                      // what these buffers add to the handle
 
-    // ---- sparse levels ----
-    // exact SPADE-interior reduction (ace_sparse.h): per resolution level (index = log2(res_div)) the classification buffers
-    // and one work list per distinct number of 64-row tiles among the level's ACEs; gtab: [max_batch][19][2][C max]
-    SparseLevel sp_level[6][2];                // [level][0: tiles of 32 x 8 | 1: tiles of 32 x 16]
-    std::vector<SparseWork> sp_work[6];
-    float* gtab = nullptr;
+    // ---- exact SPADE-interior reduction (ace_sparse.h; per-level buffers: Level) ----
+    float* gtab = nullptr;                     // [max_batch][19][2][C max]
     float* gtab_side = nullptr;                // overlap mode: the table of the interior passes on the side stream
     float* p6 = nullptr;                       // per-call column / row sums of the style LUT of the ACE being run: [mb][19][6][2][C]
 
