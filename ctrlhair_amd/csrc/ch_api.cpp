@@ -680,6 +680,40 @@ int ch_png_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, 
     return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, f + hipGetErrorString(e));
 }
 
+// ---- JPEG encoding (jpeg_encode.hip) ---------------------------------------------------------------------------------------------------
+namespace {
+bool jpeg_dims_ok(int H, int W, int C, int subsampling) {
+    return (C == 1 || C == 3) && (subsampling == 0 || subsampling == 2) && H >= 1 && W >= 1 && H <= 32768 && W <= 32768 &&
+           (int64_t)H * W <= (1 << 30);
+}
+}  // namespace
+
+size_t ch_jpeg_scan_bound(int H, int W, int C, int subsampling) {
+    return jpeg_dims_ok(H, W, C, subsampling) ? chk::jpeg_scan_bound(H, W, C, subsampling) : 0;
+}
+
+size_t ch_jpeg_encode_workspace_bytes(int N, int H, int W, int C, int subsampling) {
+    return (N >= 1 && N <= 65535 && jpeg_dims_ok(H, W, C, subsampling)) ? chk::jpeg_encode_workspace_bytes(N, H, W, C, subsampling) : 0;
+}
+
+int ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int quality, int subsampling, uint8_t* out, int64_t* sizes,
+                   void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    const std::string f = "ch_jpeg_encode: ";
+    if (!img || !out || !sizes || !workspace) return fail(h, CH_ERR_ARG, f + "null pointer");
+    if (C != 1 && C != 3) return fail(h, CH_ERR_ARG, f + "C must be 1 (grey) or 3 (RGB)");
+    if (quality < 1 || quality > 100) return fail(h, CH_ERR_ARG, f + "quality outside 1..100");
+    if (subsampling != 0 && subsampling != 2) return fail(h, CH_ERR_ARG, f + "subsampling must be 0 (4:4:4) or 2 (4:2:0)");
+    if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, f + "N outside 1..65535");
+    if (!jpeg_dims_ok(H, W, C, subsampling)) return fail(h, CH_ERR_ARG, f + "image too small or too large (sides 1..32768, H * W <= 2^30)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
+    if (workspace_bytes < chk::jpeg_encode_workspace_bytes(N, H, W, C, subsampling))
+        return fail(h, CH_ERR_ARG, f + "workspace smaller than ch_jpeg_encode_workspace_bytes");
+    DeviceGuard guard(h->device);
+    hipError_t e = chk::jpeg_encode(img, N, H, W, C, quality, subsampling, out, sizes, workspace, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, f + hipGetErrorString(e));
+}
+
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {
     if (!h || !name) return CH_ERR_ARG;
     if (dev_ptr) h->sean.taps[name] = dev_ptr;

@@ -267,4 +267,11 @@ size_t png_decode_workspace_bytes(int N, int H, int W, int C);
 hipError_t png_decode(const uint8_t* streams, const int64_t* offsets, int N, int H, int W, int C, uint8_t* img, int32_t* status, void* ws,
                       hipStream_t s);
 
+// jpeg_encode.hip: N uint8 images [N,H,W,C] (C = 1 or 3) -> N baseline-JPEG entropy-coded scans (libjpeg's integer arithmetic, the
+// Annex K Huffman tables, byte-stuffed and padded).  subsampling: 0 = 4:4:4, 2 = 4:2:0 (ignored for C = 1).  See ch_jpeg_encode.
+size_t jpeg_scan_bound(int H, int W, int C, int subsampling);
+size_t jpeg_encode_workspace_bytes(int N, int H, int W, int C, int subsampling);
+hipError_t jpeg_encode(const uint8_t* img, int N, int H, int W, int C, int quality, int subsampling, uint8_t* out, int64_t* sizes, void* ws,
+                       hipStream_t s);
+
 }  // namespace chk

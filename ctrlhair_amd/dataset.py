@@ -20,11 +20,13 @@ On-disk formats are the reference's:
     python -m ctrlhair_amd.dataset codes    <root> <dataset> [--batch 16]
     python -m ctrlhair_amd.dataset rgb      <root> <dataset> [--batch 16]     (no network weights: ctrlhair_amd.colorstats)
     python -m ctrlhair_amd.dataset colorvar <root> <dataset> [--batch 16]
-    python -m ctrlhair_amd.dataset crop <src_dir> <root> <dataset> --landmarks <file> [--size 256]
+    python -m ctrlhair_amd.dataset crop <src_dir> <root> <dataset> --landmarks <file> [--size 256] [--png host|device]
+                                          [--jpeg host|device] [--jpeg-quality 75] [--jpeg-subsampling 420|444]
                                           (dataset_scripts/script_crop.py: FFHQ-align every photo of <src_dir> into
                                            <root>/<dataset>/images_256/<name>; no network weights: ctrlhair_amd.alignment)
     python -m ctrlhair_amd.dataset uncrop <photos> <edits> <out> --landmarks <file> [--size S]
-                                          [--labels DIR [--matte] [--matte-radius R] [--matte-eps E]]
+                                          [--labels DIR [--matte] [--matte-radius R] [--matte-eps E]] [--png host|device]
+                                          [--jpeg host|device] [--jpeg-quality 75] [--jpeg-subsampling 420|444]
                                           (the inverse of crop: paste the edited crop <edits>/<name> back into <photos>/<name> with the
                                            same landmarks and write the photo-sized result to <out>/<name>; ctrlhair_amd.alignment.
                                            --labels: 8-bit label PNGs <DIR>/<stem>.png of the crops; only their hair is pasted, and with
@@ -55,6 +57,9 @@ On-disk formats are the reference's:
     (masks, crop, uncrop and directions take --png host|device: 'device' encodes their PNG files with ch_png_encode,
      ctrlhair_amd.pngenc, instead of downloading the pixels for Pillow; the pixels are the same, the file bytes are not;
      directions --png device --png-stride: the encoder also matches at the sheet's column pitch (ch_png_encode_dist): smaller sheets)
+    (crop and uncrop take --jpeg host|device for their .jpg / .jpeg names: 'device' encodes them with ch_jpeg_encode,
+     ctrlhair_amd.jpegenc, instead of downloading the pixels for Pillow; the FILES are the same, byte for byte, as Pillow's at the same
+     --jpeg-quality and --jpeg-subsampling, whose defaults 75 and 420 are what Pillow's save() uses when given neither; .bmp stays Pillow's)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -119,9 +124,21 @@ def write_label_png(path: str, label: np.ndarray) -> None:
 # ---- batched drivers (HairEditor on the HIP library) -----------------------------------------------------------------
 def _png_encoder(png: str, owner):
     """None for png='host'; for 'device' the device encoder (pngenc.PngEncoder) on `owner`'s handle and device.  The option names who
-    writes PNG files: a file of another format (a .jpg name of the crop jobs) is Pillow's either way."""
+    writes PNG files: a .jpg name of the crop jobs follows the jpeg option (_jpeg_writer), any other format is Pillow's either way."""
     from .pngenc import PngEncoder, check_png_mode
     return PngEncoder(owner.handle, owner.device) if check_png_mode(png) == 'device' else None
+
+
+def _jpeg_writer(jpeg: str, quality, subsampling, owner):
+    """(encoder, save_options) for the .jpg / .jpeg names of the crop jobs.  jpeg='host': (None, options) -- Pillow writes the file, with
+    no options at all while quality and subsampling are at their defaults (75, 4:2:0: what save() then uses), so that nothing changes
+    for callers that pass neither.  jpeg='device': (jpegenc.JpegEncoder on `owner`'s handle and device, options); the same file bytes."""
+    from .jpegenc import JpegEncoder, check_jpeg_mode, check_jpeg_params
+    quality, subsampling = check_jpeg_params(quality, subsampling)
+    options = {'quality': quality, 'subsampling': subsampling}
+    if check_jpeg_mode(jpeg) == 'device':
+        return JpegEncoder(owner.handle, owner.device), options
+    return None, ({} if (quality, subsampling) == (75, 2) else options)
 
 
 def _png_decoder(decode: str, owner):
@@ -133,6 +150,10 @@ def _png_decoder(decode: str, owner):
 
 def _is_png(name: str) -> bool:
     return name.lower().endswith('.png')
+
+
+def _is_jpeg(name: str) -> bool:
+    return name.lower().endswith(('.jpg', '.jpeg'))
 
 
 def extract_masks(editor, img_dir: str, label_dir: str, batch: int = 16, rank: int = 0, world: int = 1,
@@ -275,13 +296,16 @@ def find_landmarks(landmarks: Dict[str, np.ndarray], dataset: str, file_name: st
 
 
 def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = 256, rank: int = 0,
-               world: int = 1, png: str = 'host'):
+               world: int = 1, png: str = 'host', jpeg: str = 'host', jpeg_quality: int = 75, jpeg_subsampling=2):
     """dataset_scripts/script_crop.py:36-54 for this rank's shard of `src_dir`: align every photo that has landmarks
     (`aligner`: alignment.FaceAligner) and write it to `out_dir/<name>`.  Returns (done, skipped): the file names written and the
-    ones without a landmark entry, which are reported and left out.  png='device': .png names are encoded on the device."""
+    ones without a landmark entry, which are reported and left out.  png='device': .png names are encoded on the device.  jpeg='device':
+    .jpg / .jpeg names are encoded on the device, to the bytes Pillow writes at jpeg_quality and jpeg_subsampling (0 / '444' or
+    2 / '420'); jpeg='host' passes those two to Pillow when they are not its defaults."""
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
     encoder = _png_encoder(png, aligner)
+    jpeg_encoder, jpeg_options = _jpeg_writer(jpeg, jpeg_quality, jpeg_subsampling, aligner)
     done, skipped = [], []
     for n in shard(list_images(src_dir), rank, world):
         lm = find_landmarks(landmarks, dataset, n)
@@ -294,8 +318,12 @@ def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dic
             encoder.write([os.path.join(out_dir, n)], crop[None])
             done.append(n)
             continue
+        if jpeg_encoder is not None and _is_jpeg(n):
+            jpeg_encoder.write([os.path.join(out_dir, n)], crop[None], **jpeg_options)
+            done.append(n)
+            continue
         crop = crop.cpu().numpy() if hasattr(crop, 'cpu') else np.asarray(crop)
-        Image.fromarray(crop).save(os.path.join(out_dir, n))
+        Image.fromarray(crop).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}))
         done.append(n)
     return done, skipped
 
@@ -314,19 +342,23 @@ def label_weight(label_path: str, S: int) -> np.ndarray:
 
 
 def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = None,
-                 rank: int = 0, world: int = 1, label_dir: str = None, matte=None, png: str = 'host'):
+                 rank: int = 0, world: int = 1, label_dir: str = None, matte=None, png: str = 'host', jpeg: str = 'host',
+                 jpeg_quality: int = 75, jpeg_subsampling=2):
     """The inverse of crop_faces for this rank's shard of `photo_dir`: paste the edited crop `edit_dir/<name>` back into the photo
     `photo_dir/<name>` it was aligned from (same landmarks, same file names) and write the photo-sized result to `out_dir/<name>`.
     size: the crops' side (default: each edit's own).  label_dir: per-image weight from `label_dir/<stem>.png` (hair = 255); matte
     (True or a dict, alignment.matte_params; needs label_dir): that weight refined by a guided filter of the photo.  Returns
     (done, skipped); a photo without landmarks, without an edit or (with label_dir) without a label map is reported and left out.
-    png='device': .png names are encoded on the device (the photo-sized result is never downloaded)."""
+    png='device': .png names are encoded on the device (the photo-sized result is never downloaded).  jpeg='device': the same for
+    .jpg / .jpeg names, to the bytes Pillow writes at jpeg_quality and jpeg_subsampling (0 / '444' or 2 / '420'); jpeg='host' passes
+    those two to Pillow when they are not its defaults.  Neither path carries the photo's EXIF or ICC data over."""
     from PIL import Image
     from .alignment import align_plan
     if matte is not None and label_dir is None:
         raise ValueError('matte refines a weight map: it needs label_dir')
     os.makedirs(out_dir, exist_ok=True)
     encoder = _png_encoder(png, aligner)
+    jpeg_encoder, jpeg_options = _jpeg_writer(jpeg, jpeg_quality, jpeg_subsampling, aligner)
     done, skipped = [], []
     for n in shard(list_images(photo_dir), rank, world):
         lm = find_landmarks(landmarks, dataset, n)
@@ -350,8 +382,10 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
             out = aligner.paste_back(photo, edit, plan, weight=label_weight(label, S), matte=matte)[0]
         if encoder is not None and _is_png(n):
             encoder.write([os.path.join(out_dir, n)], out[None])
+        elif jpeg_encoder is not None and _is_jpeg(n):
+            jpeg_encoder.write([os.path.join(out_dir, n)], out[None], **jpeg_options)
         else:
-            Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n))
+            Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}))
         done.append(n)
     return done, skipped
 
@@ -628,7 +662,12 @@ def _main_crop(argv):
     ap.add_argument('--landmarks', required=True, help='.npz or pickled dict: image name -> [68,2] pixel landmarks')
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
+    ap.add_argument('--jpeg', choices=('host', 'device'), default='host', help='who writes .jpg / .jpeg files: Pillow on the host (default) or ch_jpeg_encode on the device (the same file bytes)')
+    ap.add_argument('--jpeg-quality', type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's own default)")
+    ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help="JPEG chroma subsampling (default 420, Pillow's own default)")
     args = ap.parse_args(argv)
+    if not 1 <= args.jpeg_quality <= 100:
+        ap.error('--jpeg-quality must be in 1..100')
     import torch
     from . import lib
     from .alignment import FaceAligner
@@ -636,7 +675,8 @@ def _main_crop(argv):
     torch.cuda.set_device(local)
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = crop_faces(aligner, args.src_dir, os.path.join(args.root, args.dataset, 'images_256'), args.dataset,
-                               load_landmarks(args.landmarks), args.size, rank, world, png=args.png)
+                               load_landmarks(args.landmarks), args.size, rank, world, png=args.png, jpeg=args.jpeg,
+                               jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} without landmarks')
 
 
@@ -654,7 +694,12 @@ def _main_uncrop(argv):
     ap.add_argument('--matte-radius', type=int, default=None, help='matte window radius in photo pixels, 1..64 (default: 4 crop pixels)')
     ap.add_argument('--matte-eps', type=float, default=None, help='matte regularisation (default 1e-4)')
     ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
+    ap.add_argument('--jpeg', choices=('host', 'device'), default='host', help='who writes .jpg / .jpeg files: Pillow on the host (default) or ch_jpeg_encode on the device (the same file bytes)')
+    ap.add_argument('--jpeg-quality', type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's own default)")
+    ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help="JPEG chroma subsampling (default 420, Pillow's own default)")
     args = ap.parse_args(argv)
+    if not 1 <= args.jpeg_quality <= 100:
+        ap.error('--jpeg-quality must be in 1..100')
     matte = None
     if args.matte or args.matte_radius is not None or args.matte_eps is not None:
         if args.labels is None:
@@ -672,7 +717,8 @@ def _main_uncrop(argv):
     torch.cuda.set_device(local)
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = uncrop_faces(aligner, args.photos, args.edits, args.out, args.dataset, load_landmarks(args.landmarks), args.size,
-                                 rank, world, label_dir=args.labels, matte=matte, png=args.png)
+                                 rank, world, label_dir=args.labels, matte=matte, png=args.png, jpeg=args.jpeg,
+                                 jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
 
 

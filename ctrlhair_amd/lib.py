@@ -49,6 +49,9 @@ SYMBOLS = {
     'ch_png_encode_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
     'ch_png_encode': (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_png_encode_dist': (_I, [_VP, _VP, _I, _I, _I, _I, _I, _VP, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
+    'ch_jpeg_scan_bound': (C.c_size_t, [_I, _I, _I, _I]),
+    'ch_jpeg_encode_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I, _I]),
+    'ch_jpeg_encode': (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_png_decode_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
     'ch_png_decode': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_mask_warp_workspace_bytes': (C.c_size_t, [_I]),

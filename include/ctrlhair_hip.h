@@ -409,6 +409,27 @@ size_t ch_png_decode_workspace_bytes(int N, int H, int W, int C);
 int    ch_png_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, int N, int H, int W, int C, uint8_t* img,
                      int32_t* status, void* workspace, size_t workspace_bytes, ch_stream_t stream);
 
+/* ---- JPEG encoding on the device: crops and paste-backs of .jpg photos leave as compressed bytes -----------------------------------
+ * ch_jpeg_encode turns N images img uint8 [N,H,W,C] (device pointer; C = 1 grey, 3 interleaved RGB; RGBA is refused) into N
+ * entropy-coded scans of baseline JPEG (ITU-T T.81, sequential DCT, Huffman): the bytes between the SOS header and the EOI marker,
+ * byte-stuffed and padded.  Image n's scan starts at out + n * ch_jpeg_scan_bound(H, W, C, subsampling) and is sizes[n] bytes long
+ * (out uint8, sizes int64 [N]: device pointers).  The caller writes the markers around it (ctrlhair_amd.jpegenc.wrap_jpeg).
+ *   quality      1..100, libjpeg's scaling of the Annex K quantisation tables
+ *   subsampling  0: 4:4:4;  2: 4:2:0 (Pillow's numbering); ignored for C = 1
+ *   No restart markers, no progressive mode, the Annex K.3 Huffman tables (libjpeg without optimize_coding).
+ * The arithmetic is libjpeg's, all of it integer -- 16-bit fixed-point RGB -> YCbCr, 2x2 chroma averaging with the alternating bias,
+ * its edge replication and dummy blocks, the slow-integer forward DCT and its quantiser -- so the scan is the one libjpeg and
+ * libjpeg-turbo (Pillow) write for the same pixels and parameters, byte for byte, and is the same in every call and batch position.
+ * ch_jpeg_scan_bound: a block codes into at most 20 + 63 * 26 = 1658 bits (a category-11 DC difference behind a 9-bit code, 63 AC terms
+ *   of size 10 behind 16-bit codes); the last byte is padded; every byte may be 0xFF and then takes a 0x00 behind it:
+ *   bound = 2 * ceil(blocks * 1658 / 8) + 2, with blocks = the blocks of the scan, dummy luma blocks of 4:2:0 included.
+ * workspace: caller-owned device buffer (16-byte aligned) of ch_jpeg_encode_workspace_bytes(N, H, W, C, subsampling) bytes.
+ * Limits: sides 1..32768, H * W <= 2^30, N <= 65535.  Both size functions return 0 for arguments the call would refuse. */
+size_t ch_jpeg_scan_bound(int H, int W, int C, int subsampling);
+size_t ch_jpeg_encode_workspace_bytes(int N, int H, int W, int C, int subsampling);
+int    ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int quality, int subsampling, uint8_t* out,
+                      int64_t* sizes, void* workspace, size_t workspace_bytes, ch_stream_t stream);
+
 /* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
  * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image
  * edge extended 10 px, mask_adaptor.py:119-131), the pair's triangle mesh is deformed as rigidly as possible (libigl's per-element
