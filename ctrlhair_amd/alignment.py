@@ -14,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import lib as _lib
+from .devop import DeviceOp
 
 PLAN_LEN = 24                   # CH_ALIGN_PLAN_LEN
 UNALIGN_PLAN_LEN = 16           # CH_UNALIGN_PLAN_LEN
@@ -227,23 +227,8 @@ def matte_params(matte, scale):
     return int(radius), eps
 
 
-class FaceAligner:
+class FaceAligner(DeviceOp):
     """recreate_aligned_images on the device.  Attached to HipModels as `aligner`; also usable alone (no network weights)."""
-
-    def __init__(self, handle=None, device=None):
-        import torch
-        if handle is None:
-            dev = torch.device(device) if device is not None else torch.device('cuda', 0)
-            handle = _lib.Handle(dev.index or 0)         # raises without the library or a GPU
-        self.handle = handle
-        self.device = torch.device(device) if device is not None else torch.device('cuda', handle.device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('FaceAligner runs on the GPU only (no CPU fallback exists)')
-        self._ws = None
-
-    def _stream(self):
-        import torch
-        return torch.cuda.current_stream(self.device).cuda_stream
 
     def _u8(self, a, channels=None):
         import torch
@@ -257,14 +242,6 @@ class FaceAligner:
         if t.dim() != 3 or (channels is not None and t.shape[2] != channels):
             raise ValueError(f'expected an [H,W,{channels or "C"}] image, got {tuple(t.shape)}')
         return t
-
-    def _workspace(self, need):
-        import torch
-        if need == 0:
-            need = 256
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     @staticmethod
     def _f64(a):
@@ -282,7 +259,7 @@ class FaceAligner:
             raise ValueError(f'empty target size {size}')
         out = torch.empty(Hd, Wd, Cn, dtype=torch.uint8, device=self.device)
         need = int(self.handle.lib.ch_resample_lanczos_workspace_bytes(Hs, Ws, Cn, Hd, Wd))
-        ws = self._workspace(need)
+        ws = self._buffer('_ws',need)
         self.handle.call('ch_resample_lanczos_u8', x.data_ptr(), Hs, Ws, Cn, out.data_ptr(), Hd, Wd, ws.data_ptr(), ws.numel(),
                          self._stream())
         return out
@@ -295,7 +272,7 @@ class FaceAligner:
         T, S = int(transform_size), int(output_size)
         coef, cp = self._f64(quad_coefficients(corners, T))
         out = torch.empty(S, S, 3, dtype=torch.uint8, device=self.device)
-        ws = self._workspace(int(self.handle.lib.ch_quad_warp_workspace_bytes(T, S)))
+        ws = self._buffer('_ws',int(self.handle.lib.ch_quad_warp_workspace_bytes(T, S)))
         self.handle.call('ch_quad_warp_resample_u8', x.data_ptr(), int(x.shape[0]), int(x.shape[1]), cp, T, S, out.data_ptr(),
                          ws.data_ptr(), ws.numel(), self._stream())
         return out
@@ -313,7 +290,7 @@ class FaceAligner:
         if pads.min() < 1:
             raise ValueError(f'pad widths must be >= 1, got {tuple(pads)}')
         out = torch.empty(Hs + int(pads[1]) + int(pads[3]), Ws + int(pads[0]) + int(pads[2]), 3, dtype=torch.uint8, device=self.device)
-        ws = self._workspace(int(self.handle.lib.ch_align_pad_workspace_bytes(Hs, Ws, pp, radius)))
+        ws = self._buffer('_ws',int(self.handle.lib.ch_align_pad_workspace_bytes(Hs, Ws, pp, radius)))
         self.handle.call('ch_align_pad_feather_u8', x.data_ptr(), Hs, Ws, pp, wp, radius, out.data_ptr(), ws.data_ptr(), ws.numel(),
                          self._stream())
         return out
@@ -331,7 +308,7 @@ class FaceAligner:
         need = int(self.handle.lib.ch_face_align_workspace_bytes(H, W, pp, radius))
         if need == 0:
             raise ValueError('the plan does not fit the photo (see ch_face_align in include/ctrlhair_hip.h)')
-        ws = self._workspace(need)
+        ws = self._buffer('_ws',need)
         out = torch.empty(S, S, 3, dtype=torch.uint8, device=self.device)
         self.handle.call('ch_face_align', x.data_ptr(), H, W, pp, gp, radius, out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
         return out
@@ -394,7 +371,7 @@ class FaceAligner:
         need = int(self.handle.lib.ch_face_unalign_matte_workspace_bytes(H, W, pp, radius))
         if need == 0:
             raise ValueError('the plan does not fit the photo (see ch_face_unalign_matte in include/ctrlhair_hip.h)')
-        ws = self._workspace(need)
+        ws = self._buffer('_ws',need)
         alpha = torch.empty(bx[3] - bx[1], bx[2] - bx[0], dtype=torch.float32, device=self.device) if return_alpha else None
         self.handle.call('ch_face_unalign_matte', x.data_ptr(), H, W, e.data_ptr(), N, wp, pp, feather, radius, eps, out.data_ptr(),
                          None if alpha is None else alpha.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())

@@ -13,11 +13,12 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .devop import DeviceOp
 
 
-class PoissonBlender:
+class PoissonBlender(DeviceOp):
     def __init__(self, handle: _lib.Handle, device: torch.device, max_iters: int = 4000, rel_tol: float = 1e-7):
-        self.handle, self.device = handle, device
+        super().__init__(handle, device)
         self.max_iters, self.rel_tol = max_iters, rel_tol
         self.last_iters = 0              # blend_batch: per-image lists
         self.last_converged = True
@@ -45,13 +46,11 @@ class PoissonBlender:
             fp = face_parsing if isinstance(face_parsing, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(face_parsing)))
             f = self._u8(fp, (-1, H, W)).expand(B, H, W).contiguous()
             out = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
-            self.handle.call('ch_blend_mask_batch', t.data_ptr(), f.data_ptr(), out.data_ptr(), B, H, W,
-                             torch.cuda.current_stream(self.device).cuda_stream)
+            self.handle.call('ch_blend_mask_batch', t.data_ptr(), f.data_ptr(), out.data_ptr(), B, H, W, self._stream())
             return out
         t, f = self._u8(target_parsing, (H, W)), self._u8(face_parsing, (H, W))
         out = torch.empty(H, W, dtype=torch.uint8, device=self.device)
-        self.handle.call('ch_blend_mask', t.data_ptr(), f.data_ptr(), out.data_ptr(), H, W,
-                         torch.cuda.current_stream(self.device).cuda_stream)
+        self.handle.call('ch_blend_mask', t.data_ptr(), f.data_ptr(), out.data_ptr(), H, W, self._stream())
         return out
 
     def __call__(self, source, target, mask, with_gamma=True) -> np.ndarray:
@@ -64,8 +63,7 @@ class PoissonBlender:
         out = torch.empty(H, W, 3, dtype=torch.uint8, device=self.device)
         iters = C.c_int(0)
         self.handle.call('ch_poisson_blend', s.data_ptr(), t.data_ptr(), m.data_ptr(), out.data_ptr(), H, W,
-                         1 if with_gamma else 0, self.max_iters, float(self.rel_tol), C.byref(iters),
-                         torch.cuda.current_stream(self.device).cuda_stream)
+                         1 if with_gamma else 0, self.max_iters, float(self.rel_tol), C.byref(iters), self._stream())
         # negated count (INT_MIN for zero iterations) = rel_tol not reached (include/ctrlhair_hip.h)
         self.last_iters = 0 if iters.value == -2 ** 31 else abs(iters.value)
         self.last_converged = iters.value >= 0
@@ -90,7 +88,7 @@ class PoissonBlender:
         m = (m.to(self.device).reshape(B, H, W) != 0).to(torch.uint8).contiguous()
         out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)
         chunk = max(1, int(self.max_workspace_bytes) // self.workspace_bytes(H, W))
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         counts = []
         for i in range(0, B, chunk):
             n = min(chunk, B - i)

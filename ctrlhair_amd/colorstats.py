@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import hostutil as U
-from . import lib as _lib
+from .devop import DeviceOp
 from .hostutil import HAIR_IDX
 
 NSTAT = 22                # CH_COLOR_STATS: [n, sum c (3), c^2 (3), c^3 (3), c^4 (3), c0c1, c0c2, c1c2, H, H^2, S, S^2, V, V^2]
@@ -47,20 +47,13 @@ def _size(size):
     return int(h), int(w)
 
 
-class HairColorStats:
+class HairColorStats(DeviceOp):
     """Device side: resize, eroded hair mask and masked sums on one ch_handle.  Inputs are numpy arrays or torch tensors
     (uint8 or convertible); outputs are device tensors, except `sums` (numpy int64 [B, NSTAT])."""
-
-    def __init__(self, handle: _lib.Handle, device):
-        self.handle = handle
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
 
     def _u8(self, a) -> torch.Tensor:
         t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a)))
         return t.to(self.device).to(torch.uint8).contiguous()
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
 
     def resize(self, img, size) -> torch.Tensor:
         """cv2.resize(img, size) (INTER_LINEAR, size = (w, h) or an int) of uint8 [H,W,C] / [B,H,W,C] -> uint8 [B,h,w,C]."""

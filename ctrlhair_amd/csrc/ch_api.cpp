@@ -46,6 +46,34 @@ struct DeviceGuard {
         if (switched) (void)hipSetDevice(prev);
     }
 };
+// The tail of every entry point that launches: f() runs with the handle's device current; its hipError_t becomes CH_OK, or CH_ERR_HIP with
+// `prefix` ("ch_name: ") and HIP's text as the message.
+template <class F>
+int launch(ch_handle* h, const char* prefix, F&& f) {
+    DeviceGuard guard(h->device);
+    const hipError_t e = f();
+    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string(prefix) + hipGetErrorString(e));
+}
+// The same for the model calls, whose f() returns "" or what went wrong: CH_ERR_STATE for a model that is not finalized, else CH_ERR_HIP
+// (an exception included), with `name` in front of the message.
+template <class F>
+int model_call(ch_handle* h, const char* name, F&& f) {
+    if (!h) return CH_ERR_ARG;
+    DeviceGuard guard(h->device);
+    try {
+        const std::string e = f();
+        if (!e.empty()) return fail(h, e.find("not finalized") != std::string::npos ? CH_ERR_STATE : CH_ERR_HIP, std::string(name) + ": " + e);
+    } catch (const std::exception& ex) {
+        return fail(h, CH_ERR_HIP, std::string(name) + ": " + ex.what());
+    }
+    return CH_OK;
+}
+// CH_OK, or CH_ERR_ARG for a workspace of `have` bytes where the size query `query_name` (with its argument list, if the message shows one)
+// asks for `need`
+int workspace_short(ch_handle* h, const char* prefix, size_t have, size_t need, const char* query_name) {
+    return have >= need ? CH_OK : fail(h, CH_ERR_ARG, std::string(prefix) + "workspace smaller than " + query_name);
+}
+hipStream_t hs(ch_stream_t stream) { return static_cast<hipStream_t>(stream); }
 }  // namespace
 
 // ---- face alignment (face_align.hip) ---------------------------------------------------------------------------------------------
@@ -209,18 +237,6 @@ size_t ch_sean_noise_floats(const ch_handle* h, int S) {
     return h->sean.noise_floats(S);
 }
 
-#define CH_CALL(name, expr)                                                             \
-    if (!h) return CH_ERR_ARG;                                                          \
-    DeviceGuard guard(h->device);                                                       \
-    try {                                                                               \
-        std::string e = (expr);                                                         \
-        if (!e.empty()) return fail(h, e.find("not finalized") != std::string::npos ? CH_ERR_STATE : CH_ERR_HIP, \
-                                    std::string(name) + ": " + e);                      \
-    } catch (const std::exception& ex) {                                                \
-        return fail(h, CH_ERR_HIP, std::string(name) + ": " + ex.what());               \
-    }                                                                                   \
-    return CH_OK;
-
 // what every ch_sean_* call checks before it runs: CH_OK, or the status to return (with the handle's message set)
 static int sean_precheck(ch_handle* h, const char* name, bool args_ok, const char* what = "bad argument") {
     if (!h) return CH_ERR_ARG;
@@ -231,58 +247,57 @@ static int sean_precheck(ch_handle* h, const char* name, bool args_ok, const cha
 int ch_sean_generate(ch_handle* h, const uint8_t* labels, const float* codes, const float* noise, uint64_t seed,
                      float* out, int B, int S, ch_stream_t stream) {
     if (int rc = sean_precheck(h, "ch_sean_generate", labels && codes && out, "null pointer")) return rc;
-    CH_CALL("ch_sean_generate", h->sean.generate(labels, codes, noise, seed, out, B, S, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_sean_generate", [&] { return h->sean.generate(labels, codes, noise, seed, out, B, S, hs(stream)); });
 }
 int ch_sean_draw_noise(ch_handle* h, uint64_t seed, float* noise, int B, int S, ch_stream_t stream) {
     if (int rc = sean_precheck(h, "ch_sean_draw_noise", noise && B >= 1)) return rc;
-    CH_CALL("ch_sean_draw_noise", h->sean.draw_noise(seed, noise, B, S, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_sean_draw_noise", [&] { return h->sean.draw_noise(seed, noise, B, S, hs(stream)); });
 }
 int ch_sean_encode(ch_handle* h, const float* img, const uint8_t* labels, float* codes, int B, int S,
                    ch_stream_t stream) {
     if (int rc = sean_precheck(h, "ch_sean_encode", img && labels && codes && B >= 1)) return rc;
-    CH_CALL("ch_sean_encode", h->sean.encode(img, labels, codes, B, S, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_sean_encode", [&] { return h->sean.encode(img, labels, codes, B, S, hs(stream)); });
 }
 int ch_sean_encode_features(ch_handle* h, const float* img, int B, int S, ch_stream_t stream) {
     if (int rc = sean_precheck(h, "ch_sean_encode_features", img && B >= 1)) return rc;
-    CH_CALL("ch_sean_encode_features", h->sean.encode(img, nullptr, nullptr, B, S, static_cast<hipStream_t>(stream), 1))
+    return model_call(h, "ch_sean_encode_features", [&] { return h->sean.encode(img, nullptr, nullptr, B, S, hs(stream), 1); });
 }
 int ch_sean_encode_regions(ch_handle* h, const uint8_t* labels, float* codes, int B, int S, ch_stream_t stream) {
     if (int rc = sean_precheck(h, "ch_sean_encode_regions", labels && codes && B >= 1)) return rc;
-    CH_CALL("ch_sean_encode_regions", h->sean.encode(nullptr, labels, codes, B, S, static_cast<hipStream_t>(stream), 2))
+    return model_call(h, "ch_sean_encode_regions", [&] { return h->sean.encode(nullptr, labels, codes, B, S, hs(stream), 2); });
 }
 
 int ch_color_generate(ch_handle* h, const float* noise, const float* cond, float* code, int B, ch_stream_t stream) {
     if (h && (!noise || !cond || !code || B < 1)) return fail(h, CH_ERR_ARG, "ch_color_generate: bad argument");
-    CH_CALL("ch_color_generate", h->color.generate(noise, cond, code, B, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_color_generate", [&] { return h->color.generate(noise, cond, code, B, hs(stream)); });
 }
 int ch_color_encode(ch_handle* h, const float* code, float* out11, int B, ch_stream_t stream) {
     if (h && (!code || !out11 || B < 1)) return fail(h, CH_ERR_ARG, "ch_color_encode: bad argument");
-    CH_CALL("ch_color_encode", h->color.encode(code, out11, B, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_color_encode", [&] { return h->color.encode(code, out11, B, hs(stream)); });
 }
 int ch_color_predict(ch_handle* h, const float* code, float* out4, int B, ch_stream_t stream) {
     if (h && (!code || !out4 || B < 1)) return fail(h, CH_ERR_ARG, "ch_color_predict: bad argument");
-    CH_CALL("ch_color_predict", h->color.predict(code, out4, B, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_color_predict", [&] { return h->color.predict(code, out4, B, hs(stream)); });
 }
 int ch_shape_encode(ch_handle* h, const uint8_t* labels, float* hair_code, float* face_code, int B, ch_stream_t stream) {
     if (h && (!labels || (!hair_code && !face_code) || B < 1)) return fail(h, CH_ERR_ARG, "ch_shape_encode: bad argument");
-    CH_CALL("ch_shape_encode", h->shape.encode(labels, hair_code, face_code, B, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_shape_encode", [&] { return h->shape.encode(labels, hair_code, face_code, B, hs(stream)); });
 }
 int ch_shape_decode(ch_handle* h, const float* hair_code, const float* face_code, float* hair_logit, float* face_logit,
                     uint8_t* labels, float* probs, int B, ch_stream_t stream) {
     if (h && (!face_code || B < 1 || ((labels || probs || hair_logit) && !hair_code)))
         return fail(h, CH_ERR_ARG, "ch_shape_decode: bad argument");
-    CH_CALL("ch_shape_decode", h->shape.decode(hair_code, face_code, hair_logit, face_logit, labels, probs, B,
-                                               static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_shape_decode", [&] { return h->shape.decode(hair_code, face_code, hair_logit, face_logit, labels, probs, B, hs(stream)); });
 }
 int ch_shape_combine(ch_handle* h, const float* hair_logit, const float* face_logit, uint8_t* labels, float* probs, int B,
                      ch_stream_t stream) {
     if (h && (!hair_logit || !face_logit || !labels || B < 1)) return fail(h, CH_ERR_ARG, "ch_shape_combine: bad argument");
-    CH_CALL("ch_shape_combine", h->shape.combine(hair_logit, face_logit, labels, probs, B, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_shape_combine", [&] { return h->shape.combine(hair_logit, face_logit, labels, probs, B, hs(stream)); });
 }
 int ch_bisenet_parse(ch_handle* h, const float* img, uint8_t* labels, float* logits, int B, int H, int W,
                      ch_stream_t stream) {
     if (h && (!img || !labels || B < 1)) return fail(h, CH_ERR_ARG, "ch_bisenet_parse: bad argument");
-    CH_CALL("ch_bisenet_parse", h->bisenet.parse(img, labels, logits, B, H, W, static_cast<hipStream_t>(stream)))
+    return model_call(h, "ch_bisenet_parse", [&] { return h->bisenet.parse(img, labels, logits, B, H, W, hs(stream)); });
 }
 
 int ch_blend_mask_batch(ch_handle* h, const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int B, int H, int W,
@@ -290,9 +305,7 @@ int ch_blend_mask_batch(ch_handle* h, const uint8_t* target_parsing, const uint8
     if (!h) return CH_ERR_ARG;
     if (!target_parsing || !face_parsing || !out || B < 1 || B > 65535 || H < 1 || W < 1)
         return fail(h, CH_ERR_ARG, "ch_blend_mask: bad argument");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::blend_mask_batch(target_parsing, face_parsing, out, B, H, W, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_blend_mask: ") + hipGetErrorString(e));
+    return launch(h, "ch_blend_mask: ", [&] { return chk::blend_mask_batch(target_parsing, face_parsing, out, B, H, W, hs(stream)); });
 }
 
 int ch_blend_mask(ch_handle* h, const uint8_t* target_parsing, const uint8_t* face_parsing, uint8_t* out, int H, int W,
@@ -314,9 +327,8 @@ int ch_poisson_blend_batch(ch_handle* h, const uint8_t* source, const uint8_t* t
         if (hipMalloc(&h->blend_ws, need) != hipSuccess) return fail(h, CH_ERR_HIP, "ch_poisson_blend: workspace allocation failed");
         h->blend_ws_bytes = need;
     }
-    hipError_t e = chk::poisson_blend_batch(source, target, mask, out, B, H, W, with_gamma, max_iters, rel_tol, h->blend_ws, iters,
-                                            static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_poisson_blend: ") + hipGetErrorString(e));
+    return launch(h, "ch_poisson_blend: ",
+                  [&] { return chk::poisson_blend_batch(source, target, mask, out, B, H, W, with_gamma, max_iters, rel_tol, h->blend_ws, iters, hs(stream)); });
 }
 
 int ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target, const uint8_t* mask, uint8_t* out, int H, int W,
@@ -326,14 +338,25 @@ int ch_poisson_blend(ch_handle* h, const uint8_t* source, const uint8_t* target,
 
 size_t ch_mask_warp_workspace_bytes(int B) { return chk::mask_warp_workspace_bytes(B); }
 
+namespace {
+// the checks ch_mask_warp_batch and ch_mask_warp_batch_dev share; `fn` names the entry point in the messages
+int mask_warp_precheck(const char* fn, ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
+                       const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, const uint8_t* labels_out, const void* workspace,
+                       size_t workspace_bytes, int B) {
+    if (!h) return CH_ERR_ARG;
+    const std::string f = std::string(fn) + ": ";
+    if (!hair_labels || !face_labels || !V || !F || !desc || !labels_out || !workspace || B < 1 || B > 65535 || (!U_in && (!b || !bc)))
+        return fail(h, CH_ERR_ARG, f + "bad argument");
+    return workspace_short(h, f.c_str(), workspace_bytes, chk::mask_warp_workspace_bytes(B), "ch_mask_warp_workspace_bytes(B)");
+}
+}  // namespace
+
 int ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
                        const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out, float* uv_out,
                        float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!hair_labels || !face_labels || !V || !F || !desc || !labels_out || !workspace || B < 1 || B > 65535 || (!U_in && (!b || !bc)))
-        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch: bad argument");
-    if (workspace_bytes < chk::mask_warp_workspace_bytes(B))
-        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch: workspace smaller than ch_mask_warp_workspace_bytes(B)");
+    if (int rc = mask_warp_precheck("ch_mask_warp_batch", h, hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, workspace,
+                                    workspace_bytes, B))
+        return rc;
     for (int i = 0; i < B; ++i) {
         const int32_t* d = desc + 6 * i;
         if (d[0] < 0 || d[2] < 0 || d[4] < 0 || d[5] < 0)
@@ -343,24 +366,22 @@ int ch_mask_warp_batch(ch_handle* h, const uint8_t* hair_labels, const uint8_t* 
                                            std::to_string(d[3]) + " triangles; supported: 3.." + std::to_string(chk::WARP_MAX_V) +
                                            " vertices, 1.." + std::to_string(chk::WARP_MAX_F) + " triangles");
     }
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::mask_warp_batch(hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, uv_out, U_out, workspace, B,
-                                        CH_WARP_OUTER_ITERS, CH_WARP_MAX_CG, CH_WARP_REL_TOL, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_mask_warp_batch: ") + hipGetErrorString(e));
+    return launch(h, "ch_mask_warp_batch: ", [&] {
+        return chk::mask_warp_batch(hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, uv_out, U_out, workspace, B,
+                                    CH_WARP_OUTER_ITERS, CH_WARP_MAX_CG, CH_WARP_REL_TOL, hs(stream));
+    });
 }
 
 int ch_mask_warp_batch_dev(ch_handle* h, const uint8_t* hair_labels, const uint8_t* face_labels, const float* V, const int32_t* F,
                            const int32_t* b, const float* bc, const int32_t* desc, const float* U_in, uint8_t* labels_out, float* uv_out,
                            float* U_out, void* workspace, size_t workspace_bytes, int B, ch_stream_t stream) {
-    if (!h) return CH_ERR_ARG;
-    if (!hair_labels || !face_labels || !V || !F || !desc || !labels_out || !workspace || B < 1 || B > 65535 || (!U_in && (!b || !bc)))
-        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch_dev: bad argument");
-    if (workspace_bytes < chk::mask_warp_workspace_bytes(B))
-        return fail(h, CH_ERR_ARG, "ch_mask_warp_batch_dev: workspace smaller than ch_mask_warp_workspace_bytes(B)");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::mask_warp_batch_dev(hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, uv_out, U_out, workspace, B,
-                                            CH_WARP_OUTER_ITERS, CH_WARP_MAX_CG, CH_WARP_REL_TOL, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_mask_warp_batch_dev: ") + hipGetErrorString(e));
+    if (int rc = mask_warp_precheck("ch_mask_warp_batch_dev", h, hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, workspace,
+                                    workspace_bytes, B))
+        return rc;
+    return launch(h, "ch_mask_warp_batch_dev: ", [&] {
+        return chk::mask_warp_batch_dev(hair_labels, face_labels, V, F, b, bc, desc, U_in, labels_out, uv_out, U_out, workspace, B,
+                                        CH_WARP_OUTER_ITERS, CH_WARP_MAX_CG, CH_WARP_REL_TOL, hs(stream));
+    });
 }
 
 size_t ch_delaunay_workspace_bytes(int B) { return chk::delaunay_workspace_bytes(B); }
@@ -370,17 +391,15 @@ int ch_delaunay_batch(ch_handle* h, const float* V, const int32_t* v_desc, int32
     if (!h) return CH_ERR_ARG;
     if (!V || !v_desc || !F || !n_f || !status || !workspace || B < 1 || B > 65535)
         return fail(h, CH_ERR_ARG, "ch_delaunay_batch: bad argument");
-    if (workspace_bytes < chk::delaunay_workspace_bytes(B))
-        return fail(h, CH_ERR_ARG, "ch_delaunay_batch: workspace smaller than ch_delaunay_workspace_bytes(B)");
+    if (int rc = workspace_short(h, "ch_delaunay_batch: ", workspace_bytes, chk::delaunay_workspace_bytes(B), "ch_delaunay_workspace_bytes(B)"))
+        return rc;
     for (int i = 0; i < B; ++i)
         if (v_desc[2 * i] < 0) return fail(h, CH_ERR_ARG, "ch_delaunay_batch: negative offset in v_desc[" + std::to_string(i) + "]");
     static_assert(CH_DELAUNAY_OK == chk::DELAUNAY_OK && CH_DELAUNAY_BAD_COUNT == chk::DELAUNAY_BAD_COUNT &&
                       CH_DELAUNAY_OFF_GRID == chk::DELAUNAY_OFF_GRID && CH_DELAUNAY_DUPLICATE == chk::DELAUNAY_DUPLICATE &&
                       CH_DELAUNAY_COLLINEAR == chk::DELAUNAY_COLLINEAR && CH_DELAUNAY_INTERNAL == chk::DELAUNAY_INTERNAL,
                   "status codes of the header and of delaunay.hip");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::delaunay_batch(V, v_desc, F, n_f, status, workspace, B, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_delaunay_batch: ") + hipGetErrorString(e));
+    return launch(h, "ch_delaunay_batch: ", [&] { return chk::delaunay_batch(V, v_desc, F, n_f, status, workspace, B, hs(stream)); });
 }
 
 size_t ch_resample_lanczos_workspace_bytes(int Hs, int Ws, int C, int Hd, int Wd) {
@@ -393,11 +412,11 @@ int ch_resample_lanczos_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, int
     if (!h) return CH_ERR_ARG;
     if (!src || !dst || !workspace || !align_dims_ok(Hs, Ws) || !align_dims_ok(Hd, Wd) || C < 1 || C > 4)
         return fail(h, CH_ERR_ARG, "ch_resample_lanczos_u8: bad argument");
-    if (workspace_bytes < chk::lanczos_workspace_bytes(Hs, Ws, C, Hd, Wd))
-        return fail(h, CH_ERR_ARG, "ch_resample_lanczos_u8: workspace smaller than ch_resample_lanczos_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::lanczos_resample_u8(h->align_cache, src, (long long)Ws * C, Hs, Ws, C, dst, Hd, Wd, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_resample_lanczos_u8: ") + hipGetErrorString(e));
+    const size_t need = chk::lanczos_workspace_bytes(Hs, Ws, C, Hd, Wd);
+    if (int rc = workspace_short(h, "ch_resample_lanczos_u8: ", workspace_bytes, need, "ch_resample_lanczos_workspace_bytes")) return rc;
+    return launch(h, "ch_resample_lanczos_u8: ", [&] {
+        return chk::lanczos_resample_u8(h->align_cache, src, (long long)Ws * C, Hs, Ws, C, dst, Hd, Wd, workspace, hs(stream));
+    });
 }
 
 size_t ch_quad_warp_workspace_bytes(int T, int S) {
@@ -412,11 +431,11 @@ int ch_quad_warp_resample_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, c
         return fail(h, CH_ERR_ARG, "ch_quad_warp_resample_u8: bad argument");
     for (int i = 0; i < 8; ++i)
         if (!std::isfinite(coef[i])) return fail(h, CH_ERR_ARG, "ch_quad_warp_resample_u8: quad coefficient is not finite");
-    if (workspace_bytes < chk::quad_warp_workspace_bytes(T, S))
-        return fail(h, CH_ERR_ARG, "ch_quad_warp_resample_u8: workspace smaller than ch_quad_warp_workspace_bytes(T, S)");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::quad_warp_resample_u8(h->align_cache, src, (long long)Ws * 3, Hs, Ws, coef, T, S, dst, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_quad_warp_resample_u8: ") + hipGetErrorString(e));
+    const size_t need = chk::quad_warp_workspace_bytes(T, S);
+    if (int rc = workspace_short(h, "ch_quad_warp_resample_u8: ", workspace_bytes, need, "ch_quad_warp_workspace_bytes(T, S)")) return rc;
+    return launch(h, "ch_quad_warp_resample_u8: ", [&] {
+        return chk::quad_warp_resample_u8(h->align_cache, src, (long long)Ws * 3, Hs, Ws, coef, T, S, dst, workspace, hs(stream));
+    });
 }
 
 size_t ch_align_pad_workspace_bytes(int Hs, int Ws, const int32_t* pads, int radius) {
@@ -433,10 +452,10 @@ int ch_align_pad_feather_u8(ch_handle* h, const uint8_t* src, int Hs, int Ws, co
         return fail(h, CH_ERR_ARG, "ch_align_pad_feather_u8: bad argument (pads must be >= 1)");
     const size_t need = ch_align_pad_workspace_bytes(Hs, Ws, pads, radius);
     if (need == 0) return fail(h, CH_ERR_ARG, "ch_align_pad_feather_u8: padded size out of range");
-    if (workspace_bytes < need) return fail(h, CH_ERR_ARG, "ch_align_pad_feather_u8: workspace smaller than ch_align_pad_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::align_pad_feather_u8(src, (long long)Ws * 3, Hs, Ws, pads, gauss_w, radius, dst, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_align_pad_feather_u8: ") + hipGetErrorString(e));
+    if (int rc = workspace_short(h, "ch_align_pad_feather_u8: ", workspace_bytes, need, "ch_align_pad_workspace_bytes")) return rc;
+    return launch(h, "ch_align_pad_feather_u8: ", [&] {
+        return chk::align_pad_feather_u8(src, (long long)Ws * 3, Hs, Ws, pads, gauss_w, radius, dst, workspace, hs(stream));
+    });
 }
 
 size_t ch_face_align_workspace_bytes(int H, int W, const double* plan, int radius) {
@@ -454,11 +473,9 @@ int ch_face_align(ch_handle* h, const uint8_t* src, int H, int W, const double* 
     const std::string why = parse_plan(plan, H, W, p);
     if (!why.empty()) return fail(h, CH_ERR_ARG, "ch_face_align: " + why);
     if (p.do_pad && !gauss_w) return fail(h, CH_ERR_ARG, "ch_face_align: the plan pads but gauss_w is null");
-    if (workspace_bytes < chk::face_align_workspace_bytes(H, W, p, radius) + 256)
-        return fail(h, CH_ERR_ARG, "ch_face_align: workspace smaller than ch_face_align_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::face_align(h->align_cache, src, H, W, p, gauss_w, radius, dst, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_align: ") + hipGetErrorString(e));
+    const size_t need = chk::face_align_workspace_bytes(H, W, p, radius) + 256;
+    if (int rc = workspace_short(h, "ch_face_align: ", workspace_bytes, need, "ch_face_align_workspace_bytes")) return rc;
+    return launch(h, "ch_face_align: ", [&] { return chk::face_align(h->align_cache, src, H, W, p, gauss_w, radius, dst, workspace, hs(stream)); });
 }
 
 // ---- paste-back (face_unalign.hip, face_matte.hip) ------------------------------------------------------------------------------------
@@ -468,9 +485,7 @@ int ch_face_unalign(ch_handle* h, const uint8_t* photo, int H, int W, const uint
     chk::UnalignPlan p;
     const std::string why = parse_unalign(photo, H, W, edits, N, plan, feather_px, out, p);
     if (!why.empty()) return fail(h, CH_ERR_ARG, "ch_face_unalign: " + why);
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::face_unalign(photo, edits, weight, p, H, W, N, feather_px, out, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_unalign: ") + hipGetErrorString(e));
+    return launch(h, "ch_face_unalign: ", [&] { return chk::face_unalign(photo, edits, weight, p, H, W, N, feather_px, out, hs(stream)); });
 }
 
 size_t ch_face_unalign_matte_workspace_bytes(int H, int W, const double* plan, int radius) {
@@ -495,13 +510,11 @@ int ch_face_unalign_matte(ch_handle* h, const uint8_t* photo, int H, int W, cons
     if (!(eps > 0.0) || !std::isfinite(eps)) return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: eps must be positive and finite");
     if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
         return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: workspace is null or not 256-byte aligned");
-    if (workspace_bytes < chk::face_matte_workspace_bytes(p.x1 - p.x0, p.y1 - p.y0))
-        return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: workspace smaller than ch_face_unalign_matte_workspace_bytes");
+    const size_t need = chk::face_matte_workspace_bytes(p.x1 - p.x0, p.y1 - p.y0);
+    if (int rc = workspace_short(h, "ch_face_unalign_matte: ", workspace_bytes, need, "ch_face_unalign_matte_workspace_bytes")) return rc;
     if (reinterpret_cast<uintptr_t>(alpha_out) % 4 != 0) return fail(h, CH_ERR_ARG, "ch_face_unalign_matte: alpha_out is not 4-byte aligned");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::face_unalign_matte(photo, edits, weight, p, H, W, N, feather_px, radius, eps, out, alpha_out, workspace,
-                                           static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_face_unalign_matte: ") + hipGetErrorString(e));
+    return launch(h, "ch_face_unalign_matte: ",
+                  [&] { return chk::face_unalign_matte(photo, edits, weight, p, H, W, N, feather_px, radius, eps, out, alpha_out, workspace, hs(stream)); });
 }
 
 // ---- median style codes (style_medoid.hip) ---------------------------------------------------------------------------------------
@@ -527,11 +540,9 @@ int ch_style_medoid(ch_handle* h, const float* codes, const int64_t* seg_offsets
         return fail(h, CH_ERR_ARG, "ch_style_medoid: bad argument (dim a multiple of 4, seg_offsets ascending from 0, n_split >= 0)");
     if (!index || !mean || !workspace || (!codes && seg_offsets[R] > 0) || (reinterpret_cast<uintptr_t>(codes) & 15))
         return fail(h, CH_ERR_ARG, "ch_style_medoid: null output or workspace, or codes not 16-byte aligned");
-    if (workspace_bytes < chk::style_medoid_workspace_bytes(seg_offsets, R, n_split))
-        return fail(h, CH_ERR_ARG, "ch_style_medoid: workspace smaller than ch_style_medoid_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::style_medoid(codes, seg_offsets, R, dim, n_split, index, sums, mean, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_style_medoid: ") + hipGetErrorString(e));
+    const size_t need = chk::style_medoid_workspace_bytes(seg_offsets, R, n_split);
+    if (int rc = workspace_short(h, "ch_style_medoid: ", workspace_bytes, need, "ch_style_medoid_workspace_bytes")) return rc;
+    return launch(h, "ch_style_medoid: ", [&] { return chk::style_medoid(codes, seg_offsets, R, dim, n_split, index, sums, mean, workspace, hs(stream)); });
 }
 
 int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, int Hs, int Ws, int C, int Hd, int Wd,
@@ -539,9 +550,7 @@ int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, i
     if (!h) return CH_ERR_ARG;
     if (!src || !dst || B < 1 || B > 65535 || Hs < 1 || Ws < 1 || C < 1 || C > 4 || Hd < 1 || Hd > 65535 || Wd < 1)
         return fail(h, CH_ERR_ARG, "ch_resize_linear_u8: bad argument");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::resize_linear_u8(src, dst, B, Hs, Ws, C, Hd, Wd, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_resize_linear_u8: ") + hipGetErrorString(e));
+    return launch(h, "ch_resize_linear_u8: ", [&] { return chk::resize_linear_u8(src, dst, B, Hs, Ws, C, Hd, Wd, hs(stream)); });
 }
 
 int ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, int label, int ksize, uint8_t* mask, int H, int W,
@@ -558,9 +567,7 @@ int ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, in
     const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
     for (int dy = -r; dy <= r; ++dy)
         rows.hw[dy + r] = (int)std::nearbyint(r * std::sqrt(((double)r * r - (double)dy * dy) * inv_r2));
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::hair_erode(labels, B, Hl, Wl, label, rows, mask, H, W, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_hair_erode: ") + hipGetErrorString(e));
+    return launch(h, "ch_hair_erode: ", [&] { return chk::hair_erode(labels, B, Hl, Wl, label, rows, mask, H, W, hs(stream)); });
 }
 
 int ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums, ch_stream_t stream) {
@@ -568,9 +575,7 @@ int ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, i
     if (!img || !mask || !sums || B < 1 || B > 65535 || H < 1 || W < 1) return fail(h, CH_ERR_ARG, "ch_hair_color_stats: bad argument");
     if ((int64_t)H * W > INT64_MAX / (255LL * 255 * 255 * 255))
         return fail(h, CH_ERR_ARG, "ch_hair_color_stats: H * W too large for exact int64 sums of c^4");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::hair_color_stats(img, mask, B, H, W, sums, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_hair_color_stats: ") + hipGetErrorString(e));
+    return launch(h, "ch_hair_color_stats: ", [&] { return chk::hair_color_stats(img, mask, B, H, W, sums, hs(stream)); });
 }
 
 int ch_sheet_compose(ch_handle* h, const void* src, int kind, int n, int Hs, int Ws, const int32_t* cells, const uint8_t* lut, uint8_t* canvas,
@@ -583,9 +588,8 @@ int ch_sheet_compose(ch_handle* h, const void* src, int kind, int n, int Hs, int
         return fail(h, CH_ERR_ARG, "ch_sheet_compose: sizes must be positive (margin >= 0)");
     if ((int64_t)rows * H > INT32_MAX || (int64_t)cols * ((int64_t)W + margin) * 3 > INT32_MAX || (int64_t)Hs * Ws > INT32_MAX)
         return fail(h, CH_ERR_ARG, "ch_sheet_compose: sheet or source too large");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::sheet_compose(src, kind, n, Hs, Ws, cells, lut, canvas, rows, cols, H, W, margin, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_sheet_compose: ") + hipGetErrorString(e));
+    return launch(h, "ch_sheet_compose: ",
+                  [&] { return chk::sheet_compose(src, kind, n, Hs, Ws, cells, lut, canvas, rows, cols, H, W, margin, hs(stream)); });
 }
 
 int ch_sweep_stats(ch_handle* h, const void* img, int kind, const uint8_t* labels, const int32_t* ref, int N, int H, int W, int lh, int lw,
@@ -597,9 +601,7 @@ int ch_sweep_stats(ch_handle* h, const void* img, int kind, const uint8_t* label
     if (H < 1 || W < 1 || lh < 1 || lw < 1) return fail(h, CH_ERR_ARG, "ch_sweep_stats: sizes must be positive");
     if (H > 32768 || W > 32768 || (int64_t)H * W > (1 << 30) || (int64_t)lh * lw > (1 << 30))
         return fail(h, CH_ERR_ARG, "ch_sweep_stats: image or label map too large (sides <= 32768, H * W <= 2^30)");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::sweep_stats(img, kind, labels, ref, N, H, W, lh, lw, stats, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_sweep_stats: ") + hipGetErrorString(e));
+    return launch(h, "ch_sweep_stats: ", [&] { return chk::sweep_stats(img, kind, labels, ref, N, H, W, lh, lw, stats, hs(stream)); });
 }
 
 // ---- PNG encoding (png_encode.hip) -----------------------------------------------------------------------------------------------
@@ -636,11 +638,9 @@ int png_encode_checked(const char* fn, ch_handle* h, const uint8_t* img, int N, 
             if (dist[j] == dist[k]) return fail(h, CH_ERR_ARG, f + "duplicate distance");
     }
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
-    if (workspace_bytes < chk::png_encode_workspace_bytes(N, H, W, C))
-        return fail(h, CH_ERR_ARG, f + "workspace smaller than ch_png_encode_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::png_encode_dist(img, N, H, W, C, filter, dist, ndist, out, sizes, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, f + hipGetErrorString(e));
+    if (int rc = workspace_short(h, f.c_str(), workspace_bytes, chk::png_encode_workspace_bytes(N, H, W, C), "ch_png_encode_workspace_bytes"))
+        return rc;
+    return launch(h, f.c_str(), [&] { return chk::png_encode_dist(img, N, H, W, C, filter, dist, ndist, out, sizes, workspace, hs(stream)); });
 }
 }  // namespace
 
@@ -673,11 +673,9 @@ int ch_png_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, 
     if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, f + "N outside 1..65535");
     if (!png_dims_ok(H, W, C)) return fail(h, CH_ERR_ARG, f + "C must be 1, 3 or 4, sides 1..32768, H * W <= 2^30");
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
-    if (workspace_bytes < chk::png_decode_workspace_bytes(N, H, W, C))
-        return fail(h, CH_ERR_ARG, f + "workspace smaller than ch_png_decode_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::png_decode(streams, offsets, N, H, W, C, img, status, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, f + hipGetErrorString(e));
+    if (int rc = workspace_short(h, f.c_str(), workspace_bytes, chk::png_decode_workspace_bytes(N, H, W, C), "ch_png_decode_workspace_bytes"))
+        return rc;
+    return launch(h, f.c_str(), [&] { return chk::png_decode(streams, offsets, N, H, W, C, img, status, workspace, hs(stream)); });
 }
 
 // ---- JPEG encoding (jpeg_encode.hip) ---------------------------------------------------------------------------------------------------
@@ -707,11 +705,9 @@ int ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C,
     if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, f + "N outside 1..65535");
     if (!jpeg_dims_ok(H, W, C, subsampling)) return fail(h, CH_ERR_ARG, f + "image too small or too large (sides 1..32768, H * W <= 2^30)");
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
-    if (workspace_bytes < chk::jpeg_encode_workspace_bytes(N, H, W, C, subsampling))
-        return fail(h, CH_ERR_ARG, f + "workspace smaller than ch_jpeg_encode_workspace_bytes");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::jpeg_encode(img, N, H, W, C, quality, subsampling, out, sizes, workspace, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, f + hipGetErrorString(e));
+    const size_t need = chk::jpeg_encode_workspace_bytes(N, H, W, C, subsampling);
+    if (int rc = workspace_short(h, f.c_str(), workspace_bytes, need, "ch_jpeg_encode_workspace_bytes")) return rc;
+    return launch(h, f.c_str(), [&] { return chk::jpeg_encode(img, N, H, W, C, quality, subsampling, out, sizes, workspace, hs(stream)); });
 }
 
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {
@@ -846,9 +842,7 @@ int ch_set_option(ch_handle* h, const char* key, int value) {
 
 int ch_mfma_peak(ch_handle* h, int kind, int ms_target, double* tflops) {
     if (!h || !tflops || kind < 0 || kind > 1 || ms_target < 1 || ms_target > 2000) return fail(h, CH_ERR_ARG, "ch_mfma_peak: bad argument");
-    DeviceGuard guard(h->device);
-    hipError_t e = chk::mfma_peak(kind, ms_target, tflops, nullptr);
-    return e == hipSuccess ? CH_OK : fail(h, CH_ERR_HIP, std::string("ch_mfma_peak: ") + hipGetErrorString(e));
+    return launch(h, "ch_mfma_peak: ", [&] { return chk::mfma_peak(kind, ms_target, tflops, nullptr); });
 }
 
 int ch_profile_enable(ch_handle* h, int on) {

@@ -25,6 +25,7 @@ import torch
 
 from . import hostutil as U
 from . import lib as _lib
+from .devop import DeviceOp
 
 NSTAT = 16                          # CH_SWEEP_STATS
 DIMS = {'shape': 16, 'texture': 8}  # shape_branch/config.py hair_dim, color_texture_branch/config.py noise_dim
@@ -69,10 +70,6 @@ def mask_lut(draw_type: int) -> np.ndarray:
 
 
 # ---- device side ---------------------------------------------------------------------------------------------------------------
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _image_kind(t: torch.Tensor, what: str) -> int:
     if t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == 3:
         return KIND_FLOAT
@@ -89,12 +86,11 @@ def sheet_png_distances(cols: int, W: int, margin: int) -> tuple:
     return (pitch,) if cols > 1 and pitch <= 32767 else ()
 
 
-class ContactSheet:
+class ContactSheet(DeviceOp):
     """util/canvas_grid.py Canvas on the device: uint8 [rows * H, cols * W + margin * (cols - 1), 3], filled with 255."""
 
     def __init__(self, handle: _lib.Handle, device, rows: int, cols: int, cell, margin: int = 0):
-        self.handle = handle
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        super().__init__(handle, device)
         self.H, self.W = (int(cell), int(cell)) if isinstance(cell, (int, np.integer)) else (int(cell[0]), int(cell[1]))
         self.rows, self.cols, self.margin = int(rows), int(cols), int(margin)
         if min(self.rows, self.cols, self.H, self.W) < 1 or self.margin < 0:
@@ -136,7 +132,7 @@ class ContactSheet:
         cells_dev = torch.from_numpy(cells.astype(np.int32)).to(self.device)
         self.handle.call('ch_sheet_compose', src.data_ptr(), kind, n, Hs, Ws, cells_dev.data_ptr(),
                          lut.data_ptr() if lut is not None else None, self.canvas.data_ptr(), self.rows, self.cols, self.H, self.W,
-                         self.margin, _stream(self.device))
+                         self.margin, self._stream())
         return self
 
     def numpy(self) -> np.ndarray:
@@ -147,12 +143,8 @@ class ContactSheet:
         return sheet_png_distances(self.cols, self.W, self.margin)
 
 
-class SweepStats:
+class SweepStats(DeviceOp):
     """ch_sweep_stats on one ch_handle: exact per-render measurements (column layout: include/ctrlhair_hip.h, CH_SWEEP_STATS)."""
-
-    def __init__(self, handle: _lib.Handle, device):
-        self.handle = handle
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
 
     def measure(self, images: torch.Tensor, labels: torch.Tensor, ref) -> torch.Tensor:
         """images float32 [N,3,H,W] in [-1,1] or uint8 [N,H,W,3]; labels uint8 [N,h,w] (nearest-mapped to H x W); ref: per render
@@ -175,7 +167,7 @@ class SweepStats:
         images, labels = images.to(self.device).contiguous(), labels.to(self.device).contiguous()
         out = torch.empty(N, NSTAT, dtype=torch.int64, device=self.device)
         self.handle.call('ch_sweep_stats', images.data_ptr(), kind, labels.data_ptr(), ref_dev.data_ptr(), N, H, W,
-                         int(labels.shape[1]), int(labels.shape[2]), out.data_ptr(), _stream(self.device))
+                         int(labels.shape[1]), int(labels.shape[2]), out.data_ptr(), self._stream())
         return out
 
 

@@ -16,6 +16,8 @@ from typing import List, Sequence
 
 import numpy as np
 
+from .devop import DeviceOp
+
 JPEG_MODES = ('host', 'device')
 SUBSAMPLINGS = (0, 2)                     # Pillow's numbering: 0 = 4:4:4, 2 = 4:2:0
 SUBSAMPLING_NAMES = {'444': 0, '420': 2}  # the command line's names
@@ -100,22 +102,8 @@ def wrap_jpeg(scan: bytes, H: int, W: int, C: int, quality: int = 75, subsamplin
     return b''.join(parts)
 
 
-class JpegEncoder:
+class JpegEncoder(DeviceOp):
     """ch_jpeg_encode on one ch_handle.  No CPU fallback: the constructor needs the library and a GPU."""
-
-    def __init__(self, handle, device):
-        import torch
-        self.handle = handle
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
-        self._ws = self._out = self._pinned = None
-
-    def _grown(self, name: str, need: int, **kw):
-        import torch
-        buf = getattr(self, name)
-        if buf is None or buf.numel() < need:
-            buf = torch.empty(max(need, 256), dtype=torch.uint8, **kw)
-            setattr(self, name, buf)
-        return buf
 
     @staticmethod
     def _shape(images):
@@ -140,21 +128,11 @@ class JpegEncoder:
         bound, need = int(lib.ch_jpeg_scan_bound(H, W, C, subsampling)), int(lib.ch_jpeg_encode_workspace_bytes(N, H, W, C, subsampling))
         if bound == 0 or need == 0:
             raise ValueError(f'JpegEncoder: ch_jpeg_encode rejects N={N}, H={H}, W={W} (sides 1..32768, H * W <= 2^30, N <= 65535)')
-        ws, out = self._grown('_ws', need, device=self.device), self._grown('_out', N * bound, device=self.device)
+        ws, out = self._buffer('_ws', need), self._buffer('_out', N * bound)
         sizes = torch.empty(N, dtype=torch.int64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         self.handle.call('ch_jpeg_encode', x.data_ptr(), N, H, W, C, quality, subsampling, out.data_ptr(), sizes.data_ptr(), ws.data_ptr(),
-                         ws.numel(), stream)
-        lens = [int(v) for v in sizes.cpu()]                                   # download 1 (synchronises)
-        if any(v < 1 or v > bound for v in lens):
-            raise RuntimeError(f'ch_jpeg_encode returned scan lengths {lens} outside 1..{bound}')
-        packed = out[:lens[0]] if N == 1 else torch.cat([out[n * bound:n * bound + lens[n]] for n in range(N)])
-        total = sum(lens)
-        stage = self._grown('_pinned', total, pin_memory=True)
-        stage[:total].copy_(packed)                                            # download 2: exactly the compressed bytes
-        raw = stage[:total].numpy().tobytes()
-        offs = np.concatenate([[0], np.cumsum(lens)])
-        return [raw[offs[n]:offs[n + 1]] for n in range(N)]
+                         ws.numel(), self._stream())
+        return self._fetch_ragged(out, bound, sizes, 1, 'ch_jpeg_encode returned scan lengths')
 
     def encode(self, images, quality: int = 75, subsampling: int = 2) -> List[bytes]:
         """uint8 device tensor [N,H,W,C] or [N,H,W] -> N whole JPEG files (bytes)."""

@@ -15,6 +15,7 @@ import torch
 
 from . import hostutil as U
 from . import lib as _lib
+from .devop import DeviceOp
 
 HAIR_IDX = 13   # global_value_utils.py:52
 
@@ -22,10 +23,6 @@ HAIR_IDX = 13   # global_value_utils.py:52
 def _np(v):
     a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
     return a if a.dtype in (np.float32, np.int64) else a.astype(np.float32)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 # ---- shape_branch/shape_util.py -------------------------------------------------------------------------------------
@@ -51,11 +48,8 @@ def split_hair_face(mask: torch.Tensor):
     return mask[:, [HAIR_IDX]], torch.cat([mask[:, :HAIR_IDX], mask[:, HAIR_IDX + 1:]], dim=1)
 
 
-class ShapeGenerator:
+class ShapeGenerator(DeviceOp):
     """shape_branch/model.py::Generator (inference methods :164-199) on the HIP library."""
-
-    def __init__(self, handle: _lib.Handle, device: torch.device):
-        self.handle, self.device = handle, device
 
     def load_state_dict(self, sd: Dict[str, object], max_batch: int = 4, f16x3: bool = True):
         """f16x3: the decoder's 3x3 convs from 4x4 resolution up on the split-operand f16 MFMA kernels (f32-class; default) or,
@@ -75,7 +69,7 @@ class ShapeGenerator:
         B = labels.shape[0]
         hair = torch.empty(B, 16, device=labels.device)
         face = torch.empty(B, 1024, device=labels.device)
-        self.handle.call('ch_shape_encode', labels.data_ptr(), hair.data_ptr(), face.data_ptr(), B, _stream(labels.device))
+        self.handle.call('ch_shape_encode', labels.data_ptr(), hair.data_ptr(), face.data_ptr(), B, self._stream())
         return hair, face
 
     def forward_hair_encoder(self, hair: torch.Tensor, testing: bool = False):
@@ -86,7 +80,7 @@ class ShapeGenerator:
         lab = lab.to(torch.uint8).contiguous()
         B = lab.shape[0]
         out = torch.empty(B, 16, device=hair.device)
-        self.handle.call('ch_shape_encode', lab.data_ptr(), out.data_ptr(), None, B, _stream(hair.device))
+        self.handle.call('ch_shape_encode', lab.data_ptr(), out.data_ptr(), None, B, self._stream())
         return out
 
     def forward_face_encoder(self, face: torch.Tensor):
@@ -96,7 +90,7 @@ class ShapeGenerator:
         lab = torch.where(mx > 0.5, idx, torch.full_like(idx, 255)).to(torch.uint8).contiguous()
         B = lab.shape[0]
         out = torch.empty(B, 1024, device=face.device)
-        self.handle.call('ch_shape_encode', lab.data_ptr(), None, out.data_ptr(), B, _stream(face.device))
+        self.handle.call('ch_shape_encode', lab.data_ptr(), None, out.data_ptr(), B, self._stream())
         return out
 
     def _decode(self, hair_code, face_code, want_hair=False, want_face=False, want_labels=False, want_probs=False):
@@ -108,7 +102,7 @@ class ShapeGenerator:
         lab = torch.empty(B, 256, 256, dtype=torch.uint8, device=dev) if (want_labels or want_probs) else None
         pr = torch.empty(B, 19, 256, 256, device=dev) if want_probs else None
         p = lambda t: t.data_ptr() if t is not None else None
-        self.handle.call('ch_shape_decode', p(hc), face_code.data_ptr(), p(hl), p(fl), p(lab), p(pr), B, _stream(dev))
+        self.handle.call('ch_shape_decode', p(hc), face_code.data_ptr(), p(hl), p(fl), p(lab), p(pr), B, self._stream())
         return hl, fl, lab, pr
 
     def forward_hair_decoder(self, hair_code, face_code):
@@ -124,7 +118,7 @@ class ShapeGenerator:
         lab = torch.empty(B, 256, 256, dtype=torch.uint8, device=dev)
         pr = torch.empty(B, 19, 256, 256, device=dev)
         self.handle.call('ch_shape_combine', hair_logit.data_ptr(), face_logit.data_ptr(), lab.data_ptr(), pr.data_ptr(), B,
-                         _stream(dev))
+                         self._stream())
         return pr
 
     def forward_decode_by_code(self, hair_code, face_code):
@@ -146,11 +140,11 @@ class _Callable:
         return self
 
 
-class ColorTextureModels:
+class ColorTextureModels(DeviceOp):
     """color_texture_branch/solver.py::Solver(training=False): .gen, .dis, .rgb_model callables + edit_infer."""
 
     def __init__(self, handle: _lib.Handle, device: torch.device):
-        self.handle, self.device = handle, device
+        super().__init__(handle, device)
         self.gen = _Callable(self._gen)
         self.dis = _Callable(self._dis)
         self.rgb_model = _Callable(self._rgb)
@@ -173,21 +167,21 @@ class ColorTextureModels:
         cond = torch.cat([self._f(data['noise_curliness']), self._f(data['rgb_mean']), self._f(data['pca_std'])], dim=1).contiguous()
         B = noise.shape[0]
         code = torch.empty(B, 512, device=self.device)
-        self.handle.call('ch_color_generate', noise.data_ptr(), cond.data_ptr(), code.data_ptr(), B, _stream(self.device))
+        self.handle.call('ch_color_generate', noise.data_ptr(), cond.data_ptr(), code.data_ptr(), B, self._stream())
         return {'code': code}
 
     def _dis(self, data):      # Discriminator.forward, model.py:108-127 (cfg 045 slices)
         code = self._f(data['code'])
         B = code.shape[0]
         out = torch.empty(B, 11, device=self.device)
-        self.handle.call('ch_color_encode', code.data_ptr(), out.data_ptr(), B, _stream(self.device))
+        self.handle.call('ch_color_encode', code.data_ptr(), out.data_ptr(), B, self._stream())
         return {'adv': out[:, 0:1], 'noise': out[:, 1:9], 'noise_curliness': out[:, 9:10]}     # slices only: a list index is an H2D copy
 
     def _rgb(self, data):      # Predictor.forward, predictor_model.py:32-41 (predict_dict: rgb_mean 3, pca_std 1)
         code = self._f(data['code'])
         B = code.shape[0]
         out = torch.empty(B, 4, device=self.device)
-        self.handle.call('ch_color_predict', code.data_ptr(), out.data_ptr(), B, _stream(self.device))
+        self.handle.call('ch_color_predict', code.data_ptr(), out.data_ptr(), B, self._stream())
         return {'rgb_mean': out[:, 0:3], 'pca_std': out[:, 3:4]}
 
     def edit_infer(self, hair_code, data):     # solver.py:78-83
@@ -204,13 +198,10 @@ _MEAN = (0.485, 0.456, 0.406)     # my_parsing_util.py:27
 _STD = (0.229, 0.224, 0.225)
 
 
-class FaceParsing:
+class FaceParsing(DeviceOp):
     """external_code/face_parsing/my_parsing_util.py::FaceParsing with the network on the HIP library.
     Unlike the reference's class-level lazy singleton (:24,38-44) an instance owns its handle; `parsing_img` and
     `swap_parsing_label_to_celeba_mask` keep the reference's signatures."""
-
-    def __init__(self, handle: _lib.Handle, device: torch.device):
-        self.handle, self.device = handle, device
 
     def load_state_dict(self, sd: Dict[str, object], max_batch: int = 8, max_size: int = 512, f16x3: bool = True):
         """f16x3: the stride-1 convs on the split-operand f16 MFMA kernels (f32-class; default) or, False, every conv on the
@@ -230,7 +221,7 @@ class FaceParsing:
         lab = torch.empty(B, H, W, dtype=torch.uint8, device=img.device)
         lg = torch.empty(B, 19, H, W, device=img.device) if want_logits else None
         self.handle.call('ch_bisenet_parse', img.data_ptr(), lab.data_ptr(), lg.data_ptr() if want_logits else None, B, H, W,
-                         _stream(img.device))
+                         self._stream())
         return lab, lg
 
     def normalise(self, img_u8_hwc: np.ndarray) -> torch.Tensor:

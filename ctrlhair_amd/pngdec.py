@@ -16,6 +16,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
+from .devop import DeviceOp
 from .pngenc import PNG_SIGNATURE
 
 CHANNELS = {0: 1, 2: 3, 6: 4}             # PNG colour type -> channels, bit depth 8
@@ -79,23 +80,12 @@ def parse_png(data: bytes) -> Tuple[int, int, int, bytes]:
     return H, W, CHANNELS[colour], b''.join(idat)
 
 
-class PngDecoder:
+class PngDecoder(DeviceOp):
     """ch_png_decode on one ch_handle.  The constructor needs the library and a GPU; the Pillow fallback is per FILE (see the module)."""
 
     def __init__(self, handle, device):
-        import torch
-        self.handle = handle
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        super().__init__(handle, device)
         self.fallbacks = 0
-        self._ws = self._in = self._pinned = None
-
-    def _grown(self, name: str, need: int, **kw):
-        import torch
-        buf = getattr(self, name)
-        if buf is None or buf.numel() < need:
-            buf = torch.empty(max(need, 256), dtype=torch.uint8, **kw)
-            setattr(self, name, buf)
-        return buf
 
     def upload(self, streams: Sequence[bytes]):
         """N zlib streams -> (device buffer, where the streams start in it, N): one buffer -- the offsets table, then (from a multiple of
@@ -105,11 +95,11 @@ class PngDecoder:
         np.cumsum([len(z) for z in streams], out=offs[1:])
         data_at = 8 * (N + 1) + (-8 * (N + 1)) % _ALIGN
         total = data_at + max(int(offs[N]), 1)
-        stage = self._grown('_pinned', total, pin_memory=True)
+        stage = self._buffer('_pinned', total, pinned=True)
         host = stage[:total].numpy()
         host[:8 * (N + 1)] = np.frombuffer(offs.tobytes(), np.uint8)
         host[data_at:data_at + int(offs[N])] = np.frombuffer(b''.join(streams), np.uint8)
-        dev = self._grown('_in', total, device=self.device)
+        dev = self._buffer('_in', total)
         dev[:total].copy_(stage[:total], non_blocking=True)
         return dev, data_at, N
 
@@ -120,11 +110,11 @@ class PngDecoder:
         need = int(self.handle.lib.ch_png_decode_workspace_bytes(N, H, W, C))
         if need == 0:
             raise ValueError(f'PngDecoder: ch_png_decode rejects N={N}, H={H}, W={W}, C={C} (C 1/3/4, sides 1..32768, H * W <= 2^30, N 1..65535)')
-        ws = self._grown('_ws', need, device=self.device)
+        ws = self._buffer('_ws', need)
         img = torch.empty((N, H, W, C), dtype=torch.uint8, device=self.device)
         status = torch.empty(N, dtype=torch.int32, device=self.device)
         self.handle.call('ch_png_decode', dev.data_ptr() + data_at, dev.data_ptr(), N, H, W, C, img.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                         ws.numel(), torch.cuda.current_stream(self.device).cuda_stream)
+                         ws.numel(), self._stream())
         return img, status
 
     def decode_streams(self, streams: Sequence[bytes], H: int, W: int, C: int):

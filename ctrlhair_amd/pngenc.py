@@ -21,6 +21,8 @@ from typing import List, Sequence
 
 import numpy as np
 
+from .devop import DeviceOp
+
 ADLER_MOD = 65521
 PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
 COLOUR_TYPE = {1: 0, 3: 2, 4: 6}          # channels -> PNG colour type (grey, RGB, RGBA), bit depth 8
@@ -82,23 +84,12 @@ def wrap_png(zlib_stream: bytes, H: int, W: int, C: int) -> bytes:
     return b''.join(parts)
 
 
-class PngEncoder:
+class PngEncoder(DeviceOp):
     """ch_png_encode / ch_png_encode_dist on one ch_handle.  No CPU fallback: the constructor needs the library and a GPU."""
 
     def __init__(self, handle, device):
-        import torch
-        self.handle = handle
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        super().__init__(handle, device)
         self.chunk = int(handle.lib.ch_png_chunk_bytes())
-        self._ws = self._out = self._pinned = None
-
-    def _grown(self, name: str, need: int, **kw):
-        import torch
-        buf = getattr(self, name)
-        if buf is None or buf.numel() < need:
-            buf = torch.empty(max(need, 256), dtype=torch.uint8, **kw)
-            setattr(self, name, buf)
-        return buf
 
     def streams(self, images, filter: int = -1, distances: Sequence[int] = ()) -> List[bytes]:
         """uint8 device tensor [N,H,W,C] or [N,H,W] -> the N zlib streams (bytes).  Two downloads: the lengths, then the bytes.
@@ -121,25 +112,15 @@ class PngEncoder:
         bound, need = int(lib.ch_png_zlib_bound(H, W, C)), int(lib.ch_png_encode_workspace_bytes(N, H, W, C))
         if bound == 0 or need == 0:
             raise ValueError(f'PngEncoder: ch_png_encode rejects N={N}, H={H}, W={W} (sides 1..32768, H * W <= 2^30, N <= 65535)')
-        ws, out = self._grown('_ws', need, device=self.device), self._grown('_out', N * bound, device=self.device)
+        ws, out = self._buffer('_ws', need), self._buffer('_out', N * bound)
         sizes = torch.empty(N, dtype=torch.int64, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         if dist:
             self.handle.call('ch_png_encode_dist', x.data_ptr(), N, H, W, C, int(filter), (ctypes.c_int * len(dist))(*dist), len(dist),
-                             out.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+                             out.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
         else:
             self.handle.call('ch_png_encode', x.data_ptr(), N, H, W, C, int(filter), out.data_ptr(), sizes.data_ptr(), ws.data_ptr(),
-                             ws.numel(), stream)
-        lens = [int(v) for v in sizes.cpu()]                                   # download 1 (synchronises)
-        if any(v < 8 or v > bound for v in lens):
-            raise RuntimeError(f'ch_png_encode returned stream lengths {lens} outside 8..{bound}')
-        packed = out[:lens[0]] if N == 1 else torch.cat([out[n * bound:n * bound + lens[n]] for n in range(N)])
-        total = sum(lens)
-        stage = self._grown('_pinned', total, pin_memory=True)
-        stage[:total].copy_(packed)                                            # download 2: exactly the compressed bytes
-        raw = stage[:total].numpy().tobytes()
-        offs = np.concatenate([[0], np.cumsum(lens)])
-        return [raw[offs[n]:offs[n + 1]] for n in range(N)]
+                             ws.numel(), self._stream())
+        return self._fetch_ragged(out, bound, sizes, 8, 'ch_png_encode returned stream lengths')
 
     def encode(self, images, filter: int = -1, distances: Sequence[int] = ()) -> List[bytes]:
         """uint8 device tensor [N,H,W,C] or [N,H,W] -> N whole PNG files (bytes)."""

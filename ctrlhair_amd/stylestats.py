@@ -16,6 +16,8 @@ from typing import Optional
 
 import numpy as np
 
+from .devop import DeviceOp
+
 N_REGIONS, STYLE_LEN = 19, 512
 PACKAGED = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'mean_style_code.npz')
 NPZ_KEYS = ('mean', 'median')
@@ -112,23 +114,8 @@ def read_reference_tree(dir_name: str) -> dict:
 
 
 # ---- device side -----------------------------------------------------------------------------------------------------------------
-class StyleMedoid:
+class StyleMedoid(DeviceOp):
     """ch_style_medoid on one ch_handle.  No CPU fallback: the constructor needs the library and a GPU."""
-
-    def __init__(self, handle=None, device=None):
-        import torch
-        from . import lib as _lib
-        if device is None:
-            device = torch.device('cuda', handle.device if handle is not None else 0)
-        self.device = torch.device(device) if not isinstance(device, torch.device) else device
-        self.handle = handle if handle is not None else _lib.Handle(self.device.index or 0)
-        self._ws = None
-
-    def _workspace(self, need):
-        import torch
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def segments(self, rows, seg_offsets, n_split: int = 0, want_sums: bool = True):
         """rows float32 [total, dim] (numpy is uploaded), seg_offsets int64 [R+1] -> device tensors (index int32 [R], sums float64
@@ -144,13 +131,12 @@ class StyleMedoid:
         need = int(self.handle.lib.ch_style_medoid_workspace_bytes(op, R, dim, int(n_split)))
         if need == 0:
             raise ValueError(f'ch_style_medoid rejects R={R}, dim={dim}, n_split={n_split} (dim must be a multiple of 4)')
-        ws = self._workspace(need)
+        ws = self._buffer('_ws', need)
         index = torch.empty(R, dtype=torch.int32, device=self.device)
         sums = torch.empty(int(off[-1]), dtype=torch.float64, device=self.device) if want_sums else None
         mean = torch.empty(R, dim, dtype=torch.float32, device=self.device)
         self.handle.call('ch_style_medoid', x.data_ptr(), op, R, dim, int(n_split), index.data_ptr(),
-                         sums.data_ptr() if sums is not None else None, mean.data_ptr(), ws.data_ptr(), ws.numel(),
-                         torch.cuda.current_stream(self.device).cuda_stream)
+                         sums.data_ptr() if sums is not None else None, mean.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
         return index, sums, mean
 
     def median_style_codes(self, codes) -> dict:

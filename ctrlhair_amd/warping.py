@@ -21,7 +21,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import lib as _lib
+from .devop import DeviceOp
 
 HAIR_IDX = 13
 IMG = 512                       # the warp is defined on 512 x 512 parsings (mask_adaptor.py:121-122)
@@ -151,19 +151,11 @@ def check_mesh(V, F, b):
         raise ValueError('mesh has non-finite vertices')
 
 
-class MaskWarper:
+class MaskWarper(DeviceOp):
     """The built-in warper of Backend.transfer_latent_representation('shape') and EditPipeline.transfer_shape."""
 
     def __init__(self, handle=None, device=None):
-        import torch
-        if handle is None:
-            dev = torch.device(device) if device is not None else torch.device('cuda', 0)
-            handle = _lib.Handle(dev.index or 0)         # raises without the library or a GPU
-        self.handle = handle
-        self.device = torch.device(device) if device is not None else torch.device('cuda', handle.device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('MaskWarper runs on the GPU only (no CPU fallback exists)')
-        self._ws = self._dws = None
+        super().__init__(handle, device)
         self.last_mesh_status = self.last_mesh = None     # of the last warp_batch(mesher='device')
 
     # ---- the ABI call ---------------------------------------------------------------------------------------------------
@@ -211,12 +203,11 @@ class MaskWarper:
         out = torch.empty(B, IMG, IMG, dtype=torch.uint8, device=dev)
         uv = torch.empty(B, CANVAS, CANVAS, 2, dtype=torch.float32, device=dev) if return_uv else None
         Uout = torch.empty(vo, 2, dtype=torch.float32, device=dev) if return_U else None
-        need = int(self.handle.lib.ch_mask_warp_workspace_bytes(B))
-        self._workspace('_ws', need)
+        ws = self._buffer('_ws', int(self.handle.lib.ch_mask_warp_workspace_bytes(B)))
         ptr = lambda t: t.data_ptr() if t is not None else None
         self.handle.call('ch_mask_warp_batch', hair.data_ptr(), face.data_ptr(), Vd.data_ptr(), Fd.data_ptr(), bd.data_ptr(),
                          bcd.data_ptr(), desc.ctypes.data_as(C.c_void_p), ptr(Uin), out.data_ptr(), ptr(uv), ptr(Uout),
-                         self._ws.data_ptr(), need, B, torch.cuda.current_stream(dev).cuda_stream)
+                         ws.data_ptr(), ws.numel(), B, self._stream())
         if not (return_uv or return_U):
             return out
         res = {'labels': out}
@@ -237,14 +228,6 @@ class MaskWarper:
             return r[0]
         return {k: v[0] for k, v in r.items()}
 
-    def _workspace(self, name, need):
-        import torch
-        ws = getattr(self, name, None)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            setattr(self, name, ws)
-        return ws
-
     def _delaunay(self, Vd, counts):
         """ch_delaunay_batch on packed device points.  -> (F int32 [B,MAX_F,3], n_f int32 [B], status int32 [B]) on the device;
         the workspace (its counters included) stays in self._dws.  No synchronisation."""
@@ -256,10 +239,9 @@ class MaskWarper:
         F = torch.empty(B, MAX_F, 3, dtype=torch.int32, device=self.device)
         n_f = torch.empty(B, dtype=torch.int32, device=self.device)
         status = torch.empty(B, dtype=torch.int32, device=self.device)
-        need = int(self.handle.lib.ch_delaunay_workspace_bytes(B))
-        ws = self._workspace('_dws', need)
+        ws = self._buffer('_dws', int(self.handle.lib.ch_delaunay_workspace_bytes(B)))
         self.handle.call('ch_delaunay_batch', Vd.data_ptr(), v_desc.ctypes.data_as(C.c_void_p), F.data_ptr(), n_f.data_ptr(),
-                         status.data_ptr(), ws.data_ptr(), need, B, torch.cuda.current_stream(self.device).cuda_stream)
+                         status.data_ptr(), ws.data_ptr(), ws.numel(), B, self._stream())
         return F, n_f, status
 
     def delaunay_counters(self, B):
@@ -302,11 +284,10 @@ class MaskWarper:
         F, n_f, status = self._delaunay(Vd, counts)
         descd[:, 3] = n_f                              # a failed set has n_f = 0: the warp refuses its descriptor, identity map
         out = torch.empty(B, IMG, IMG, dtype=torch.uint8, device=self.device)
-        need = int(self.handle.lib.ch_mask_warp_workspace_bytes(B))
-        ws = self._workspace('_ws', need)
+        ws = self._buffer('_ws', int(self.handle.lib.ch_mask_warp_workspace_bytes(B)))
         self.handle.call('ch_mask_warp_batch_dev', hair.data_ptr(), face.data_ptr(), Vd.data_ptr(), F.data_ptr(), bd.data_ptr(),
-                         bcd.data_ptr(), descd.data_ptr(), None, out.data_ptr(), None, None, ws.data_ptr(), need, B,
-                         torch.cuda.current_stream(self.device).cuda_stream)
+                         bcd.data_ptr(), descd.data_ptr(), None, out.data_ptr(), None, None, ws.data_ptr(), ws.numel(), B,
+                         self._stream())
         self.last_mesh_status = status
         self.last_mesh = {'V': Vd.view(-1, 2), 'counts': counts, 'F': F, 'n_f': n_f, 'bc': targets}
         return out
