@@ -828,19 +828,9 @@ __global__ __launch_bounds__(256, 8) void ace_interior_f32_tile4_kernel(const Ac
 // are 1.14 rounds and the second round runs on an almost empty machine: measured at the nine launch shapes of B = 16, 512^2
 // (profiles/r07_interior_groups_bench.txt), 128 pixels, C = 512: 422 us with one group per block, 475 with two (2048 blocks); 256 pixels,
 // C = 256: 399 / 382 / 415 us with 1 / 2 / 4; 512 pixels, C = 128: 667 / 654 / 645 us.  What the loop saves is 2-3 % of a launch.
-static int interior_num_cus() {
-    static int ncus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!ncus[dev]) {
-        int n = 0;
-        ncus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return ncus[dev];
-}
 int ace_interior_groups(const AceInteriorParams& q) {
     const int ngrp = (q.C + IN_CG - 1) / IN_CG;
-    const long long tiles = (long long)q.B * ((q.W + 127) / 128) * ((q.H + 7) / 8), need = 16LL * interior_num_cus();
+    const long long tiles = (long long)q.B * ((q.W + 127) / 128) * ((q.H + 7) / 8), need = 16LL * device_cus();
     int G = 1;
     for (int d = 2; d <= ngrp; ++d) {
         if (ngrp % d) continue;

@@ -819,7 +819,7 @@ const OptRow OPTION_TABLE[] = {
     {"sean.sparse_th", BY_SEAN, RAW, 0, 0, SEAN_FIELD(sparse_th)},           // tile height of the compaction: 8 / 16, 0 = chosen per layer
     {"sean.sparse_min", BY_SEAN, RAW, 0, 0, SEAN_FIELD(sparse_min_r)},       // smallest ACE resolution served by the sparse path
     {"sean.dbg_sel", NEVER, RAW, 0, 0, SEAN_FIELD(dbg_sel)},                 // index of the ACE launch that sean.dbg bit 256 cycle-stamps
-    {"sean.dbg", NEVER, RAW, 0, 0, [](ch_handle* h, int v) { h->sean.opt.dbg = v; }, guard_dbg},      // profiling switches (conv_mfma.h)
+    {"sean.dbg", NEVER, RAW, 0, 0, [](ch_handle* h, int v) { h->sean.opt.dbg = v; }, guard_dbg},      // profiling switches (dbg_bits.h)
 };
 #undef SEAN_FIELD
 #undef OPT_FIELD

@@ -78,7 +78,7 @@ __device__ __forceinline__ void ace_sparse_body(const ConvParams& p, float* smem
 
     // sean.dbg bit 256 (profiling only): lane 0 of every wave stamps s_memtime at block start / after the prologue barrier /
     // after the k-loop / after the epilogue, plus its NSUB (tools/sparse_timeline.py)
-    const bool stamp = (p.dbg & 256) && p.partial && lane == 0;
+    const bool stamp = (p.dbg & DBG_STAMP) && p.partial && lane == 0;
     long long* stamps = reinterpret_cast<long long*>(p.partial) + ((long long)blockIdx.x * 4 + (tid >> 6)) * 5;
     if (stamp) { stamps[0] = __builtin_amdgcn_s_memtime(); stamps[4] = NSUB; }
     stage(0, 0);

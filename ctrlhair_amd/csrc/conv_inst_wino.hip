@@ -2,32 +2,9 @@
 #include "conv_pw.h"
 #include <algorithm>
 #include "conv_wino.h"
+#include "launch.h"
 
 namespace chk {
-
-static int wino_num_cus() {
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
-template <class K>
-static hipError_t wino_attr(K kern, int bytes, bool (&done)[64]) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        done[dev] = true;
-    }
-    return hipSuccess;
-}
 
 // out = act(sum over the K slices (in slice order) + bias + residual): the second pass of a split-K launch of wino_plain_kernel
 __global__ __launch_bounds__(256) void wino_splitk_reduce_kernel(const float* __restrict__ partial, float* __restrict__ out, const float* __restrict__ bias,
@@ -65,7 +42,7 @@ hipError_t conv_wino_plain(WinoParams p, hipStream_t s) {
     wino_fill_launch(p);
     p.ksplit = 1;
     if (p.partial && !p.d2s && p.W % 4 == 0) {        // far fewer tasks than CUs and a long k-loop: slices of the input channels
-        const int cus = wino_num_cus();
+        const int cus = device_cus();
         int ks = 1;
         while (ks < 8 && 2 * ks * p.ntasks <= cus && p.nks % (2 * ks) == 0 && p.nks / (2 * ks) >= 16 &&
                (long long)2 * ks * p.B * p.Cout * p.H * p.W <= p.partial_cap)
@@ -76,20 +53,19 @@ hipError_t conv_wino_plain(WinoParams p, hipStream_t s) {
         }
     }
     if (p.nks / p.ksplit < wino::NST) p.claim = nullptr;     // (the issue side may run two tasks ahead: static split only)
-    const int grid = p.ntasks < wino_num_cus() ? p.ntasks : wino_num_cus();
-    static bool d0[64] = {}, d1[64] = {}, d2[64] = {};
+    const int grid = persistent_grid(p.ntasks);
     if (p.d2s) {
-        hipError_t e = wino_attr(wino_plain_kernel<1>, wino::LDS_BYTES, d1);
+        hipError_t e = dyn_lds<wino_plain_kernel<1>>(wino::LDS_BYTES);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(wino_plain_kernel<1>, dim3(grid), dim3(512), wino::LDS_BYTES, s, p);
         return hipGetLastError();
     }
     if (p.in_up) {
-        hipError_t e = wino_attr(wino_plain_kernel<2>, wino::LDS_BYTES, d2);
+        hipError_t e = dyn_lds<wino_plain_kernel<2>>(wino::LDS_BYTES);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(wino_plain_kernel<2>, dim3(grid), dim3(512), wino::LDS_BYTES, s, p);
     } else {
-        hipError_t e = wino_attr(wino_plain_kernel<0>, wino::LDS_BYTES, d0);
+        hipError_t e = dyn_lds<wino_plain_kernel<0>>(wino::LDS_BYTES);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(wino_plain_kernel<0>, dim3(grid), dim3(512), wino::LDS_BYTES, s, p);
     }
@@ -106,30 +82,30 @@ hipError_t conv_wino_plain(WinoParams p, hipStream_t s) {
 template <int RT>
 static hipError_t launch_pw(PwParams p, hipStream_t s) {
     using Cfg = PwCfg<RT>;
-    static bool d0[64] = {};
-    hipError_t e = wino_attr(pw_conv_kernel<RT>, Cfg::LDS_BYTES, d0);
+    int cus = 0;
+    hipError_t e = dyn_lds<pw_conv_kernel<RT>>(Cfg::LDS_BYTES, &cus);
     if (e != hipSuccess) return e;
     const int nrt = (p.Cout + 31) / 32;
     p.nrg = (nrt + RT - 1) / RT;
     p.npt = p.HW / Cfg::PXB;
     p.ntasks = p.B * p.npt * p.nrg;
     p.nst = p.Cin / 16;
-    const int grid = p.ntasks < wino_num_cus() ? p.ntasks : wino_num_cus();
+    const int grid = persistent_grid(p.ntasks, cus);
     hipLaunchKernelGGL(pw_conv_kernel<RT>, dim3(grid), dim3(512), Cfg::LDS_BYTES, s, p);
     return hipGetLastError();
 }
 template <int RP>
 static hipError_t launch_pw_wide(PwParams p, hipStream_t s) {
     using Cfg = PwWideCfg<RP>;
-    static bool d0[64] = {};
-    hipError_t e = wino_attr(pw_conv_wide_kernel<RP>, Cfg::LDS_BYTES, d0);
+    int cus = 0;
+    hipError_t e = dyn_lds<pw_conv_wide_kernel<RP>>(Cfg::LDS_BYTES, &cus);
     if (e != hipSuccess) return e;
     const int nrt = (p.Cout + 31) / 32;
     p.nrg = (nrt + Cfg::RTB - 1) / Cfg::RTB;
     p.npt = p.HW / Cfg::PXB;
     p.ntasks = p.B * p.npt * p.nrg;
     p.nst = p.Cin / 16;
-    const int grid = p.ntasks < wino_num_cus() ? p.ntasks : wino_num_cus();
+    const int grid = persistent_grid(p.ntasks, cus);
     hipLaunchKernelGGL(pw_conv_wide_kernel<RP>, dim3(grid), dim3(512), Cfg::LDS_BYTES, s, p);
     return hipGetLastError();
 }
@@ -150,8 +126,8 @@ hipError_t conv_pw_grouped(PwParams p, int ntasks, hipStream_t s) {
     if (p.Cin % 16 || p.Cout < 1 || !p.groups || p.ngroups < 1 || ntasks < 1) return hipErrorInvalidValue;      // (rows beyond Cout: zero rows of the packed operand, masked at the store)
     const bool wide = p.wide && p.Cout > 64;
     if (wide && ntasks % (Wide::PXB / 128)) return hipErrorInvalidValue;
-    static bool d0[64] = {}, d1[64] = {};
-    hipError_t e = wide ? wino_attr(pw_conv_wide_kernel<2>, Wide::LDS_BYTES, d1) : wino_attr(pw_conv_kernel<4>, Cfg::LDS_BYTES, d0);
+    int cus = 0;
+    hipError_t e = wide ? dyn_lds<pw_conv_wide_kernel<2>>(Wide::LDS_BYTES, &cus) : dyn_lds<pw_conv_kernel<4>>(Cfg::LDS_BYTES, &cus);
     if (e != hipSuccess) return e;
     p.in = p.wpk = nullptr;
     p.out = nullptr;
@@ -161,7 +137,7 @@ hipError_t conv_pw_grouped(PwParams p, int ntasks, hipStream_t s) {
     p.npt = 0;
     p.ntasks = wide ? ntasks / (Wide::PXB / 128) : ntasks;
     p.nst = p.Cin / 16;
-    const int grid = p.ntasks < wino_num_cus() ? p.ntasks : wino_num_cus();
+    const int grid = persistent_grid(p.ntasks, cus);
     if (wide) hipLaunchKernelGGL(pw_conv_wide_kernel<2>, dim3(grid), dim3(512), Wide::LDS_BYTES, s, p);
     else hipLaunchKernelGGL(pw_conv_kernel<4>, dim3(grid), dim3(512), Cfg::LDS_BYTES, s, p);
     return hipGetLastError();
@@ -169,10 +145,10 @@ hipError_t conv_pw_grouped(PwParams p, int ntasks, hipStream_t s) {
 
 template <int TH>
 static hipError_t launch_wino_ace(const WinoAceParams& p, hipStream_t s) {
-    static bool d0[64] = {};
-    hipError_t e = wino_attr(wino_ace_kernel<TH>, WaCfg<TH>::LDS_BYTES, d0);
+    int cus = 0;
+    hipError_t e = dyn_lds<wino_ace_kernel<TH>>(WaCfg<TH>::LDS_BYTES, &cus);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(wino_ace_kernel<TH>, dim3(wino_num_cus()), dim3(512), WaCfg<TH>::LDS_BYTES, s, p);
+    hipLaunchKernelGGL(wino_ace_kernel<TH>, dim3(cus), dim3(512), WaCfg<TH>::LDS_BYTES, s, p);
     return hipGetLastError();
 }
 hipError_t conv_wino_ace(WinoAceParams p, hipStream_t s) {
@@ -181,10 +157,10 @@ hipError_t conv_wino_ace(WinoAceParams p, hipStream_t s) {
         p.nrt = (p.C + 15) / 16;
         if (p.nrt > 2 * 65535) return hipErrorInvalidValue;
         p.K = 128 + (p.wsty ? 20 : 0);
-        static bool d0[64] = {};
-        hipError_t e = wino_attr(wino_ace_gather_kernel<0>, winog::LDS_BYTES, d0);
+        int cus = 0;
+        hipError_t e = dyn_lds<wino_ace_gather_kernel<0>>(winog::LDS_BYTES, &cus);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(wino_ace_gather_kernel<0>, dim3(wino_num_cus()), dim3(512), winog::LDS_BYTES, s, p);
+        hipLaunchKernelGGL(wino_ace_gather_kernel<0>, dim3(cus), dim3(512), winog::LDS_BYTES, s, p);
         return hipGetLastError();
     }
     if ((p.TH != 16 && p.TH != 32) || p.H % p.TH || p.W % wino::TW || !p.zero || !p.qlist || !p.qcnt || !p.work || !p.total || (p.C & 3))

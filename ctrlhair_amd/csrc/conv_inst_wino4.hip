@@ -1,31 +1,17 @@
 // conv_inst_wino4.hip -- instantiation + launcher of the Winograd F(4x4,3x3) exact-f32 MFMA kernel (conv_wino4.h)
 #include "conv_wino4v.h"
 #include "conv_wino4_split.h"
+#include "launch.h"
 
 namespace chk {
 
 hipError_t conv_wino4_plain(Wino4Params p, hipStream_t s) {
     if (!wino4_supported(p.H, p.W, p.Cin) || !p.in || !p.wpk || !p.out || (p.reflect && (p.res_up || p.H < 2 || p.W < 2))) return hipErrorInvalidValue;
     wino4_fill_launch(p);
-    static bool done[64] = {};
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_plain_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_plain_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_plain_split_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_plain_split_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-        done[dev] = true;
-    }
-    const int grid = p.ntasks < cus[dev] ? p.ntasks : cus[dev];
+    int cus = 0;
+    hipError_t e = dyn_lds<wino4_plain_kernel<0>, wino4_plain_kernel<1>, wino4_plain_split_kernel<0>, wino4_plain_split_kernel<1>>(wino4::LDS_BYTES, &cus);
+    if (e != hipSuccess) return e;
+    const int grid = persistent_grid(p.ntasks, cus);
     // positions, not rows, split between the two waves of a tile group (conv_wino4_split.h): bit-identical results
     if (p.wpk_split && (p.split > 0 || (p.split < 0 && wino4_split_pays(p)))) {
         if (p.nks & 1) return hipErrorInvalidValue;
@@ -48,19 +34,10 @@ hipError_t conv_wino4_ace(Wino4AceParams p, hipStream_t s) {
     p.nks = p.wsty ? 38 : 32;
     p.rb = p.nrt >= 4 ? 4 : p.nrt;
     p.tbk = 32 / p.rb;
-    static bool done[64] = {};
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_ace_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-        done[dev] = true;
-    }
-    const int grid = p.ntasks < cus[dev] ? p.ntasks : cus[dev];
+    int cus = 0;
+    hipError_t e = dyn_lds<wino4_ace_kernel<0>>(wino4::LDS_BYTES, &cus);
+    if (e != hipSuccess) return e;
+    const int grid = persistent_grid(p.ntasks, cus);
     hipLaunchKernelGGL(wino4_ace_kernel<0>, dim3(grid), dim3(512), wino4::LDS_BYTES, s, p);
     return hipGetLastError();
 }
@@ -155,24 +132,8 @@ hipError_t wino4_style_pack(const float* lut, float* wsty, int B, int C, hipStre
 
 
 // ---- pre-transformed input route (conv_wino4v.h) ---------------------------------------------------------------------------------------
-static hipError_t wino4v_device(int& cus) {
-    static bool done[64] = {};
-    static int ncu[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4v_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4v::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(wino4v_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, wino4v::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        ncu[dev] = v;
-        done[dev] = true;
-    }
-    cus = ncu[dev];
-    return hipSuccess;
-}
+// both kernels' LDS limits from the first call of either launcher
+static hipError_t wino4v_attr(int& cus) { return dyn_lds<wino4v_kernel<0>, wino4v_kernel<1>>(wino4v::LDS_BYTES, &cus); }
 hipError_t wino4v_pack(const Wino4vPackParams& p, hipStream_t s) {
     if (!p.in || !p.v || p.H % 32 || p.W % 32 || p.H < 32 || p.W < 32 || p.nks <= 0 || p.pitch % 4 || p.xoff % 4 || (p.reflect && p.padded)) return hipErrorInvalidValue;
     const long long blocks = (long long)p.B * (p.H / 32) * (p.W / 32) * p.nks;
@@ -192,9 +153,9 @@ hipError_t conv_wino4v_plain(Wino4Params p, hipStream_t s) {
     p.rb = p.nrt >= W4V_RB ? W4V_RB : p.nrt;
     p.tbk = 32 / p.rb;
     int cus = 0;
-    hipError_t e = wino4v_device(cus);
+    hipError_t e = wino4v_attr(cus);
     if (e != hipSuccess) return e;
-    const int grid = p.ntasks < cus ? p.ntasks : cus;
+    const int grid = persistent_grid(p.ntasks, cus);
     hipLaunchKernelGGL(wino4v_kernel<0>, dim3(grid), dim3(512), wino4v::LDS_BYTES, s, p);
     return hipGetLastError();
 }
@@ -209,9 +170,9 @@ hipError_t conv_wino4v_ace(Wino4AceParams p, hipStream_t s) {
     p.rb = p.nrt >= 4 ? 4 : p.nrt;
     p.tbk = 32 / p.rb;
     int cus = 0;
-    hipError_t e = wino4v_device(cus);
+    hipError_t e = wino4v_attr(cus);
     if (e != hipSuccess) return e;
-    const int grid = p.ntasks < cus ? p.ntasks : cus;
+    const int grid = persistent_grid(p.ntasks, cus);
     hipLaunchKernelGGL(wino4v_kernel<1>, dim3(grid), dim3(512), wino4v::LDS_BYTES, s, p);
     return hipGetLastError();
 }

@@ -24,17 +24,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dbg_bits.h"
+#include "launch.h"
+
 // Timing ablations (skipped loads / epilogues / gathers: WRONG RESULTS) and superseded kernel versions kept for A/B measurements
 // exist only in builds with -DCH_ABLATE (make ABLATE=1); the default library contains none of them and ch_set_option rejects
-// their sean.dbg bits.
+// their sean.dbg bits (CH_ABLATE_DBG_MASK; every bit is named in dbg_bits.h).
 #ifdef CH_ABLATE
 #define CH_ABL(x) (x)
 #else
 #define CH_ABL(x) 0
 #endif
-// sean.dbg bits that need a CH_ABLATE build: 1 / 2 / 4 / 8 skip loads, the MFMA loop, epilogues; 2048 conv_sh16_ws2_kernel;
-// 65536 / 1048576 / 2097152 / 16777216 earlier interior-pass kernels; 4194304 no style-LUT gathers
-constexpr int CH_ABLATE_DBG_MASK = 1 | 2 | 4 | 8 | 2048 | 65536 | 1048576 | 2097152 | 16777216 | 4194304;
 
 namespace chk {
 
@@ -105,7 +105,7 @@ struct ConvParams {
     int s2d_cr, s2d_phase0; // S2D instantiations of conv_sh16_kernel (stride-2 convs): real input channels (Cin = phases x s2d_cr)
                             // and the first phase (0: 2x2-tap form of a k3 / k4 pad-1 kernel; 3: 1x1 stride-2 conv)
     int mtiles_hint_small;  // set by the caller when the layer has few tiles (prefer the split-K path over the persistent kernel)
-    int dbg;                // perf experiments only: 1 = skip staging after chunk 0, 2 = skip the MFMA loop
+    int dbg;                // perf experiments only: the bits of option "sean.dbg" (dbg_bits.h)
     // exact SPADE-interior reduction (ace_sparse.h): boundary pixels of the level's tiles and the block tasks of this launch
     const uint16_t* sp_list;
     const int* sp_cnt;
@@ -152,7 +152,7 @@ __device__ __forceinline__ void ace_epilogue_f32(const ConvParams& p, f32x16 (&a
     const uint8_t* lb = p.lab + (long long)b * HW;
     const float* xb = p.x + (long long)b * C * xHW;
     float* ob = p.out + (long long)b * C * HW;
-    const float* Lb = (p.lut && !CH_ABL(p.dbg & 4194304)) ? p.lut + (long long)b * 19 * 9 * 2 * C : nullptr;   // (bit: timing ablation)
+    const float* Lb = (p.lut && !CH_ABL(p.dbg & DBG_NO_LUT_GATHER)) ? p.lut + (long long)b * 19 * 9 * 2 * C : nullptr;   // (bit: timing ablation)
     // Pixel (n) outer: the nine (label, tap) row offsets of the pixel's style-LUT gathers are computed once and shared by its
     // four channel runs (as 32-bit element offsets from the sample's LUT: <= 19*9*2*C floats); the five parameter float4 of a
     // run are re-read per pixel from L1 instead (per-tap 64-bit address arithmetic was the larger cost).
@@ -564,16 +564,8 @@ __global__ void splitk_reduce_kernel(const ConvParams p) {
 template <int KS, int STRIDE, int WM, int TW, int TH, int TB, int CK, int EPI, bool FUSE = false>
 hipError_t launch_conv(ConvParams p, int rows, hipStream_t stream) {
     using Cfg = ConvCfg<KS, STRIDE, WM, TW, TH, TB, CK, EPI>;
-    auto kern = conv_mfma_kernel<KS, STRIDE, WM, TW, TH, TB, CK, EPI, FUSE>;
-    static bool attr_set[64] = {};                           // per device (a process may own handles on several GPUs)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
+    constexpr auto kern = conv_mfma_kernel<KS, STRIDE, WM, TW, TH, TB, CK, EPI, FUSE>;
+    if (hipError_t e = dyn_lds<kern>(Cfg::LDS_BYTES)) return e;
     p.nchunks = (p.Cin + CK - 1) / CK;
     if (p.Hin == 0) { p.Hin = p.H; p.Win = p.W; }
     if (p.pad < 0) p.pad = KS / 2;

@@ -264,7 +264,7 @@ __device__ __forceinline__ void sh16_epilogue(const ConvParams& p, f32x16 (&acc)
                 }
             }
         if (p.out_amax && p.splitk <= 1) {
-            amax = sh16_wave_max(amax);
+            amax = wave_max(amax);
             if (lane == 0) sh16_slot_max(p.out_amax, amax * SH16_ACT_SCALE);
         }
     } else {  // EPI_ACE -> SH16 output.  Loop order: channel-run (rq) outer so that only one run's parameters
@@ -372,7 +372,7 @@ __device__ __forceinline__ void sh16_epilogue(const ConvParams& p, f32x16 (&acc)
         } else {
             body(std::false_type{});
             if (p.out_amax) {
-                amax = sh16_wave_max(amax);
+                amax = wave_max(amax);
                 if (lane == 0) sh16_slot_max(p.out_amax, amax);
             }
         }
@@ -629,16 +629,16 @@ __global__ __launch_bounds__(256, 2) void conv_sh16_kernel(const ConvParams p) {
         }
     };
 
-    if (!CH_ABL(p.dbg & 8)) stage(c_lo, 0);
+    if (!CH_ABL(p.dbg & DBG_SKIP_FIRST_STAGE)) stage(c_lo, 0);
     __syncthreads();
 
     for (int ch = c_lo; ch < c_hi; ++ch) {
-        if (ch + 1 < c_hi && !CH_ABL(p.dbg & 1)) stage(ch + 1, (ch + 1 - c_lo) & 1);
+        if (ch + 1 < c_hi && !CH_ABL(p.dbg & DBG_SKIP_STAGING)) stage(ch + 1, (ch + 1 - c_lo) & 1);
         if constexpr (FUSE) {
             if (ch + 1 == c_hi) stage2(0, (ch + 1 - c_lo) & 1);
         }
         const uint4* sb = smem_u + ((ch - c_lo) & 1) * UNITS;
-        if (CH_ABL(p.dbg & 2)) { __syncthreads(); continue; }
+        if (CH_ABL(p.dbg & DBG_SKIP_MFMA)) { __syncthreads(); continue; }
         const uint4* Ac = Ap + (long long)ch * (NT * 4 * 64);
         uint4 a_cur[4];
 #pragma unroll
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(256, 2) void conv_sh16_kernel(const ConvParams p) {
         }
     }
 
-    if (CH_ABL(p.dbg & 4)) return;
+    if (CH_ABL(p.dbg & DBG_SKIP_EPILOGUE)) return;
     sh16_epilogue<TW, TH, TB, EPI, TERMS == 2, D2S>(p, acc, mtile64, wn, lane, x0, y0, b0, ks, ROT);
 }
 
@@ -1167,7 +1167,7 @@ __global__ __launch_bounds__(512, 2) void conv_sh16_ws_kernel(const ConvParams p
     const float extra = (pre && p.pass == 1) ? sh16_dyn_extra(*p.out_amax) : 1.f;
     // dbg bit 256 (profiling only): wave 0 of every block stamps s_memtime at tile start / end of the k-loop / end of the
     // epilogue into p.partial (3 x int64 per tile, 64 tiles per block)
-    const bool stamp = (p.dbg & 256) && wn == 0 && lane == 0 && p.partial;
+    const bool stamp = (p.dbg & DBG_STAMP) && wn == 0 && lane == 0 && p.partial;
     long long* stamps = reinterpret_cast<long long*>(p.partial) + (long long)blockIdx.x * 64 * 3;
     for (int k = 0; k < my_tiles; ++k) {
         int mtile64, x0, y0, b0;
@@ -1386,7 +1386,7 @@ __global__ __launch_bounds__(512, 2) void conv_sh16_ws_kernel(const ConvParams p
         // after the last chunk's barrier the consumers no longer touch LDS: the loaders go on staging the next tile
         // while the epilogue runs
         if (stamp && k < 64) stamps[k * 3 + 1] = __builtin_amdgcn_s_memtime();
-        if (CH_ABL(p.dbg & 4)) continue;
+        if (CH_ABL(p.dbg & DBG_SKIP_EPILOGUE)) continue;
         if constexpr (!pre) {
             sh16_epilogue<TW, TH, TB, EPI, TERMS == 2>(p, acc, mtile64, wn, lane, x0, y0, b0);
         } else {
@@ -1470,7 +1470,7 @@ __global__ __launch_bounds__(512, 2) void conv_sh16_ws_kernel(const ConvParams p
     }
     if constexpr (pre) {
         if (p.pass != 1 && p.out_amax) {                       // one atomic per consumer wave per launch
-            amax = sh16_wave_max(amax);
+            amax = wave_max(amax);
             if (lane == 0) sh16_slot_max(p.out_amax, amax);
         }
     }
@@ -1481,25 +1481,13 @@ hipError_t launch_sh16_ws(ConvParams p, int rows, hipStream_t stream) {
     using Cfg = ShCfg<KS, TW, TH, TB>;
     if (p.in_mode != IN_DIRECT) return hipErrorInvalidValue;     // input views are implemented in conv_sh16_kernel only
     if (CP && !(p.sp_work && p.sp_list && p.sp_cnt && p.sp_total)) return hipErrorInvalidValue;
-    auto kern = conv_sh16_ws_kernel<KS, TW, TH, TB, EPI, TERMS, CP>;
+    constexpr auto kern = conv_sh16_ws_kernel<KS, TW, TH, TB, EPI, TERMS, CP>;
     // 2 x (patch + A fragments) + (ACE) small epilogue operands: parameters, noise, label patch
     constexpr int V3_STAGE = Cfg::UNITS + KS * KS * 4 * 64;
     constexpr int V3_LDS = EPI == EPI_ACE ? (2 * V3_STAGE + 40 + 128) * 16 + ((TB * (TH + 2) * (TW + 2) + 15) / 16) * 16 + (CP ? (129 + (CP == 3 ? 120 : (CP == 2 ? 40 : 0))) * 16 : 0)
                                           : 2 * V3_STAGE * 16;
-    // per device: a process may own handles on several GPUs (ch_api.cpp DeviceGuard)
-    static bool attr_set[64] = {};
-    static int ncus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           V3_LDS);
-        if (e != hipSuccess) return e;
-        hipDeviceProp_t prop;
-        ncus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        attr_set[dev] = true;
-    }
-    const int ncu = ncus[dev];
+    int ncu = 0;
+    if (hipError_t e = dyn_lds<kern>(V3_LDS, &ncu)) return e;
     p.nchunks = (p.Cin + 15) / 16;
     p.mtiles = (rows + 63) / 64;
     p.tiles_x = (p.W + TW - 1) / TW;
@@ -1507,8 +1495,7 @@ hipError_t launch_sh16_ws(ConvParams p, int rows, hipStream_t stream) {
     p.tiles_b = (p.B + TB - 1) / TB;
     p.splitk = 1;
     const int ntiles = p.mtiles * p.tiles_x * p.tiles_y * p.tiles_b;
-    const int grid = ntiles < ncu ? ntiles : ncu;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), V3_LDS, stream, p);
+    hipLaunchKernelGGL(kern, dim3(persistent_grid(ntiles, ncu)), dim3(512), V3_LDS, stream, p);
     return hipGetLastError();
 }
 
@@ -1564,16 +1551,8 @@ template <int KS, int TW, int TH, int TB, int EPI, int TERMS = 3, bool FUSE = fa
           bool D2S = false>
 hipError_t launch_sh16(ConvParams p, int rows, hipStream_t stream) {
     using Cfg = ShCfg<KS, TW, TH, TB>;
-    auto kern = conv_sh16_kernel<KS, TW, TH, TB, EPI, TERMS, FUSE, INC4, S2D, D2S>;
-    static bool attr_set[64] = {};                           // per device (a process may own handles on several GPUs)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           Cfg::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
+    constexpr auto kern = conv_sh16_kernel<KS, TW, TH, TB, EPI, TERMS, FUSE, INC4, S2D, D2S>;
+    if (hipError_t e = dyn_lds<kern>(Cfg::LDS_BYTES)) return e;
     p.nchunks = (p.Cin + 15) / 16;
     p.mtiles = (rows + 63) / 64;
     p.tiles_x = (p.W + TW - 1) / TW;
@@ -1616,9 +1595,9 @@ hipError_t launch_sh16_ws2(ConvParams p, int rows, hipStream_t stream);     // c
 inline bool sh16_ace_uses_ws(const ConvParams& p) {
     const int rows = ((p.C + 31) / 32) * 64;
     const long long ntiles = (long long)(rows / 64) * ((p.W + 31) / 32) * ((p.H + 15) / 16) * p.B;
-    if (CH_ABL(p.dbg & 2048) && p.Cin == 128 && p.W >= 32) return false;
+    if (CH_ABL(p.dbg & DBG_WS2) && p.Cin == 128 && p.W >= 32) return false;
     const bool ws_ok = p.W >= 32 && p.Cin >= 48;
-    return ws_ok && ((p.dbg & 64) || (!(p.dbg & 128) && ntiles >= 512));
+    return ws_ok && ((p.dbg & DBG_WS_FORCE) || (!(p.dbg & DBG_WS_OFF) && ntiles >= 512));
 }
 
 template <int TERMS>
@@ -1631,10 +1610,10 @@ hipError_t dispatch_sh16_ace(const ConvParams& p, hipStream_t s) {
     // dbg bit 2048: the experimental kernel of conv_sh16_ws2.h (epilogue pipelined into the next tile's k-loop; correct,
     // but its half-size tiles double the A-fragment traffic and the loaders cannot deliver it: DESIGN.md section 7)
 #ifdef CH_ABLATE
-    if ((p.dbg & 2048) && p.Cin == 128 && p.W >= 32) return launch_sh16_ws2<TERMS>(p, rows, s);
+    if ((p.dbg & DBG_WS2) && p.Cin == 128 && p.W >= 32) return launch_sh16_ws2<TERMS>(p, rows, s);
 #endif
     const bool ws_ok = p.W >= 32 && p.Cin >= 48;
-    if (ws_ok && ((p.dbg & 64) || (!(p.dbg & 128) && ntiles >= 512))) {
+    if (ws_ok && ((p.dbg & DBG_WS_FORCE) || (!(p.dbg & DBG_WS_OFF) && ntiles >= 512))) {
         {        // pixel-level compaction when the caller passes the per-tile lists (sean_model.cpp); every operand format since round 6
             if (p.sp_work && p.sp_list) {
                 hipError_t e = launch_sh16_ws<3, 32, 16, 1, EPI_ACE, TERMS, 1>(p, rows, s);
@@ -1664,9 +1643,9 @@ hipError_t dispatch_sh16_plain(const ConvParams& p, hipStream_t s) {
     // on it (measured per layer, B = 16: 762 -> 672 us, 1478 -> 1330, 1454 -> 1368); with more tiles -- the 256^2 / 512^2
     // layers, HBM-heavy -- it is level or slower (1463 -> 1430, 1574 -> 1626) and the 2-blocks-per-CU kernel stays.
     const long long ntiles = (long long)((p.Mrows + 63) / 64) * ((p.W + 31) / 32) * ((p.H + 15) / 16) * p.B;
-    const bool ws_auto = KS == 3 && !(p.dbg & 128) && ntiles >= 512 && ntiles <= 2048 && p.Cin >= 48 && p.in_mode == IN_DIRECT &&
+    const bool ws_auto = KS == 3 && !(p.dbg & DBG_WS_OFF) && ntiles >= 512 && ntiles <= 2048 && p.Cin >= 48 && p.in_mode == IN_DIRECT &&
                          p.pad_mode == PAD_ZERO;
-    if (((p.dbg & 64) || ws_auto) && p.W >= 32 && !(p.partial && p.mtiles_hint_small) && !p.in2)
+    if (((p.dbg & DBG_WS_FORCE) || ws_auto) && p.W >= 32 && !(p.partial && p.mtiles_hint_small) && !p.in2)
         return launch_sh16_ws<KS, 32, 16, 1, EPI_PLAIN, TERMS>(p, p.Mrows, s);
     if (p.in2) {        // 3x3 conv with a fused 1x1 second operand (ResBlock shortcut): 32x16 tiles only
         if constexpr (KS == 3) {

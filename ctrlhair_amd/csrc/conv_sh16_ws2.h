@@ -171,12 +171,12 @@ __global__ __launch_bounds__(512, 2) void conv_sh16_ws2_kernel(const ConvParams 
         __syncthreads();                                      // stage 0 ready
         auto iter = [&](int q, uint4 (&stg)[NLD]) {
             const int k = q / NCH, ch = q % NCH;
-            if (q + 1 < Q && !(p.dbg & 1)) {
+            if (q + 1 < Q && !(p.dbg & DBG_SKIP_STAGING)) {
                 dma_A(q + 1);
                 store_chunk((q + 1) & 1, stg);
             }
             if (ch == NCH - 1) epi_store(k);                  // consumers read these after this iteration's barrier
-            if (q + 3 < Q && !(p.dbg & 1)) {
+            if (q + 3 < Q && !(p.dbg & DBG_SKIP_STAGING)) {
                 load_chunk(q + 3, stg);
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
             } else {
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(512, 2) void conv_sh16_ws2_kernel(const ConvParams 
 
     __syncthreads();                                          // stage 0 ready
     int q = 0;
-    const bool stamp = (p.dbg & 256) && wn == 0 && lane == 0 && p.partial;      // profiling only (tools/ws_timeline.py)
+    const bool stamp = (p.dbg & DBG_STAMP) && wn == 0 && lane == 0 && p.partial;      // profiling only (tools/ws_timeline.py)
     long long* stamps = reinterpret_cast<long long*>(p.partial) + (long long)blockIdx.x * 64 * 3;
     for (int k = 0; k < my_tiles; ++k) {
         if (stamp && k < 64) stamps[k * 3] = __builtin_amdgcn_s_memtime();
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(512, 2) void conv_sh16_ws2_kernel(const ConvParams 
                 bh[n] = sbp[ub[n]];
                 bl[n] = sbp[ub[n] + PLANE];
             }
-            const bool epi = !(p.dbg & 4);
+            const bool epi = !(p.dbg & DBG_SKIP_EPILOGUE);
             if (epi) step_begin(ch);
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(512, 2) void conv_sh16_ws2_kernel(const ConvParams 
         tail(std::integral_constant<int, 7>{});
     }
     if (p.pass != 1 && p.out_amax) {                           // one atomic per consumer wave per launch
-        amax = sh16_wave_max(amax);
+        amax = wave_max(amax);
         if (lane == 0) sh16_slot_max(p.out_amax, amax);
     }
 }
@@ -454,22 +454,8 @@ hipError_t launch_sh16_ws2(ConvParams p, int rows, hipStream_t stream) {
     if (p.Cin != 128 || p.in_mode != IN_DIRECT) return hipErrorInvalidValue;
     constexpr int UNITS = 4 * 34 * 10, STAGE = UNITS + 9 * 4 * 64, SMALL = 40 + 64 + (10 * 34 + 15) / 16;
     constexpr int LDS = (2 * STAGE + 2 * SMALL) * 16;
-    static bool attr_set[64] = {};                           // per device (a process may own handles on several GPUs)
-    static int ncus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sh16_ws2_kernel<TERMS, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sh16_ws2_kernel<TERMS, false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        hipDeviceProp_t prop;
-        ncus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        attr_set[dev] = true;
-    }
-    const int ncu = ncus[dev];
+    int ncu = 0;
+    if (hipError_t e = dyn_lds<conv_sh16_ws2_kernel<TERMS, true>, conv_sh16_ws2_kernel<TERMS, false>>(LDS, &ncu)) return e;
     p.nchunks = 8;
     p.mtiles = (rows + 63) / 64;
     p.tiles_x = (p.W + 31) / 32;
@@ -477,7 +463,7 @@ hipError_t launch_sh16_ws2(ConvParams p, int rows, hipStream_t stream) {
     p.tiles_b = p.B;
     p.splitk = 1;
     const int ntiles = p.mtiles * p.tiles_x * p.tiles_y * p.tiles_b;
-    const int grid = ntiles < ncu ? ntiles : ncu;
+    const int grid = persistent_grid(ntiles, ncu);
     if (p.lut) hipLaunchKernelGGL((conv_sh16_ws2_kernel<TERMS, true>), dim3(grid), dim3(512), LDS, stream, p);
     else hipLaunchKernelGGL((conv_sh16_ws2_kernel<TERMS, false>), dim3(grid), dim3(512), LDS, stream, p);
     return hipGetLastError();

@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace chk {
 
@@ -371,12 +372,7 @@ __device__ inline LaneBlock load_lane_block(const int16_t* __restrict__ coef, co
 // exclusive scan over the workgroup's NT values in thread order; wsum: 4 words of LDS; total: the sum
 __device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t& total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
+    const uint32_t x = wave_scan_incl(v, lane);
     __syncthreads();                                                          // the previous round's readers are done with wsum
     if (lane == 63) wsum[w] = x;
     __syncthreads();
@@ -500,8 +496,7 @@ __global__ __launch_bounds__(NT) void jpeg_ffcount_kernel(const uint8_t* __restr
     if ((uint64_t)blockIdx.x * NT * 4 >= nb) return;
     const uint32_t* raww = reinterpret_cast<const uint32_t*>(rawbuf + (size_t)n * g.rawBytes);
     int c = at < nb ? ff_bytes(raww[at >> 2], at, nb) : 0;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+    c = wave_sum(c);
     if ((tid & 63) == 0) ffcnt[(size_t)n * g.nsegB + (size_t)blockIdx.x * (NT / 64) + (tid >> 6)] = (uint32_t)c;
 }
 

@@ -2,16 +2,12 @@
 // wave64 shuffle reductions for the normalisation statistics, pooling, up-sampling/argmax epilogues, GEMV.
 #include "kernels.h"
 #include "sh16.h"
+#include "launch.h"
 
 namespace chk {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 // block (256 threads) sum, result broadcast to all threads; `red` = 4 floats of LDS
 __device__ __forceinline__ float block_sum(float v, float* red) {
     v = wave_sum(v);
@@ -1456,31 +1452,23 @@ __global__ __launch_bounds__(256) void lut_gemv_mfma_kernel(const float* __restr
         }
     }
 }
+template <int NT>
+static hipError_t launch_lut_gemv(const float* x, const float* W, float* out, int N, int rows, int grid, hipStream_t s) {
+    constexpr int LDS = (int)(NT * 16 * LUTG_XP * sizeof(float));
+    if (hipError_t e = dyn_lds<lut_gemv_mfma_kernel<NT>>(LDS)) return e;
+    hipLaunchKernelGGL(lut_gemv_mfma_kernel<NT>, dim3(grid), dim3(256), LDS, s, x, W, out, N, rows);
+    return hipGetLastError();
+}
 hipError_t lut_gemv_mfma(const float* x, const float* W, float* out, int N, int rows, hipStream_t s) {
     if (N < 1 || N > 64 || rows < 1) return hipErrorInvalidValue;
-    const int nt = (N + 15) / 16;
-    const size_t lds = (size_t)nt * 16 * LUTG_XP * sizeof(float);
     const int ntile = (rows + 15) / 16;
     const int grid = (ntile + 3) / 4 < 1024 ? (ntile + 3) / 4 : 1024;
-    static bool attr_done[4][64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-#define LUTG_LAUNCH(NT_)                                                                                                                          \
-    {                                                                                                                                             \
-        if (!attr_done[NT_ - 1][dev]) {                                                                                                           \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lut_gemv_mfma_kernel<NT_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                               (int)(NT_ * 16 * LUTG_XP * sizeof(float)));                                                        \
-            if (e != hipSuccess) return e;                                                                                                        \
-            attr_done[NT_ - 1][dev] = true;                                                                                                       \
-        }                                                                                                                                         \
-        hipLaunchKernelGGL(lut_gemv_mfma_kernel<NT_>, dim3(grid), dim3(256), lds, s, x, W, out, N, rows);                                         \
+    switch ((N + 15) / 16) {
+        case 1: return launch_lut_gemv<1>(x, W, out, N, rows, grid, s);
+        case 2: return launch_lut_gemv<2>(x, W, out, N, rows, grid, s);
+        case 3: return launch_lut_gemv<3>(x, W, out, N, rows, grid, s);
+        default: return launch_lut_gemv<4>(x, W, out, N, rows, grid, s);
     }
-    if (nt == 1) LUTG_LAUNCH(1)
-    else if (nt == 2) LUTG_LAUNCH(2)
-    else if (nt == 3) LUTG_LAUNCH(3)
-    else LUTG_LAUNCH(4)
-#undef LUTG_LAUNCH
-    return hipGetLastError();
 }
 
 // EigenGAN subspace injection (model_eigengan.py:27-31,76-81): h[b,:] = lrelu(h[b,:] + U (L * z[b,:]) + mu), z 2-d

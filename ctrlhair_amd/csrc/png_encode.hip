@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace chk {
 
@@ -53,11 +54,7 @@ Layout layout(int N, int H, int W, int C) {
 // ---- block-wide scans over one int per thread (NT threads, every thread calls) -----------------------------------------------
 __device__ __forceinline__ int scan_add_excl(int v, int* sh, int* total) {          // sh: 4 ints
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
+    const int x = wave_scan_incl(v, lane);
     __syncthreads();                                                                // (sh may still be read from the scan before)
     if (lane == 63) sh[wave] = x;
     __syncthreads();

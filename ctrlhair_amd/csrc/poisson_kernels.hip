@@ -23,12 +23,13 @@
 #include <vector>
 
 #include "kernels.h"
+#include "wave_ops.h"
 
 namespace chk {
 
 // sum of v over the 256-thread block, returned to every thread (fixed order -> run-to-run deterministic)
 __device__ __forceinline__ double pb_block_sum(double v, double* sh) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -2,6 +2,7 @@
 // gfx950 only (wave64).  Every kernel is predicated for arbitrary shapes.
 #include "kernels.h"
 #include "sh16.h"
+#include "launch.h"
 
 namespace chk {
 
@@ -402,28 +403,9 @@ bool spade_hidden_wq_supported(int H, int W) {
 __global__ void spade_hidden_level_kernel(const uint8_t* lab, const uint8_t* u5, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base,
                                           const int* mode, const float* table, const float* bias, float* out, float* patch, int B, int H, int W, int kout,
                                           int onehot, int tcs, int pitch, int xoff);      // (below, beside the patch kernel)
-// LDS limit of the three kernels and the CU count of the current device, once per device
-static hipError_t spade_hidden_wq_device(int& ncu) {
-    static bool done[64] = {};
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    if (!done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(spade_hidden_wq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           hid::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(spade_hidden_wq_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                hid::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(spade_hidden_level_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, hid::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-        done[dev] = true;
-    }
-    ncu = cus[dev];
-    return hipSuccess;
+// LDS limit of the three kernels, once per device: the first call of any of their launchers sets all three
+static hipError_t spade_hidden_wq_attr(int& ncu) {
+    return dyn_lds<spade_hidden_wq_kernel, spade_hidden_wq_grouped_kernel, spade_hidden_level_kernel>(hid::LDS_BYTES, &ncu);
 }
 static int spade_hidden_wq_tcs(int W) {
     const int TC = (W & (W - 1)) ? 32 : (W < 512 ? W : 512);
@@ -438,10 +420,10 @@ hipError_t spade_hidden_wq(const uint8_t* lab, const uint8_t* u5, const float* t
     if (pitch <= 0) { pitch = W; xoff = 0; }
     if (xoff < 0 || (xoff > 0 && pitch < W + xoff + 1)) return hipErrorInvalidValue;
     int ncu = 0;
-    if (hipError_t e = spade_hidden_wq_device(ncu)) return e;
+    if (hipError_t e = spade_hidden_wq_attr(ncu)) return e;
     const int tcs = spade_hidden_wq_tcs(W);
     const int ntasks = B * (H * W / 1024);
-    const int grid = ntasks < ncu ? ntasks : ncu;
+    const int grid = persistent_grid(ntasks, ncu);
     hipLaunchKernelGGL(spade_hidden_wq_kernel, dim3(grid), dim3(1024), hid::LDS_BYTES, s, lab, u5, table, bias, out, B, H, W, kout, onehot, tcs,
                        pitch, xoff, skip_if_patch);
     return hipGetLastError();
@@ -452,7 +434,7 @@ hipError_t spade_hidden_wq_grouped(HiddenGroup& g, hipStream_t s) {
     if (g.n < 0 || g.n > HiddenGroup::MAX || g.B < 1) return hipErrorInvalidValue;
     if (g.n == 0) return hipSuccess;
     int ncu = 0;
-    if (hipError_t e = spade_hidden_wq_device(ncu)) return e;
+    if (hipError_t e = spade_hidden_wq_attr(ncu)) return e;
     int grid = 0;
     for (int k = 0; k < g.n; ++k) {
         HiddenGroup::Entry& e = g.e[k];
@@ -559,29 +541,19 @@ hipError_t spade_hidden_level(const uint8_t* lab, const uint8_t* u5, const unsig
     if (pitch <= 0) { pitch = W; xoff = 0; }
     if (xoff < 0 || (xoff > 0 && pitch < W + xoff + 1)) return hipErrorInvalidValue;
     int ncu = 0;
-    if (hipError_t e = spade_hidden_wq_device(ncu)) return e;
-    hipLaunchKernelGGL(spade_hidden_level_kernel, dim3(ncu), dim3(1024), hid::LDS_BYTES, s, lab, u5, gq, gq_n, gq_cap, chunk_base, mode, table, bias, out, patch,
-                       B, H, W, kout, onehot, spade_hidden_wq_tcs(W), pitch, xoff);
+    if (hipError_t e = spade_hidden_wq_attr(ncu)) return e;
+    hipLaunchKernelGGL(spade_hidden_level_kernel, dim3(ncu), dim3(1024), hid::LDS_BYTES, s, lab, u5, gq, gq_n, gq_cap, chunk_base, mode, table, bias,
+                       out, patch, B, H, W, kout, onehot, spade_hidden_wq_tcs(W), pitch, xoff);
     return hipGetLastError();
 }
 hipError_t spade_hidden_patch(const uint8_t* lab, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,
                               const float* table, const float* bias, float* patch, int B, int H, int W, int kout, hipStream_t s) {
     if (B < 1 || B > 32 || (kout != hid::K && kout != hid::K + 20)) return hipErrorInvalidValue;
-    static bool done[64] = {};
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     constexpr int LDS = (hid::T_FLOATS + hid::K) * 4;
-    if (!done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(spade_hidden_patch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-        done[dev] = true;
-    }
-    hipLaunchKernelGGL(spade_hidden_patch_kernel, dim3(cus[dev]), dim3(1024), LDS, s, lab, gq, gq_n, gq_cap, chunk_base, mode, table, bias, patch, B, H, W,
-                       kout);
+    int ncu = 0;
+    if (hipError_t e = dyn_lds<spade_hidden_patch_kernel>(LDS, &ncu)) return e;
+    hipLaunchKernelGGL(spade_hidden_patch_kernel, dim3(ncu), dim3(1024), LDS, s, lab, gq, gq_n, gq_cap, chunk_base, mode, table, bias, patch, B,
+                       H, W, kout);
     return hipGetLastError();
 }
 // chunk_base[b] = chunks of 64 quads of the samples before b (chunk_base[B]: all); *mode = 1 when they fit `cap_chunks` (and there are any)

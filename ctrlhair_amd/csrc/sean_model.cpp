@@ -902,7 +902,7 @@ struct SeanBuild {
                 if (w.mode == 3) {
                     w.work2 = static_cast<unsigned*>(B.dalloc((size_t)L.cap_tiles * ((mt + 1) / 2) * sizeof(unsigned)));
                     w.total2 = static_cast<int*>(B.dalloc(4 * sizeof(int)));
-                    if (mt >= 4 && !(opt.dbg & 67108864))
+                    if (mt >= 4 && !(opt.dbg & DBG_NO_WORK_QUADS))
                         w.work3 = static_cast<unsigned*>(B.dalloc((size_t)L.cap_tiles * ((mt + 3) / 4) * sizeof(unsigned)));
                 }
                 m.levels[k].sp_work.push_back(w);
@@ -1270,7 +1270,7 @@ struct Runner {
                     // ahead of the classification: every pixel)
                     // (exact-f32 path: skipping pixels of the NCHW planes made the kernel slower at every granularity tried -- it is bound by
                     // its LDS table reads, not by the writes; the map stays available behind sean.dbg bit 131072)
-                    if (!full && (m.opt.use_sh16 ? p.compact : (m.opt.dbg & 131072) != 0)) p.need = V.sp[p.ti].need;
+                    if (!full && (m.opt.use_sh16 ? p.compact : (m.opt.dbg & DBG_F32_NEED_MAP) != 0)) p.need = V.sp[p.ti].need;
                     if (!full && m.opt.use_sh16 && !p.compact) p.tile_cnt = V.sp[p.ti].cnt;
                 }
             }
@@ -1390,7 +1390,7 @@ struct Runner {
         if (!pl.wino()) m.pad_state.erase(actv_buf);
         if (m.opt.use_sh16)
             check(onehot_conv3x3_sh16(lab, a.actv_table, a.actv_bias, actv_buf, B, r, r, HID, 1, a.actv_scale, s, m.opt.terms == 2, pl.need, pl.tile_cnt,
-                                      (m.opt.dbg & 33554432) ? 1 : 0), "mlp_shared");
+                                      (m.opt.dbg & DBG_ONEHOT_NO_COMPACT) ? 1 : 0), "mlp_shared");
         else if (pl.wino()) {
             // Winograd ACE path: hidden activations (+ the one-hot planes of a styled ACE, which feed the style k-steps) in one
             // persistent pass into the padded planes the ACE kernels read (conv_wino.h WINO_AXOFF), whole 64-byte groups of pixels
@@ -1603,7 +1603,7 @@ struct Runner {
             ip.onepass = m.opt.int_onepass;     // (tile4 kernel: 128 key slots and the narrow channel step for code-dense blocks)
             // (tile4 kernel, r >= 128: 0 = whole 128-byte lines that hold an interior pixel, ace_sparse.hip; sean.dbg bit 134217728: the
             //  block rule of rounds 3-5 for A/B)
-            ip.fill_min = (x_up && r < 128) ? 257 : ((r >= 128 && !(m.opt.dbg & 134217728)) ? 0 : 128);
+            ip.fill_min = (x_up && r < 128) ? 257 : ((r >= 128 && !(m.opt.dbg & DBG_INTERIOR_FILL128)) ? 0 : 128);
             if (mode.overlap) {
                 // beside the boundary conv of the same ACE (disjoint output pixels -- so no block may fill its boundary pixels),
                 // on the few CUs of the side stream; the consumer of `out` waits for ev_int below
@@ -1673,8 +1673,8 @@ struct Runner {
         p.in_scale_inv = 1.f / a.actv_scale;
         p.out_scale = a.out_scale;
         p.out_amax = m.amax_slots + 2 * a.index;
-        if ((m.opt.dbg & 256) && a.index == m.opt.dbg_sel) p.partial = m.splitk_ws;      // cycle stamps of this launch (profiling)
-        else p.dbg &= ~256;
+        if ((m.opt.dbg & DBG_STAMP) && a.index == m.opt.dbg_sel) p.partial = m.splitk_ws;      // cycle stamps of this launch (profiling)
+        else p.dbg &= ~DBG_STAMP;
         return p;
     }
     double dense_bytes(const AcePlan& p, const AceIO& io) const {
@@ -1697,16 +1697,16 @@ struct Runner {
         ip.out_scale = a.out_scale;
         ip.out_amax = m.amax_slots + 2 * a.index;
         ip.bf16 = m.opt.terms == 2;
-        ip.single = (m.opt.use_sh16 && m.opt.terms != 3 && !(m.opt.dbg & 268435456)) ? 1 : 0;      // (dbg bit: A/B)
-        ip.variant = m.opt.use_sh16 ? (compact ? 1 : 0) : (CH_ABL(m.opt.dbg & 65536) ? 1 : (CH_ABL(m.opt.dbg & 1048576) ? 2 : 0));
+        ip.single = (m.opt.use_sh16 && m.opt.terms != 3 && !(m.opt.dbg & DBG_INTERIOR_NO_SINGLE)) ? 1 : 0;      // (dbg bit: A/B)
+        ip.variant = m.opt.use_sh16 ? (compact ? 1 : 0) : (CH_ABL(m.opt.dbg & DBG_INTERIOR_VEC4) ? 1 : (CH_ABL(m.opt.dbg & DBG_INTERIOR_SECTORS) ? 2 : 0));
         // blocks of 32 x 8 pixels; mostly-interior blocks write every pixel (the conv below overwrites the boundary pixels).
         // Exact-f32 pass: filling pays only where x is read at full size (measured, tools/interior_bench.hip).
         // dbg bit 2097152: the row-shaped kernels of the first version (A/B)
-        ip.impl = CH_ABL(m.opt.dbg & 2097152) ? 1 : 0;
+        ip.impl = CH_ABL(m.opt.dbg & DBG_INTERIOR_ROWS) ? 1 : 0;
         ip.fill_min = m.opt.use_sh16 ? 128 : (x_up ? 257 : 128);
         // (impl 2, four pixels per thread: 10 % ahead at 512^2 in tools/interior_bench.hip, no difference in the generator
         // step -- 159.7 vs 159.9 images/s -- so the one-pixel kernel stays; dbg bit 16777216 selects it)
-        if (!m.opt.use_sh16 && CH_ABL(m.opt.dbg & 16777216) && r >= 128) {
+        if (!m.opt.use_sh16 && CH_ABL(m.opt.dbg & DBG_INTERIOR_TILE4) && r >= 128) {
             ip.impl = 2;
             ip.fill_min = 128;
         }
@@ -1749,7 +1749,7 @@ struct Runner {
         c.act = ACT_NONE;
         c.partial = m.splitk_ws;
         c.partial_cap = m.splitk_cap;
-        c.dbg &= ~256;
+        c.dbg &= ~DBG_STAMP;
         timed(1, dense_flops(pl), dense_bytes(pl, io), [&] {
             check(conv_plain3(c, st), "spade conv (plain, split-K)");
             check(ace_finish_f32(m.gb_small, rowsP, io.x, io.x_up, a.bias_g, a.bias_b, a.bn_a, a.bn_d, a.nv, io.noise, io.nf, pl.lab, q.lut,
@@ -1771,7 +1771,7 @@ struct Runner {
 
     // fuse: optional (weights, input) of a 1x1 conv added into this 3x3 conv's accumulators (f16x3 path, W >= 32, no split-K)
     bool can_fuse_1x1(const ConvLayer& w, int r) const {
-        return !(m.opt.dbg & 32) && w.KS == 3 && r >= 32 && !conv_few_tiles(w.Cout, (long long)B * r * r);
+        return !(m.opt.dbg & DBG_NO_FUSE_1X1) && w.KS == 3 && r >= 32 && !conv_few_tiles(w.Cout, (long long)B * r * r);
     }
     // one plain conv call of this chunk as the routes see it (net_common.h): the handle's environment, the residual, split-K scratch
     ConvOpts conv_opts(const float* res, int res_up) const {
@@ -1889,7 +1889,7 @@ struct ZencRunner {
     // the ConvTranspose and the InstanceNorm + lrelu that follows it
     void conv_transpose() {
         if (f16path) {
-            if (m.opt.dbg & 16384) {         // the earlier form, kept for comparison: 3x3 conv over the zero-inserted x2 view
+            if (m.opt.dbg & DBG_ZENC_ZEROINS) {         // the earlier form, kept for comparison: 3x3 conv over the zero-inserted x2 view
                 ConvParams t = sh16(m.z10, m.dx, m.hs, h4 * h4, h2);
                 t.in_mode = IN_UP2_ZEROINS;
                 ck(conv_sh16_plain(t, 3, st), "zenc convT (f16x3)");
@@ -2163,11 +2163,11 @@ SeanModel::ChunkMode SeanModel::chunk_mode(int B, int S) const {
     c.project_all = fcmu_batched && !opt.use_sh16 && (B * LABEL_NC > 64 || opt.batch_inv);
     c.grouped = c.project_all && lut_groups && lut_ngroups > 0;
     // interactive-size jobs: everything that depends on labels / codes only runs ahead on the side stream
-    const bool side_ok = side && !prof_on && !(opt.dbg & 4096);
+    const bool side_ok = side && !prof_on && !(opt.dbg & DBG_NO_SIDE_STREAM);
     c.prepass = side_ok && overlap_on && large && c.grouped;      // large job on an overlap handle
     c.overlap = c.prepass && gtab_side;
     if (c.prepass || (side_ok && ahead_full && !large)) c.ahead = ChunkMode::FULL;
-    else if (side_ok && (fcmu_batched || !opt.use_sh16) && !(opt.dbg & 8192) && !c.grouped) c.ahead = ChunkMode::LUTS;
+    else if (side_ok && (fcmu_batched || !opt.use_sh16) && !(opt.dbg & DBG_NO_LUT_AHEAD) && !c.grouped) c.ahead = ChunkMode::LUTS;
     c.prologue = pro_on && !prof_on && c.ahead != ChunkMode::FULL && large;
     return c;
 }

@@ -142,8 +142,8 @@ struct SeanOptions {
     int sparse_min_r = 64;                     // option "sean.sparse_min": smallest resolution served by the sparse path
     long long ahead_pixels = -1;               // option "sean.ahead": largest B*S*S served in run-ahead mode (-1: default 2 x 512^2; build() resolves it
                                                //   into SeanModel::ahead_limit)
-    int dbg = 0;               // perf experiments (conv_mfma.h ConvParams::dbg)
-    int dbg_sel = 16;          // dbg bit 256: index of the ACE launch whose tiles are cycle-stamped
+    int dbg = 0;               // perf experiments: bits of chk::Dbg (dbg_bits.h)
+    int dbg_sel = 16;          // DBG_STAMP: index of the ACE launch whose tiles are cycle-stamped
 };
 
 struct SeanModel {

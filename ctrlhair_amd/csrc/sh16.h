@@ -21,6 +21,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wave_ops.h"
+
 namespace chk {
 
 constexpr float SH16_MAX = 65504.f;
@@ -64,12 +66,6 @@ __device__ __forceinline__ void sh16_split_any(float v, float s, int bf16, _Floa
     }
 }
 
-__device__ __forceinline__ float sh16_wave_max(float m) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-    return m;
-}
-
 // Record a wave's maximum in a slot.  Same-address atomics serialise in L2 (~13 ns each, measured: 32k waves of an
 // elementwise kernel spent 0.38 ms there), so the slot is read first and the atomic only issued by waves that would raise
 // it -- a stale read costs an unnecessary atomic, never a missed one (the slot only grows).  Call from one lane per wave.
@@ -83,7 +79,7 @@ __device__ __forceinline__ void sh16_slot_max(unsigned* slot, float v) {
 constexpr int SH16_EW_THREADS = 1024, SH16_EW_BLOCKS = 512;
 __device__ __forceinline__ void sh16_block_slot_max(unsigned* slot, float v) {
     __shared__ float s_wmax[16];
-    v = sh16_wave_max(v);
+    v = wave_max(v);
     if ((threadIdx.x & 63) == 0) s_wmax[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0 && slot) {

@@ -161,7 +161,8 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   ch_finalize; a handle finalised with 0 has no classification buffers and rejects 1 afterwards (CH_ERR_STATE).
  * "sean.sparse_min", "sean.sparse_th", "sean.sh16_compact": tuning knobs of that reduction (before ch_finalize).
  * "sean.dbg": profiling switches.  The bits that skip work (wrong results) or select superseded kernel versions exist only in
- *   libraries built with -DCH_ABLATE (make -C ctrlhair_amd/csrc ABLATE=1); the default build rejects them (CH_ERR_ARG).
+ *   libraries built with -DCH_ABLATE (make -C ctrlhair_amd/csrc ABLATE=1); the default build rejects them (CH_ERR_ARG).  Every bit
+ *   is listed, with its value and meaning, in ctrlhair_amd/csrc/dbg_bits.h.
  * "sean.dbg_sel" (default 16; any time): index of the ACE launch that "sean.dbg" bit 256 cycle-stamps. */
 int  ch_set_option(ch_handle* h, const char* key, int value);
 
