@@ -125,7 +125,8 @@ __host__ __device__ inline AceCode ace_code_decode(int code) {
 }
 __host__ __device__ inline int ace_frame_code(int o, int A, int s) { return ACE_PAIR_CODES + ((o * 19 + A) * 4 + (s - 1)); }
 hipError_t ace_classify(const uint8_t* lab, uint8_t* u5, uint8_t* need, uint16_t* list, int* cnt, int B, int H, int W, int TH,
-                        hipStream_t s, uint16_t* e16 = nullptr, bool frame = false);
+                        hipStream_t s, uint16_t* e16 = nullptr, bool frame = false,
+                        const int* memo_hit = nullptr);      // memo_hit: device word of the label memo (kernels.h); returns at once where it reads 1
 // E[code][gamma|beta][C] (float) from the column / row sums of the SPADE gamma/beta weights W6[gb][k][6][C] (double; 0..2: sum over dy of
 // tap (dy, dx = -1, 0, 1), 3..5: sum over dx of tap (dy = -1, 0, 1)) and the hidden vectors hv[orientation][ACE_EDGE_HV][128] (double; index
 // 0..18: a_j, 19 + (A * 19 + B) * 2 + (0: window X X Y = AAB | 1: window X Y Y = ABB), 741 + A * 2 + (0: window OUTSIDE A A | 1: window

@@ -45,7 +45,8 @@ template <int TH>
 __global__ __launch_bounds__(32 * TH) void ace_classify_kernel(const uint8_t* __restrict__ lab, uint8_t* __restrict__ u5,
                                                              uint8_t* __restrict__ need, uint16_t* __restrict__ list,
                                                              int* __restrict__ cnt, int H, int W, int tiles_x, int tiles_y,
-                                                             uint16_t* __restrict__ e16, bool frame) {
+                                                             uint16_t* __restrict__ e16, bool frame, const int* __restrict__ memo_hit) {
+    if (memo_hit && *memo_hit) return;      // (label memo, kernels.h: the maps and lists of the previous call stand)
     constexpr int NT = 32 * TH, PW = 38, PH = TH + 6, BW = 34, BH = TH + 2, NW = NT / 64;
     __shared__ uint8_t patch[PH * PW];       // labels of the tile + 3 pixels around it (255 outside the image)
     __shared__ uint8_t bflag[BH * BW];       // boundary flags of the tile + 1 pixel around it
@@ -129,11 +130,11 @@ __global__ __launch_bounds__(32 * TH) void ace_classify_kernel(const uint8_t* __
 }
 
 hipError_t ace_classify(const uint8_t* lab, uint8_t* u5, uint8_t* need, uint16_t* list, int* cnt, int B, int H, int W, int TH,
-                        hipStream_t s, uint16_t* e16, bool frame) {
+                        hipStream_t s, uint16_t* e16, bool frame, const int* memo_hit) {
     const int tx = (W + 31) / 32, ty = (H + TH - 1) / TH;
     frame = frame && e16;
-    if (TH == 8) hipLaunchKernelGGL(ace_classify_kernel<8>, dim3(B * tx * ty), dim3(256), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16, frame);
-    else if (TH == 16) hipLaunchKernelGGL(ace_classify_kernel<16>, dim3(B * tx * ty), dim3(512), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16, frame);
+    if (TH == 8) hipLaunchKernelGGL(ace_classify_kernel<8>, dim3(B * tx * ty), dim3(256), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16, frame, memo_hit);
+    else if (TH == 16) hipLaunchKernelGGL(ace_classify_kernel<16>, dim3(B * tx * ty), dim3(512), 0, s, lab, u5, need, list, cnt, H, W, tx, ty, e16, frame, memo_hit);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -733,6 +733,23 @@ int ch_sean_scale_report(ch_handle* h, float* host_out, int n) {
     return CH_OK;
 }
 
+// a query, like ch_sean_noise_floats: the value is the result, -1 says that there is none (ch_last_error says why)
+long long ch_sean_label_memo_stats(ch_handle* h) {
+    if (!h) return -1;
+    if (!h->sean_ready) {
+        fail(h, CH_ERR_STATE, "ch_sean_label_memo_stats: SEAN weights not finalized");
+        return -1;
+    }
+    DeviceGuard guard(h->device);
+    int calls = 0, hits = 0;
+    const std::string e = h->sean.label_memo_stats(&calls, &hits);
+    if (!e.empty()) {
+        fail(h, CH_ERR_HIP, "ch_sean_label_memo_stats: " + e);
+        return -1;
+    }
+    return (long long)calls << 32 | (long long)(unsigned)hits;
+}
+
 int ch_sean_debug_read(ch_handle* h, void* host_out, size_t bytes) {
     if (!h || !host_out) return CH_ERR_ARG;
     if (!h->sean_ready || !h->sean.splitk_ws) return fail(h, CH_ERR_STATE, "ch_sean_debug_read: SEAN weights not finalized");
@@ -795,6 +812,9 @@ const OptRow OPTION_TABLE[] = {
     // exact-f32 Winograd path, handles beyond the run-ahead sizes: 1 = the label / code-only products of the ACEs from grouped launches at the start
     // of a chunk (default; off by itself with sean.f16x3, sean.overlap or while profiling is enabled), 0 = every ACE launches its own, inline
     {"sean.prologue", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(prologue)},
+    // handles with the ACE prologue: 1 = the label-only products of a chunk stay on the device and their launches return at once while the calls
+    // bring the same label maps (default; sean_model.h memo_state), 0 = no memo: every call rebuilds them
+    {"sean.label_memo", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(label_memo)},
     {"sean.overlap", BY_SEAN, CLAMP, 0, MAXI, SEAN_FIELD(overlap)},        // CUs of the side streams of the overlap mode (sean_model.h), 0 = off
     {"sean.wino4_force", NEVER, BOOL, 0, 0, SEAN_FIELD(wino4_force)},        // 1 = F(4x4,3x3) wherever the shape allows, even with fewer tasks than CUs (tests / measurements)
     {"sean.patch", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(patch)},                  // 1 = pre-gathered hidden-activation patches for levels with few boundary quads (default), 0 = planes only
@@ -835,6 +855,7 @@ int ch_set_option(ch_handle* h, const char* key, int value) {
         if (frozen) return fail(h, CH_ERR_STATE, std::string("ch_set_option(") + key + ") must precede ch_finalize");
         if (int rc = r.guard ? r.guard(h, value) : CH_OK) return rc;
         r.set(h, r.map == BOOL ? value != 0 : (r.map == CLAMP ? std::max(r.lo, std::min(r.hi, value)) : value));
+        ++h->sean.memo_epoch;      // (label memo: what an earlier call left on the device was built under other options)
         return CH_OK;
     }
     return fail(h, CH_ERR_ARG, std::string("unknown option '") + key + "'");

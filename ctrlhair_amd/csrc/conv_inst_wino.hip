@@ -158,6 +158,14 @@ hipError_t conv_wino_ace(WinoAceParams p, hipStream_t s) {
         if (p.nrt > 2 * 65535) return hipErrorInvalidValue;
         p.K = 128 + (p.wsty ? 20 : 0);
         int cus = 0;
+        if (p.cache) {      // unstyled ACE with the label memo: the conv (or nothing, on a hit) + the pass over the stored gamma / beta (or nothing)
+            if (p.wsty || !p.memo_hit || !p.patch || !p.patch_mode || p.cache_cap < 1) return hipErrorInvalidValue;
+            hipError_t e = dyn_lds<wino_ace_gather_kernel<1>>(winog::LDS_BYTES, &cus);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(wino_ace_gather_kernel<1>, dim3(cus), dim3(512), winog::LDS_BYTES, s, p);
+            hipLaunchKernelGGL(wino_ace_cached_kernel<0>, dim3(p.cache_cap < 4 * cus ? p.cache_cap : 4 * cus), dim3(512), 0, s, p);
+            return hipGetLastError();
+        }
         hipError_t e = dyn_lds<wino_ace_gather_kernel<0>>(winog::LDS_BYTES, &cus);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(wino_ace_gather_kernel<0>, dim3(cus), dim3(512), winog::LDS_BYTES, s, p);
@@ -321,19 +329,23 @@ __device__ __forceinline__ int wino_geo_level(const WinoGeoGroup& g, int tile) {
     return k;
 }
 __global__ __launch_bounds__(128) void wino_quad_list_grouped_kernel(WinoGeoGroup g) {
+    if (g.memo_hit && *g.memo_hit) return;
     const WinoGeoGroup::Level& L = g.l[wino_geo_level(g, (int)blockIdx.x)];
     wino_quad_list_block<16>(L.u5, L.qlist, L.qcnt, L.pcnt, L.H, L.W, L.W / 32, L.H / 16, (int)blockIdx.x - L.tile0);
 }
 __global__ __launch_bounds__(1024) void wino_gather_scan_grouped_kernel(WinoGeoGroup g) {
+    if (g.memo_hit && *g.memo_hit) return;
     const WinoGeoGroup::Level& L = g.l[blockIdx.x / g.B];
     wino_gather_scan_block(L.qcnt, L.qoff, L.gq_n, (L.W / 32) * (L.H / 16), (int)(blockIdx.x % g.B));
 }
 __global__ __launch_bounds__(128) void wino_gather_fill_grouped_kernel(WinoGeoGroup g) {
+    if (g.memo_hit && *g.memo_hit) return;
     const WinoGeoGroup::Level& L = g.l[wino_geo_level(g, (int)blockIdx.x)];
     wino_gather_fill_block(L.qlist, L.qcnt, L.qoff, L.gq, L.gq_cap, L.W / 32, L.H / 16, (int)blockIdx.x - L.tile0);
 }
 // blocks 0 .. nw - 1: the task lists; blocks nw .. nw + nl - 1: the chunk bases and patch flags of the levels (wino_chunk_base's loop)
 __global__ __launch_bounds__(1024) void wino_geo_tail_grouped_kernel(WinoGeoGroup g) {
+    if (g.memo_hit && *g.memo_hit) return;
     if ((int)blockIdx.x < g.nw) {
         const WinoGeoGroup::Work& w = g.w[blockIdx.x];
         const WinoGeoGroup::Level& L = g.l[w.level];

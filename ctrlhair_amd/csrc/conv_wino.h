@@ -604,6 +604,13 @@ struct WinoAceParams {
     const float* patch;     // patch buffer, or null
     const int* chunk_base;  // [B + 1]
     const int* patch_mode;  // device flag
+    // gather mode, unstyled ACE with the label memo (sean_model.h memo_state): gamma and beta of the boundary quads after the output transform
+    // depend on labels and weights alone.  While the level is in patch mode the launch that runs the conv also stores them, per task and
+    // lane, as [task][unit 8 = 2 channel + (gamma | beta)][thread 512][4 pixels] (a wave's store: 1 KB, contiguous); on a hit (*memo_hit == 1)
+    // it returns at once and wino_ace_cached_kernel, launched behind it, walks the same task list and runs the same epilogue on the stored values.
+    float* cache;           // [cache_cap][8][512][4], or null
+    int cache_cap;          // tasks the cache holds (the launches use it only while total[0] <= cache_cap)
+    const int* memo_hit;
     int nrt, ntx, nty, K;   // set by the launcher
 };
 // Tile height 32 (16 x 16 quads) or 16 (16 x 8 quads), chosen per resolution level by the caller: a sparse tile must hold enough
@@ -932,7 +939,95 @@ constexpr int NPD = 2, PDW = 4096, NST = 5, ADW2 = 2 * wino::ADW, SDW = PDW + AD
 constexpr int LDS_BYTES = NST * SDW * 4;                         // 128 KB
 }  // namespace winog
 
-template <int DUMMY>
+// entry `slot` of task t's chunk of 64 quads (clamped to the sample's list), and what a lane needs to know of task t: sample, row tile,
+// first pixel of its quad, whether its wave has work in the task (active) and whether its own slot holds a quad (valid)
+__device__ __forceinline__ unsigned winog_task_quad(const WinoAceParams& p, int t, int slot) {
+    const unsigned wk = p.work[t];
+    const int b = wk & 31, chunk = (wk >> 5) & 2047;
+    const int nq = p.gq_n[b];
+    int qi = chunk * 64 + slot;
+    qi = qi < nq ? qi : nq - 1;
+    return p.gq[(long long)b * p.gq_cap + qi];
+}
+struct WinogCtx { int b, rt, y, x; bool active, valid; };
+__device__ __forceinline__ WinogCtx winog_task_ctx(const WinoAceParams& p, int t, int wave, int cslot) {
+    WinogCtx c;
+    const unsigned wk = p.work[t];
+    c.b = wk & 31;
+    const int chunk = (wk >> 5) & 2047, pair = wk >> 16;
+    const int nq = p.gq_n[c.b];
+    c.rt = 2 * pair + (wave >> 2);
+    c.active = chunk * 64 + (wave & 3) * 16 < nq && c.rt < p.nrt;
+    c.valid = c.active && chunk * 64 + cslot < nq;
+    const unsigned q = winog_task_quad(p, t, cslot);
+    c.y = (int)(q >> 16);
+    c.x = (int)(q & 0xFFFFu);
+    return c;
+}
+// The ACE epilogue of a lane of the gather kernel: four channels c0 .. c0 + 3 (c0 = 16 rt + 4 kk) x the 2 x 2 pixels of its quad.
+// gamma_beta(i, g, e) hands over gamma and beta of channel c0 + i at the four pixels (00, 01, 10, 11), without the biases -- from the
+// accumulators (wino_ace_gather_kernel) or from the cache (wino_ace_cached_kernel).  The modulation is spelled out product by product, no
+// contraction left to the compiler, so that every kernel that runs it gives the same bits: these are the fused operations hipcc chose for the
+// expression (a x + n noise + d) (1 + bias_g + gamma) + (bias_b + beta) in this kernel before it was shared (pixel 00 rounds n noise and fuses
+// a x, the other three round a x and fuse n noise).
+template <class F>
+__device__ __forceinline__ void winog_ace_epilogue(const WinoAceParams& p, const WinogCtx& cur, int kk, F gamma_beta) {
+#pragma clang fp contract(off)
+    const int HW = p.H * p.W;
+    const int b = cur.b, y = cur.y, x = cur.x;
+    const int xW = p.W >> p.x_up, xHW = xW * (p.H >> p.x_up);
+    const float* nzp = p.noise + (long long)b * p.noise_bstride + (long long)x * p.H + y;      // plane layout [W][H]
+    const float2 nz0 = *reinterpret_cast<const float2*>(nzp), nz1 = *reinterpret_cast<const float2*>(nzp + p.H);
+    const int c0 = cur.rt * 16 + 4 * kk, c0c = c0 < p.C ? c0 : p.C - 4;
+    const float4 pg = *reinterpret_cast<const float4*>(p.bias_g + c0c), pb = *reinterpret_cast<const float4*>(p.bias_b + c0c);
+    const float4 pa = *reinterpret_cast<const float4*>(p.bn_a + c0c), pd = *reinterpret_cast<const float4*>(p.bn_d + c0c);
+    const float4 pn = *reinterpret_cast<const float4*>(p.nv + c0c);
+    float2 xr0[4], xr1[4];
+    const float* xp0 = p.x + ((long long)b * p.C + c0c) * xHW;
+    if (p.x_up) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float xv = xp0[(long long)i * xHW + (y >> 1) * xW + (x >> 1)];
+            xr0[i] = xr1[i] = make_float2(xv, xv);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            xr0[i] = *reinterpret_cast<const float2*>(xp0 + (long long)i * xHW + y * xW + x);
+            xr1[i] = *reinterpret_cast<const float2*>(xp0 + (long long)i * xHW + (y + 1) * xW + x);
+        }
+    }
+    const float g_[4] = {pg.x, pg.y, pg.z, pg.w}, b_[4] = {pb.x, pb.y, pb.z, pb.w};
+    const float a_[4] = {pa.x, pa.y, pa.z, pa.w}, d_[4] = {pd.x, pd.y, pd.z, pd.w}, n_[4] = {pn.x, pn.y, pn.z, pn.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + i;
+        float g[4], e[4];
+        gamma_beta(i, g, e);
+        const float gb = 1.f + g_[i], bb = b_[i];
+        const float t00 = __builtin_fmaf(a_[i], xr0[i].x, n_[i] * nz0.x) + d_[i];
+        const float t01 = __builtin_fmaf(n_[i], nz1.x, a_[i] * xr0[i].y) + d_[i];
+        const float t10 = __builtin_fmaf(n_[i], nz0.y, a_[i] * xr1[i].x) + d_[i];
+        const float t11 = __builtin_fmaf(n_[i], nz1.y, a_[i] * xr1[i].y) + d_[i];
+        float o00 = __builtin_fmaf(t00, gb + g[0], bb + e[0]);
+        float o01 = __builtin_fmaf(t01, gb + g[1], bb + e[1]);
+        float o10 = __builtin_fmaf(t10, gb + g[2], bb + e[2]);
+        float o11 = __builtin_fmaf(t11, gb + g[3], bb + e[3]);
+        if (p.act != ACT_NONE) {
+            o00 = apply_act(o00, p.act); o01 = apply_act(o01, p.act);
+            o10 = apply_act(o10, p.act); o11 = apply_act(o11, p.act);
+        }
+        if (cur.valid && c < p.C) {
+            float* op = p.out + ((long long)b * p.C + c) * HW + y * p.W + x;
+            *reinterpret_cast<float2*>(op) = make_float2(o00, o01);
+            *reinterpret_cast<float2*>(op + p.W) = make_float2(o10, o11);
+        }
+    }
+}
+
+// MEMO = 1: the launch of an unstyled ACE with the label memo (WinoAceParams::cache): returns at once on a hit in patch mode, else stores
+// gamma and beta of its tasks beside running its epilogue.  MEMO = 0: neither.
+template <int MEMO>
 __global__ __launch_bounds__(512, 1) void wino_ace_gather_kernel(const WinoAceParams p) {
     using namespace wino;
     constexpr int WA_NST = winog::NST, WA_NLD = winog::NLD, WA_PDW = winog::PDW;
@@ -943,6 +1038,11 @@ __global__ __launch_bounds__(512, 1) void wino_ace_gather_kernel(const WinoAcePa
     const int n = lane & 15, kk = lane >> 4;
     const int G = gridDim.x;
     const int ntasks = p.total[0];
+    bool caching = false;
+    if constexpr (MEMO != 0) {
+        caching = __builtin_amdgcn_readfirstlane(*p.patch_mode) == 1 && ntasks <= p.cache_cap;
+        if (caching && __builtin_amdgcn_readfirstlane(*p.memo_hit) == 1) return;      // (wino_ace_cached_kernel serves this call)
+    }
     // static split: block lb takes tasks lb, lb + G, ... (the row pairs of a chunk of quads are consecutive entries: one XCD, the same
     // time); dynamic: tasks claimed from the XCD's counter (wino_claim_task).  This kernel's ring fills all 160 KB of LDS, so the
     // claimed task travels from wave 0 to the other waves through device memory: p.claim[16 + 2 blockIdx + parity], written after
@@ -969,7 +1069,6 @@ __global__ __launch_bounds__(512, 1) void wino_ace_gather_kernel(const WinoAcePa
     }
     if (lb >= ntasks) return;
     const int nks = 32, nk = nks + (p.wsty ? 5 : 0);
-    const int HW = p.H * p.W;
     constexpr unsigned SB = winog::SDW * 4, RING = WA_NST * SB;
     const unsigned lds0 = (unsigned)(size_t)(wino_lds_void*)smem;
 
@@ -985,14 +1084,7 @@ __global__ __launch_bounds__(512, 1) void wino_ace_gather_kernel(const WinoAcePa
     unsigned so_in = 0, so_a = 0;
     const bool from_patch = p.patch != nullptr && p.patch_mode != nullptr && __builtin_amdgcn_readfirstlane(*p.patch_mode) == 1;
     const unsigned APL4 = from_patch ? 4096u : (unsigned)APL * 4u;      // bytes from one channel's patch rows to the next one's
-    auto task_quad = [&](int t, int slot) {                       // entry `slot` of task t's chunk (clamped to the sample's list)
-        const unsigned wk = p.work[t];
-        const int b = wk & 31, chunk = (wk >> 5) & 2047;
-        const int nq = p.gq_n[b];
-        int qi = chunk * 64 + slot;
-        qi = qi < nq ? qi : nq - 1;
-        return p.gq[(long long)b * p.gq_cap + qi];
-    };
+    auto task_quad = [&](int t, int slot) { return winog_task_quad(p, t, slot); };
     auto issue_task = [&](int t, unsigned q) {                    // q = task_quad(t, lane), fetched a task ahead
         const unsigned wk = p.work[t];
         const int ib = wk & 31, pair = wk >> 16;
@@ -1039,21 +1131,8 @@ __global__ __launch_bounds__(512, 1) void wino_ace_gather_kernel(const WinoAcePa
 #pragma unroll
         for (int m = 0; m < 2; ++m) acc[x][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int cslot = (wave & 3) * 16 + n;                        // this lane's quad slot; row tile 2 * pair + (wave >> 2)
-    struct Ctx { int b, rt, y, x; bool active, valid; };
-    auto task_ctx = [&](int t) {
-        Ctx c;
-        const unsigned wk = p.work[t];
-        c.b = wk & 31;
-        const int chunk = (wk >> 5) & 2047, pair = wk >> 16;
-        const int nq = p.gq_n[c.b];
-        c.rt = 2 * pair + (wave >> 2);
-        c.active = chunk * 64 + (wave & 3) * 16 < nq && c.rt < p.nrt;
-        c.valid = c.active && chunk * 64 + cslot < nq;
-        const unsigned q = task_quad(t, cslot);
-        c.y = (int)(q >> 16);
-        c.x = (int)(q & 0xFFFFu);
-        return c;
-    };
+    using Ctx = WinogCtx;
+    auto task_ctx = [&](int t) { return winog_task_ctx(p, t, wave, cslot); };
     Ctx cur = task_ctx(lb);
     const int aoff = WA_PDW + (wave >> 2) * ADW;
     const int boff = kk * 1024 + cslot * 4;                       // [channel][patch row][slot][4]
@@ -1176,58 +1255,24 @@ __global__ __launch_bounds__(512, 1) void wino_ace_gather_kernel(const WinoAcePa
         for (int c = nk - AHEAD; c < nk; ++c) kstep();
         unsigned jnext = 0;                                     // dynamic claiming: the task after next, answered during the epilogue
         if (dyn && more && tid == 0) jnext = __hip_atomic_fetch_add(p.claim + wino_xcc_id(), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // ---- ACE epilogue (as wino_ace_kernel) ---------------------------------------------------------------------------------
+        // ---- ACE epilogue (winog_ace_epilogue; gamma / beta: the output transform of the accumulators) -------------------------------
         if (cur.active) {
-            const int b = cur.b, y = cur.y, x = cur.x;
-            const int xW = p.W >> p.x_up, xHW = xW * (p.H >> p.x_up);
-            const float* nzp = p.noise + (long long)b * p.noise_bstride + (long long)x * p.H + y;      // plane layout [W][H]
-            const float2 nz0 = *reinterpret_cast<const float2*>(nzp), nz1 = *reinterpret_cast<const float2*>(nzp + p.H);
-            const int c0 = cur.rt * 16 + 4 * kk, c0c = c0 < p.C ? c0 : p.C - 4;
-            const float4 pg = *reinterpret_cast<const float4*>(p.bias_g + c0c), pb = *reinterpret_cast<const float4*>(p.bias_b + c0c);
-            const float4 pa = *reinterpret_cast<const float4*>(p.bn_a + c0c), pd = *reinterpret_cast<const float4*>(p.bn_d + c0c);
-            const float4 pn = *reinterpret_cast<const float4*>(p.nv + c0c);
-            float2 xr0[4], xr1[4];
-            const float* xp0 = p.x + ((long long)b * p.C + c0c) * xHW;
-            if (p.x_up) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float xv = xp0[(long long)i * xHW + (y >> 1) * xW + (x >> 1)];
-                    xr0[i] = xr1[i] = make_float2(xv, xv);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    xr0[i] = *reinterpret_cast<const float2*>(xp0 + (long long)i * xHW + y * xW + x);
-                    xr1[i] = *reinterpret_cast<const float2*>(xp0 + (long long)i * xHW + (y + 1) * xW + x);
-                }
-            }
-            const float g_[4] = {pg.x, pg.y, pg.z, pg.w}, b_[4] = {pb.x, pb.y, pb.z, pb.w};
-            const float a_[4] = {pa.x, pa.y, pa.z, pa.w}, d_[4] = {pd.x, pd.y, pd.z, pd.w}, n_[4] = {pn.x, pn.y, pn.z, pn.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = c0 + i;
-                float M[16], g00, g01, g10, g11, e00, e01, e10, e11;
+            winog_ace_epilogue(p, cur, kk, [&](int i, float (&g)[4], float (&e)[4]) {
+                float M[16];
 #pragma unroll
                 for (int xi = 0; xi < 16; ++xi) M[xi] = acc[xi][0][i];
-                wino_out_transform(M, g00, g01, g10, g11);
+                wino_out_transform(M, g[0], g[1], g[2], g[3]);
 #pragma unroll
                 for (int xi = 0; xi < 16; ++xi) M[xi] = acc[xi][1][i];
-                wino_out_transform(M, e00, e01, e10, e11);
-                const float gb = 1.f + g_[i], bb = b_[i];
-                float o00 = (a_[i] * xr0[i].x + n_[i] * nz0.x + d_[i]) * (gb + g00) + (bb + e00);
-                float o01 = (a_[i] * xr0[i].y + n_[i] * nz1.x + d_[i]) * (gb + g01) + (bb + e01);
-                float o10 = (a_[i] * xr1[i].x + n_[i] * nz0.y + d_[i]) * (gb + g10) + (bb + e10);
-                float o11 = (a_[i] * xr1[i].y + n_[i] * nz1.y + d_[i]) * (gb + g11) + (bb + e11);
-                if (p.act != ACT_NONE) {
-                    o00 = apply_act(o00, p.act); o01 = apply_act(o01, p.act);
-                    o10 = apply_act(o10, p.act); o11 = apply_act(o11, p.act);
+                wino_out_transform(M, e[0], e[1], e[2], e[3]);
+                if constexpr (MEMO != 0) {
+                    if (caching) {
+                        float4* cp = reinterpret_cast<float4*>(p.cache) + ((long long)ct * 8 + 2 * i) * 512 + tid;
+                        cp[0] = make_float4(g[0], g[1], g[2], g[3]);
+                        cp[512] = make_float4(e[0], e[1], e[2], e[3]);
+                    }
                 }
-                if (cur.valid && c < p.C) {
-                    float* op = p.out + ((long long)b * p.C + c) * HW + y * p.W + x;
-                    *reinterpret_cast<float2*>(op) = make_float2(o00, o01);
-                    *reinterpret_cast<float2*>(op + p.W) = make_float2(o10, o11);
-                }
-            }
+            });
         }
 #pragma unroll
         for (int x2 = 0; x2 < 16; ++x2)
@@ -1242,6 +1287,33 @@ __global__ __launch_bounds__(512, 1) void wino_ace_gather_kernel(const WinoAcePa
         ct = tn;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no LDS-DMA may outlive the block
+}
+
+// The hit path of an unstyled ACE with the label memo: one block per task of the gather kernel's list (grid-stride), the same lanes, the
+// stored gamma / beta instead of the conv.  Returns at once unless the gather launch ahead of it did (same conditions, same words).
+template <int DUMMY>      // (a template like the kernels above: the header is included by several translation units)
+__global__ __launch_bounds__(512) void wino_ace_cached_kernel(const WinoAceParams p) {
+    const int ntasks = p.total[0];
+    if (!(__builtin_amdgcn_readfirstlane(*p.patch_mode) == 1 && ntasks <= p.cache_cap && __builtin_amdgcn_readfirstlane(*p.memo_hit) == 1)) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 15, kk = lane >> 4;
+    const int cslot = (wave & 3) * 16 + n;
+    for (int t = blockIdx.x; t < ntasks; t += gridDim.x) {
+        const WinogCtx cur = winog_task_ctx(p, t, wave, cslot);
+        if (!cur.active) continue;
+        const float4* cp = reinterpret_cast<const float4*>(p.cache) + (long long)t * 8 * 512 + tid;
+        float4 gv[4], ev[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            gv[i] = cp[(2 * i) * 512];
+            ev[i] = cp[(2 * i + 1) * 512];
+        }
+        winog_ace_epilogue(p, cur, kk, [&](int i, float (&g)[4], float (&e)[4]) {
+            g[0] = gv[i].x; g[1] = gv[i].y; g[2] = gv[i].z; g[3] = gv[i].w;
+            e[0] = ev[i].x; e[1] = ev[i].y; e[2] = ev[i].z; e[3] = ev[i].w;
+        });
+    }
 }
 
 inline bool wino_supported(int H, int W, int Cin) { return H % wino::TH == 0 && W % wino::TW == 0 && Cin % 8 == 0 && H >= 16; }
@@ -1307,6 +1379,7 @@ struct WinoGeoGroup {
     Level l[MAX_L];
     Work w[MAX_W];
     int nl, nw, B;
+    const int* memo_hit;        // optional (label memo, kernels.h): the four launches return at once where it reads 1
 };
 hipError_t wino_geometry_grouped(WinoGeoGroup& g, hipStream_t s);
 hipError_t wino_gather_worklist(const int* gq_n, const int* pcnt, int B, int tiles_per_sample, int nrt, unsigned* work, int* total, hipStream_t s);

@@ -8,7 +8,13 @@
 #include <vector>
 
 namespace chk {
-hipError_t label_downsample(const uint8_t* in, uint8_t* out, int B, int S, int r, hipStream_t s);
+// memo_hit (here and below; optional): device word of the label memo (SeanModel::memo_state); the kernel returns at once where it reads 1
+hipError_t label_downsample(const uint8_t* in, uint8_t* out, int B, int S, int r, hipStream_t s, const int* memo_hit = nullptr);
+// Label memo: the words of its device state, and the two launches at the start of an eligible chunk (compare `bytes` of labels with the
+// copy, 16-byte aligned both; then decide MEMO_HIT from MEMO_VALID, MEMO_DIFF and the key (B, S, epoch)) / of any other chunk (MEMO_VALID = 0)
+enum { MEMO_VALID = 0, MEMO_DIFF = 1, MEMO_HIT = 2, MEMO_KEY = 3, MEMO_CALLS = 6, MEMO_HITS = 7, MEMO_WORDS = 8 };
+hipError_t label_memo_begin(const uint8_t* labels, uint8_t* copy, long long bytes, int* state, int B, int S, int epoch, hipStream_t s);
+hipError_t label_memo_invalidate(int* state, hipStream_t s);
 // need (optional, [B][H][W]): pixels with need == 0 are not written (ace_sparse.h: nothing reads them)
 hipError_t onehot_conv3x3(const uint8_t* lab, const float* table, const float* bias, float* out, int B, int H, int W,
                           int K, int relu, hipStream_t s, int c4 = 0, const uint8_t* need = nullptr, int kout = 0);
@@ -47,6 +53,7 @@ struct HiddenGroup {
     };
     Entry e[MAX];
     int n, B;
+    const int* memo_hit;      // optional (label memo): the whole launch returns at once where it reads 1
 };
 hipError_t spade_hidden_wq_grouped(HiddenGroup& g, hipStream_t s);
 // the same activations as pre-gathered 4 x 4 patches of the boundary quads, chunk by chunk of 64 (conv_wino.h WinoAceParams::patch); both
@@ -57,7 +64,7 @@ hipError_t spade_hidden_patch(const uint8_t* lab, const unsigned* gq, const int*
 // body of the kernel that would not have returned at once (chunks with the ACE prologue, sean_model.cpp)
 hipError_t spade_hidden_level(const uint8_t* lab, const uint8_t* u5, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,
                               const float* table, const float* bias, float* out, float* patch, int B, int H, int W, int kout, int onehot, int pitch,
-                              int xoff, hipStream_t s);
+                              int xoff, hipStream_t s, const int* memo_hit = nullptr);      // memo_hit: returns at once on 1 in patch mode (`patch` then is the caller's to keep)
 hipError_t wino_chunk_base(const int* gq_n, int B, int cap_chunks, int* chunk_base, int* mode, hipStream_t s);
 // `scale`: power-of-two scale of an SH16 output / input tensor (sh16.h)
 hipError_t onehot_conv3x3_sh16(const uint8_t* lab, const float* table, const float* bias, void* out, int B, int H, int W,

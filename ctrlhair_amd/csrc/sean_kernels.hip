@@ -76,7 +76,8 @@ hipError_t ace_finish_f32(const float* gb, int rowsP, const float* x, int x_up, 
 // ---------------------------------------------------------------------------------------------------------
 // F.interpolate(seg, size, mode='nearest') on the label map (generator.py:75, normalization.py:115):
 // src = floor(dst * in/out); in/out is an integer here (S / r).
-__global__ void label_down_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int B, int S, int r) {
+__global__ void label_down_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int B, int S, int r, const int* __restrict__ memo_hit) {
+    if (memo_hit && *memo_hit) return;      // (label memo: the map of the previous call stands)
     const long long n = (long long)B * r * r;
     const int f = S / r;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -86,10 +87,56 @@ __global__ void label_down_kernel(const uint8_t* __restrict__ in, uint8_t* __res
     }
 }
 
-hipError_t label_downsample(const uint8_t* in, uint8_t* out, int B, int S, int r, hipStream_t s) {
+hipError_t label_downsample(const uint8_t* in, uint8_t* out, int B, int S, int r, hipStream_t s, const int* memo_hit) {
     const long long n = (long long)B * r * r;
     const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(label_down_kernel, dim3(grid), dim3(256), 0, s, in, out, B, S, r);
+    hipLaunchKernelGGL(label_down_kernel, dim3(grid), dim3(256), 0, s, in, out, B, S, r, memo_hit);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Label memo (sean_model.h SeanModel::memo_state): does this chunk bring the label maps of the previous one?  The compare kernel reads the
+// incoming maps and the handle's copy in 16-byte words; a word that differs is written into the copy and marks `diff`.  The one-thread
+// decision kernel then sets hit = valid && !diff && (the key of this enqueue == the stored key), re-arms the state and counts.  Every
+// memoized kernel reads `hit` once, at its top.  Nothing here depends on a value the host learns per call: the same sequence replays in a graph.
+__global__ __launch_bounds__(256) void label_memo_compare_kernel(const uint4* __restrict__ in, uint4* __restrict__ copy, long long n16, int* __restrict__ state) {
+    bool d = false;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n16; i += (long long)gridDim.x * 256) {
+        const uint4 a = in[i], c = copy[i];
+        if (a.x != c.x || a.y != c.y || a.z != c.z || a.w != c.w) {
+            copy[i] = a;
+            d = true;
+        }
+    }
+    if (__any(d) && (threadIdx.x & 63) == 0) atomicOr(state + MEMO_DIFF, 1);
+}
+__global__ void label_memo_decide_kernel(int* __restrict__ state, int B, int S, int epoch) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int hit = (state[MEMO_VALID] == 1 && state[MEMO_DIFF] == 0 && state[MEMO_KEY] == B && state[MEMO_KEY + 1] == S && state[MEMO_KEY + 2] == epoch) ? 1 : 0;
+    state[MEMO_HIT] = hit;
+    state[MEMO_VALID] = 1;
+    state[MEMO_DIFF] = 0;
+    state[MEMO_KEY] = B;
+    state[MEMO_KEY + 1] = S;
+    state[MEMO_KEY + 2] = epoch;
+    state[MEMO_CALLS] += 1;
+    state[MEMO_HITS] += hit;
+}
+__global__ void label_memo_invalidate_kernel(int* __restrict__ state) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) state[MEMO_VALID] = state[MEMO_HIT] = 0;
+}
+hipError_t label_memo_begin(const uint8_t* labels, uint8_t* copy, long long bytes, int* state, int B, int S, int epoch, hipStream_t s) {
+    if (!labels || !copy || !state || bytes <= 0 || (bytes & 15) || (reinterpret_cast<uintptr_t>(labels) & 15) || (reinterpret_cast<uintptr_t>(copy) & 15))
+        return hipErrorInvalidValue;
+    const long long n16 = bytes >> 4;
+    const int grid = (int)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048);
+    hipLaunchKernelGGL(label_memo_compare_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const uint4*>(labels), reinterpret_cast<uint4*>(copy), n16, state);
+    hipLaunchKernelGGL(label_memo_decide_kernel, dim3(1), dim3(64), 0, s, state, B, S, epoch);
+    return hipGetLastError();
+}
+hipError_t label_memo_invalidate(int* state, hipStream_t s) {
+    if (!state) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(label_memo_invalidate_kernel, dim3(1), dim3(64), 0, s, state);
     return hipGetLastError();
 }
 
@@ -387,6 +434,7 @@ __global__ __launch_bounds__(1024) void spade_hidden_wq_kernel(const uint8_t* __
 // ACE prologue (sean_model.cpp): the hidden planes of several ACEs from one launch -- block -> (entry, block of the entry); a block
 // keeps ONE label table in LDS, so the entries own disjoint runs of blocks
 __global__ __launch_bounds__(1024) void spade_hidden_wq_grouped_kernel(HiddenGroup g) {
+    if (g.memo_hit && *g.memo_hit) return;      // (label memo: every entry writes its own buffer, which still holds these planes)
     int k = 0;
     while (k + 1 < g.n && (int)blockIdx.x >= g.e[k + 1].start) ++k;
     const HiddenGroup::Entry& e = g.e[k];
@@ -402,7 +450,7 @@ bool spade_hidden_wq_supported(int H, int W) {
 
 __global__ void spade_hidden_level_kernel(const uint8_t* lab, const uint8_t* u5, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base,
                                           const int* mode, const float* table, const float* bias, float* out, float* patch, int B, int H, int W, int kout,
-                                          int onehot, int tcs, int pitch, int xoff);      // (below, beside the patch kernel)
+                                          int onehot, int tcs, int pitch, int xoff, const int* memo_hit);      // (below, beside the patch kernel)
 // LDS limit of the three kernels, once per device: the first call of any of their launchers sets all three
 static hipError_t spade_hidden_wq_attr(int& ncu) {
     return dyn_lds<spade_hidden_wq_kernel, spade_hidden_wq_grouped_kernel, spade_hidden_level_kernel>(hid::LDS_BYTES, &ncu);
@@ -529,13 +577,16 @@ __global__ __launch_bounds__(1024) void spade_hidden_level_kernel(const uint8_t*
                                                                   const int* __restrict__ gq_n, int gq_cap, const int* __restrict__ chunk_base,
                                                                   const int* __restrict__ mode, const float* __restrict__ table,
                                                                   const float* __restrict__ bias, float* __restrict__ out, float* __restrict__ patch, int B,
-                                                                  int H, int W, int kout, int onehot, int tcs, int pitch, int xoff) {
+                                                                  int H, int W, int kout, int onehot, int tcs, int pitch, int xoff,
+                                                                  const int* __restrict__ memo_hit) {
+    // label memo: `patch` is this ACE's own buffer and still holds the patches of these labels; the planes are shared by the level, so they are rebuilt
+    if (*mode == 1 && memo_hit && *memo_hit) return;
     if (*mode == 1) spade_hidden_patch_block(lab, gq, gq_n, gq_cap, chunk_base, table, bias, patch, B, H, W, kout, (int)blockIdx.x, (int)gridDim.x);
     else spade_hidden_wq_block(lab, u5, table, bias, out, B, H, W, kout, onehot, tcs, pitch, xoff, (int)blockIdx.x, (int)gridDim.x);
 }
 hipError_t spade_hidden_level(const uint8_t* lab, const uint8_t* u5, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,
                               const float* table, const float* bias, float* out, float* patch, int B, int H, int W, int kout, int onehot, int pitch,
-                              int xoff, hipStream_t s) {
+                              int xoff, hipStream_t s, const int* memo_hit) {
     if (B < 1 || B > 32 || kout != hid::K + (onehot ? 20 : 0) || !spade_hidden_wq_supported(H, W) || !mode || !chunk_base || !gq || !gq_n || !patch || !out)
         return hipErrorInvalidValue;
     if (pitch <= 0) { pitch = W; xoff = 0; }
@@ -543,7 +594,7 @@ hipError_t spade_hidden_level(const uint8_t* lab, const uint8_t* u5, const unsig
     int ncu = 0;
     if (hipError_t e = spade_hidden_wq_attr(ncu)) return e;
     hipLaunchKernelGGL(spade_hidden_level_kernel, dim3(ncu), dim3(1024), hid::LDS_BYTES, s, lab, u5, gq, gq_n, gq_cap, chunk_base, mode, table, bias,
-                       out, patch, B, H, W, kout, onehot, spade_hidden_wq_tcs(W), pitch, xoff);
+                       out, patch, B, H, W, kout, onehot, spade_hidden_wq_tcs(W), pitch, xoff, memo_hit);
     return hipGetLastError();
 }
 hipError_t spade_hidden_patch(const uint8_t* lab, const unsigned* gq, const int* gq_n, int gq_cap, const int* chunk_base, const int* mode,

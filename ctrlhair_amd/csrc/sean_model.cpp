@@ -945,6 +945,36 @@ struct SeanBuild {
             }
             if (a.styled && m.wsty) m.pro_wsty[a.index] = alloc((size_t)mb * ((a.C + 15) / 16) * 5 * 2048);
         });
+        return label_memo_buffers();
+    }
+    // Label memo (sean_model.h): the copy of the labels, the state words, per gather-route ACE a patch buffer (styled: the size of the shared
+    // patchbuf at the ACE's plane count) or the gamma / beta of its boundary quads (unstyled: 64 KB per task, as many tasks as a level in patch
+    // mode can have -- patch_cap_chunks chunks x the ACE's row pairs)
+    std::string label_memo_buffers() {
+        m.memo_patch.assign(m.n_aces, nullptr);
+        m.memo_gb.assign(m.n_aces, nullptr);
+        m.memo_gb_cap.assign(m.n_aces, 0);
+        m.memo_bytes = 0;
+        m.memo_lab = nullptr;
+        m.memo_state = nullptr;
+        if (!opt.label_memo) return "";
+        m.memo_bytes = (size_t)mb * ms * ms + MEMO_WORDS * sizeof(int);
+        m.memo_lab = static_cast<uint8_t*>(B.dalloc((size_t)mb * ms * ms));
+        m.memo_state = static_cast<int*>(B.dalloc(MEMO_WORDS * sizeof(int)));
+        if (!m.memo_lab || !m.memo_state) return "";      // (B.err names the failure)
+        if (hipMemset(m.memo_state, 0, MEMO_WORDS * sizeof(int)) != hipSuccess) return "hipMemset failed (label memo state)";
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            const int r = m.levels[level_of(a.res_div)].r;
+            if (!m.patchbuf || !m.wino_work(a, r) || m.ace_route_shape(a, r) != AceRoute::WinoQuads || !m.levels[level_of(a.res_div)].wq.gq) return;
+            size_t floats = (size_t)m.patch_cap_chunks * (HID + 20) * 1024;
+            if (a.styled) m.memo_patch[a.index] = B.falloc(floats);
+            else {
+                m.memo_gb_cap[a.index] = m.patch_cap_chunks * (((a.C + 15) / 16 + 1) / 2);
+                floats = (size_t)m.memo_gb_cap[a.index] * 8 * 512 * 4;
+                m.memo_gb[a.index] = B.falloc(floats);
+            }
+            m.memo_bytes += floats * 4;
+        });
         return "";
     }
 };
@@ -998,6 +1028,12 @@ void SeanModel::destroy() {
     pro_p6.clear();
     pro_wsty.clear();
     pro_on = false;
+    memo_patch.clear();
+    memo_gb.clear();
+    memo_gb_cap.clear();
+    memo_lab = nullptr;
+    memo_state = nullptr;
+    memo_dirty = false;
     splitk_side = nullptr;
     for (auto& r : prof) {
         ev_pool.push_back(r.e0);
@@ -1158,7 +1194,7 @@ struct Runner {
         if (p.ti >= 0 && lp.classify[p.ti] && !ld.cls[p.ti]) {
             const SparseLevel& S = V.sp[p.ti];
             const SeanModel::LevelMarks mk = lp.marks[p.ti];
-            check(ace_classify(p.lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, mk.edges ? S.e16 : nullptr, mk.frame), "ace_classify");
+            check(ace_classify(p.lab, S.u5, S.need, S.list, S.cnt, B, r, r, S.TH, st, mk.edges ? S.e16 : nullptr, mk.frame, memo_hit), "ace_classify");
             ld.cls[p.ti] = true;
         }
         if (p.route == AceRoute::WinoQuads) {
@@ -1202,8 +1238,36 @@ struct Runner {
             }
         }
     }
+    // Label memo (sean_model.h): the device word the memoized launches of this chunk read, nullptr on a chunk that is not eligible.
+    // memo_begin runs first in a chunk.  Eligible: the only chunk of its call, in prologue mode, with every gather level's geometry inside the
+    // grouped launches (the direct launches of prepare() carry no memo word) and labels that can be read in 16-byte words.  Such a chunk
+    // clears the pads of the memoized hidden planes where their geometry changed -- ahead of the decision: a memset must not follow it -- then
+    // compares and decides; any other chunk of a handle with the memo clears MEMO_VALID, as does whatever left the memoized buffers in doubt.
+    const int* memo_hit = nullptr;
+    void memo_begin(const uint8_t* labfull, bool only_chunk) {
+        if (!m.memo_state) return;
+        bool ok = m.opt.label_memo && only_chunk && mode.prologue && (reinterpret_cast<uintptr_t>(labfull) & 15) == 0;
+        int nl = 0, nw = 0;
+        for (const LevelPlan& lp : lplans) {
+            if (!lp.quads) continue;
+            ok = ok && lp.grouped;
+            ++nl;
+            for (unsigned b = lp.wino_lists; b; b &= b - 1) ++nw;
+        }
+        ok = ok && nl <= WinoGeoGroup::MAX_L && nw <= WinoGeoGroup::MAX_W;
+        bool fresh = m.memo_dirty;
+        if (ok)
+            for (const AcePlan& p : plans)
+                if (p.hidden == AcePlan::GROUP) fresh = zero_pads(m.pro_actv[p.a->index], p.r, p.kout, st) || fresh;
+        if (!ok || fresh) check(label_memo_invalidate(m.memo_state, st), "label memo (invalidate)");
+        m.memo_dirty = false;
+        if (!ok) return;
+        check(label_memo_begin(labfull, m.memo_lab, (long long)B * S * S, m.memo_state, B, S, m.memo_epoch, st), "label memo (compare, decide)");
+        memo_hit = m.memo_state + MEMO_HIT;
+    }
     void geo_flush() {
         if (!geo) return;
+        geo->memo_hit = memo_hit;
         if (geo->nl) check(wino_geometry_grouped(*geo, st), "level geometry (grouped)");
         geo->nl = geo->nw = 0;
         for (Launched& l : launched) l.geo_slot = -1;
@@ -1371,15 +1435,21 @@ struct Runner {
     }
     // the zero columns left and right of the image in a padded hidden buffer: the label-table kernels never write them, so they are cleared
     // whenever the buffer changes its geometry (first use, another image size) -- per-pixel pad stores cost 200 us per 512^2 launch
-    void zero_pads(float* buf, int r, int kout, hipStream_t s) {
+    // (returns whether it cleared the buffer)
+    bool zero_pads(float* buf, int r, int kout, hipStream_t s) {
         const long long geo = ((long long)r << 20) | ((long long)kout << 8) | 1;
         auto it = m.pad_state.find(buf);
-        if (it != m.pad_state.end() && it->second == geo) return;
+        if (it != m.pad_state.end() && it->second == geo) return false;
         check(hipMemsetAsync(buf, 0, (size_t)m.max_batch * kout * r * wino_apitch(r) * sizeof(float), s), "hidden activations: zero pads");
         m.pad_state[buf] = geo;
+        return true;
     }
     // The SPADE hidden activations of one ACE (label table) into actv_buf, on stream s.  The route decides both the layout (Winograd routes:
     // padded planes, the one-hot planes of a styled ACE behind the hidden channels; else [B][128][H][W]) and the kernel that reads it.
+    // the patch buffer of a gather-route ACE: its own on a chunk with the label memo, else the shared one
+    float* patch_buf(const AcePlan& pl) const { return (memo_hit && m.memo_patch[pl.a->index]) ? m.memo_patch[pl.a->index] : m.patchbuf; }
+    // ... the gamma / beta cache of an unstyled one (its patches, in the shared buffer, are not needed on a hit: the conv does not run)
+    float* gb_cache(const AcePlan& pl) const { return (memo_hit && pl.patch && !pl.wsty) ? m.memo_gb[pl.a->index] : nullptr; }
     void build_hidden(const AcePlan& pl, hipStream_t s, float* actv_buf) {
         const AceW& a = *pl.a;
         const int r = pl.r, kout = pl.kout;
@@ -1400,9 +1470,11 @@ struct Runner {
             const SeanModel::WinoLevel* PL = pl.patch;
             const bool pm = PL && PL->gq && PL->patch_mode && m.patchbuf;
             if (pm && mode.prologue && PL->chunk_base) {
-                // chunks with the prologue: both sources from one launch, the device flag picks the body (kernels.h)
+                // chunks with the prologue: both sources from one launch, the device flag picks the body (kernels.h); with the label memo the
+                // patches go to the ACE's own buffer and stay (patch_buf)
                 check(spade_hidden_level(lab, u5, PL->gq, PL->gq_n, PL->gq_cap, PL->chunk_base, PL->patch_mode, a.actv_table,
-                                         a.actv_bias, actv_buf, m.patchbuf, B, r, r, kout, a.styled ? 1 : 0, wino_apitch(r), WINO_AXOFF, s),
+                                         a.actv_bias, actv_buf, patch_buf(pl), B, r, r, kout, a.styled ? 1 : 0, wino_apitch(r), WINO_AXOFF, s,
+                                         (patch_buf(pl) != m.patchbuf || gb_cache(pl)) ? memo_hit : nullptr),
                       "mlp_shared (planes or pre-gathered patches)");
                 return;
             }
@@ -1468,6 +1540,7 @@ struct Runner {
         StylePackGroup sg{};
         WinoGeoGroup gg{};
         hg.B = tg.B = sg.B = gg.B = B;
+        hg.memo_hit = memo_hit;
         geo = &gg;
         tg.lut_rs = 1;
         tg.lut_bs = LABEL_NC;
@@ -1631,7 +1704,7 @@ struct Runner {
         w.actv = q.actv;
         w.wpk = a.spade_wino;
         w.wsty = p.wsty;      // (style images: the shared buffer, packed below, or the prologue's)
-        w.patch = p.patch ? m.patchbuf : nullptr;
+        w.patch = p.patch ? patch_buf(p) : nullptr;
         w.chunk_base = L.chunk_base;
         w.patch_mode = L.patch_mode;
         w.qlist = L.qlist;
@@ -1644,6 +1717,9 @@ struct Runner {
         w.gq_n = L.gq_n;
         w.gq_cap = L.gq_cap;
         w.claim = w.gq ? next_claim() : nullptr;
+        w.cache = gb_cache(p);
+        w.cache_cap = w.cache ? m.memo_gb_cap[a.index] : 0;
+        w.memo_hit = w.cache ? memo_hit : nullptr;
         // executed FLOPs = wave tasks x (32 rows x 16 quads x 16 positions x K) x 2; dense = the direct conv over every pixel
         timed(1, dense_flops(p), 0.0, SpStat{p.W->total + 4, 2.0 * 32 * 16 * 16 * ktot, 4.0 * ktot + xpp + opp, 4.0 * 2.0 * a.C * ktot * 16, npix}, [&] {
             if (p.wsty && !p.pre_wsty) check(wino_style_pack(q.lut, p.wsty, B, a.C, st), "wino_style_pack");
@@ -1983,7 +2059,8 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             R.check(gen_noise(noise_ws, (long long)B * nf, chunk_seed(seed, bo), st), "gen_noise");
             nz = noise_ws;
         }
-        for (int k = 1; k <= 5; ++k) R.check(label_downsample(lab, levels[k].lab, B, S, S >> k, st), "label_downsample");
+        R.memo_begin(lab, Btot <= max_batch);
+        for (int k = 1; k <= 5; ++k) R.check(label_downsample(lab, levels[k].lab, B, S, S >> k, st, R.memo_hit), "label_downsample");
         if (opt.use_sh16) R.check(hipMemsetAsync(amax_slots, 0, 64 * sizeof(unsigned), st), "amax slots");
         if (mode.project_all) {     // (smaller batches take the GEMV branch of Runner::build_lut, which projects per ACE)
             // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout)
@@ -2048,6 +2125,7 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             std::swap(x, y);
         }
         R.check(conv_img_tanh(x, img_w, img_b, out + (size_t)bo * 3 * S * S, B, ngf, S, S, st, opt.use_sh16 ? 1 : 0, img_w4), "conv_img");
+        if (!R.err.empty()) memo_dirty = true;      // (the decision kernel may have run ahead of a launch that failed)
         if (!R.err.empty()) return join(R.err);
     }
     return join("");
@@ -2075,6 +2153,15 @@ std::string SeanModel::encode(const float* img, const uint8_t* labels, float* co
         if (phase != 1) R.means(labels + (size_t)bo * S * S, codes_out + (size_t)bo * LABEL_NC * STYLE);
         if (!R.err.empty()) return R.err;
     }
+    return "";
+}
+
+std::string SeanModel::label_memo_stats(int* calls, int* hits) {
+    int st[MEMO_WORDS] = {};
+    if (memo_state && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(st, memo_state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess))
+        return "label memo: state read failed";
+    *calls = st[MEMO_CALLS];
+    *hits = st[MEMO_HITS];
     return "";
 }
 

@@ -93,6 +93,9 @@ struct SeanOptions {
     int prologue = 1;                          // option "sean.prologue": exact-f32 Winograd path, handles beyond the run-ahead sizes: what the ACEs build from
                                                //   labels, codes and weights alone comes from a few grouped launches at the start of a chunk, into per-ACE
                                                //   buffers (SeanModel::pro_on); 0 = every ACE launches its own, inline
+    int label_memo = 1;                        // option "sean.label_memo": handles with the ACE prologue, calls of one chunk: 1 = the label-only products of a chunk
+                                               //   (SeanModel::memo_state) are kept on the device and their launches return at once while the calls bring
+                                               //   the same label maps; 0 = every call rebuilds them (launch for launch as without the memo)
     // Overlap mode (round 5; option "sean.overlap" = CUs of the side streams, 0 = off; exact-f32 Winograd path, jobs beyond the
     // run-ahead sizes): the HBM-bound kernels -- label tables of all ACEs, interior passes -- run on streams whose CU mask holds
     // `overlap` CUs (hipExtStreamCreateWithCUMask: every XCD gives overlap / 8 of its CUs), beside the matrix-bound convs on the
@@ -272,6 +275,26 @@ struct SeanModel {
     bool pro_on = false;
     std::vector<float*> pro_actv, pro_gtab, pro_p6, pro_wsty;
     size_t pro_bytes = 0;                      // what these buffers add to the handle
+    // Label memo (option "sean.label_memo"; handles with pro_on): sliders, sweeps and direction searches render one mask with many codes, call
+    // after call, so what a chunk builds from labels and weights alone -- level label maps, classification, level geometry, the hidden planes of
+    // the F(4x4)-route ACEs, the pre-gathered patches of the gather-route ACEs -- is still in place when the next call brings the same maps.
+    // The device decides (kernels.h label_memo_begin): `memo_lab` is the handle's copy of the last eligible chunk's maps, `memo_state` the words
+    // MEMO_*; a memoized kernel reads memo_state[MEMO_HIT] at its top and returns on 1.  The host never learns the answer and enqueues the same
+    // launches either way (eager or in a captured graph).  Eligible: the only chunk of a call, in prologue mode, whose level geometry fits the
+    // grouped launches (Runner::memo_begin); any other chunk clears MEMO_VALID in stream order.  A memoized kernel reads labels and memoized
+    // products only, and writes buffers nothing else writes: the level buffers, pro_actv and `memo_patch` (one patch buffer per styled
+    // gather-route ACE in place of the shared patchbuf).  `memo_epoch` is part of the key: ch_set_option bumps it.
+    uint8_t* memo_lab = nullptr;
+    int* memo_state = nullptr;
+    int memo_epoch = 0;
+    bool memo_dirty = false;                   // a generate() ended in an error after its decision kernel: the next eligible chunk invalidates first
+    std::vector<float*> memo_patch;
+    // unstyled gather-route ACEs (up_3): gamma and beta of the boundary quads are label-only too.  In patch mode the conv launch stores them per
+    // task (conv_wino.h WinoAceParams::cache); on a hit it returns at once and wino_ace_cached_kernel modulates from the stored values.
+    std::vector<float*> memo_gb;
+    std::vector<int> memo_gb_cap;              // tasks each holds
+    size_t memo_bytes = 0;                     // what the memo adds to the handle
+    std::string label_memo_stats(int* calls, int* hits);      // synchronous read-back of MEMO_CALLS / MEMO_HITS (tests and tools)
 
     // ---- exact SPADE-interior reduction (ace_sparse.h; per-level buffers: Level) ----
     float* gtab = nullptr;                     // [max_batch][19][2][C max]

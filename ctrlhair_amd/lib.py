@@ -75,6 +75,7 @@ SYMBOLS = {
     'ch_sean_set_tap': (_I, [_VP, C.c_char_p, _VP]),
     'ch_sean_scale_report': (_I, [_VP, C.POINTER(C.c_float), _I]),
     'ch_sean_debug_read': (_I, [_VP, _VP, C.c_size_t]),
+    'ch_sean_label_memo_stats': (C.c_longlong, [_VP]),
     'ch_mfma_peak': (_I, [_VP, _I, _I, C.POINTER(_D)]),
     'ch_profile_enable': (_I, [_VP, _I]),
     'ch_profile_read': (_I, [_VP, _I, C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
@@ -169,6 +170,14 @@ class Handle:
         self._check(self.lib.ch_sean_scale_report(self._h, buf, 36), 'ch_sean_scale_report')
         a = np.array(buf[:], dtype=np.float32)
         return {'ace': a[0::2].copy(), 'style': a[1::2].copy()}
+
+    def sean_label_memo_stats(self):
+        """(calls, hits) of the generator's label memo (option 'sean.label_memo'): chunks that went through its decision, and those that
+        found the label maps of the chunk before.  Synchronises."""
+        v = int(self.lib.ch_sean_label_memo_stats(self._h))
+        if v < 0:
+            raise RuntimeError(f'ch_sean_label_memo_stats failed: {self.lib.ch_last_error(self._h).decode()}')
+        return v >> 32, v & 0xFFFFFFFF
 
     def mfma_peak(self, kind: int, ms_target: int = 30) -> float:
         """TFLOP/s this device sustains on an MFMA-only loop (kind 0: f32 32x32x2, 1: f16 32x32x16).  Synchronises."""

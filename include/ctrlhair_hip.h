@@ -149,6 +149,11 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   column / row sums and F(2x2) style images of the ACEs from 128 pixels -- comes from a few grouped launches at the start of the chunk,
  *   into per-ACE buffers (+456 MiB on a 16 x 512^2 handle at ngf = 64).  Bit-identical results.  Off by
  *   itself with "sean.f16x3", "sean.overlap" and while ch_profile_enable is on.  0 = every ACE launches its own kernels, inline.
+ * "sean.label_memo" (default 1; before ch_finalize; handles with "sean.prologue" in effect): the label-only products of a chunk -- level
+ *   label maps, classification, level geometry, hidden planes of the 32 / 64-pixel ACEs, pre-gathered patches of the ACEs from 128 pixels
+ *   (one patch buffer per ACE) -- stay on the device; a call of one chunk compares its label maps with the handle's copy on the device and
+ *   the launches that build those products return at once when nothing changed (same shapes, same options).  Bit-identical results.
+ *   0 = no memo and none of its buffers.  ch_sean_label_memo_stats counts.
  * "sean.hidden_wq" (default 1; any time): every Winograd ACE level (32 pixels and more) takes the SPADE hidden activations and the
  *   one-hot planes from one persistent kernel (csrc/sean_kernels.hip spade_hidden_wq).  1 = on the gather levels it writes only the
  *   64-byte pixel groups that a boundary quad's patch touches; 0 = the same kernel over every pixel (bit-identical results).  The dense
@@ -620,6 +625,11 @@ int  ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr);
  * recorded by the last ch_sean_generate batch chunk: entry 2i = output of ACE layer i (execution order), 2i+1 = its style
  * projections; 0 = not written.  Synchronises the device (not for the hot path). */
 int  ch_sean_scale_report(ch_handle* h, float* host_out, int n);
+
+/* Label memo (option "sean.label_memo"), a query: calls << 32 | hits -- how many chunks of ch_sean_generate went through the memo's decision so
+ * far (`calls`) and how many of them found the label maps of the chunk before (`hits`); 0 on a handle without the memo; -1 without a
+ * finalised SEAN model or when the read fails (ch_last_error).  Synchronises the device (tests, tools). */
+long long ch_sean_label_memo_stats(ch_handle* h);
 
 /* Profiling hook (tools/ only): copies the first `bytes` of the generator's split-K scratch to host memory; with option
  * "sean.dbg" bit 256 the wave-specialised conv kernel leaves per-tile cycle stamps there.  Synchronises the device. */
