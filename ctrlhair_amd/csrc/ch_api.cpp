@@ -13,6 +13,7 @@
 #include "aux_models.h"
 #include "sean_model.h"
 #include "kernels.h"
+#include "jpeg_entropy_core.h"
 #include "png_inflate_core.h"
 
 struct ch_handle {
@@ -708,6 +709,42 @@ int ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C,
     const size_t need = chk::jpeg_encode_workspace_bytes(N, H, W, C, subsampling);
     if (int rc = workspace_short(h, f.c_str(), workspace_bytes, need, "ch_jpeg_encode_workspace_bytes")) return rc;
     return launch(h, f.c_str(), [&] { return chk::jpeg_encode(img, N, H, W, C, quality, subsampling, out, sizes, workspace, hs(stream)); });
+}
+
+// ---- JPEG decoding (jpeg_decode.hip, jpeg_entropy_core.h) -------------------------------------------------------------------------------
+namespace {
+bool jpeg_dec_dims_ok(int H, int W, int C, int sampling) {
+    return (C == 1 || C == 3) && sampling >= 0 && sampling <= (C == 3 ? 2 : 0) && H >= 1 && W >= 1 && H <= 32768 && W <= 32768 &&
+           (int64_t)H * W <= (1 << 30);
+}
+}  // namespace
+
+size_t ch_jpeg_decode_workspace_bytes(int N, int H, int W, int C, int sampling) {
+    return (N >= 1 && N <= 65535 && jpeg_dec_dims_ok(H, W, C, sampling)) ? chk::jpeg_decode_workspace_bytes(N, H, W, C, sampling) : 0;
+}
+
+int ch_jpeg_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C, int sampling,
+                   int rounds, uint8_t* img, int32_t* status, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    namespace je = chk::jpegent;
+    static_assert(CH_JPEG_DEC_OK == je::OK && CH_JPEG_DEC_BAD_CODE == je::BAD_CODE && CH_JPEG_DEC_BAD_INDEX == je::BAD_INDEX &&
+                      CH_JPEG_DEC_INPUT_END == je::INPUT_END && CH_JPEG_DEC_BLOCKS == je::BLOCKS && CH_JPEG_DEC_NOT_SYNCED == je::NOT_SYNCED &&
+                      CH_JPEG_DEC_TOO_LONG == je::TOO_LONG && CH_JPEG_DEC_MARKER == je::MARKER && CH_JPEG_DEC_RANGE == je::RANGE &&
+                      CH_JPEG_DEC_TABLE_BYTES == je::TABLE_BYTES && CH_JPEG_DEC_DEFAULT_ROUNDS == je::DEFAULT_ROUNDS,
+                  "constants of the header and of jpeg_entropy_core.h");
+    if (!h) return CH_ERR_ARG;
+    const std::string f = "ch_jpeg_decode: ";
+    if (!streams || !offsets || !tables || !img || !status || !workspace) return fail(h, CH_ERR_ARG, f + "null pointer");
+    if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, f + "N outside 1..65535");
+    if (C != 1 && C != 3) return fail(h, CH_ERR_ARG, f + "C must be 1 (grey) or 3 (YCbCr -> RGB)");
+    if (sampling < 0 || sampling > (C == 3 ? 2 : 0))
+        return fail(h, CH_ERR_ARG, f + "sampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), and 0 for C = 1");
+    if (rounds < 0 || rounds > je::MAX_ROUNDS) return fail(h, CH_ERR_ARG, f + "rounds outside 0..64");
+    if (!jpeg_dec_dims_ok(H, W, C, sampling)) return fail(h, CH_ERR_ARG, f + "image too small or too large (sides 1..32768, H * W <= 2^30)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
+    const size_t need = chk::jpeg_decode_workspace_bytes(N, H, W, C, sampling);
+    if (int rc = workspace_short(h, f.c_str(), workspace_bytes, need, "ch_jpeg_decode_workspace_bytes")) return rc;
+    return launch(h, f.c_str(),
+                  [&] { return chk::jpeg_decode(streams, offsets, tables, N, H, W, C, sampling, rounds, img, status, workspace, hs(stream)); });
 }
 
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {

@@ -281,4 +281,12 @@ size_t jpeg_encode_workspace_bytes(int N, int H, int W, int C, int subsampling);
 hipError_t jpeg_encode(const uint8_t* img, int N, int H, int W, int C, int quality, int subsampling, uint8_t* out, int64_t* sizes, void* ws,
                        hipStream_t s);
 
+// jpeg_decode.hip: N baseline-JPEG entropy-coded scans (stream n = streams[offsets[n], offsets[n + 1]), its table block at tables +
+// n * 2048; jpeg_entropy_core.h) -> uint8 images [N,H,W,C] (C = 1 or 3).  sampling: 0 = 4:4:4 (and grey), 1 = 4:2:2, 2 = 4:2:0.  rounds:
+// launches of the state hand-over between chunks, 0 = the default.  status[n]: jpegent::Status.  See ch_jpeg_decode.
+int jpeg_decode_default_rounds();
+size_t jpeg_decode_workspace_bytes(int N, int H, int W, int C, int sampling);
+hipError_t jpeg_decode(const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C, int sampling, int rounds,
+                       uint8_t* img, int32_t* status, void* ws, hipStream_t s);
+
 }  // namespace chk

@@ -21,12 +21,12 @@ On-disk formats are the reference's:
     python -m ctrlhair_amd.dataset rgb      <root> <dataset> [--batch 16]     (no network weights: ctrlhair_amd.colorstats)
     python -m ctrlhair_amd.dataset colorvar <root> <dataset> [--batch 16]
     python -m ctrlhair_amd.dataset crop <src_dir> <root> <dataset> --landmarks <file> [--size 256] [--png host|device]
-                                          [--jpeg host|device] [--jpeg-quality 75] [--jpeg-subsampling 420|444]
+                                          [--jpeg host|device] [--jpeg-quality 75] [--jpeg-subsampling 420|444] [--decode host|device]
                                           (dataset_scripts/script_crop.py: FFHQ-align every photo of <src_dir> into
                                            <root>/<dataset>/images_256/<name>; no network weights: ctrlhair_amd.alignment)
     python -m ctrlhair_amd.dataset uncrop <photos> <edits> <out> --landmarks <file> [--size S]
                                           [--labels DIR [--matte] [--matte-radius R] [--matte-eps E]] [--png host|device]
-                                          [--jpeg host|device] [--jpeg-quality 75] [--jpeg-subsampling 420|444]
+                                          [--jpeg host|device] [--jpeg-quality 75] [--jpeg-subsampling 420|444] [--decode host|device]
                                           (the inverse of crop: paste the edited crop <edits>/<name> back into <photos>/<name> with the
                                            same landmarks and write the photo-sized result to <out>/<name>; ctrlhair_amd.alignment.
                                            --labels: 8-bit label PNGs <DIR>/<stem>.png of the crops; only their hair is pasted, and with
@@ -60,6 +60,9 @@ On-disk formats are the reference's:
     (crop and uncrop take --jpeg host|device for their .jpg / .jpeg names: 'device' encodes them with ch_jpeg_encode,
      ctrlhair_amd.jpegenc, instead of downloading the pixels for Pillow; the FILES are the same, byte for byte, as Pillow's at the same
      --jpeg-quality and --jpeg-subsampling, whose defaults 75 and 420 are what Pillow's save() uses when given neither; .bmp stays Pillow's)
+    (crop and uncrop take --decode host|device for the photos and edits they read: 'device' uploads the files' bytes and decodes them
+     there, .jpg / .jpeg with ch_jpeg_decode (ctrlhair_amd.jpegdec), .png with ch_png_decode; the pixels are Pillow's, so the results are
+     the same files; progressive JPEGs and whatever else the device does not take are decoded by Pillow, file by file)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -146,6 +149,37 @@ def _png_decoder(decode: str, owner):
     who decodes the PNG files a job reads; whatever the device does not decode is Pillow's, file by file (PngDecoder.fallbacks)."""
     from .pngdec import PngDecoder, check_decode_mode
     return PngDecoder(owner.handle, owner.device) if check_decode_mode(decode) == 'device' else None
+
+
+class _PhotoReader:
+    """read_rgb for the crop jobs with decode='device': .jpg / .jpeg files through jpegdec.JpegDecoder, .png files through
+    pngdec.PngDecoder, on `owner`'s handle and device; anything else, and every file a decoder hands back, is Pillow's.  The pixels are
+    device tensors and the same as read_rgb's; fallbacks counts the files Pillow decoded."""
+
+    def __init__(self, owner):
+        from .jpegdec import JpegDecoder
+        from .pngdec import PngDecoder
+        self.jpeg, self.png, self.other = JpegDecoder(owner.handle, owner.device), PngDecoder(owner.handle, owner.device), 0
+        self.device = owner.device
+
+    @property
+    def fallbacks(self) -> int:
+        return self.jpeg.fallbacks + self.png.fallbacks + self.other
+
+    def read_rgb(self, path: str):
+        import torch
+        if _is_jpeg(path):
+            return self.jpeg.read_rgb([path])[0]
+        if _is_png(path):
+            return self.png.read_rgb([path])[0]
+        self.other += 1
+        return torch.from_numpy(np.array(read_rgb(path))).to(self.device)
+
+
+def _photo_reader(decode: str, owner):
+    """None for decode='host' (dataset.read_rgb reads the photos); for 'device' a _PhotoReader on `owner`'s handle and device."""
+    from .pngdec import check_decode_mode
+    return _PhotoReader(owner) if check_decode_mode(decode) == 'device' else None
 
 
 def _is_png(name: str) -> bool:
@@ -296,16 +330,21 @@ def find_landmarks(landmarks: Dict[str, np.ndarray], dataset: str, file_name: st
 
 
 def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = 256, rank: int = 0,
-               world: int = 1, png: str = 'host', jpeg: str = 'host', jpeg_quality: int = 75, jpeg_subsampling=2):
+               world: int = 1, png: str = 'host', jpeg: str = 'host', jpeg_quality: int = 75, jpeg_subsampling=2, decode: str = 'host',
+               stats: dict = None):
     """dataset_scripts/script_crop.py:36-54 for this rank's shard of `src_dir`: align every photo that has landmarks
     (`aligner`: alignment.FaceAligner) and write it to `out_dir/<name>`.  Returns (done, skipped): the file names written and the
     ones without a landmark entry, which are reported and left out.  png='device': .png names are encoded on the device.  jpeg='device':
     .jpg / .jpeg names are encoded on the device, to the bytes Pillow writes at jpeg_quality and jpeg_subsampling (0 / '444' or
-    2 / '420'); jpeg='host' passes those two to Pillow when they are not its defaults."""
+    2 / '420'); jpeg='host' passes those two to Pillow when they are not its defaults.  decode='device': the photos are decoded on the
+    device (.jpg / .jpeg: jpegdec.JpegDecoder, .png: pngdec.PngDecoder; the same pixels, so the same files); what a decoder does not take
+    is Pillow's, file by file, and counted in stats['fallbacks'] when a dict is passed."""
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
     encoder = _png_encoder(png, aligner)
     jpeg_encoder, jpeg_options = _jpeg_writer(jpeg, jpeg_quality, jpeg_subsampling, aligner)
+    reader = _photo_reader(decode, aligner)
+    read = read_rgb if reader is None else reader.read_rgb
     done, skipped = [], []
     for n in shard(list_images(src_dir), rank, world):
         lm = find_landmarks(landmarks, dataset, n)
@@ -313,7 +352,7 @@ def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dic
             print(f'crop: no landmarks for {n}, skipped')
             skipped.append(n)
             continue
-        crop, _ = aligner.align(read_rgb(os.path.join(src_dir, n)), lm[:68], size)
+        crop, _ = aligner.align(read(os.path.join(src_dir, n)), lm[:68], size)
         if encoder is not None and _is_png(n):
             encoder.write([os.path.join(out_dir, n)], crop[None])
             done.append(n)
@@ -325,6 +364,8 @@ def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dic
         crop = crop.cpu().numpy() if hasattr(crop, 'cpu') else np.asarray(crop)
         Image.fromarray(crop).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}))
         done.append(n)
+    if stats is not None:
+        stats['fallbacks'] = 0 if reader is None else reader.fallbacks
     return done, skipped
 
 
@@ -343,7 +384,7 @@ def label_weight(label_path: str, S: int) -> np.ndarray:
 
 def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = None,
                  rank: int = 0, world: int = 1, label_dir: str = None, matte=None, png: str = 'host', jpeg: str = 'host',
-                 jpeg_quality: int = 75, jpeg_subsampling=2):
+                 jpeg_quality: int = 75, jpeg_subsampling=2, decode: str = 'host', stats: dict = None):
     """The inverse of crop_faces for this rank's shard of `photo_dir`: paste the edited crop `edit_dir/<name>` back into the photo
     `photo_dir/<name>` it was aligned from (same landmarks, same file names) and write the photo-sized result to `out_dir/<name>`.
     size: the crops' side (default: each edit's own).  label_dir: per-image weight from `label_dir/<stem>.png` (hair = 255); matte
@@ -351,7 +392,8 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
     (done, skipped); a photo without landmarks, without an edit or (with label_dir) without a label map is reported and left out.
     png='device': .png names are encoded on the device (the photo-sized result is never downloaded).  jpeg='device': the same for
     .jpg / .jpeg names, to the bytes Pillow writes at jpeg_quality and jpeg_subsampling (0 / '444' or 2 / '420'); jpeg='host' passes
-    those two to Pillow when they are not its defaults.  Neither path carries the photo's EXIF or ICC data over."""
+    those two to Pillow when they are not its defaults.  Neither path carries the photo's EXIF or ICC data over.  decode='device': the
+    photos and the edits are decoded on the device, as in crop_faces (stats['fallbacks']: the files Pillow decoded after all)."""
     from PIL import Image
     from .alignment import align_plan
     if matte is not None and label_dir is None:
@@ -359,6 +401,8 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
     os.makedirs(out_dir, exist_ok=True)
     encoder = _png_encoder(png, aligner)
     jpeg_encoder, jpeg_options = _jpeg_writer(jpeg, jpeg_quality, jpeg_subsampling, aligner)
+    reader = _photo_reader(decode, aligner)
+    read = read_rgb if reader is None else reader.read_rgb
     done, skipped = [], []
     for n in shard(list_images(photo_dir), rank, world):
         lm = find_landmarks(landmarks, dataset, n)
@@ -371,7 +415,7 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
             print(f'uncrop: no label map for {n}, skipped')
             skipped.append(n)
             continue
-        photo, edit = read_rgb(os.path.join(photo_dir, n)), read_rgb(os.path.join(edit_dir, n))
+        photo, edit = read(os.path.join(photo_dir, n)), read(os.path.join(edit_dir, n))
         S = int(edit.shape[0]) if size is None else int(size)
         if edit.shape[:2] != (S, S):
             raise ValueError(f'{os.path.join(edit_dir, n)}: expected a {S} x {S} crop, got {edit.shape[1]} x {edit.shape[0]}')
@@ -387,6 +431,8 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
         else:
             Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}))
         done.append(n)
+    if stats is not None:
+        stats['fallbacks'] = 0 if reader is None else reader.fallbacks
     return done, skipped
 
 
@@ -665,6 +711,7 @@ def _main_crop(argv):
     ap.add_argument('--jpeg', choices=('host', 'device'), default='host', help='who writes .jpg / .jpeg files: Pillow on the host (default) or ch_jpeg_encode on the device (the same file bytes)')
     ap.add_argument('--jpeg-quality', type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's own default)")
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help="JPEG chroma subsampling (default 420, Pillow's own default)")
+    ap.add_argument('--decode', choices=('host', 'device'), default='host', help='who decodes the files read: Pillow on the host (default), or the device: ch_jpeg_decode for .jpg / .jpeg, ch_png_decode for .png (the same pixels, so the same results; whatever the device does not take is Pillow\'s, file by file)')
     args = ap.parse_args(argv)
     if not 1 <= args.jpeg_quality <= 100:
         ap.error('--jpeg-quality must be in 1..100')
@@ -676,7 +723,7 @@ def _main_crop(argv):
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = crop_faces(aligner, args.src_dir, os.path.join(args.root, args.dataset, 'images_256'), args.dataset,
                                load_landmarks(args.landmarks), args.size, rank, world, png=args.png, jpeg=args.jpeg,
-                               jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling)
+                               jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, decode=args.decode)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} without landmarks')
 
 
@@ -697,6 +744,7 @@ def _main_uncrop(argv):
     ap.add_argument('--jpeg', choices=('host', 'device'), default='host', help='who writes .jpg / .jpeg files: Pillow on the host (default) or ch_jpeg_encode on the device (the same file bytes)')
     ap.add_argument('--jpeg-quality', type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's own default)")
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help="JPEG chroma subsampling (default 420, Pillow's own default)")
+    ap.add_argument('--decode', choices=('host', 'device'), default='host', help='who decodes the files read: Pillow on the host (default), or the device: ch_jpeg_decode for .jpg / .jpeg, ch_png_decode for .png (the same pixels, so the same results; whatever the device does not take is Pillow\'s, file by file)')
     args = ap.parse_args(argv)
     if not 1 <= args.jpeg_quality <= 100:
         ap.error('--jpeg-quality must be in 1..100')
@@ -718,7 +766,7 @@ def _main_uncrop(argv):
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = uncrop_faces(aligner, args.photos, args.edits, args.out, args.dataset, load_landmarks(args.landmarks), args.size,
                                  rank, world, label_dir=args.labels, matte=matte, png=args.png, jpeg=args.jpeg,
-                                 jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling)
+                                 jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, decode=args.decode)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
 
 

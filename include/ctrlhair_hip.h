@@ -436,6 +436,52 @@ size_t ch_jpeg_encode_workspace_bytes(int N, int H, int W, int C, int subsamplin
 int    ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int C, int quality, int subsampling, uint8_t* out,
                       int64_t* sizes, void* workspace, size_t workspace_bytes, ch_stream_t stream);
 
+/* ---- JPEG decoding on the device: the photos and edits of the crop and paste-back jobs arrive as compressed bytes -------------------
+ * ch_jpeg_decode turns N entropy-coded scans of baseline JPEG (SOF0: sequential DCT, Huffman, 8 bits, one scan holding all components,
+ * no restart interval) into N images img uint8 [N,H,W,C] (device pointer; C = 1 grey, 3 RGB from YCbCr).  The images of one call share
+ * H, W, C and sampling: 0 = 4:4:4 (required for C = 1), 1 = 4:2:2, 2 = 4:2:0 (Pillow's numbering; luma 1x1, 2x1, 2x2, chroma 1x1).
+ * Stream n is the bytes streams[offsets[n] .. offsets[n + 1]) between the SOS header and the EOI marker, stuffed (streams uint8, offsets
+ * int64 [N + 1]: device pointers).  tables (uint8, device): per image a block of CH_JPEG_DEC_TABLE_BYTES bytes: at 64 * c the 8-bit
+ * quantiser of component c in natural (row-major) order; at 192 + 272 * (2 * c + k) the DC (k = 0) and AC (k = 1) Huffman table of
+ * component c as BITS[16] and HUFFVAL[256] (any tables, not only Annex K).  The markers are the caller's: jpegdec.parse_jpeg.
+ * The Huffman decode is parallel WITHIN a scan: subsequences of 128 bytes, one lane each, start from the guess "a block begins here",
+ * hand their exit state to the next and repeat until nothing changes (Huffman streams re-synchronise); chunks of 64 subsequences hand
+ * over between `rounds` kernel launches (0: the default, CH_JPEG_DEC_DEFAULT_ROUNDS; at most 64).  A stream whose chain of states is
+ * not whole after them is NOT_SYNCED, never wrong pixels.  The arithmetic behind it is libjpeg's, all of it integer -- the
+ * slow-integer inverse DCT, fancy upsampling (h2v1, h2v2; replication when the chroma plane is at most 2 samples wide), 16-bit
+ * fixed-point YCbCr -> RGB -- so for status 0 the pixels are libjpeg's and libjpeg-turbo's (Pillow's), byte for byte.
+ * status[n] (int32 [N], device): CH_JPEG_DEC_OK, or
+ *   BAD_CODE      bits that are no code of the table in force, or a DC symbol above 15
+ *   BAD_INDEX     a run that carries the coefficient index past 63
+ *   INPUT_END     the stream ends before the last block (or is empty)
+ *   BLOCKS        the stream holds more symbols than the image's blocks take
+ *   NOT_SYNCED    see above: decode it elsewhere or call again with more rounds
+ *   TOO_LONG      more than min(512 * blocks, 2^28 - 1) bytes: longer than any valid scan (64 symbols of 31 bits per block, all stuffed)
+ *   MARKER        a 0xFF followed by a byte other than 0x00 inside the stream
+ *   RANGE         a dequantised coefficient or a first-pass value beyond +-8191, or a sample before the range limit outside -512..511:
+ *                 values no sane file holds, at which libjpeg's C code, its SIMD code and 32-bit arithmetic part ways
+ * and the pixels of that image are unspecified.  For every byte sequence: the work for image n reads no stream byte outside
+ * [offsets[n], offsets[n + 1]), writes nothing outside image n's slice of img, of status and of the workspace, and terminates.
+ * workspace: caller-owned device buffer (16-byte aligned) of ch_jpeg_decode_workspace_bytes(N, H, W, C, sampling) bytes (0 for arguments
+ * the call would reject).  1 <= N <= 65535, 1 <= H, W <= 32768, H * W <= 2^30.  Enqueues on `stream` without synchronising or
+ * allocating.  No atomics between workgroups, no result read from the launch that writes it: image n is the same in every batch and
+ * every call. */
+#define CH_JPEG_DEC_OK 0
+#define CH_JPEG_DEC_BAD_CODE 1
+#define CH_JPEG_DEC_BAD_INDEX 2
+#define CH_JPEG_DEC_INPUT_END 3
+#define CH_JPEG_DEC_BLOCKS 4
+#define CH_JPEG_DEC_NOT_SYNCED 5
+#define CH_JPEG_DEC_TOO_LONG 6
+#define CH_JPEG_DEC_MARKER 7
+#define CH_JPEG_DEC_RANGE 8
+#define CH_JPEG_DEC_TABLE_BYTES 2048
+#define CH_JPEG_DEC_DEFAULT_ROUNDS 8
+size_t ch_jpeg_decode_workspace_bytes(int N, int H, int W, int C, int sampling);
+int    ch_jpeg_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C,
+                      int sampling, int rounds, uint8_t* img, int32_t* status, void* workspace, size_t workspace_bytes,
+                      ch_stream_t stream);
+
 /* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
  * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image
  * edge extended 10 px, mask_adaptor.py:119-131), the pair's triangle mesh is deformed as rigidly as possible (libigl's per-element

@@ -24,12 +24,15 @@ if ROOT not in sys.path:
 
 BUF_BYTES = 4 << 20
 NO_MESSAGE = ('ch_sean_set_tap', 'ch_profile_enable')      # with a handle these refuse without a message, or not at all
+# Entry points added after the table was recorded.  The table is a snapshot that guards the messages of the entry points it holds; a
+# later entry point's refusals and messages are asserted where it is tested (ch_jpeg_decode: tests/test_hip_jpegdec.py::test_abi_refusals)
+AFTER_THE_TABLE = ('ch_jpeg_decode',)
 
 
 def handle_entries(symbols):
-    """Names of the entry points whose first argument is the handle."""
+    """Names of the entry points whose first argument is the handle (those of the recorded table: not AFTER_THE_TABLE)."""
     return sorted(n for n, (res, args) in symbols.items()
-                  if (res is C.c_int and args[:1] == [C.c_void_p]) or n == 'ch_sean_noise_floats')
+                  if n not in AFTER_THE_TABLE and ((res is C.c_int and args[:1] == [C.c_void_p]) or n == 'ch_sean_noise_floats'))
 
 
 def _zero(argtype):
