@@ -723,16 +723,20 @@ size_t ch_jpeg_decode_workspace_bytes(int N, int H, int W, int C, int sampling) 
     return (N >= 1 && N <= 65535 && jpeg_dec_dims_ok(H, W, C, sampling)) ? chk::jpeg_decode_workspace_bytes(N, H, W, C, sampling) : 0;
 }
 
-int ch_jpeg_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C, int sampling,
-                   int rounds, uint8_t* img, int32_t* status, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+namespace {
+// ch_jpeg_decode (restart == nullptr) and ch_jpeg_decode_rst: one body, the entry's name in the messages
+int jpeg_decode_entry(const char* entry, ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, const uint32_t* restart,
+                      int N, int H, int W, int C, int sampling, int rounds, uint8_t* img, int32_t* status, void* workspace, size_t workspace_bytes,
+                      ch_stream_t stream) {
     namespace je = chk::jpegent;
     static_assert(CH_JPEG_DEC_OK == je::OK && CH_JPEG_DEC_BAD_CODE == je::BAD_CODE && CH_JPEG_DEC_BAD_INDEX == je::BAD_INDEX &&
                       CH_JPEG_DEC_INPUT_END == je::INPUT_END && CH_JPEG_DEC_BLOCKS == je::BLOCKS && CH_JPEG_DEC_NOT_SYNCED == je::NOT_SYNCED &&
                       CH_JPEG_DEC_TOO_LONG == je::TOO_LONG && CH_JPEG_DEC_MARKER == je::MARKER && CH_JPEG_DEC_RANGE == je::RANGE &&
+                      CH_JPEG_DEC_RESTART == je::RESTART &&
                       CH_JPEG_DEC_TABLE_BYTES == je::TABLE_BYTES && CH_JPEG_DEC_DEFAULT_ROUNDS == je::DEFAULT_ROUNDS,
                   "constants of the header and of jpeg_entropy_core.h");
     if (!h) return CH_ERR_ARG;
-    const std::string f = "ch_jpeg_decode: ";
+    const std::string f = std::string(entry) + ": ";
     if (!streams || !offsets || !tables || !img || !status || !workspace) return fail(h, CH_ERR_ARG, f + "null pointer");
     if (N < 1 || N > 65535) return fail(h, CH_ERR_ARG, f + "N outside 1..65535");
     if (C != 1 && C != 3) return fail(h, CH_ERR_ARG, f + "C must be 1 (grey) or 3 (YCbCr -> RGB)");
@@ -743,8 +747,24 @@ int ch_jpeg_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets,
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(h, CH_ERR_ARG, f + "workspace not 16-byte aligned");
     const size_t need = chk::jpeg_decode_workspace_bytes(N, H, W, C, sampling);
     if (int rc = workspace_short(h, f.c_str(), workspace_bytes, need, "ch_jpeg_decode_workspace_bytes")) return rc;
-    return launch(h, f.c_str(),
-                  [&] { return chk::jpeg_decode(streams, offsets, tables, N, H, W, C, sampling, rounds, img, status, workspace, hs(stream)); });
+    return launch(h, f.c_str(), [&] {
+        return chk::jpeg_decode(streams, offsets, tables, restart, N, H, W, C, sampling, rounds, img, status, workspace, hs(stream));
+    });
+}
+}  // namespace
+
+int ch_jpeg_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C, int sampling,
+                   int rounds, uint8_t* img, int32_t* status, void* workspace, size_t workspace_bytes, ch_stream_t stream) {
+    return jpeg_decode_entry("ch_jpeg_decode", h, streams, offsets, tables, nullptr, N, H, W, C, sampling, rounds, img, status, workspace,
+                             workspace_bytes, stream);
+}
+
+int ch_jpeg_decode_rst(ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, const uint32_t* restart, int N, int H,
+                       int W, int C, int sampling, int rounds, uint8_t* img, int32_t* status, void* workspace, size_t workspace_bytes,
+                       ch_stream_t stream) {
+    if (h && !restart) return fail(h, CH_ERR_ARG, "ch_jpeg_decode_rst: null pointer");
+    return jpeg_decode_entry("ch_jpeg_decode_rst", h, streams, offsets, tables, restart, N, H, W, C, sampling, rounds, img, status, workspace,
+                             workspace_bytes, stream);
 }
 
 int ch_sean_set_tap(ch_handle* h, const char* name, float* dev_ptr) {

@@ -1,4 +1,4 @@
-// ch_jpeg_decode (include/ctrlhair_hip.h): N baseline-JPEG scans -> N images.
+// ch_jpeg_decode and ch_jpeg_decode_rst (include/ctrlhair_hip.h): N baseline-JPEG scans -> N images.
 //
 // Entropy stage, parallel WITHIN a scan (jpeg_entropy_core.h has every address decision and runs on the CPU under sanitizers):
 //   jpeg_sync_kernel    `rounds` launches.  One wavefront per chunk of 64 subsequences of 128 bytes, the chunk's bytes and the image's six
@@ -16,6 +16,12 @@
 //   jpeg_colour_kernel  fancy upsampling of the chroma planes (h2v1 / h2v2, replication when the plane is at most 2 wide) fused with the
 //                       16-bit fixed-point YCbCr -> RGB, 16 pixels per thread, 16-byte stores when the rows allow.
 // Integer arithmetic only, no atomics: image n is a pure function of its bytes, the same in every batch and every call.
+//
+// Restart intervals (ch_jpeg_decode_rst: restart[n] MCUs per interval; a workgroup serves one stream, so the choice is uniform in it).  The
+// sync and write kernels run the RST instantiation of the entropy core: lanes jump over RSTm markers into the one state every decoder has
+// behind a marker.  jpeg_write_kernel, which decodes the true chain from true block ordinals, judges every jump (je::RstAudit) and turns
+// the stream into RESTART; jpeg_dc_kernel restarts its prefix sums at every interval.  restart == nullptr or restart[n] == 0 (or an
+// interval that holds the whole scan) takes the code without any of this.
 #include <hip/hip_runtime.h>
 
 #include "jpeg_entropy_core.h"
@@ -118,10 +124,11 @@ __device__ inline je::State shfl_up_state(je::State s) {
 __global__ __launch_bounds__(64) void jpeg_sync_kernel(const uint8_t* __restrict__ streams, const int64_t* __restrict__ offsets,
                                                        const uint8_t* __restrict__ tables, je::Geometry g, uint32_t bound, uint32_t nsub_max,
                                                        const je::SubState* __restrict__ prev, je::SubState* __restrict__ cur,
-                                                       int32_t* __restrict__ flags) {
+                                                       int32_t* __restrict__ flags, const uint32_t* __restrict__ restart) {
     __shared__ ChunkShared sh;
     const int n = blockIdx.y, lane = threadIdx.x;
     const uint32_t c = blockIdx.x;
+    const bool rst = restart && je::effective_restart(g, restart[n]);
     const uint8_t* in;
     const uint32_t len = stream_of(streams, offsets, n, bound, in);
     const uint32_t nsub = (len + je::SUBSEQ - 1) / je::SUBSEQ;
@@ -133,7 +140,7 @@ __global__ __launch_bounds__(64) void jpeg_sync_kernel(const uint8_t* __restrict
     je::State own{0, 0};
     bool changed = false;
     if (active) {
-        own = i ? je::guess(i, in[i * je::SUBSEQ - 1], in[i * je::SUBSEQ]) : je::State{0, 0};
+        if (i) own = rst ? je::guess_rst(i, in[i * je::SUBSEQ - 1], in[i * je::SUBSEQ]) : je::guess(i, in[i * je::SUBSEQ - 1], in[i * je::SUBSEQ]);
         if (!prev) {
             st.entry = own;
             changed = true;
@@ -151,16 +158,24 @@ __global__ __launch_bounds__(64) void jpeg_sync_kernel(const uint8_t* __restrict
         return;
     }
     const je::Window w = stage_chunk(sh, in, len, c, tables + (size_t)n * je::TABLE_BYTES, lane);
-    // a marker inside the scan: 0xFF followed by a byte that is no stuffing
+    // a marker inside the scan: 0xFF followed by a byte that is no stuffing (nor, in a stream with restart intervals, RST0..RST7)
     if (active) {
         const uint32_t b0 = i * je::SUBSEQ, b1 = b0 + je::SUBSEQ < len - 1 ? b0 + je::SUBSEQ : len - 1;
         bool marker = false;
-        for (uint32_t b = b0; b < b1; ++b) marker |= je::byte_at(w, b) == 0xFF && je::byte_at(w, b + 1) != 0;
+        if (rst) {
+            for (uint32_t b = b0; b < b1; ++b) marker |= je::byte_at(w, b) == 0xFF && je::byte_at(w, b + 1) != 0 && !je::is_rst(je::byte_at(w, b + 1));
+        } else {
+            for (uint32_t b = b0; b < b1; ++b) marker |= je::byte_at(w, b) == 0xFF && je::byte_at(w, b + 1) != 0;
+        }
         if (marker) flags[2 * n] = 1;
     }
     const uint32_t end = (i + 1) * je::SUBSEQ < len ? (i + 1) * je::SUBSEQ : len;
     for (int round = 0; round <= je::LANES; ++round) {
-        if (changed) je::run_subseq(sh.huff, g, w, len, end, st.entry, 0u, je::NoSink{}, st.exit, st.count);
+        if (changed) {
+            je::NoAudit none;
+            if (rst) je::run_subseq<true>(sh.huff, g, w, len, end, st.entry, 0u, je::NoSink{}, none, st.exit, st.count);
+            else je::run_subseq<false>(sh.huff, g, w, len, end, st.entry, 0u, je::NoSink{}, none, st.exit, st.count);
+        }
         const je::State before = shfl_up_state(st.exit);
         changed = false;
         if (active && lane) {
@@ -242,7 +257,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void jpeg_chain_kernel(const int64_t*
 __global__ __launch_bounds__(64) void jpeg_write_kernel(const uint8_t* __restrict__ streams, const int64_t* __restrict__ offsets,
                                                         const uint8_t* __restrict__ tables, je::Geometry g, uint32_t bound, uint32_t nsub_max,
                                                         const je::SubState* __restrict__ fin, const uint32_t* __restrict__ first,
-                                                        const int32_t* __restrict__ status, int16_t* __restrict__ coef) {
+                                                        int32_t* status, int16_t* __restrict__ coef, const uint32_t* __restrict__ restart) {
     __shared__ ChunkShared sh;
     const int n = blockIdx.y, lane = threadIdx.x;
     const uint32_t c = blockIdx.x;
@@ -258,21 +273,39 @@ __global__ __launch_bounds__(64) void jpeg_write_kernel(const uint8_t* __restric
     const uint32_t end = (i + 1) * je::SUBSEQ < len ? (i + 1) * je::SUBSEQ : len;
     je::State ex;
     uint32_t cnt;
-    je::run_subseq(sh.huff, g, w, len, end, fin[at].entry, first[at], je::CoefSink{coef + (uint64_t)n * g.nblocks * 64, g.nblocks}, ex, cnt);
+    const je::CoefSink sink{coef + (uint64_t)n * g.nblocks * 64, g.nblocks};
+    const uint32_t ri = restart ? je::effective_restart(g, restart[n]) : 0u;
+    if (ri) {
+        je::RstAudit audit{ri * (uint32_t)g.bpm, g.nblocks, false};
+        je::run_subseq<true>(sh.huff, g, w, len, end, fin[at].entry, first[at], sink, audit, ex, cnt);
+        // the same value from every lane that stores it; the workgroups that read OK above, before it, only write coefficients nobody reads
+        if (audit.bad) status[n] = je::RESTART;
+    } else {
+        je::NoAudit none;
+        je::run_subseq<false>(sh.huff, g, w, len, end, fin[at].entry, first[at], sink, none, ex, cnt);
+    }
 }
 
 constexpr int DC_PER_THREAD = 8;
 
-// DC differences -> DC values, per component in scan order
-__global__ __launch_bounds__(SCAN_THREADS) void jpeg_dc_kernel(je::Geometry g, const int32_t* __restrict__ status, int16_t* __restrict__ coef) {
+// DC differences -> DC values, per component in scan order.  With a restart interval the predictor is 0 at the start of every interval:
+// the value is S(j) - S(head(j) - 1), S the sums over the whole scan as without one, and the head of item j's interval follows from its
+// index alone.  Every S at the end of an interval goes through LDS (ends[k + 1]: of the k-th interval that touches this group of items;
+// ends[0]: of the one before, carried from group to group).  All of it modulo 2^16, which is what the stored values are.
+__global__ __launch_bounds__(SCAN_THREADS) void jpeg_dc_kernel(je::Geometry g, const int32_t* __restrict__ status, int16_t* __restrict__ coef,
+                                                               const uint32_t* __restrict__ restart) {
+    constexpr uint32_t GROUP = SCAN_THREADS * DC_PER_THREAD;
     __shared__ uint32_t buf[SCAN_THREADS];
+    __shared__ uint32_t ends[GROUP + 1];
     const int n = blockIdx.y, comp = blockIdx.x, t = threadIdx.x;
     if (status[n] != je::OK) return;
     const uint32_t per = comp == 0 ? (uint32_t)g.luma : 1u, firstb = comp == 0 ? 0u : (uint32_t)g.luma + comp - 1;
     const uint32_t nmcu = g.nblocks / (uint32_t)g.bpm, items = nmcu * per;
+    const uint32_t ri = restart ? je::effective_restart(g, restart[n]) : 0u, seg = ri * per;          // items per interval
     int16_t* cf = coef + (uint64_t)n * g.nblocks * 64;
     uint32_t carry = 0;
-    for (uint32_t j0 = 0; j0 < items; j0 += SCAN_THREADS * DC_PER_THREAD) {    // a thread sums DC_PER_THREAD neighbours, the workgroup scans the sums
+    if (ri && t == 0) ends[0] = 0;                                             // (block_scan's barriers stand before its first use)
+    for (uint32_t j0 = 0; j0 < items; j0 += GROUP) {                           // a thread sums DC_PER_THREAD neighbours, the workgroup scans the sums
         const uint32_t base = j0 + t * DC_PER_THREAD;
         uint32_t v[DC_PER_THREAD], run = 0;
 #pragma unroll
@@ -284,11 +317,30 @@ __global__ __launch_bounds__(SCAN_THREADS) void jpeg_dc_kernel(je::Geometry g, c
         }
         const uint32_t inc = block_scan(run, buf);
         const uint32_t before = carry + inc - run;
+        if (!ri) {
 #pragma unroll
-        for (int k = 0; k < DC_PER_THREAD; ++k) {
-            const uint32_t j = base + k;
-            const uint64_t blk = (uint64_t)(j / per) * g.bpm + firstb + j % per;
-            if (j < items) cf[blk * 64] = (int16_t)(uint16_t)(before + v[k]);
+            for (int k = 0; k < DC_PER_THREAD; ++k) {
+                const uint32_t j = base + k;
+                const uint64_t blk = (uint64_t)(j / per) * g.bpm + firstb + j % per;
+                if (j < items) cf[blk * 64] = (int16_t)(uint16_t)(before + v[k]);
+            }
+        } else {
+            const uint32_t s0 = j0 / seg, s1 = (j0 + GROUP) / seg;             // the first interval in this group of items and in the next
+#pragma unroll
+            for (int k = 0; k < DC_PER_THREAD; ++k) {
+                const uint32_t j = base + k;
+                if (j < items && (j + 1) % seg == 0) ends[j / seg - s0 + 1] = before + v[k];         // index <= GROUP
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < DC_PER_THREAD; ++k) {
+                const uint32_t j = base + k;
+                const uint64_t blk = (uint64_t)(j / per) * g.bpm + firstb + j % per;
+                if (j < items) cf[blk * 64] = (int16_t)(uint16_t)(before + v[k] - ends[j / seg - s0]);
+            }
+            const uint32_t next = ends[s1 - s0];                               // S(s1 * seg - 1); s1 - s0 <= GROUP; read only if a group follows
+            __syncthreads();
+            if (t == 0) ends[0] = next;
         }
         buf[t] = inc;
         __syncthreads();
@@ -480,8 +532,8 @@ int jpeg_decode_default_rounds() { return je::DEFAULT_ROUNDS; }
 
 size_t jpeg_decode_workspace_bytes(int N, int H, int W, int C, int sampling) { return make_layout(make_shape(H, W, C, sampling), N).total; }
 
-hipError_t jpeg_decode(const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C, int sampling, int rounds,
-                       uint8_t* img, int32_t* status, void* ws, hipStream_t st) {
+hipError_t jpeg_decode(const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, const uint32_t* restart, int N, int H, int W, int C,
+                       int sampling, int rounds, uint8_t* img, int32_t* status, void* ws, hipStream_t st) {
     const Shape s = make_shape(H, W, C, sampling);
     const Layout l = make_layout(s, N);
     uint8_t* w = static_cast<uint8_t*>(ws);
@@ -498,11 +550,11 @@ hipError_t jpeg_decode(const uint8_t* streams, const int64_t* offsets, const uin
     const dim3 chunks((s.nsub_max + je::LANES - 1) / je::LANES, N);
     for (int k = 0; k < rounds; ++k)
         hipLaunchKernelGGL(jpeg_sync_kernel, chunks, dim3(64), 0, st, streams, offsets, tables, s.g, s.bound, s.nsub_max,
-                           k ? state[(k - 1) & 1] : (const je::SubState*)nullptr, state[k & 1], flags);
+                           k ? state[(k - 1) & 1] : (const je::SubState*)nullptr, state[k & 1], flags, restart);
     const je::SubState* fin = state[(rounds - 1) & 1];
     hipLaunchKernelGGL(jpeg_chain_kernel, dim3(N), dim3(SCAN_THREADS), 0, st, offsets, s.g, s.bound, s.nsub_max, fin, first, flags, status);
-    hipLaunchKernelGGL(jpeg_write_kernel, chunks, dim3(64), 0, st, streams, offsets, tables, s.g, s.bound, s.nsub_max, fin, first, status, coef);
-    hipLaunchKernelGGL(jpeg_dc_kernel, dim3(C, N), dim3(SCAN_THREADS), 0, st, s.g, status, coef);
+    hipLaunchKernelGGL(jpeg_write_kernel, chunks, dim3(64), 0, st, streams, offsets, tables, s.g, s.bound, s.nsub_max, fin, first, status, coef, restart);
+    hipLaunchKernelGGL(jpeg_dc_kernel, dim3(C, N), dim3(SCAN_THREADS), 0, st, s.g, status, coef, restart);
     const uint64_t groups = ((uint64_t)N * s.g.nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS;
     const int cap = 16 * device_cus();
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)(groups < (uint64_t)cap ? groups : (uint64_t)cap)), dim3(IDCT_THREADS), 0, st, coef, tables,

@@ -283,10 +283,11 @@ hipError_t jpeg_encode(const uint8_t* img, int N, int H, int W, int C, int quali
 
 // jpeg_decode.hip: N baseline-JPEG entropy-coded scans (stream n = streams[offsets[n], offsets[n + 1]), its table block at tables +
 // n * 2048; jpeg_entropy_core.h) -> uint8 images [N,H,W,C] (C = 1 or 3).  sampling: 0 = 4:4:4 (and grey), 1 = 4:2:2, 2 = 4:2:0.  rounds:
-// launches of the state hand-over between chunks, 0 = the default.  status[n]: jpegent::Status.  See ch_jpeg_decode.
+// launches of the state hand-over between chunks, 0 = the default.  status[n]: jpegent::Status.  restart: null, or per stream its restart
+// interval in MCUs (device, [N]; 0 = none).  See ch_jpeg_decode and ch_jpeg_decode_rst.
 int jpeg_decode_default_rounds();
 size_t jpeg_decode_workspace_bytes(int N, int H, int W, int C, int sampling);
-hipError_t jpeg_decode(const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C, int sampling, int rounds,
-                       uint8_t* img, int32_t* status, void* ws, hipStream_t s);
+hipError_t jpeg_decode(const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, const uint32_t* restart, int N, int H, int W, int C,
+                       int sampling, int rounds, uint8_t* img, int32_t* status, void* ws, hipStream_t s);
 
 }  // namespace chk

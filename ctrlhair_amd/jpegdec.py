@@ -1,4 +1,4 @@
-"""JPEG files to pixels that are wanted on the device: ch_jpeg_decode (include/ctrlhair_hip.h, csrc/jpeg_decode.hip) Huffman-decodes the
+"""JPEG files to pixels that are wanted on the device: ch_jpeg_decode_rst (include/ctrlhair_hip.h, csrc/jpeg_decode.hip) Huffman-decodes the
 entropy-coded scans of a batch of files there -- in parallel WITHIN each scan, by self-synchronising subsequences (csrc/jpeg_entropy_core.h)
 -- and dequantises, inverse-transforms, upsamples and colour-converts them with libjpeg's integer arithmetic; the host reads the markers.
 
@@ -8,7 +8,9 @@ and the pixels never exist on the host.  For every stream the device accepts (it
 `Image.open(path).convert('RGB')` (or 'L' for grey files) returns, byte for byte (Pillow on libjpeg-turbo).
 
 Only what the device decodes is parsed: baseline sequential Huffman (SOF0), 8 bits, one scan holding all components, 1 component or 3
-(YCbCr; luma sampled 1x1, 2x1 or 2x2, chroma 1x1), 8-bit quantisers, any Huffman tables, no restart interval.  Everything else -- and
+(YCbCr; luma sampled 1x1, 2x1 or 2x2, chroma 1x1), 8-bit quantisers, any Huffman tables, with or without a restart interval (DRI and
+RST0..RST7, as cameras write them: parse_jpeg_restart; parse_jpeg keeps refusing them).  A file whose restart markers are not where its
+interval puts them has status RESTART: libjpeg's resynchronisation of damaged intervals is Pillow's.  Everything else -- and
 every stream the device refuses (its status is non-zero) -- goes to Pillow, file by file (dataset.read_rgb / read_gray), so results and
 errors are the host path's by construction; JpegDecoder.fallbacks counts those files.  EXIF orientation is not applied (nor by read_rgb).
 """
@@ -28,11 +30,12 @@ SAMPLINGS = {0x11: 0, 0x21: 1, 0x22: 2}   # luma sampling byte of SOF0 -> Pillow
 MAX_STREAM = 1 << 28
 _ALIGN = 16
 _MARKER = re.compile(rb'\xff[^\x00]')
+_MARKER_NOT_RST = re.compile(rb'\xff[^\x00\xd0-\xd7]')
 _SOF_NAMES = {0xC1: 'extended sequential', 0xC2: 'progressive', 0xC3: 'lossless', 0xC5: 'differential sequential', 0xC6: 'differential progressive',
               0xC7: 'differential lossless', 0xC9: 'arithmetic coding', 0xCA: 'arithmetic coding', 0xCB: 'arithmetic coding',
               0xCD: 'arithmetic coding', 0xCE: 'arithmetic coding', 0xCF: 'arithmetic coding'}
 
-STATUS_NAMES = ('OK', 'BAD_CODE', 'BAD_INDEX', 'INPUT_END', 'BLOCKS', 'NOT_SYNCED', 'TOO_LONG', 'MARKER', 'RANGE')
+STATUS_NAMES = ('OK', 'BAD_CODE', 'BAD_INDEX', 'INPUT_END', 'BLOCKS', 'NOT_SYNCED', 'TOO_LONG', 'MARKER', 'RANGE', 'RESTART')
 NOT_SYNCED = 5
 
 
@@ -65,11 +68,23 @@ def _check_huffman(cls: int, bits: bytes, vals: bytes) -> None:
 def parse_jpeg(data: bytes) -> Tuple[int, int, int, int, bytes, bytes]:
     """A JPEG file -> (H, W, C, sampling, table block, the entropy-coded scan).  sampling: 0 = 4:4:4 (and grey), 1 = 4:2:2, 2 = 4:2:0.
     table block: TABLE_BYTES bytes -- per component its quantiser in natural order, its DC and its AC Huffman table as BITS and HUFFVAL.
-    Raises Unsupported for everything outside the module's scope and for a damaged container."""
+    Raises Unsupported for everything outside the module's scope -- a restart interval included: parse_jpeg_restart -- and for a damaged
+    container."""
+    return _parse(data, False)[:6]
+
+
+def parse_jpeg_restart(data: bytes) -> Tuple[int, int, int, int, bytes, bytes, int]:
+    """parse_jpeg with restart intervals in scope -> (H, W, C, sampling, table block, scan, Ri).  Ri: the DRI segment's MCUs per interval
+    (the last one before the scan; 0 without one, and then everything is parse_jpeg's).  With Ri > 0 the scan -- the bytes between the SOS
+    header and EOI -- keeps its RST0..RST7 markers; any other marker inside it stays Unsupported."""
+    return _parse(data, True)
+
+
+def _parse(data: bytes, restart_ok: bool):
     data = bytes(data)
     if data[:2] != b'\xff\xd8':
         raise Unsupported('no SOI marker')
-    pos, quant, huff, frame, jfif, adobe = 2, {}, {}, None, False, None
+    pos, quant, huff, frame, jfif, adobe, ri = 2, {}, {}, None, False, None, 0
     while True:
         if pos + 2 > len(data):
             raise Unsupported('truncated: no SOS marker')
@@ -121,8 +136,9 @@ def parse_jpeg(data: bytes) -> Tuple[int, int, int, int, bytes, bytes]:
         elif m == 0xDD:
             if len(body) != 2:
                 raise Unsupported('bad DRI')
-            if body != b'\0\0':
+            if body != b'\0\0' and not restart_ok:
                 raise Unsupported('restart interval (DRI)')
+            ri = struct.unpack('>H', body)[0]
         elif m == 0xE0 and body[:5] == b'JFIF\0':
             jfif = True
         elif m == 0xEE and body[:5] == b'Adobe' and len(body) >= 12:
@@ -171,7 +187,7 @@ def parse_jpeg(data: bytes) -> Tuple[int, int, int, int, bytes, bytes]:
                 raise Unsupported(f'Huffman table {ident:02x} is missing')
             at = _TABLE_HUFF + (2 * k + cls) * _TABLE_HUFF_STRIDE
             tables[at:at + _TABLE_HUFF_STRIDE] = huff[ident]
-    found = _MARKER.search(data, pos)
+    found = (_MARKER_NOT_RST if ri else _MARKER).search(data, pos)
     if found is None:
         raise Unsupported('no EOI marker')
     if data[found.start() + 1] != 0xD9:
@@ -179,7 +195,7 @@ def parse_jpeg(data: bytes) -> Tuple[int, int, int, int, bytes, bytes]:
     scan = data[pos:found.start()]
     if len(scan) > stream_bound(H, W, C, sampling):
         raise Unsupported('a scan longer than any valid one')
-    return H, W, C, sampling, bytes(tables), scan
+    return H, W, C, sampling, bytes(tables), scan, ri
 
 
 class JpegDecoder(DeviceOp):
@@ -189,67 +205,85 @@ class JpegDecoder(DeviceOp):
         super().__init__(handle, device)
         self.fallbacks = 0
 
-    def upload(self, streams: Sequence[bytes], tables: Sequence[bytes]):
-        """N scans and their table blocks -> (device buffer, where the tables and the streams start in it, N): one buffer -- the offsets
-        table, the table blocks, the streams without gaps (each part from a multiple of 16 bytes) -- packed in pinned memory and uploaded
-        in one copy."""
+    def upload(self, streams: Sequence[bytes], tables: Sequence[bytes], restart: Sequence[int] = None):
+        """N scans and their table blocks -> (device buffer, where the tables and the streams start in it, N[, where the restart intervals
+        start]): one buffer -- the offsets table, (restart: the intervals as uint32,) the table blocks, the streams without gaps (each part
+        from a multiple of 16 bytes) -- packed in pinned memory and uploaded in one copy.  restart: per stream its Ri (parse_jpeg_restart);
+        None: all 0, the buffer and the call of a decoder without restart intervals."""
         N = len(streams)
         if len(tables) != N or any(len(t) != TABLE_BYTES for t in tables):
             raise ValueError(f'JpegDecoder: one table block of {TABLE_BYTES} bytes per stream')
+        if restart is not None and (len(restart) != N or any(not 0 <= int(r) <= 0xFFFFFFFF for r in restart)):
+            raise ValueError('JpegDecoder: one restart interval (0..2^32 - 1 MCUs) per stream')
         offs = np.zeros(N + 1, np.int64)
         np.cumsum([len(z) for z in streams], out=offs[1:])
         tables_at = 8 * (N + 1) + (-8 * (N + 1)) % _ALIGN
+        restart_at = tables_at
+        if restart is not None:
+            tables_at += 4 * N + (-4 * N) % _ALIGN
         data_at = tables_at + N * TABLE_BYTES
         total = data_at + max(int(offs[N]), 1)
         stage = self._buffer('_pinned', total, pinned=True)
         host = stage[:total].numpy()
         host[:8 * (N + 1)] = np.frombuffer(offs.tobytes(), np.uint8)
+        if restart is not None:
+            host[restart_at:restart_at + 4 * N] = np.frombuffer(np.asarray([int(r) for r in restart], np.uint32).tobytes(), np.uint8)
         host[tables_at:data_at] = np.frombuffer(b''.join(tables), np.uint8)
         host[data_at:data_at + int(offs[N])] = np.frombuffer(b''.join(streams), np.uint8)
         dev = self._buffer('_in', total)
         dev[:total].copy_(stage[:total], non_blocking=True)
-        return dev, tables_at, data_at, N
+        return (dev, tables_at, data_at, N) if restart is None else (dev, tables_at, data_at, N, restart_at)
 
     def _reject(self, N, H, W, C, sampling):
         return ValueError(f'JpegDecoder: ch_jpeg_decode rejects N={N}, H={H}, W={W}, C={C}, sampling={sampling} (C 1/3, sampling 0/1/2 and 0 '
                           f'for C = 1, sides 1..32768, H * W <= 2^30, N 1..65535)')
 
     def launch(self, uploaded, H: int, W: int, C: int, sampling: int, rounds: int = 0):
-        """One ch_jpeg_decode call on what upload() returned -> (uint8 [N,H,W,C], int32 [N] statuses), device tensors; no synchronisation."""
+        """One ch_jpeg_decode call (ch_jpeg_decode_rst when upload() was given restart intervals) on what upload() returned -> (uint8
+        [N,H,W,C], int32 [N] statuses), device tensors; no synchronisation."""
         import torch
-        dev, tables_at, data_at, N = uploaded
+        dev, tables_at, data_at, N = uploaded[:4]
         need = int(self.handle.lib.ch_jpeg_decode_workspace_bytes(N, H, W, C, sampling))
         if need == 0:
             raise self._reject(N, H, W, C, sampling)
         ws = self._buffer('_ws', need)
         img = torch.empty((N, H, W, C), dtype=torch.uint8, device=self.device)
         status = torch.empty(N, dtype=torch.int32, device=self.device)
-        self.handle.call('ch_jpeg_decode', dev.data_ptr() + data_at, dev.data_ptr(), dev.data_ptr() + tables_at, N, H, W, C, sampling, rounds,
-                         img.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+        if len(uploaded) == 4:
+            self.handle.call('ch_jpeg_decode', dev.data_ptr() + data_at, dev.data_ptr(), dev.data_ptr() + tables_at, N, H, W, C, sampling, rounds,
+                             img.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+        else:
+            self.handle.call('ch_jpeg_decode_rst', dev.data_ptr() + data_at, dev.data_ptr(), dev.data_ptr() + tables_at,
+                             dev.data_ptr() + uploaded[4], N, H, W, C, sampling, rounds, img.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                             ws.numel(), self._stream())
         return img, status
 
-    def decode_streams(self, streams: Sequence[bytes], tables: Sequence[bytes], H: int, W: int, C: int, sampling: int, rounds: int = 0):
+    def decode_streams(self, streams: Sequence[bytes], tables: Sequence[bytes], H: int, W: int, C: int, sampling: int, rounds: int = 0,
+                       restart: Sequence[int] = None):
         """N scans of images of one shape -> (uint8 device tensor [N,H,W,C], int32 device tensor [N] of CH_JPEG_DEC_* statuses).  One
         upload, one ch_jpeg_decode call, one synchronisation at the end (the pinned stage and the input buffer are reused by the next
-        call).  rounds: launches of the hand-over between chunks, 0 for the library's default."""
+        call).  rounds: launches of the hand-over between chunks, 0 for the library's default.  restart: per stream its restart interval
+        in MCUs, the scans then with their RSTm markers (ch_jpeg_decode_rst); None: none has one."""
         import torch
         if int(self.handle.lib.ch_jpeg_decode_workspace_bytes(len(streams), H, W, C, sampling)) == 0:
             raise self._reject(len(streams), H, W, C, sampling)
-        out = self.launch(self.upload(streams, tables), H, W, C, sampling, rounds)
+        out = self.launch(self.upload(streams, tables, restart), H, W, C, sampling, rounds)
         torch.cuda.current_stream(self.device).synchronize()
         return out
 
     def decode(self, blobs: Sequence[bytes], rounds: int = 0):
         """JPEG files (bytes) -> (tensors, statuses): per file a uint8 device tensor [H,W,3] ([H,W] for grey files) and the CH_JPEG_DEC_*
         status of its scan (non-zero: the pixels are unspecified).  Files are grouped by (H, W, C, sampling), one ch_jpeg_decode call per
-        group.  Raises Unsupported for a file parse_jpeg refuses."""
-        parsed = [parse_jpeg(b) for b in blobs]
+        group, whatever the files' restart intervals.  Raises Unsupported for a file parse_jpeg_restart refuses."""
+        parsed = [parse_jpeg_restart(b) for b in blobs]
         groups = {}
         for i, p in enumerate(parsed):
             groups.setdefault(p[:4], []).append(i)
         tensors, statuses = [None] * len(parsed), [0] * len(parsed)
         for (H, W, C, sampling), idx in groups.items():
-            img, status = self.decode_streams([parsed[i][5] for i in idx], [parsed[i][4] for i in idx], H, W, C, sampling, rounds)
+            restart = [parsed[i][6] for i in idx]
+            img, status = self.decode_streams([parsed[i][5] for i in idx], [parsed[i][4] for i in idx], H, W, C, sampling, rounds,
+                                              restart if any(restart) else None)
             status = status.cpu().tolist()
             for k, i in enumerate(idx):
                 tensors[i] = img[k, :, :, 0] if C == 1 else img[k]
@@ -267,7 +301,7 @@ class JpegDecoder(DeviceOp):
                 with open(p, 'rb') as f:
                     data = f.read()
                 try:
-                    C = parse_jpeg(data)[2]
+                    C = parse_jpeg_restart(data)[2]
                 except Unsupported:
                     continue
                 if gray and C != 1:                                             # convert('L') weighs the channels: Pillow's arithmetic

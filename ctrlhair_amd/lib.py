@@ -54,6 +54,7 @@ SYMBOLS = {
     'ch_jpeg_encode': (_I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_jpeg_decode_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I, _I]),
     'ch_jpeg_decode': (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
+    'ch_jpeg_decode_rst': (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_png_decode_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
     'ch_png_decode': (_I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_mask_warp_workspace_bytes': (C.c_size_t, [_I]),

@@ -458,6 +458,7 @@ int    ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int
  *   NOT_SYNCED    see above: decode it elsewhere or call again with more rounds
  *   TOO_LONG      more than min(512 * blocks, 2^28 - 1) bytes: longer than any valid scan (64 symbols of 31 bits per block, all stuffed)
  *   MARKER        a 0xFF followed by a byte other than 0x00 inside the stream
+ *   RESTART       ch_jpeg_decode_rst only: the restart markers are not where the interval puts them (see below)
  *   RANGE         a dequantised coefficient or a first-pass value beyond +-8191, or a sample before the range limit outside -512..511:
  *                 values no sane file holds, at which libjpeg's C code, its SIMD code and 32-bit arithmetic part ways
  * and the pixels of that image are unspecified.  For every byte sequence: the work for image n reads no stream byte outside
@@ -465,7 +466,28 @@ int    ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int
  * workspace: caller-owned device buffer (16-byte aligned) of ch_jpeg_decode_workspace_bytes(N, H, W, C, sampling) bytes (0 for arguments
  * the call would reject).  1 <= N <= 65535, 1 <= H, W <= 32768, H * W <= 2^30.  Enqueues on `stream` without synchronising or
  * allocating.  No atomics between workgroups, no result read from the launch that writes it: image n is the same in every batch and
- * every call. */
+ * every call.
+ *
+ * ch_jpeg_decode_rst is ch_jpeg_decode for scans with restart intervals: restart (uint32 [N], device) holds per stream the Ri of its DRI
+ * segment, MCUs per interval, 0 = none; the stream then keeps its RSTm markers (0xFF 0xD0..0xD7).  ch_jpeg_decode is the all-zero case,
+ * with byte-identical results, and the workspace is the same (ch_jpeg_decode_workspace_bytes).  For stream n with Ri > 0:
+ *   1. An RSTm is legal in one place only: directly after the block that completes MCU number k * Ri (k >= 1, not after the last MCU),
+ *      behind at most 7 pad bits, which are discarded unread as libjpeg does, with m == (k - 1) mod 8.  After it the decoder is at the
+ *      byte behind the marker, block 0 of an MCU, zigzag index 0.
+ *   2. RESTART: a marker missing at such a boundary, a marker anywhere else, a wrong m, two markers back to back; whole extra bytes or a
+ *      fill 0xFF before a marker where the decoder gets as far as the marker (bytes that are no codes end it earlier, with BAD_CODE or
+ *      BAD_INDEX; a fill 0xFF that decodes is MARKER by rule 3).  The pixels are unspecified, as for every non-zero status.
+ *   3. 0xFF followed by anything other than 0x00 or 0xD0..0xD7 stays MARKER.
+ *   4. The DC predictors are 0 at the start of every interval.
+ *   5. Ri at or above the image's MCU count expects no marker: the stream decodes as by ch_jpeg_decode (a marker in it is MARKER).
+ *   6. Every guarantee above carries over word for word: for every byte sequence and every Ri the work for image n reads nothing outside
+ *      its stream, writes nothing outside its slices and terminates; no atomics between workgroups; image n is the same in every batch
+ *      and every call; a stream is NOT_SYNCED, never wrong pixels.
+ * A lane of the entropy stage whose next symbol does not fit before a marker continues from the state behind it whatever state it
+ * arrived in, so wrong guesses converge at the first marker; whether a jump was legal is judged on the true chain only, where the block
+ * ordinals are known.  A lane cannot drop the padding by count as libjpeg does: padding that reads as a whole symbol (only with a
+ * Huffman table that assigns the all-ones code, which T.81 forbids) is RESTART.  libjpeg's resynchronisation of damaged intervals is
+ * not restated: those streams are RESTART, decode them elsewhere. */
 #define CH_JPEG_DEC_OK 0
 #define CH_JPEG_DEC_BAD_CODE 1
 #define CH_JPEG_DEC_BAD_INDEX 2
@@ -475,12 +497,16 @@ int    ch_jpeg_encode(ch_handle* h, const uint8_t* img, int N, int H, int W, int
 #define CH_JPEG_DEC_TOO_LONG 6
 #define CH_JPEG_DEC_MARKER 7
 #define CH_JPEG_DEC_RANGE 8
+#define CH_JPEG_DEC_RESTART 9
 #define CH_JPEG_DEC_TABLE_BYTES 2048
 #define CH_JPEG_DEC_DEFAULT_ROUNDS 8
 size_t ch_jpeg_decode_workspace_bytes(int N, int H, int W, int C, int sampling);
 int    ch_jpeg_decode(ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, int N, int H, int W, int C,
                       int sampling, int rounds, uint8_t* img, int32_t* status, void* workspace, size_t workspace_bytes,
                       ch_stream_t stream);
+int    ch_jpeg_decode_rst(ch_handle* h, const uint8_t* streams, const int64_t* offsets, const uint8_t* tables, const uint32_t* restart, int N,
+                          int H, int W, int C, int sampling, int rounds, uint8_t* img, int32_t* status, void* workspace,
+                          size_t workspace_bytes, ch_stream_t stream);
 
 /* ---- Hair-shape transfer: the mask warp of wrap_codes/mask_adaptor.py:87-143 (hair_mask_transfer_wrap), batched -------------
  * For each of B pairs: the donor's hair mask (hair_labels == 13) is padded to the 672 x 672 canvas (80-px border, hair on an image

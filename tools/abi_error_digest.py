@@ -25,8 +25,9 @@ if ROOT not in sys.path:
 BUF_BYTES = 4 << 20
 NO_MESSAGE = ('ch_sean_set_tap', 'ch_profile_enable')      # with a handle these refuse without a message, or not at all
 # Entry points added after the table was recorded.  The table is a snapshot that guards the messages of the entry points it holds; a
-# later entry point's refusals and messages are asserted where it is tested (ch_jpeg_decode: tests/test_hip_jpegdec.py::test_abi_refusals)
-AFTER_THE_TABLE = ('ch_jpeg_decode',)
+# later entry point's refusals and messages are asserted where it is tested (ch_jpeg_decode: tests/test_hip_jpegdec.py::test_abi_refusals,
+# ch_jpeg_decode_rst: tests/test_hip_jpegdec_rst.py::test_abi_refusals)
+AFTER_THE_TABLE = ('ch_jpeg_decode', 'ch_jpeg_decode_rst')
 
 
 def handle_entries(symbols):
