@@ -13,6 +13,7 @@
 #include "aux_models.h"
 #include "sean_model.h"
 #include "kernels.h"
+#include "ingest_batch.h"
 #include "jpeg_entropy_core.h"
 #include "png_inflate_core.h"
 
@@ -552,6 +553,47 @@ int ch_resize_linear_u8(ch_handle* h, const uint8_t* src, uint8_t* dst, int B, i
     if (!src || !dst || B < 1 || B > 65535 || Hs < 1 || Ws < 1 || C < 1 || C > 4 || Hd < 1 || Hd > 65535 || Wd < 1)
         return fail(h, CH_ERR_ARG, "ch_resize_linear_u8: bad argument");
     return launch(h, "ch_resize_linear_u8: ", [&] { return chk::resize_linear_u8(src, dst, B, Hs, Ws, C, Hd, Wd, hs(stream)); });
+}
+
+// ---- image ingest (ingest.hip) ------------------------------------------------------------------------------------------------------
+size_t ch_ingest_workspace_bytes(const void* batch, size_t batch_bytes, int N, int P, int mode) {
+    size_t need = 0;
+    return chk::ingest_check(batch, batch_bytes, N, P, mode, need).empty() ? need : 0;
+}
+
+namespace {
+static_assert(CH_INGEST_PIL_BILINEAR == chk::INGEST_PIL && CH_INGEST_CV2_LINEAR == chk::INGEST_CV2 && CH_INGEST_LABELS == chk::INGEST_LABELS &&
+                  CH_INGEST_DESC_BYTES == sizeof(chk::IngestImage) && CH_INGEST_MAX_SIDE == chk::INGEST_MAX_SIDE &&
+                  CH_INGEST_MAX_OUT == chk::INGEST_MAX_OUT,
+              "ingest constants of the header and of kernels.h");
+// the checks both ingest entries share behind their null-pointer test: the batch, then the workspace
+int ingest_refuse(ch_handle* h, const char* prefix, const void* batch, size_t batch_bytes, int N, int P, int mode, const void* workspace,
+                  size_t workspace_bytes) {
+    size_t need = 0;
+    const std::string why = chk::ingest_check(batch, batch_bytes, N, P, mode, need);
+    if (!why.empty()) return fail(h, CH_ERR_ARG, std::string(prefix) + why);
+    if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return fail(h, CH_ERR_ARG, std::string(prefix) + "workspace is not 256-byte aligned");
+    return workspace_short(h, prefix, workspace_bytes, need, "ch_ingest_workspace_bytes");
+}
+}  // namespace
+
+int ch_ingest_images(ch_handle* h, const void* batch, size_t batch_bytes, int N, int P, int mode, const float* lut, float* out, void* workspace,
+                     size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!batch || !lut || !out || !workspace) return fail(h, CH_ERR_ARG, "ch_ingest_images: null pointer");
+    if (mode != CH_INGEST_PIL_BILINEAR && mode != CH_INGEST_CV2_LINEAR) return fail(h, CH_ERR_ARG, "ch_ingest_images: mode is not 0 or 1");
+    if (reinterpret_cast<uintptr_t>(lut) % 4 != 0 || reinterpret_cast<uintptr_t>(out) % 16 != 0)
+        return fail(h, CH_ERR_ARG, "ch_ingest_images: lut is not 4-byte aligned or out is not 16-byte aligned");
+    if (int rc = ingest_refuse(h, "ch_ingest_images: ", batch, batch_bytes, N, P, mode, workspace, workspace_bytes)) return rc;
+    return launch(h, "ch_ingest_images: ", [&] { return chk::ingest_images(batch, batch_bytes, N, P, mode, lut, out, workspace, hs(stream)); });
+}
+
+int ch_ingest_labels(ch_handle* h, const void* batch, size_t batch_bytes, int N, int S, uint8_t* out, void* workspace, size_t workspace_bytes,
+                     ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!batch || !out || !workspace) return fail(h, CH_ERR_ARG, "ch_ingest_labels: null pointer");
+    if (int rc = ingest_refuse(h, "ch_ingest_labels: ", batch, batch_bytes, N, S, CH_INGEST_LABELS, workspace, workspace_bytes)) return rc;
+    return launch(h, "ch_ingest_labels: ", [&] { return chk::ingest_labels(batch, batch_bytes, N, S, out, workspace, hs(stream)); });
 }
 
 int ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, int label, int ksize, uint8_t* mask, int H, int W,

@@ -10,28 +10,11 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "linear_tap.h"
 
 namespace chk {
 
-// ---- uint8 bilinear resize ----------------------------------------------------------------------------------------------
-// One axis of hostutil._linear_taps: f = (i + 0.5) * (n_in / n_out) - 0.5 in double (no contraction: the host rounds the
-// product and the difference separately), floor, fraction rounded to f32, zero fraction at clamped taps, 11-bit weights
-// rint(f * 2048) and rint((1 - f) * 2048) in f32.
-__device__ __forceinline__ void linear_tap(int i, int n_out, int n_in, int& i0, int& i1, int& w0, int& w1) {
-#pragma clang fp contract(off)
-    const double scale = (double)n_in / (double)n_out;
-    const double fd = ((double)i + 0.5) * scale - 0.5;
-    const double fl = floor(fd);
-    int k = (int)fl;
-    float f = (float)(fd - fl);
-    if (k < 0 || k >= n_in - 1) f = 0.f;
-    k = k < 0 ? 0 : (k > n_in - 1 ? n_in - 1 : k);
-    i0 = k;
-    i1 = k + 1 < n_in - 1 ? k + 1 : n_in - 1;
-    w1 = (int)rintf(f * 2048.f);
-    w0 = (int)rintf((1.f - f) * 2048.f);
-}
-
+// ---- uint8 bilinear resize (taps and weights of one axis: linear_tap.h) ---------------------------------------------------
 // one thread per output pixel, all C channels: rows = a0 * p[x0] + a1 * p[x1] (int32), >> 4, then
 // ((b0 * top) >> 16) + ((b1 * bot) >> 16) + 2 >> 2, saturated
 __global__ __launch_bounds__(256) void resize_linear_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int Hs,

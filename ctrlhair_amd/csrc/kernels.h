@@ -159,6 +159,14 @@ hipError_t hair_erode(const uint8_t* labels, int B, int Hl, int Wl, int label, c
                       hipStream_t s);
 hipError_t hair_color_stats(const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums, hipStream_t s);
 
+// ingest.hip: a ragged batch of decoded uint8 images -> float32 [N,3,P,P] network input (Pillow's antialiased BILINEAR or cv2's
+// INTER_LINEAR resize, then a float table [3][256] indexed by the resized byte), and of label maps -> uint8 [N,S,S] (nearest).
+// batch: HOST bytes, N descriptors and then the coefficient tables they point to (ingest_batch.h); the launchers take only a batch
+// that ingest_check has passed, and a workspace of the size it returned.
+hipError_t ingest_images(const void* batch, size_t batch_bytes, int N, int P, int mode, const float* lut, float* out, void* ws,
+                         hipStream_t s);
+hipError_t ingest_labels(const void* batch, size_t batch_bytes, int N, int S, uint8_t* out, void* ws, hipStream_t s);
+
 // sheet.hip: contact sheets and per-render measurements of a direction search (shape_branch/script_find_direction.py:55-76,
 // util/canvas_grid.py:15-31).  See ch_sheet_compose / ch_sweep_stats in ctrlhair_hip.h.
 constexpr int SWEEP_NSTAT = 16;               // == CH_SWEEP_STATS

@@ -16,8 +16,8 @@ On-disk formats are the reference's:
   rgb_stat_dict.pkl, color_var_stat_dict.pkl   the merged dicts;  hsv_stat_dict_ordered.pkl   uint8 [N,3] table of the colour
                                         sliders (script_get_rgb_hsv_label.py:70-90; load with hostutil.DistTranslation(root=<root>))
 
-    python -m ctrlhair_amd.dataset masks    <root> <dataset> [--batch 16] [--png host|device]
-    python -m ctrlhair_amd.dataset codes    <root> <dataset> [--batch 16]
+    python -m ctrlhair_amd.dataset masks    <root> <dataset> [--batch 16] [--png host|device] [--decode host|device]
+    python -m ctrlhair_amd.dataset codes    <root> <dataset> [--batch 16] [--decode host|device]
     python -m ctrlhair_amd.dataset rgb      <root> <dataset> [--batch 16]     (no network weights: ctrlhair_amd.colorstats)
     python -m ctrlhair_amd.dataset colorvar <root> <dataset> [--batch 16]
     python -m ctrlhair_amd.dataset crop <src_dir> <root> <dataset> --landmarks <file> [--size 256] [--png host|device]
@@ -63,6 +63,8 @@ On-disk formats are the reference's:
     (crop and uncrop take --decode host|device for the photos and edits they read: 'device' uploads the files' bytes and decodes them
      there, .jpg / .jpeg with ch_jpeg_decode (ctrlhair_amd.jpegdec), .png with ch_png_decode; the pixels are Pillow's, so the results are
      the same files; progressive JPEGs and whatever else the device does not take are decoded by Pillow, file by file)
+    (masks and codes take --decode host|device too: 'device' decodes a batch's files in the same way and then resizes and normalises them
+     there in one call, ch_ingest_images / ch_ingest_labels (ctrlhair_amd.ingest): the networks see the same tensors bit for bit)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
 """
 import os
@@ -175,6 +177,30 @@ class _PhotoReader:
         self.other += 1
         return torch.from_numpy(np.array(read_rgb(path))).to(self.device)
 
+    def _read_many(self, paths, gray: bool) -> List:
+        import torch
+        paths = list(paths)
+        out = [None] * len(paths)
+        for decoder, takes in ((self.jpeg, _is_jpeg), (self.png, _is_png)):
+            idx = [i for i, p in enumerate(paths) if takes(p)]
+            if idx:                                          # one call per decoder and batch; it counts its own fallbacks
+                for i, t in zip(idx, (decoder.read_gray if gray else decoder.read_rgb)([paths[i] for i in idx])):
+                    out[i] = t
+        for i, p in enumerate(paths):
+            if out[i] is None:
+                self.other += 1
+                out[i] = torch.from_numpy(np.array((read_gray if gray else read_rgb)(p))).to(self.device)
+        return out
+
+    def read_rgb_many(self, paths) -> List:
+        """read_rgb of a batch, in the order of `paths`: one JpegDecoder call for its .jpg / .jpeg files and one PngDecoder call for its
+        .png files (each groups equal sizes into one launch); uint8 device tensors [H,W,3]."""
+        return self._read_many(paths, gray=False)
+
+    def read_gray_many(self, paths) -> List:
+        """dataset.read_gray of a batch in the same way: uint8 device tensors [H,W]; only grey files are decoded on the device."""
+        return self._read_many(paths, gray=True)
+
 
 def _photo_reader(decode: str, owner):
     """None for decode='host' (dataset.read_rgb reads the photos); for 'device' a _PhotoReader on `owner`'s handle and device."""
@@ -190,20 +216,35 @@ def _is_jpeg(name: str) -> bool:
     return name.lower().endswith(('.jpg', '.jpeg'))
 
 
+def _image_ingest(reader, owner):
+    """None without a reader (decode='host'); else ingest.ImageIngest on `owner`'s handle and device."""
+    from .ingest import ImageIngest
+    return None if reader is None else ImageIngest(owner.handle, owner.device)
+
+
 def extract_masks(editor, img_dir: str, label_dir: str, batch: int = 16, rank: int = 0, world: int = 1,
-                  parse_size: int = 512, png: str = 'host') -> List[str]:
+                  parse_size: int = 512, png: str = 'host', decode: str = 'host', stats: dict = None) -> List[str]:
     """BiSeNet-parse every image of `img_dir` (this rank's shard) and write `label_dir/<name>.png`.
     Per image identical to FaceParsing.parsing_img + swap_parsing_label_to_celeba_mask (my_parsing_util.py:31-54).
-    png='device': the label maps of a batch are encoded on the device in one call (the same pixels in another file)."""
+    png='device': the label maps of a batch are encoded on the device in one call (the same pixels in another file).
+    decode='device': the files of a batch are decoded on the device (.jpg / .jpeg: jpegdec.JpegDecoder, .png: pngdec.PngDecoder) and
+    resized and normalised there in one call (ingest.ImageIngest.parse_input): the network sees the same float32 tensor bit for bit, so
+    the label maps are the same; what a decoder does not take is Pillow's, file by file, and counted in stats['fallbacks'] when a dict
+    is passed.  With png='device' as well the host touches file bytes only."""
     import torch
     from PIL import Image
     os.makedirs(label_dir, exist_ok=True)
     fp = editor.face_parsing
     encoder = _png_encoder(png, fp)
+    reader = _photo_reader(decode, fp)
+    ingest = _image_ingest(reader, fp)
     done = []
     for names in batches(shard(list_images(img_dir), rank, world), batch):
-        x = torch.cat([fp.normalise(np.asarray(Image.fromarray(read_rgb(os.path.join(img_dir, n)))
-                                               .resize((parse_size, parse_size), Image.BILINEAR))) for n in names], dim=0)
+        if reader is not None:
+            x = ingest.parse_input(reader.read_rgb_many([os.path.join(img_dir, n) for n in names]), parse_size, lut=fp.ingest_lut())
+        else:
+            x = torch.cat([fp.normalise(np.asarray(Image.fromarray(read_rgb(os.path.join(img_dir, n)))
+                                                   .resize((parse_size, parse_size), Image.BILINEAR))) for n in names], dim=0)
         labels, _ = fp.parse_tensor(x)                       # uint8 [B,512,512], CelebAMask-HQ ids
         if encoder is not None:
             encoder.write([os.path.join(label_dir, os.path.splitext(n)[0] + '.png') for n in names], labels)
@@ -213,28 +254,42 @@ def extract_masks(editor, img_dir: str, label_dir: str, batch: int = 16, rank: i
         for n, lab in zip(names, labels):
             write_label_png(os.path.join(label_dir, os.path.splitext(n)[0] + '.png'), lab)
             done.append(n)
+    if stats is not None:
+        stats['fallbacks'] = 0 if reader is None else reader.fallbacks
     return done
 
 
 def encode_sean_codes(editor, img_dir: str, label_dir: str, code_dir: str, dataset: str, batch: int = 16, rank: int = 0,
-                      world: int = 1) -> Dict[str, np.ndarray]:
+                      world: int = 1, decode: str = 'host', stats: dict = None) -> Dict[str, np.ndarray]:
     """Zencoder style codes of every (image, label) pair of this rank's shard -> `code_dir/<dataset>___<name>.pkl`.
-    Per image identical to HairEditor.get_code(preprocess_img(img), preprocess_mask(label)) (hair_editor.py:121-157)."""
+    Per image identical to HairEditor.get_code(preprocess_img(img), preprocess_mask(label)) (hair_editor.py:121-157).
+    decode='device': the image and label files of a batch are decoded on the device and brought to the network's size there
+    (ingest.ImageIngest.sean_input / labels: the same tensors bit for bit); fallbacks to Pillow are counted in stats['fallbacks']."""
     import torch
     os.makedirs(code_dir, exist_ok=True)
     gen = editor.models.generator
+    reader = _photo_reader(decode, gen)
+    ingest = _image_ingest(reader, gen)
     out = {}
     for names in batches(shard(list_images(img_dir), rank, world), batch):
-        imgs = np.concatenate([editor.preprocess_img(read_rgb(os.path.join(img_dir, n))) for n in names], axis=0)
-        labs = np.concatenate([editor.preprocess_mask(read_gray(os.path.join(label_dir, os.path.splitext(n)[0] + '.png')))[0]
-                               for n in names], axis=0)
-        codes = gen.encode(torch.from_numpy(imgs.astype(np.float32)).to(editor.device),
-                           torch.from_numpy(labs.astype(np.uint8)).to(editor.device)).cpu().numpy()
+        if reader is not None:
+            imgs = ingest.sean_input(reader.read_rgb_many([os.path.join(img_dir, n) for n in names]), editor.img_size)
+            labs = ingest.labels(reader.read_gray_many([os.path.join(label_dir, os.path.splitext(n)[0] + '.png') for n in names]),
+                                 editor.img_size)
+            codes = gen.encode(imgs, labs).cpu().numpy()
+        else:
+            imgs = np.concatenate([editor.preprocess_img(read_rgb(os.path.join(img_dir, n))) for n in names], axis=0)
+            labs = np.concatenate([editor.preprocess_mask(read_gray(os.path.join(label_dir, os.path.splitext(n)[0] + '.png')))[0]
+                                   for n in names], axis=0)
+            codes = gen.encode(torch.from_numpy(imgs.astype(np.float32)).to(editor.device),
+                               torch.from_numpy(labs.astype(np.uint8)).to(editor.device)).cpu().numpy()
         for n, c in zip(names, codes):
             key = code_key(dataset, n)
             with open(os.path.join(code_dir, key + '.pkl'), 'wb') as f:
                 pickle.dump(c, f)
             out[key] = c
+    if stats is not None:
+        stats['fallbacks'] = 0 if reader is None else reader.fallbacks
     return out
 
 
@@ -655,10 +710,11 @@ def main(argv=None):
     ap.add_argument('--weights', default='reference', help="'reference' (the Google-Drive checkpoints under the reference's "
                                                            "paths) or 'procedural'")
     ap.add_argument('--png', choices=('host', 'device'), default='host', help='who writes PNG files: Pillow on the host (default) or ch_png_encode on the device (same pixels, other file bytes)')
-    ap.add_argument('--decode', choices=('host', 'device'), default='host', help='rgb / colorvar: who decodes the PNG files read: Pillow on the host (default) or ch_png_decode on the device (same pixels, same pickles)')
+    ap.add_argument('--decode', choices=('host', 'device'), default='host',
+                    help='who decodes the files read: Pillow on the host (default) or the device.  rgb / colorvar: ch_png_decode (same pixels, same pickles).  '
+                         'masks / codes: ch_jpeg_decode for .jpg / .jpeg, ch_png_decode for .png, then the resize and the normalisation there too '
+                         '(ch_ingest_images: the same network input bit for bit); whatever the device does not take is Pillow\'s, file by file')
     args = ap.parse_args(argv)
-    if args.decode != 'host' and args.job not in COLOR_JOBS:
-        ap.error('--decode device is for the rgb and colorvar jobs')
     import torch
     from .hair_editor import HairEditor
     rank, world, local = _dist_env()
@@ -684,17 +740,19 @@ def main(argv=None):
             dist.destroy_process_group()
         return
     he = HairEditor(True, True, weights=args.weights, device=local, img_size=args.img_size, max_batch=args.batch)
+    stats = {}
     if args.job == 'masks':
-        n = len(extract_masks(he, os.path.join(base, 'images_256'), os.path.join(base, 'label'), args.batch, rank, world, png=args.png))
+        n = len(extract_masks(he, os.path.join(base, 'images_256'), os.path.join(base, 'label'), args.batch, rank, world, png=args.png,
+                              decode=args.decode, stats=stats))
     else:
         code_dir = os.path.join(args.root, 'hair_info_all_dataset', 'sean_code')
         n = len(encode_sean_codes(he, os.path.join(base, 'images_256'), os.path.join(base, 'label'), code_dir, args.dataset,
-                                  args.batch, rank, world))
+                                  args.batch, rank, world, decode=args.decode, stats=stats))
         if dist is not None:
             dist.barrier()
         if rank == 0:
             merge_pickle_dir_to_dict(code_dir, os.path.join(args.root, 'sean_code_dict.pkl'))
-    print(f'rank {rank}/{world}: {n} files')
+    print(f'rank {rank}/{world}: {n} files' + (f', {stats["fallbacks"]} decoded by Pillow' if args.decode == 'device' else ''))
     if dist is not None:
         dist.destroy_process_group()
 

@@ -232,6 +232,14 @@ class FaceParsing(DeviceOp):
         mean, std = self._norm
         return ((t - mean) / std)[None]
 
+    def ingest_lut(self) -> torch.Tensor:
+        """float32 [3,256] on the device: normalise() of every byte value per channel, evaluated once by normalise() itself over a
+        256-pixel ramp image -- the table ingest.ImageIngest.parse_input indexes, so its floats are normalise()'s bit for bit."""
+        if getattr(self, '_ingest_lut', None) is None:
+            ramp = np.repeat(np.arange(256, dtype=np.uint8).reshape(1, 256, 1), 3, axis=2)
+            self._ingest_lut = self.normalise(ramp)[0, :, 0, :].contiguous()
+        return self._ingest_lut
+
     def parsing_img(self, img, image_size: int = 512):
         """my_parsing_util.py:31-47: PIL bilinear resize to 512, normalise, net, argmax -> (parsing in BiSeNet ids,
         resized PIL image)."""

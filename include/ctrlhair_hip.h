@@ -308,6 +308,45 @@ int  ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, i
 int  ch_hair_color_stats(ch_handle* h, const uint8_t* img, const uint8_t* mask, int B, int H, int W, int64_t* sums,
                          ch_stream_t stream);
 
+/* ---- Image ingest: N decoded images of ANY sizes -> the input tensor of a network, in one call ---------------------------------
+ * The step between a decoder's uint8 [H,W,3] device tensors and float32 [N,3,P,P]: resize to P x P on 8-bit data, then
+ * out[n][c][y][x] = lut[c][resized byte].  lut: device float [3][256], whatever normalisation the caller evaluated once over the 256
+ * byte values (ctrlhair_amd/ingest.py: FaceParsing.normalise of a ramp image for the parse network, x / 127.5 - 1 for SEAN), so the
+ * floats have the bits of the caller's own arithmetic and the kernels hold none of it.
+ * ch_ingest_images, mode CH_INGEST_PIL_BILINEAR: Image.resize((P, P), Image.BILINEAR) of an 8-bit RGB image (ImagingResample).  Per
+ *   axis, in double: scale = in / out, fs = max(scale, 1), support = fs; per output i: center = (i + 0.5) scale, first =
+ *   max((int)(center - support + 0.5), 0), last = min((int)(center + support + 0.5), in), weights w_j = max(0, 1 - |(j + first -
+ *   center + 0.5) / fs|) for j < last - first, divided by their sum taken in that order, k_j = (int)(w_j 2^22 + 0.5).  A pass is
+ *   clip8(((1 << 21) + sum k_j p_j) >> 22) in int32; horizontal first into a uint8 intermediate, then vertical; a pass whose size
+ *   does not change is skipped.  The tables are the caller's (ingest.pil_bilinear_coeffs), one per distinct (in, out) pair.
+ * ch_ingest_images, mode CH_INGEST_CV2_LINEAR: cv2.resize(img, (P, P)) (INTER_LINEAR), the arithmetic of ch_resize_linear_u8: no tables.
+ * ch_ingest_labels: N uint8 label maps [h_n,w_n] -> uint8 [N,S,S], nearest: source row min((int)(y * ((double)h / S)), h - 1),
+ *   columns likewise (ch_hair_erode's mapping).
+ * batch: HOST bytes (8-byte aligned, a multiple of 16 bytes; may be freed on return): N descriptors of CH_INGEST_DESC_BYTES bytes
+ *   {uint64 device address of the pixels, int32 H, int32 W, int32 htab, int32 vtab, int64 reserved (the library's)}, then the tables.
+ *   htab / vtab: offset of the horizontal / vertical pass's table in int32 units from the start of the batch (a multiple of 4), or -1
+ *   where the pass is skipped -- always -1 for mode 1 and for labels, for mode 0 exactly when W == P / H == P.  A table is int32
+ *   {in, out, ksize, layout, bounds [out][2] = (first, count), k}: layout 1 (horizontal) stores k as [ksize][out], layout 0 (vertical)
+ *   as [out][ksize]; first >= 0, 1 <= count <= ksize, first + count <= in.  Images of one size share their tables.
+ * 1 <= N <= 65535, sides 1..CH_INGEST_MAX_SIDE, 1 <= P, S <= CH_INGEST_MAX_OUT; out: device float [N,3,P,P], 16-byte aligned
+ *   (labels: uint8 [N,S,S]).  Everything the batch says is checked on the host before the first launch: a refusal names the image.
+ * workspace: caller-owned device buffer (256-byte aligned) of ch_ingest_workspace_bytes(batch, batch_bytes, N, P, mode) bytes (labels:
+ *   mode CH_INGEST_LABELS; 0 = a batch the entry would refuse): the batch's device copy -- descriptors and tables go up in ONE copy
+ *   -- and mode 0's uint8 intermediates [H_n,P,3].  Contents undefined.
+ * One copy and at most two launches on `stream` whatever N is: no synchronisation, no allocation, integer accumulation only, no
+ *   atomics, no waiting between workgroups; image n of a batch is bit-identical to an N = 1 call. */
+#define CH_INGEST_PIL_BILINEAR 0
+#define CH_INGEST_CV2_LINEAR 1
+#define CH_INGEST_LABELS 2
+#define CH_INGEST_DESC_BYTES 32
+#define CH_INGEST_MAX_SIDE 32768
+#define CH_INGEST_MAX_OUT 4096
+size_t ch_ingest_workspace_bytes(const void* batch, size_t batch_bytes, int N, int P, int mode);
+int  ch_ingest_images(ch_handle* h, const void* batch, size_t batch_bytes, int N, int P, int mode, const float* lut, float* out,
+                      void* workspace, size_t workspace_bytes, ch_stream_t stream);
+int  ch_ingest_labels(ch_handle* h, const void* batch, size_t batch_bytes, int N, int S, uint8_t* out, void* workspace,
+                      size_t workspace_bytes, ch_stream_t stream);
+
 /* ---- Direction search: contact sheets and per-render measurements (shape_branch/script_find_direction.py:55-76,
  *      color_texture_branch/script_find_direction.py:55-74, util/canvas_grid.py:15-31) ------------------------------------------
  * ch_sheet_compose replaces Canvas.process_draw_image for n sources at once: source s goes to cell (cells[2s], cells[2s+1]) =
