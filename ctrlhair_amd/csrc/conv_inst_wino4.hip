@@ -132,10 +132,11 @@ hipError_t wino4_style_pack(const float* lut, float* wsty, int B, int C, hipStre
 
 
 // ---- pre-transformed input route (conv_wino4v.h) ---------------------------------------------------------------------------------------
-// both kernels' LDS limits from the first call of either launcher
-static hipError_t wino4v_attr(int& cus) { return dyn_lds<wino4v_kernel<0>, wino4v_kernel<1>>(wino4v::LDS_BYTES, &cus); }
+// the kernels' LDS limits from the first call of any of the launchers
+static hipError_t wino4v_attr(int& cus) { return dyn_lds<wino4v_kernel<0>, wino4v_kernel<1>, wino4v_kernel<2>>(wino4v::LDS_BYTES, &cus); }
 hipError_t wino4v_pack(const Wino4vPackParams& p, hipStream_t s) {
-    if (!p.in || !p.v || p.H % 32 || p.W % 32 || p.H < 32 || p.W < 32 || p.nks <= 0 || p.pitch % 4 || p.xoff % 4 || (p.reflect && p.padded)) return hipErrorInvalidValue;
+    if (!p.in || !p.v || p.H % 32 || p.W % 32 || p.H < 32 || p.W < 32 || p.nks <= 0 || p.pitch % 4 || p.xoff % 4 || (p.reflect && p.padded) || p.c0 < 0 || p.c0 % 4)
+        return hipErrorInvalidValue;
     const long long blocks = (long long)p.B * (p.H / 32) * (p.W / 32) * p.nks;
     if (blocks <= 0 || blocks > 0x7fffffffLL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(wino4v_pack_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, p);
@@ -159,8 +160,7 @@ hipError_t conv_wino4v_plain(Wino4Params p, hipStream_t s) {
     hipLaunchKernelGGL(wino4v_kernel<0>, dim3(grid), dim3(512), wino4v::LDS_BYTES, s, p);
     return hipGetLastError();
 }
-hipError_t conv_wino4v_ace(Wino4AceParams p, hipStream_t s) {
-    if (!wino4_ace_supported(p.H, p.W, p.C) || !p.v || !p.wpk || !p.out || !p.x || !p.noise) return hipErrorInvalidValue;
+static void wino4v_ace_fill(Wino4AceParams& p) {
     p.nrt = (p.C + 15) / 16;
     p.ntx = p.W / wino4::TS;
     p.nty = p.H / wino4::TS;
@@ -169,11 +169,28 @@ hipError_t conv_wino4v_ace(Wino4AceParams p, hipStream_t s) {
     p.nks = p.wsty ? 38 : 32;
     p.rb = p.nrt >= 4 ? 4 : p.nrt;
     p.tbk = 32 / p.rb;
+}
+hipError_t conv_wino4v_ace(Wino4AceParams p, hipStream_t s) {
+    if (!wino4_ace_supported(p.H, p.W, p.C) || !p.v || !p.wpk || !p.out || !p.x || !p.noise) return hipErrorInvalidValue;
+    wino4v_ace_fill(p);
     int cus = 0;
     hipError_t e = wino4v_attr(cus);
     if (e != hipSuccess) return e;
     const int grid = persistent_grid(p.ntasks, cus);
     hipLaunchKernelGGL(wino4v_kernel<1>, dim3(grid), dim3(512), wino4v::LDS_BYTES, s, p);
+    return hipGetLastError();
+}
+// the same tasks in the same order; the cache is indexed by (spatial tile, row tile), so it must hold every task of the launch
+hipError_t conv_wino4v_ace_memo(Wino4AceParams p, long long acc_tasks, hipStream_t s) {
+    if (!wino4_ace_supported(p.H, p.W, p.C) || !p.v || !p.wpk || !p.out || !p.x || !p.noise) return hipErrorInvalidValue;
+    if (!p.wsty || !p.v1h || !p.acc_cache || !p.memo_mode || (reinterpret_cast<uintptr_t>(p.acc_cache) & 15)) return hipErrorInvalidValue;
+    wino4v_ace_fill(p);
+    if (acc_tasks < p.ntasks) return hipErrorInvalidValue;
+    int cus = 0;
+    hipError_t e = wino4v_attr(cus);
+    if (e != hipSuccess) return e;
+    const int grid = persistent_grid(p.ntasks, cus);
+    hipLaunchKernelGGL(wino4v_kernel<2>, dim3(grid), dim3(512), wino4v::LDS_BYTES, s, p);
     return hipGetLastError();
 }
 

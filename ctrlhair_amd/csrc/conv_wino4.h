@@ -451,6 +451,12 @@ struct Wino4AceParams {
     long long noise_bstride;
     const float* v;         // conv_wino4v.h only: the pre-transformed hidden activations (wino4v_pack) -- `actv` is then unused
     int nrt, ntx, nty, ntiles, ntasks, nks, rb, tbk;      // set by the launcher
+    // conv_wino4v.h only, SPADE memo (optional): the device word of the call's mode (kernels.h SPADE_*); wino4v_kernel<1> returns unless
+    // it reads PLAIN.  The memo instantiation also takes the V image of the level's 20 one-hot planes, [tile][6][VDW], and this ACE's
+    // cache of the 36 accumulators after the hidden k-steps, [tile * nrt + row tile][idx][thread] in 16-byte units
+    const int* memo_mode;
+    const float* v1h;
+    float* acc_cache;
 };
 // GEMM row R of the packed SPADE image -> (channel, beta)
 __host__ __device__ inline void wino4_ace_row(int R, int& ch, int& beta) {

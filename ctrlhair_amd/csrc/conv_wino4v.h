@@ -55,11 +55,15 @@ struct Wino4vPackParams {
     int pitch, xoff;        // plain activations: pitch = W, xoff = 0; padded hidden-activation planes: wino_apitch(W), WINO_AXOFF
     int padded;             // 1: columns -1 and W are the planes' zero pads (read unchecked); 0: bounds-checked (zeros or reflection)
     int reflect;            // reflection padding (pad 1) instead of zeros
+    int c0;                 // first channel of k-step 0 (the k-steps cover channels c0 .. c0 + 4 nks - 1 of the K planes)
+    const int* memo_mode;   // optional (SPADE memo, kernels.h SPADE_*): the launch returns at once where bit (mode) of memo_skip is set
+    int memo_skip;
 };
 // one block = (spatial tile, k-step), wave = tile group, lane = (channel kk, tile n): the lane's 6 x 6 patch -> 36 values -> nine 16-byte
 // stores, each a contiguous kilobyte per wave
 template <int DUMMY>          // (a template so that the header can be included by several translation units)
 __global__ __launch_bounds__(256) void wino4v_pack_kernel(const Wino4vPackParams p) {
+    if (p.memo_mode && ((p.memo_skip >> *p.memo_mode) & 1)) return;
     const int lane = threadIdx.x & 63, tg = threadIdx.x >> 6;
     const int n = lane & 15, kk = lane >> 4;
     const long long blk = blockIdx.x;
@@ -68,7 +72,7 @@ __global__ __launch_bounds__(256) void wino4v_pack_kernel(const Wino4vPackParams
     const int ttx = tile % ntx, tty = (tile / ntx) % nty, b = tile / (ntx * nty);
     const int tx = n & 7, tyl = 2 * tg + (n >> 3);
     const int y0 = tty * 32 + 4 * tyl - 1, x0 = ttx * 32 + 4 * tx;          // x0: first pixel of the tile (the patch starts at x0 - 1)
-    const int ch = 4 * s + kk;
+    const int ch = p.c0 + 4 * s + kk;
     float v[36];
     if (ch < p.K) {
         const float* pl = p.in + ((long long)b * p.K + ch) * p.H * p.pitch + p.xoff;
@@ -108,11 +112,31 @@ __global__ __launch_bounds__(256) void wino4v_pack_kernel(const Wino4vPackParams
 // ---- the contraction kernel ----------------------------------------------------------------------------------------------------------
 // EPI 0: plain conv (Wino4Params, p.v set; p.in unused), EPI 1: SPADE gamma / beta + style images + ACE epilogue (Wino4AceParams, p.v set;
 // p.actv unused).  Same block / wave / lane mapping as conv_wino4.h: wave w = row half (w >> 2) x tile group (w & 3), 36 accumulators.
+//
+// EPI 2: the SPADE memo instantiation of EPI 1 for a styled ACE (p.wsty, p.v1h, p.acc_cache, p.memo_mode set; nks = 38).  K-steps 0..31
+// contract the hidden channels (V: labels and weights only, A: weights only), k-steps 32..37 the one-hot planes with the style images of
+// the sample, so a task's 36 accumulators after k-step 31 stand while the calls bring the same label maps (sean_model.h).  The mode word
+// (kernels.h SPADE_*) picks what a task is:
+//   STORE  k-steps 0..31 from (p.v, wpk) | flush group 8, write the accumulators raw to the cache, drain | k-steps 32..37 from (p.v1h, wsty)
+//   LOAD   accumulators from the cache, drain | k-steps 32..37 from (p.v1h, wsty)
+// and PLAIN returns (EPI 1 runs then; it returns on the other two).  Every accumulator receives the MFMAs of EPI 1 in the same order, k
+// ascending: the flush only moves group 8 of k-step 31 ahead of k-step 32's barrier, and the group-8 slot of k-step 32 then adds
+// (quad x 0) as it does at the start of every task.  STORE, LOAD and EPI 1 give the same words.  The two halves of a task are two segments
+// of the flat issue sequence: the ring runs on across the boundary (every k-step issues its eight loads), the accumulator traffic
+// shares vmcnt with it and is drained once per segment, like the epilogue's.
 template <int EPI>
 __global__ __launch_bounds__(512, 1) void wino4v_kernel(const std::conditional_t<EPI == 0, Wino4Params, Wino4AceParams> p) {
     using namespace wino4v;
     constexpr int ADW = wino4::ADW;
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    int ks0 = 0;                                   // first k-step of a task: 32 on LOAD (EPI 2), else 0
+    if constexpr (EPI >= 1) {      // SPADE memo: EPI 1 runs on PLAIN (or without a mode word), EPI 2 on STORE and LOAD
+        if (EPI == 2 || p.memo_mode) {
+            const int mode = __builtin_amdgcn_readfirstlane(*p.memo_mode);
+            if ((EPI == 1) != (mode == 0)) return;
+            if constexpr (EPI == 2) ks0 = mode == 2 ? 32 : 0;
+        }
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = lane & 15, kk = lane >> 4;
@@ -142,8 +166,8 @@ __global__ __launch_bounds__(512, 1) void wino4v_kernel(const std::conditional_t
     // per k-step and thread: V rounds 0..3 (+ round 4: waves 0-3), A rounds 0, 1 (source units tid and 576 + tid: idx 0..7 of each half),
     // and the lane's own ninth quad of its row half straight into a8[parity]
     const unsigned va = (unsigned)tid * 16u, va8 = (unsigned)((9 * mh + 8) * 64 + lane) * 16u;
-    int it = lb, is = 0;
-    wino_u32x4 d_v, d_a, d_s;
+    int it = lb, is = ks0;
+    wino_u32x4 d_v, d_a, d_s, d_v1;
     unsigned so_v = 0, so_a = 0;
     auto issue_task = [&]() {
         int irt, tile;
@@ -156,6 +180,13 @@ __global__ __launch_bounds__(512, 1) void wino4v_kernel(const std::conditional_t
             if (p.wsty) {
                 const int ib = tile / (p.ntx * p.nty);
                 d_s = wino_rsrc(p.wsty + ((long long)ib * p.nrt + irt) * 6 * ADW, 6u * (unsigned)ADW * 4u);
+            }
+        }
+        if constexpr (EPI == 2) {
+            d_v1 = wino_rsrc(p.v1h + (long long)tile * 6 * VDW, 6u * (unsigned)VDW * 4u);
+            if (ks0) {
+                d_v = d_v1;
+                d_a = d_s;
             }
         }
         so_v = 0;
@@ -198,16 +229,20 @@ __global__ __launch_bounds__(512, 1) void wino4v_kernel(const std::conditional_t
             so_a += (unsigned)ADW * 4u;
         }
         ++is;
-        if constexpr (EPI == 1) {
-            if (is == 32 && nk > 32) {         // the style images of the task's sample follow the hidden channels
+        if constexpr (EPI >= 1) {
+            if (is == 32 && nk > 32) {        // the style images of the task's sample follow the hidden channels
                 d_a = d_s;
                 so_a = 0;
+                if constexpr (EPI == 2) {          // ... and the level's one-hot V image the hidden V
+                    d_v = d_v1;
+                    so_v = 0;
+                }
             }
         }
         if (is == nk) {
             if (it + G < p.ntasks) {
                 it += G;
-                is = 0;
+                is = ks0;
                 issue_task();
             } else {                   // past the end: keep re-issuing the last k-step (never read; keeps the vmcnt counting uniform)
                 is = nk - 1;
@@ -307,10 +342,56 @@ __global__ __launch_bounds__(512, 1) void wino4v_kernel(const std::conditional_t
         rslot = rslot + SB == lds0 + RING ? lds0 : rslot + SB;
     };
 
+    // SPADE memo (EPI 2): a task's accumulators in the cache, 36 units of 16 bytes per thread (unit idx of thread tid at byte idx * 8192 +
+    // 16 tid of the task's 288 KB: a wave's access is a contiguous kilobyte).  Buffer accesses: one descriptor per task, the thread's offset
+    // is `va`, the unit's an SGPR -- no address registers beside the 144 accumulator registers.
+    auto acc_rsrc = [&](int L) {
+        int rt, tile;
+        task_of(L, rt, tile);
+        float* base = nullptr;
+        if constexpr (EPI == 2) base = p.acc_cache + ((long long)tile * p.nrt + rt) * (36 * 512 * 4);
+        return __builtin_amdgcn_make_buffer_rsrc(base, 0, 36 * 8192, 0x00020000);
+    };
+    // ... their loads and stores share vmcnt with the ring: drained here, once per segment (the ring's loads in flight arrive with them)
+    auto drain = [&]() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : "+v"(a8[0]), "+v"(a8[1]));
+    };
+    // (the empty asm statements are a use of every accumulator right behind the drain: whatever wait the compiler's own bookkeeping of
+    //  these loads asks for lands here, on an empty queue, and not in front of the first MFMA of the k-step loop)
+    auto acc_load = [&](int L) {
+        const auto d = acc_rsrc(L);
+#pragma unroll
+        for (int x = 0; x < 36; ++x) acc[x] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(d, va, x * 8192, 0));
+    };
+    auto acc_landed = [&]() {
+#pragma unroll
+        for (int x = 0; x < 36; ++x) asm volatile("" : "+v"(acc[x]));
+    };
+    if constexpr (EPI == 2) {
+        if (ks0) {
+            acc_load(lb);
+            drain();
+            acc_landed();
+        }
+    }
+
     for (int k = 0, ct = lb; k < mytasks; ++k, ct += G) {
-        for (int cs = 0; cs < nk; cs += 2) {      // (nk is even: the launchers)
+        for (int cs = ks0; cs < nk; cs += 2) {      // (nk is even: the launchers)
             kstep(WInt<0>{});
             kstep(WInt<1>{});
+            if constexpr (EPI == 2) {
+                if (cs == 30) {                   // STORE: the hidden k-steps are done -- group 8 of k-step 31 as before an epilogue, then the raw sums
+                    wait_ring(a8[1]);
+                    mfma4(a8[1], v8c, 8);
+                    v8c = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    const auto d = acc_rsrc(ct);
+#pragma unroll
+                    for (int x = 0; x < 36; ++x) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wino_u32x4, acc[x]), d, va, x * 8192, 0);
+                    drain();
+                }
+            }
         }
         if constexpr (W4V_CARRY) {                // group 8 of the task's last k-step (quad a8[1], loaded during the k-step before it)
             wait_ring(a8[1]);
@@ -321,12 +402,18 @@ __global__ __launch_bounds__(512, 1) void wino4v_kernel(const std::conditional_t
         task_of(ct, crt, tile);
         if constexpr (EPI == 0) wino4_plain_epilogue(p, acc, crt, tile, mh, kk, tyl, tx);
         else wino4_ace_epilogue(p, acc, crt, tile, mh, kk, tyl, tx);
+        const bool reload = EPI == 2 && ks0;      // LOAD: the next task's sums take the place of the zeros
+        if (reload) {
+            if constexpr (EPI == 2) acc_load(k + 1 < mytasks ? ct + G : ct);
+        } else {
 #pragma unroll
-        for (int x2 = 0; x2 < 36; ++x2) acc[x2] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int x2 = 0; x2 < 36; ++x2) acc[x2] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
         // the epilogue's loads / stores share the counter with the ring: drain once per task (the two quads in flight arrive with it)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" : "+v"(a8[0]), "+v"(a8[1]));
+        if constexpr (EPI == 2) acc_landed();     // (on either path: the compiler's bookkeeping does not know which one loaded)
     }
 }
 
@@ -337,5 +424,8 @@ inline bool wino4v_pays(int rows, int r) { return rows >= 512 && r <= 64; }
 hipError_t wino4v_pack(const Wino4vPackParams& p, hipStream_t s);       // conv_inst_wino4.hip
 hipError_t conv_wino4v_plain(Wino4Params p, hipStream_t s);             // p.v = V image of p's input (wino4v_pack), p.in unused
 hipError_t conv_wino4v_ace(Wino4AceParams p, hipStream_t s);            // p.v = V image of the hidden activations (+ one-hot planes)
+// SPADE memo: the memo instantiation over the same p with memo_mode, v1h and acc_cache set; acc_tasks = tasks the cache holds
+inline size_t wino4v_acc_bytes(int B, int H, int W, int C) { return (size_t)B * (H / 32) * (W / 32) * ((C + 15) / 16) * 36 * 512 * 16; }
+hipError_t conv_wino4v_ace_memo(Wino4AceParams p, long long acc_tasks, hipStream_t s);
 
 }  // namespace chk

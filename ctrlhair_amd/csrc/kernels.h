@@ -12,8 +12,13 @@ namespace chk {
 hipError_t label_downsample(const uint8_t* in, uint8_t* out, int B, int S, int r, hipStream_t s, const int* memo_hit = nullptr);
 // Label memo: the words of its device state, and the two launches at the start of an eligible chunk (compare `bytes` of labels with the
 // copy, 16-byte aligned both; then decide MEMO_HIT from MEMO_VALID, MEMO_DIFF and the key (B, S, epoch)) / of any other chunk (MEMO_VALID = 0)
-enum { MEMO_VALID = 0, MEMO_DIFF = 1, MEMO_HIT = 2, MEMO_KEY = 3, MEMO_CALLS = 6, MEMO_HITS = 7, MEMO_WORDS = 8 };
-hipError_t label_memo_begin(const uint8_t* labels, uint8_t* copy, long long bytes, int* state, int B, int S, int epoch, hipStream_t s);
+// SPADE memo (conv_wino4v.h, the memo instantiation): MEMO_ACC_VALID = the accumulator caches of the F(4x4)-route ACEs hold the sums of these
+// labels; MEMO_SPADE_MODE = what this call's launches do with them.  spade = 0: the mode stays PLAIN and the caches invalid.  Store on the
+// SECOND sight of a label set: no hit -> PLAIN, valid = 0; hit with valid = 0 -> STORE, valid = 1; hit with valid = 1 -> LOAD.
+enum { MEMO_VALID = 0, MEMO_DIFF = 1, MEMO_HIT = 2, MEMO_KEY = 3, MEMO_CALLS = 6, MEMO_HITS = 7, MEMO_ACC_VALID = 8, MEMO_SPADE_MODE = 9, MEMO_STORES = 10,
+       MEMO_LOADS = 11, MEMO_WORDS = 12 };
+enum { SPADE_PLAIN = 0, SPADE_STORE = 1, SPADE_LOAD = 2 };
+hipError_t label_memo_begin(const uint8_t* labels, uint8_t* copy, long long bytes, int* state, int B, int S, int epoch, hipStream_t s, int spade = 0);
 hipError_t label_memo_invalidate(int* state, hipStream_t s);
 // need (optional, [B][H][W]): pixels with need == 0 are not written (ace_sparse.h: nothing reads them)
 hipError_t onehot_conv3x3(const uint8_t* lab, const float* table, const float* bias, float* out, int B, int H, int W,

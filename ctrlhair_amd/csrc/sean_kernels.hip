@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void label_memo_compare_kernel(const uint4* __
     }
     if (__any(d) && (threadIdx.x & 63) == 0) atomicOr(state + MEMO_DIFF, 1);
 }
-__global__ void label_memo_decide_kernel(int* __restrict__ state, int B, int S, int epoch) {
+__global__ void label_memo_decide_kernel(int* __restrict__ state, int B, int S, int epoch, int spade) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const int hit = (state[MEMO_VALID] == 1 && state[MEMO_DIFF] == 0 && state[MEMO_KEY] == B && state[MEMO_KEY + 1] == S && state[MEMO_KEY + 2] == epoch) ? 1 : 0;
     state[MEMO_HIT] = hit;
@@ -121,17 +121,23 @@ __global__ void label_memo_decide_kernel(int* __restrict__ state, int B, int S, 
     state[MEMO_KEY + 2] = epoch;
     state[MEMO_CALLS] += 1;
     state[MEMO_HITS] += hit;
+    // SPADE memo (kernels.h): the accumulators are stored on the second sight of a label set, so a run of changing maps never pays for stores
+    const int mode = (spade && hit) ? (state[MEMO_ACC_VALID] == 1 ? SPADE_LOAD : SPADE_STORE) : SPADE_PLAIN;
+    state[MEMO_SPADE_MODE] = mode;
+    state[MEMO_ACC_VALID] = mode != SPADE_PLAIN ? 1 : 0;
+    state[MEMO_STORES] += mode == SPADE_STORE;
+    state[MEMO_LOADS] += mode == SPADE_LOAD;
 }
 __global__ void label_memo_invalidate_kernel(int* __restrict__ state) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) state[MEMO_VALID] = state[MEMO_HIT] = 0;
+    if (threadIdx.x == 0 && blockIdx.x == 0) state[MEMO_VALID] = state[MEMO_HIT] = state[MEMO_ACC_VALID] = state[MEMO_SPADE_MODE] = 0;
 }
-hipError_t label_memo_begin(const uint8_t* labels, uint8_t* copy, long long bytes, int* state, int B, int S, int epoch, hipStream_t s) {
+hipError_t label_memo_begin(const uint8_t* labels, uint8_t* copy, long long bytes, int* state, int B, int S, int epoch, hipStream_t s, int spade) {
     if (!labels || !copy || !state || bytes <= 0 || (bytes & 15) || (reinterpret_cast<uintptr_t>(labels) & 15) || (reinterpret_cast<uintptr_t>(copy) & 15))
         return hipErrorInvalidValue;
     const long long n16 = bytes >> 4;
     const int grid = (int)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048);
     hipLaunchKernelGGL(label_memo_compare_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const uint4*>(labels), reinterpret_cast<uint4*>(copy), n16, state);
-    hipLaunchKernelGGL(label_memo_decide_kernel, dim3(1), dim3(64), 0, s, state, B, S, epoch);
+    hipLaunchKernelGGL(label_memo_decide_kernel, dim3(1), dim3(64), 0, s, state, B, S, epoch, spade);
     return hipGetLastError();
 }
 hipError_t label_memo_invalidate(int* state, hipStream_t s) {

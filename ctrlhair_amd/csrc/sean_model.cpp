@@ -925,6 +925,10 @@ struct SeanBuild {
         m.pro_gtab.assign(n_aces, nullptr);
         m.pro_p6.assign(n_aces, nullptr);
         m.pro_wsty.assign(n_aces, nullptr);
+        m.memo_acc.assign(n_aces, nullptr);
+        m.memo_acc_tasks.assign(n_aces, 0);
+        m.memo_v1h[0] = m.memo_v1h[1] = nullptr;
+        m.spade_memo_on = false;
         m.pro_bytes = 0;
         m.pro_on = opt.prologue && opt.wino && !opt.use_sh16 && !m.overlap_on && (long long)mb * ms * ms > m.ahead_limit;
         if (!m.pro_on) return "";
@@ -975,6 +979,25 @@ struct SeanBuild {
             }
             m.memo_bytes += floats * 4;
         });
+        // SPADE memo (sean_model.h): the accumulator cache of every styled ACE that takes the F(4x4) V route at (mb, ms), and the two
+        // one-hot V images
+        if (!(opt.spade_memo && opt.wino >= 2 && opt.wino4v && m.vbuf && m.wsty4)) return "";
+        for_each_ace(m.blocks, [&](const AceW& a) {
+            const int r = m.levels[level_of(a.res_div)].r;
+            if (r < 32 || r % 32 || r > 64 || !a.styled || !m.pro_actv[a.index]) return;
+            if (m.ace_route_shape(a, r) != AceRoute::F4 || !wino4v_pays(2 * a.C, r) || wino4v_bytes(mb, r, r, 38) > m.vbuf_bytes) return;
+            const size_t bytes = wino4v_acc_bytes(mb, r, r, a.C);
+            m.memo_acc[a.index] = static_cast<float*>(B.dalloc(bytes));
+            m.memo_acc_tasks[a.index] = (long long)(bytes / (36 * 8192));
+            m.memo_bytes += bytes;
+            m.spade_memo_on = true;
+        });
+        if (m.spade_memo_on)
+            for (int i = 0; i < 2; ++i) {
+                const int r = 32 << i;
+                m.memo_v1h[i] = static_cast<float*>(B.dalloc(wino4v_bytes(mb, r, r, 6)));
+                m.memo_bytes += wino4v_bytes(mb, r, r, 6);
+            }
         return "";
     }
 };
@@ -1031,6 +1054,10 @@ void SeanModel::destroy() {
     memo_patch.clear();
     memo_gb.clear();
     memo_gb_cap.clear();
+    memo_acc.clear();
+    memo_acc_tasks.clear();
+    memo_v1h[0] = memo_v1h[1] = nullptr;
+    spade_memo_on = false;
     memo_lab = nullptr;
     memo_state = nullptr;
     memo_dirty = false;
@@ -1262,9 +1289,14 @@ struct Runner {
         if (!ok || fresh) check(label_memo_invalidate(m.memo_state, st), "label memo (invalidate)");
         m.memo_dirty = false;
         if (!ok) return;
-        check(label_memo_begin(labfull, m.memo_lab, (long long)B * S * S, m.memo_state, B, S, m.memo_epoch, st), "label memo (compare, decide)");
+        check(label_memo_begin(labfull, m.memo_lab, (long long)B * S * S, m.memo_state, B, S, m.memo_epoch, st, (m.opt.spade_memo && m.spade_memo_on) ? 1 : 0),
+              "label memo (compare, decide)");
         memo_hit = m.memo_state + MEMO_HIT;
+        if (m.opt.spade_memo && m.spade_memo_on) spade_mode = m.memo_state + MEMO_SPADE_MODE;
     }
+    // SPADE memo (sean_model.h): the mode word of an eligible chunk, and which level sizes had their one-hot V image packed in this chunk
+    const int* spade_mode = nullptr;
+    bool v1h_done[2] = {false, false};
     void geo_flush() {
         if (!geo) return;
         geo->memo_hit = memo_hit;
@@ -1650,9 +1682,35 @@ struct Runner {
                 check(wino4_style_pack(q.lut, m.wsty4, B, a.C, st, rows), "wino4_style_pack");
             }
             if (vroute) {
+                // SPADE memo: the same launches every call, the mode word picks which of them run -- PLAIN: pack + kernel<1> as ever;
+                // STORE: the one-hot pack of the level (first memoized ACE of the level), pack + the memo instantiation; LOAD: the
+                // memo instantiation alone, from the cache and the one-hot image of the STORE call
+                const int vi = r == 64 ? 1 : 0;
+                const long long tasks = (long long)B * (r / 32) * (r / 32) * ((a.C + 15) / 16);
+                const bool memo = spade_mode && w.wsty && (r == 32 || r == 64) && m.memo_acc[a.index] && m.memo_v1h[vi] && tasks <= m.memo_acc_tasks[a.index];
+                if (memo) {
+                    if (!v1h_done[vi]) {
+                        Wino4vPackParams v1 = vp;
+                        v1.v = m.memo_v1h[vi];
+                        v1.c0 = HID;
+                        v1.nks = 6;
+                        v1.memo_mode = spade_mode;
+                        v1.memo_skip = (1 << SPADE_PLAIN) | (1 << SPADE_LOAD);
+                        check(wino4v_pack(v1, st), "one-hot plane transform (winograd F(4x4,3x3), SPADE memo)");
+                        v1h_done[vi] = true;
+                    }
+                    vp.memo_mode = spade_mode;
+                    vp.memo_skip = 1 << SPADE_LOAD;
+                    w.memo_mode = spade_mode;
+                }
                 check(wino4v_pack(vp, st), "hidden activation transform (winograd F(4x4,3x3))");
                 w.v = m.vbuf;
                 check(conv_wino4v_ace(w, st), "spade conv (winograd F(4x4,3x3), every tile, pre-transformed input)");
+                if (memo) {
+                    w.v1h = m.memo_v1h[vi];
+                    w.acc_cache = m.memo_acc[a.index];
+                    check(conv_wino4v_ace_memo(w, m.memo_acc_tasks[a.index], st), "spade conv (winograd F(4x4,3x3), SPADE memo)");
+                }
             } else
                 check(conv_wino4_ace(w, st), "spade conv (winograd F(4x4,3x3), every tile)");
         });
@@ -2162,6 +2220,14 @@ std::string SeanModel::label_memo_stats(int* calls, int* hits) {
         return "label memo: state read failed";
     *calls = st[MEMO_CALLS];
     *hits = st[MEMO_HITS];
+    return "";
+}
+std::string SeanModel::spade_memo_stats(int* stores, int* loads) {
+    int st[MEMO_WORDS] = {};
+    if (memo_state && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(st, memo_state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess))
+        return "SPADE memo: state read failed";
+    *stores = st[MEMO_STORES];
+    *loads = st[MEMO_LOADS];
     return "";
 }
 

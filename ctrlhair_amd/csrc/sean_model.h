@@ -96,6 +96,9 @@ struct SeanOptions {
     int label_memo = 1;                        // option "sean.label_memo": handles with the ACE prologue, calls of one chunk: 1 = the label-only products of a chunk
                                                //   (SeanModel::memo_state) are kept on the device and their launches return at once while the calls bring
                                                //   the same label maps; 0 = every call rebuilds them (launch for launch as without the memo)
+    int spade_memo = 1;                        // option "sean.spade_memo": with the label memo, the styled ACEs on the F(4x4) V route: 1 = the 36 accumulators of a task
+                                               //   after its 32 hidden k-steps are kept (SeanModel::memo_acc) and a call with the same maps runs the six style
+                                               //   k-steps only; 0 = launch for launch as without it
     // Overlap mode (round 5; option "sean.overlap" = CUs of the side streams, 0 = off; exact-f32 Winograd path, jobs beyond the
     // run-ahead sizes): the HBM-bound kernels -- label tables of all ACEs, interior passes -- run on streams whose CU mask holds
     // `overlap` CUs (hipExtStreamCreateWithCUMask: every XCD gives overlap / 8 of its CUs), beside the matrix-bound convs on the
@@ -295,6 +298,17 @@ struct SeanModel {
     std::vector<int> memo_gb_cap;              // tasks each holds
     size_t memo_bytes = 0;                     // what the memo adds to the handle
     std::string label_memo_stats(int* calls, int* hits);      // synchronous read-back of MEMO_CALLS / MEMO_HITS (tests and tools)
+    // SPADE memo (option "sean.spade_memo", conv_wino4v.h): the SPADE conv of a styled ACE contracts 128 hidden channels (labels and weights
+    // only) and then 20 one-hot planes with the style images of the sample (the codes).  `memo_acc` keeps, per ACE that takes the F(4x4) V
+    // route with style images at (max_batch, max_size), the raw accumulators of every task after the hidden k-steps; `memo_v1h` the V image
+    // of the one-hot planes per level size (32 / 64 pixels; the same for every ACE of a level).  The decision kernel sets MEMO_SPADE_MODE
+    // per call: PLAIN on a label miss, STORE on the first hit of a label set, LOAD from the second on.  Each of these ACEs enqueues the
+    // plain kernel and the memo instantiation, one of which returns at once; whatever clears MEMO_VALID clears MEMO_ACC_VALID.
+    std::vector<float*> memo_acc;
+    std::vector<long long> memo_acc_tasks;     // tasks each holds
+    float* memo_v1h[2] = {nullptr, nullptr};
+    bool spade_memo_on = false;                // any memo_acc allocated: the decision kernel keeps the mode
+    std::string spade_memo_stats(int* stores, int* loads);     // synchronous read-back of MEMO_STORES / MEMO_LOADS
 
     // ---- exact SPADE-interior reduction (ace_sparse.h; per-level buffers: Level) ----
     float* gtab = nullptr;                     // [max_batch][19][2][C max]

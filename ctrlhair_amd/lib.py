@@ -82,6 +82,7 @@ SYMBOLS = {
     'ch_sean_scale_report': (_I, [_VP, C.POINTER(C.c_float), _I]),
     'ch_sean_debug_read': (_I, [_VP, _VP, C.c_size_t]),
     'ch_sean_label_memo_stats': (C.c_longlong, [_VP]),
+    'ch_sean_spade_memo_stats': (C.c_longlong, [_VP]),
     'ch_mfma_peak': (_I, [_VP, _I, _I, C.POINTER(_D)]),
     'ch_profile_enable': (_I, [_VP, _I]),
     'ch_profile_read': (_I, [_VP, _I, C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
@@ -183,6 +184,14 @@ class Handle:
         v = int(self.lib.ch_sean_label_memo_stats(self._h))
         if v < 0:
             raise RuntimeError(f'ch_sean_label_memo_stats failed: {self.lib.ch_last_error(self._h).decode()}')
+        return v >> 32, v & 0xFFFFFFFF
+
+    def sean_spade_memo_stats(self):
+        """(stores, loads) of the SPADE memo (option 'sean.spade_memo'): chunks that stored the accumulators of the styled F(4x4)-route ACEs
+        after their hidden part, and chunks that ran from the stored ones.  Synchronises."""
+        v = int(self.lib.ch_sean_spade_memo_stats(self._h))
+        if v < 0:
+            raise RuntimeError(f'ch_sean_spade_memo_stats failed: {self.lib.ch_last_error(self._h).decode()}')
         return v >> 32, v & 0xFFFFFFFF
 
     def mfma_peak(self, kind: int, ms_target: int = 30) -> float:

@@ -154,6 +154,11 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   (one patch buffer per ACE) -- stay on the device; a call of one chunk compares its label maps with the handle's copy on the device and
  *   the launches that build those products return at once when nothing changed (same shapes, same options).  Bit-identical results.
  *   0 = no memo and none of its buffers.  ch_sean_label_memo_stats counts.
+ * "sean.spade_memo" (default 1; before ch_finalize; in effect with "sean.label_memo" only): the SPADE conv of a styled 32 / 64-pixel ACE
+ *   contracts 128 hidden channels, which depend on labels and weights alone, and then the one-hot planes with the style images of the
+ *   sample.  1 = the second call in a row with the same label maps stores the Winograd-domain accumulators of every task after the hidden
+ *   part (4.2 GiB on a 16 x 512^2 handle at ngf = 64), the following ones load them and run the style part only.  Bit-identical results:
+ *   every accumulator receives the same operations in the same order.  0 = none of it.  ch_sean_spade_memo_stats counts.
  * "sean.hidden_wq" (default 1; any time): every Winograd ACE level (32 pixels and more) takes the SPADE hidden activations and the
  *   one-hot planes from one persistent kernel (csrc/sean_kernels.hip spade_hidden_wq).  1 = on the gather levels it writes only the
  *   64-byte pixel groups that a boundary quad's patch touches; 0 = the same kernel over every pixel (bit-identical results).  The dense
@@ -741,6 +746,9 @@ int  ch_sean_scale_report(ch_handle* h, float* host_out, int n);
  * far (`calls`) and how many of them found the label maps of the chunk before (`hits`); 0 on a handle without the memo; -1 without a
  * finalised SEAN model or when the read fails (ch_last_error).  Synchronises the device (tests, tools). */
 long long ch_sean_label_memo_stats(ch_handle* h);
+/* SPADE memo (option "sean.spade_memo"), the same kind of query: stores << 32 | loads -- how many of those chunks stored the accumulators of
+ * the styled F(4x4)-route ACEs and how many ran from the stored ones; 0 on a handle without it. */
+long long ch_sean_spade_memo_stats(ch_handle* h);
 
 /* Profiling hook (tools/ only): copies the first `bytes` of the generator's split-K scratch to host memory; with option
  * "sean.dbg" bit 256 the wave-specialised conv kernel leaves per-tile cycle stamps there.  Synchronises the device. */

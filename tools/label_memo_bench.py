@@ -1,12 +1,15 @@
 """The miss path of the label memo (option sean.label_memo): the headline generator job of bench.py -- exact f32, B = 16, 512 x 512, ngf = 64,
 blocky labels -- with TWO label sets alternating call by call, so that no call finds the maps of the call before it.
 
-    python tools/label_memo_bench.py [--labels alternate|same] [--steps K] [--warmup W] [--opt key=value ...]
+    python tools/label_memo_bench.py [--labels alternate|pairs|same] [--steps K] [--warmup W] [--opt key=value ...]
 
 Timed as bench.py times a leg: warm-up, synchronise, one event per step on the launch stream, synchronise; step_ms = the intervals between
-the events.  Prints one JSON line {labels, step_ms: {median, p10, p90, n}, images_per_s, memo: [calls, hits] | null}.  --labels same keeps one
-label set (the headline itself; with --opt sean.label_memo=0 it measures the library without the memo).  A library older than the memo runs
-too: the counters then read null.  Reads nothing outside the repository."""
+the events.  Prints one JSON line {labels, step_ms: {median, p10, p90, n}, images_per_s, memo: [calls, hits] | null, spade_memo: [stores,
+loads] | null}.  --labels same keeps one label set (the headline itself; with --opt sean.label_memo=0 it measures the library without the
+memo).  --labels pairs brings every label set twice -- L, L, L', L', ... -- so that every second call is a label hit that stores the SPADE
+memo's accumulators (option sean.spade_memo) and none ever loads them: its worst case; the line then also holds the medians of the first and
+of the second calls of the pairs (step_ms_first, step_ms_second).  A library older than a memo runs too: its counters then read null.
+Reads nothing outside the repository."""
 import argparse
 import json
 import os
@@ -22,7 +25,7 @@ from ctrlhair_amd.sean.generator import SeanGenerator    # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--labels', choices=('alternate', 'same'), default='alternate')
+    ap.add_argument('--labels', choices=('alternate', 'pairs', 'same'), default='alternate')
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=16)
@@ -36,24 +39,31 @@ def main():
     dev = gen.device
     codes = torch.from_numpy(P.style_codes(B)).to(dev)
     noise = torch.from_numpy(P.noise_planes(B, S, a.ngf)).to(dev)
-    sets = [torch.from_numpy(P.blocky_labels(B, S, first=first)).to(dev) for first in ((0, B) if a.labels == 'alternate' else (0,))]
+    sets = [torch.from_numpy(P.blocky_labels(B, S, first=first)).to(dev) for first in ((0,) if a.labels == 'same' else (0, B))]
+    rep = 2 if a.labels == 'pairs' else 1          # calls in a row with one label set
     out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
     for i in range(a.warmup):
-        gen.generate(sets[i % len(sets)], codes, noise, out=out)
+        gen.generate(sets[i // rep % len(sets)], codes, noise, out=out)
     torch.cuda.synchronize()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
     for i in range(a.steps):
         marks[i].record()
-        gen.generate(sets[(a.warmup + i) % len(sets)], codes, noise, out=out)
+        gen.generate(sets[(a.warmup + i) // rep % len(sets)], codes, noise, out=out)
     marks[a.steps].record()
     torch.cuda.synchronize()
     ms = np.asarray([marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)], dtype=np.float64)
     assert bool(torch.isfinite(out).all())
-    stats = getattr(gen.handle, 'sean_label_memo_stats', None)
-    print(json.dumps({'labels': a.labels, 'options': opts,
-                      'step_ms': {'median': round(float(np.median(ms)), 3), 'p10': round(float(np.percentile(ms, 10)), 3),
-                                  'p90': round(float(np.percentile(ms, 90)), 3), 'n': int(ms.size)},
-                      'images_per_s': round(B * a.steps / (ms.sum() / 1e3), 2), 'memo': list(stats()) if stats else None}), flush=True)
+    stats, spade = getattr(gen.handle, 'sean_label_memo_stats', None), getattr(gen.handle, 'sean_spade_memo_stats', None)
+
+    def summary(v):
+        return {'median': round(float(np.median(v)), 3), 'p10': round(float(np.percentile(v, 10)), 3), 'p90': round(float(np.percentile(v, 90)), 3), 'n': int(v.size)}
+    line = {'labels': a.labels, 'options': opts, 'step_ms': summary(ms)}
+    if a.labels == 'pairs':
+        first = (a.warmup + np.arange(a.steps)) % 2 == 0
+        line['step_ms_first'], line['step_ms_second'] = summary(ms[first]), summary(ms[~first])
+    line.update({'images_per_s': round(B * a.steps / (ms.sum() / 1e3), 2), 'memo': list(stats()) if stats else None,
+                 'spade_memo': list(spade()) if spade else None})
+    print(json.dumps(line), flush=True)
     gen.handle.close()
 
 
