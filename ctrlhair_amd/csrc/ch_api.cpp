@@ -863,6 +863,21 @@ long long ch_sean_spade_memo_stats(ch_handle* h) {
     }
     return (long long)stores << 32 | (long long)(unsigned)loads;
 }
+long long ch_sean_code_memo_stats(ch_handle* h) {
+    if (!h) return -1;
+    if (!h->sean_ready) {
+        fail(h, CH_ERR_STATE, "ch_sean_code_memo_stats: SEAN weights not finalized");
+        return -1;
+    }
+    DeviceGuard guard(h->device);
+    int calls = 0, hits = 0;
+    const std::string e = h->sean.code_memo_stats(&calls, &hits);
+    if (!e.empty()) {
+        fail(h, CH_ERR_HIP, "ch_sean_code_memo_stats: " + e);
+        return -1;
+    }
+    return (long long)calls << 32 | (long long)(unsigned)hits;
+}
 
 int ch_sean_debug_read(ch_handle* h, void* host_out, size_t bytes) {
     if (!h || !host_out) return CH_ERR_ARG;
@@ -932,6 +947,9 @@ const OptRow OPTION_TABLE[] = {
     // with the label memo, styled ACEs on the F(4x4) V route: 1 = the accumulators after the hidden k-steps are kept and a call with the same label
     // maps runs the style k-steps only (default; sean_model.h memo_acc), 0 = launch for launch as without it
     {"sean.spade_memo", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(spade_memo)},
+    // handles with the grouped style-LUT launch: 1 = the projections and the style LUTs stay on the device and their two launches return at once
+    // while the calls bring the same style codes (default; sean_model.h code_state), 0 = no memo: every call rebuilds them
+    {"sean.code_memo", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(code_memo)},
     {"sean.overlap", BY_SEAN, CLAMP, 0, MAXI, SEAN_FIELD(overlap)},        // CUs of the side streams of the overlap mode (sean_model.h), 0 = off
     {"sean.wino4_force", NEVER, BOOL, 0, 0, SEAN_FIELD(wino4_force)},        // 1 = F(4x4,3x3) wherever the shape allows, even with fewer tasks than CUs (tests / measurements)
     {"sean.patch", BY_SEAN, BOOL, 0, 0, SEAN_FIELD(patch)},                  // 1 = pre-gathered hidden-activation patches for levels with few boundary quads (default), 0 = planes only

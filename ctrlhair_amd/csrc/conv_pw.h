@@ -34,6 +34,7 @@ struct PwParams {
     long long in_bs;        // plain launch: floats between the samples of `in`; 0 = Cin * HW (a launch over the first Cin planes of wider samples: sean_model.cpp, Zencoder ConvTranspose)
     int wide;               // option "sean.pw_wide": 0 = pw_conv_kernel; 1 = 64-row wave tiles (pw_conv_wide_kernel) where the launcher's rule takes them
                             // (pw_wide_rule).  Grouped launch: the caller vouches for every group's HW % 256 == 0
+    const int* skip;        // optional (code memo, the grouped style-LUT launch): device word; the whole launch returns at once where it reads 1
     // set by the launcher
     int nrg, npt, ntasks, nst;
 };
@@ -73,6 +74,7 @@ __global__ __launch_bounds__(512, 1) void pw_conv_kernel(const PwParams p) {
     const int G = gridDim.x;
     const int lb = xcd_remap(blockIdx.x, G);
     if (lb >= p.ntasks) return;
+    if (p.skip && *p.skip) return;          // (code memo: every group's output still holds the LUT of these codes)
     const int mytasks = (p.ntasks - lb + G - 1) / G;
     const int nst = p.nst;
     constexpr unsigned SB = SDW * 4, RING = NST * SB;
@@ -273,6 +275,7 @@ __global__ __launch_bounds__(512, 1) void pw_conv_wide_kernel(const PwParams p) 
     const int G = gridDim.x;
     const int lb = xcd_remap(blockIdx.x, G);
     if (lb >= p.ntasks) return;
+    if (p.skip && *p.skip) return;          // (code memo: every group's output still holds the LUT of these codes)
     const int mytasks = (p.ntasks - lb + G - 1) / G;
     const int nst = p.nst;
     constexpr unsigned SB = SDW * 4, RING = NST * SB;

@@ -20,6 +20,11 @@ enum { MEMO_VALID = 0, MEMO_DIFF = 1, MEMO_HIT = 2, MEMO_KEY = 3, MEMO_CALLS = 6
 enum { SPADE_PLAIN = 0, SPADE_STORE = 1, SPADE_LOAD = 2 };
 hipError_t label_memo_begin(const uint8_t* labels, uint8_t* copy, long long bytes, int* state, int B, int S, int epoch, hipStream_t s, int spade = 0);
 hipError_t label_memo_invalidate(int* state, hipStream_t s);
+// Code memo (SeanModel::code_state): the same two launches over the style codes of an eligible chunk, with words of their own -- compare `bytes`
+// of codes with the copy as integer words (16-byte aligned both), then decide CODE_HIT from CODE_VALID, CODE_DIFF and the key (B, epoch)
+enum { CODE_VALID = 0, CODE_DIFF = 1, CODE_HIT = 2, CODE_KEY = 3, CODE_CALLS = 6, CODE_HITS = 7, CODE_WORDS = 8 };
+hipError_t code_memo_begin(const float* codes, float* copy, long long bytes, int* state, int B, int epoch, hipStream_t s);
+hipError_t code_memo_invalidate(int* state, hipStream_t s);
 // need (optional, [B][H][W]): pixels with need == 0 are not written (ace_sparse.h: nothing reads them)
 hipError_t onehot_conv3x3(const uint8_t* lab, const float* table, const float* bias, float* out, int B, int H, int W,
                           int K, int relu, hipStream_t s, int c4 = 0, const uint8_t* need = nullptr, int kout = 0);
@@ -85,7 +90,8 @@ hipError_t fc_mu(const float* codes, const float* Wt, const float* bias, float* 
                  int pass = 0, int bf16 = 0, int transposed = 1);      // transposed: the wave reduction as one transposed butterfly (same bits; 0 = 32 butterflies)
 hipError_t fc_mu_batched(const float* codes, const float* const* Wts, const float* const* biases, float* mu_base,
                          long long mu_stride, int n_aces, int B, int Npad, int bs, float scale, unsigned* amax_slots, int pass,
-                         int bf16, hipStream_t s, int sh16 = 1, int transposed = 1);
+                         int bf16, hipStream_t s, int sh16 = 1, int transposed = 1,
+                         const int* skip = nullptr);      // skip (optional): device word of the code memo; the launch returns at once where it reads 1
 // w4 (C4 path): the same weights packed [Cin/4][tap][co][4 channels] for scalar loads
 hipError_t conv_img_tanh(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int H, int W,
                          hipStream_t s, int c4 = 0, const float* w4 = nullptr);

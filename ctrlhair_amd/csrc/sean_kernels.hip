@@ -146,6 +146,39 @@ hipError_t label_memo_invalidate(int* state, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Code memo (sean_model.h SeanModel::code_state): does this chunk bring the style codes of the previous one?  The compare kernel above reads
+// the codes as integer words (equal bits are a hit whatever they encode: NaN payloads, -0.0) and marks CODE_DIFF, which sits where MEMO_DIFF
+// does; the decision is the label memo's without the SPADE mode, keyed on (B, epoch).
+static_assert((int)CODE_DIFF == (int)MEMO_DIFF, "label_memo_compare_kernel marks word MEMO_DIFF of the state it is given");
+__global__ void code_memo_decide_kernel(int* __restrict__ state, int B, int epoch) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int hit = (state[CODE_VALID] == 1 && state[CODE_DIFF] == 0 && state[CODE_KEY] == B && state[CODE_KEY + 1] == epoch) ? 1 : 0;
+    state[CODE_HIT] = hit;
+    state[CODE_VALID] = 1;
+    state[CODE_DIFF] = 0;
+    state[CODE_KEY] = B;
+    state[CODE_KEY + 1] = epoch;
+    state[CODE_CALLS] += 1;
+    state[CODE_HITS] += hit;
+}
+__global__ void code_memo_invalidate_kernel(int* __restrict__ state) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) state[CODE_VALID] = state[CODE_HIT] = 0;
+}
+hipError_t code_memo_begin(const float* codes, float* copy, long long bytes, int* state, int B, int epoch, hipStream_t s) {
+    if (!codes || !copy || !state || bytes <= 0 || (bytes & 15) || (reinterpret_cast<uintptr_t>(codes) & 15) || (reinterpret_cast<uintptr_t>(copy) & 15))
+        return hipErrorInvalidValue;
+    const long long n16 = bytes >> 4;
+    const int grid = (int)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048);
+    hipLaunchKernelGGL(label_memo_compare_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const uint4*>(codes), reinterpret_cast<uint4*>(copy), n16, state);
+    hipLaunchKernelGGL(code_memo_decide_kernel, dim3(1), dim3(64), 0, s, state, B, epoch);
+    return hipGetLastError();
+}
+hipError_t code_memo_invalidate(int* state, hipStream_t s) {
+    if (!state) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(code_memo_invalidate_kernel, dim3(1), dim3(64), 0, s, state);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // 3x3 conv on a one-hot map == 9-tap table gather (exact):  out[b,k,p] = act(bias[k] + sum_t T[label(p+t)][t][k])
 // Used for SPADE.mlp_shared (normalization.py:239-242,253) and the generator's `fc` conv (generator.py:33,76).
@@ -1054,7 +1087,9 @@ template <bool TR>
 __global__ __launch_bounds__(256) void fc_mu_batched_kernel(const float* __restrict__ codes, const float* const* __restrict__ Wts,
                                                             const float* const* __restrict__ biases, float* __restrict__ mu_base,
                                                             long long mu_stride, int B, int Npad, int bs, float scale,
-                                                            unsigned* __restrict__ amax_slots, int pass, int bf16, int sh16) {
+                                                            unsigned* __restrict__ amax_slots, int pass, int bf16, int sh16,
+                                                            const int* __restrict__ skip) {
+    if (skip && *skip) return;      // (code memo: mu_base still holds the projections of these codes)
     const int a = blockIdx.z;
     const float* Wt = Wts[a];
     if (!Wt) return;
@@ -1064,9 +1099,9 @@ __global__ __launch_bounds__(256) void fc_mu_batched_kernel(const float* __restr
 // sh16 = 0: f32 images [512][Npad] (exact-f32 path; no scale protocol, one pass); sh16 = 2: f32 in the A-fragment order of conv_pw.h
 hipError_t fc_mu_batched(const float* codes, const float* const* Wts, const float* const* biases, float* mu_base,
                          long long mu_stride, int n_aces, int B, int Npad, int bs, float scale, unsigned* amax_slots, int pass,
-                         int bf16, hipStream_t s, int sh16, int transposed) {
+                         int bf16, hipStream_t s, int sh16, int transposed, const int* skip) {
     hipLaunchKernelGGL(transposed ? fc_mu_batched_kernel<true> : fc_mu_batched_kernel<false>, dim3(512 / 16, 19, n_aces), dim3(256), 0, s, codes, Wts, biases, mu_base, mu_stride, B,
-                       Npad, bs, scale, amax_slots, pass, bf16, sh16);
+                       Npad, bs, scale, amax_slots, pass, bf16, sh16, skip);
     return hipGetLastError();
 }
 

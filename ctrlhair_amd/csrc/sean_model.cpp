@@ -751,6 +751,10 @@ struct SeanBuild {
         m.lut_groups_wide = false;
         m.lut_ngroups = m.lut_group_tiles = 0;
         m.lut_group_rows = 0.0;
+        m.code_copy = nullptr;
+        m.code_state = nullptr;
+        m.code_bytes = 0;
+        m.code_dirty = false;
         if (!(m.fcmu_batched && !opt.use_sh16 && opt.lut_grouped)) return;
         if (m.lut_ahead.empty()) m.lut_ahead.assign(m.n_aces, nullptr);
         std::vector<PwGroup> g;
@@ -779,6 +783,13 @@ struct SeanBuild {
             m.lut_groups_wide = true;
             for (const PwGroup& e : g) m.lut_groups_wide = m.lut_groups_wide && e.HW % 256 == 0;
         }
+        // Code memo (sean_model.h): the copy of the codes and the state words, on handles with the grouped launch only
+        if (!(opt.code_memo && m.lut_groups)) return;
+        m.code_bytes = (size_t)mb * LABEL_NC * STYLE * 4 + CODE_WORDS * sizeof(int);
+        m.code_copy = static_cast<float*>(B.dalloc((size_t)mb * LABEL_NC * STYLE * 4));
+        m.code_state = static_cast<int*>(B.dalloc(CODE_WORDS * sizeof(int)));
+        if (m.code_state && hipMemset(m.code_state, 0, CODE_WORDS * sizeof(int)) != hipSuccess) m.code_state = nullptr;      // (no memo)
+        if (!m.code_copy) m.code_state = nullptr;
     }
 
     // ---- Winograd ACE path: boundary-quad lists per level, task lists per (level, row tiles), per-sample style images ------
@@ -1061,6 +1072,9 @@ void SeanModel::destroy() {
     memo_lab = nullptr;
     memo_state = nullptr;
     memo_dirty = false;
+    code_copy = nullptr;
+    code_state = nullptr;
+    code_dirty = false;
     splitk_side = nullptr;
     for (auto& r : prof) {
         ev_pool.push_back(r.e0);
@@ -1293,6 +1307,19 @@ struct Runner {
               "label memo (compare, decide)");
         memo_hit = m.memo_state + MEMO_HIT;
         if (m.opt.spade_memo && m.spade_memo_on) spade_mode = m.memo_state + MEMO_SPADE_MODE;
+    }
+    // Code memo (sean_model.h): the device word that fc_mu_batched and the grouped LUT GEMM of this chunk read, nullptr on a chunk that is not
+    // eligible.  Any chunk that is not eligible clears CODE_VALID: it may write mu_all or a lut_ahead buffer by another path.  Not while
+    // profiling is enabled: its records time the launches that do the work (as the label memo, which needs the prologue, is off then).
+    const int* code_hit = nullptr;
+    void code_begin(const float* codes, bool only_chunk) {
+        if (!m.code_state) return;
+        const bool ok = m.opt.code_memo && only_chunk && mode.project_all && mode.grouped && !m.prof_on && (reinterpret_cast<uintptr_t>(codes) & 15) == 0;
+        if (!ok || m.code_dirty) check(code_memo_invalidate(m.code_state, st), "code memo (invalidate)");
+        m.code_dirty = false;
+        if (!ok) return;
+        check(code_memo_begin(codes, m.code_copy, (long long)B * LABEL_NC * STYLE * 4, m.code_state, B, m.memo_epoch, st), "code memo (compare, decide)");
+        code_hit = m.code_state + CODE_HIT;
     }
     // SPADE memo (sean_model.h): the mode word of an eligible chunk, and which level sizes had their one-hot V image packed in this chunk
     const int* spade_mode = nullptr;
@@ -1548,6 +1575,7 @@ struct Runner {
         q.groups = static_cast<const PwGroup*>(m.lut_groups);
         q.ngroups = m.lut_ngroups;
         q.wide = m.opt.pw_wide && m.lut_groups_wide;
+        q.skip = code_hit;
         const int nrg = ((N + 31) / 32 + 3) / 4;
         timed(2, 2.0 * m.lut_group_rows * STYLE * N, 4.0 * (m.lut_group_rows * STYLE + m.lut_group_rows * N + (double)m.lut_ngroups * STYLE * N),
               [&] { check(conv_pw_grouped(q, m.lut_group_tiles * nrg, st), "style LUTs (grouped GEMM)"); });
@@ -2120,10 +2148,12 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
         R.memo_begin(lab, Btot <= max_batch);
         for (int k = 1; k <= 5; ++k) R.check(label_downsample(lab, levels[k].lab, B, S, S >> k, st, R.memo_hit), "label_downsample");
         if (opt.use_sh16) R.check(hipMemsetAsync(amax_slots, 0, 64 * sizeof(unsigned), st), "amax slots");
+        R.code_begin(cd, Btot <= max_batch);
         if (mode.project_all) {     // (smaller batches take the GEMV branch of Runner::build_lut, which projects per ACE)
-            // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout)
+            // grouped LUT build: the projections are its A operand, written in fragment order (sh16 = 2: pack_pw_A layout); with the code memo
+            // both launches return at once on a chunk that brings the codes of the previous one
             R.check(fc_mu_batched(cd, fcmu_w_ptrs, fcmu_b_ptrs, mu_all, mu_stride, n_aces, B, ((B * LABEL_NC + 31) / 32) * 32, LABEL_NC, 1.f,
-                                  nullptr, 0, 0, st, mode.grouped ? 2 : 0, opt.pw_wide), "fc_mu (all ACEs)");
+                                  nullptr, 0, 0, st, mode.grouped ? 2 : 0, opt.pw_wide, R.code_hit), "fc_mu (all ACEs)");
             if (mode.grouped) R.luts_grouped();
         } else if (fcmu_batched && opt.use_sh16) {
             const int npad_c = ((B * (LABEL_NC + 1) + 31) / 32) * 32;
@@ -2183,7 +2213,7 @@ std::string SeanModel::generate(const uint8_t* labels, const float* codes, const
             std::swap(x, y);
         }
         R.check(conv_img_tanh(x, img_w, img_b, out + (size_t)bo * 3 * S * S, B, ngf, S, S, st, opt.use_sh16 ? 1 : 0, img_w4), "conv_img");
-        if (!R.err.empty()) memo_dirty = true;      // (the decision kernel may have run ahead of a launch that failed)
+        if (!R.err.empty()) memo_dirty = code_dirty = true;      // (the decision kernels may have run ahead of a launch that failed)
         if (!R.err.empty()) return join(R.err);
     }
     return join("");
@@ -2228,6 +2258,15 @@ std::string SeanModel::spade_memo_stats(int* stores, int* loads) {
         return "SPADE memo: state read failed";
     *stores = st[MEMO_STORES];
     *loads = st[MEMO_LOADS];
+    return "";
+}
+
+std::string SeanModel::code_memo_stats(int* calls, int* hits) {
+    int st[CODE_WORDS] = {};
+    if (code_state && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(st, code_state, sizeof st, hipMemcpyDeviceToHost) != hipSuccess))
+        return "code memo: state read failed";
+    *calls = st[CODE_CALLS];
+    *hits = st[CODE_HITS];
     return "";
 }
 

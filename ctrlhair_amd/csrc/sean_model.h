@@ -99,6 +99,9 @@ struct SeanOptions {
     int spade_memo = 1;                        // option "sean.spade_memo": with the label memo, the styled ACEs on the F(4x4) V route: 1 = the 36 accumulators of a task
                                                //   after its 32 hidden k-steps are kept (SeanModel::memo_acc) and a call with the same maps runs the six style
                                                //   k-steps only; 0 = launch for launch as without it
+    int code_memo = 1;                         // option "sean.code_memo": handles with the grouped style-LUT launch, calls of one chunk: 1 = the projections and
+                                               //   the style LUTs (mu_all, lut_ahead) are kept and fc_mu_batched and the grouped GEMM return at once while the
+                                               //   calls bring the same style codes (SeanModel::code_state); 0 = every call rebuilds them
     // Overlap mode (round 5; option "sean.overlap" = CUs of the side streams, 0 = off; exact-f32 Winograd path, jobs beyond the
     // run-ahead sizes): the HBM-bound kernels -- label tables of all ACEs, interior passes -- run on streams whose CU mask holds
     // `overlap` CUs (hipExtStreamCreateWithCUMask: every XCD gives overlap / 8 of its CUs), beside the matrix-bound convs on the
@@ -309,6 +312,21 @@ struct SeanModel {
     float* memo_v1h[2] = {nullptr, nullptr};
     bool spade_memo_on = false;                // any memo_acc allocated: the decision kernel keeps the mode
     std::string spade_memo_stats(int* stores, int* loads);     // synchronous read-back of MEMO_STORES / MEMO_LOADS
+    // Code memo (option "sean.code_memo"; handles with lut_groups): a shape-slider drag, a mask warp or a shape sweep changes the label maps
+    // and keeps every style code; a repeat render keeps both.  fc_mu_batched and the grouped LUT GEMM read codes and weights only and write
+    // buffers that nothing else writes on such a chunk and that outlive the call (mu_all, lut_ahead), so a chunk that brings the codes of the
+    // previous one skips both.  The device decides, as for the label memo and independent of it (kernels.h code_memo_begin): `code_copy` is
+    // the handle's copy of the last eligible chunk's codes, `code_state` the words CODE_*; the two launches read code_state[CODE_HIT] at
+    // their top and return on 1.  Eligible: the only chunk of its call, with mode.project_all && mode.grouped, profiling off and codes that
+    // can be read in 16-byte words.  Any other chunk clears CODE_VALID in stream order: the GEMV branch of Runner::build_lut and the run-ahead LUT builds
+    // (lut_src == AHEAD) write lut_ahead, the f16x3 and the ungrouped projections write mu_all in another layout.  encode() touches neither.
+    // The key is (B, memo_epoch).  Left out: ace_tables_grouped and wino_style_pack_grouped (80 us; their member set follows the plan of the
+    // call, not the codes alone) and the wino4_style_pack launches (they write the shared wsty4).
+    float* code_copy = nullptr;
+    int* code_state = nullptr;
+    bool code_dirty = false;                   // a generate() ended in an error after its decision kernel: the next eligible chunk invalidates first
+    size_t code_bytes = 0;                     // what the code memo adds to the handle
+    std::string code_memo_stats(int* calls, int* hits);        // synchronous read-back of CODE_CALLS / CODE_HITS
 
     // ---- exact SPADE-interior reduction (ace_sparse.h; per-level buffers: Level) ----
     float* gtab = nullptr;                     // [max_batch][19][2][C max]

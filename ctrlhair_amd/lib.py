@@ -83,6 +83,7 @@ SYMBOLS = {
     'ch_sean_debug_read': (_I, [_VP, _VP, C.c_size_t]),
     'ch_sean_label_memo_stats': (C.c_longlong, [_VP]),
     'ch_sean_spade_memo_stats': (C.c_longlong, [_VP]),
+    'ch_sean_code_memo_stats': (C.c_longlong, [_VP]),
     'ch_mfma_peak': (_I, [_VP, _I, _I, C.POINTER(_D)]),
     'ch_profile_enable': (_I, [_VP, _I]),
     'ch_profile_read': (_I, [_VP, _I, C.POINTER(_I), C.POINTER(_D), C.POINTER(_D), C.POINTER(_D)]),
@@ -192,6 +193,14 @@ class Handle:
         v = int(self.lib.ch_sean_spade_memo_stats(self._h))
         if v < 0:
             raise RuntimeError(f'ch_sean_spade_memo_stats failed: {self.lib.ch_last_error(self._h).decode()}')
+        return v >> 32, v & 0xFFFFFFFF
+
+    def sean_code_memo_stats(self):
+        """(calls, hits) of the code memo (option 'sean.code_memo'): chunks that went through its decision, and those that found the style
+        codes of the chunk before and skipped the projection and the grouped style-LUT GEMM.  Synchronises."""
+        v = int(self.lib.ch_sean_code_memo_stats(self._h))
+        if v < 0:
+            raise RuntimeError(f'ch_sean_code_memo_stats failed: {self.lib.ch_last_error(self._h).decode()}')
         return v >> 32, v & 0xFFFFFFFF
 
     def mfma_peak(self, kind: int, ms_target: int = 30) -> float:

@@ -159,6 +159,12 @@ int  ch_load_tensor(ch_handle* h, int model, const char* name, const void* host,
  *   sample.  1 = the second call in a row with the same label maps stores the Winograd-domain accumulators of every task after the hidden
  *   part (4.2 GiB on a 16 x 512^2 handle at ngf = 64), the following ones load them and run the style part only.  Bit-identical results:
  *   every accumulator receives the same operations in the same order.  0 = none of it.  ch_sean_spade_memo_stats counts.
+ * "sean.code_memo" (default 1; before ch_finalize; handles with "sean.lut_grouped" in effect): the projected codes and the style LUTs of all
+ *   styled ACEs stay on the device; a call of one chunk that takes the grouped launch compares its style codes, as integer words, with the
+ *   handle's copy on the device (1.2 MiB at 16 samples), and the projection and the grouped GEMM return at once when nothing changed (same
+ *   batch, same options).  Independent of "sean.label_memo"; off while ch_profile_enable is on.  Bit-identical results.  0 = no memo and
+ *   none of its buffers.
+ *   ch_sean_code_memo_stats counts.
  * "sean.hidden_wq" (default 1; any time): every Winograd ACE level (32 pixels and more) takes the SPADE hidden activations and the
  *   one-hot planes from one persistent kernel (csrc/sean_kernels.hip spade_hidden_wq).  1 = on the gather levels it writes only the
  *   64-byte pixel groups that a boundary quad's patch touches; 0 = the same kernel over every pixel (bit-identical results).  The dense
@@ -749,6 +755,9 @@ long long ch_sean_label_memo_stats(ch_handle* h);
 /* SPADE memo (option "sean.spade_memo"), the same kind of query: stores << 32 | loads -- how many of those chunks stored the accumulators of
  * the styled F(4x4)-route ACEs and how many ran from the stored ones; 0 on a handle without it. */
 long long ch_sean_spade_memo_stats(ch_handle* h);
+/* Code memo (option "sean.code_memo"), the same kind of query: calls << 32 | hits -- how many chunks went through the code memo's decision
+ * and how many of them found the style codes of the chunk before; 0 on a handle without it. */
+long long ch_sean_code_memo_stats(ch_handle* h);
 
 /* Profiling hook (tools/ only): copies the first `bytes` of the generator's split-K scratch to host memory; with option
  * "sean.dbg" bit 256 the wave-specialised conv kernel leaves per-tile cycle stamps there.  Synchronises the device. */
