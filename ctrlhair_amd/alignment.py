@@ -227,6 +227,17 @@ def matte_params(matte, scale):
     return int(radius), eps
 
 
+def read_photo(path, orient=True, reader=None):
+    """A photo file for FaceAligner.align / HairEditor.crop_face: (pixels uint8 [H,W,3], (orientation, exif bytes or None, icc profile or
+    None)).  orient: the pixels are made upright by the file's EXIF orientation, as viewers and landmark detectors see them, and the
+    EXIF block comes without the tag; landmarks found on the stored pixels move along with orient.orient_points.  reader: None -- Pillow
+    reads the file, the pixels are numpy; a device reader (dataset._PhotoReader) -- it is decoded and turned on the device, the pixels
+    are a device tensor, the same bytes."""
+    from . import dataset
+    read = dataset.read_rgb if reader is None else reader.read_rgb
+    return read(path, orient=bool(orient), metadata=True)
+
+
 class FaceAligner(DeviceOp):
     """recreate_aligned_images on the device.  Attached to HipModels as `aligner`; also usable alone (no network weights)."""
 

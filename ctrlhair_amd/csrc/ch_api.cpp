@@ -14,6 +14,7 @@
 #include "sean_model.h"
 #include "kernels.h"
 #include "ingest_batch.h"
+#include "orient_batch.h"
 #include "jpeg_entropy_core.h"
 #include "png_inflate_core.h"
 
@@ -594,6 +595,27 @@ int ch_ingest_labels(ch_handle* h, const void* batch, size_t batch_bytes, int N,
     if (!batch || !out || !workspace) return fail(h, CH_ERR_ARG, "ch_ingest_labels: null pointer");
     if (int rc = ingest_refuse(h, "ch_ingest_labels: ", batch, batch_bytes, N, S, CH_INGEST_LABELS, workspace, workspace_bytes)) return rc;
     return launch(h, "ch_ingest_labels: ", [&] { return chk::ingest_labels(batch, batch_bytes, N, S, out, workspace, hs(stream)); });
+}
+
+// ---- EXIF orientation (orient.hip) ----------------------------------------------------------------------------------------------------
+static_assert(CH_ORIENT_DESC_BYTES == sizeof(chk::OrientImage) && CH_ORIENT_MAX_SIDE == chk::ORIENT_MAX_SIDE,
+              "orient constants of the header and of orient_batch.h");
+
+size_t ch_orient_workspace_bytes(const void* batch, size_t batch_bytes, int N, size_t dst_bytes) {
+    size_t need = 0;
+    return chk::orient_check(batch, batch_bytes, N, 0, dst_bytes, need).empty() ? need : 0;
+}
+
+int ch_orient_u8(ch_handle* h, const void* batch, size_t batch_bytes, int N, uint8_t* dst, size_t dst_bytes, void* workspace,
+                 size_t workspace_bytes, ch_stream_t stream) {
+    if (!h) return CH_ERR_ARG;
+    if (!batch || !dst || !workspace) return fail(h, CH_ERR_ARG, "ch_orient_u8: null pointer");
+    size_t need = 0;
+    const std::string why = chk::orient_check(batch, batch_bytes, N, reinterpret_cast<uintptr_t>(dst), dst_bytes, need);
+    if (!why.empty()) return fail(h, CH_ERR_ARG, "ch_orient_u8: " + why);
+    if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return fail(h, CH_ERR_ARG, "ch_orient_u8: workspace is not 256-byte aligned");
+    if (int rc = workspace_short(h, "ch_orient_u8: ", workspace_bytes, need, "ch_orient_workspace_bytes")) return rc;
+    return launch(h, "ch_orient_u8: ", [&] { return chk::orient_u8(batch, batch_bytes, N, dst, workspace, hs(stream)); });
 }
 
 int ch_hair_erode(ch_handle* h, const uint8_t* labels, int B, int Hl, int Wl, int label, int ksize, uint8_t* mask, int H, int W,

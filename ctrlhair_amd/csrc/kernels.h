@@ -178,6 +178,10 @@ hipError_t ingest_images(const void* batch, size_t batch_bytes, int N, int P, in
                          hipStream_t s);
 hipError_t ingest_labels(const void* batch, size_t batch_bytes, int N, int S, uint8_t* out, void* ws, hipStream_t s);
 
+// orient.hip: EXIF orientations 1..8 of a ragged batch of uint8 images in one launch.  batch: HOST bytes, N descriptors (orient_batch.h);
+// the launcher takes only a batch that orient_check has passed, and a workspace of the size it returned.
+hipError_t orient_u8(const void* batch, size_t batch_bytes, int N, uint8_t* dst, void* ws, hipStream_t s);
+
 // sheet.hip: contact sheets and per-render measurements of a direction search (shape_branch/script_find_direction.py:55-76,
 // util/canvas_grid.py:15-31).  See ch_sheet_compose / ch_sweep_stats in ctrlhair_hip.h.
 constexpr int SWEEP_NSTAT = 16;               // == CH_SWEEP_STATS

@@ -63,6 +63,11 @@ On-disk formats are the reference's:
     (crop and uncrop take --decode host|device for the photos and edits they read: 'device' uploads the files' bytes and decodes them
      there, .jpg / .jpeg with ch_jpeg_decode (ctrlhair_amd.jpegdec), .png with ch_png_decode; the pixels are Pillow's, so the results are
      the same files; progressive JPEGs and whatever else the device does not take are decoded by Pillow, file by file)
+    (crop and uncrop take --orient [--landmark-frame upright|stored] and --metadata drop|keep: --orient makes every photo upright by its
+     EXIF orientation before it is aligned or pasted into -- Pillow's exif_transpose on the host, ch_orient_u8 (ctrlhair_amd.orient) with
+     --decode device, the same pixels -- and takes the landmarks as pixels of the upright photo, or of the stored one with
+     --landmark-frame stored; --metadata keep writes the photo's ICC profile and its EXIF block, without the orientation tag where the
+     pixels were made upright, into the output, whoever writes it.  Without them nothing changes: the stored pixels, no metadata)
     (masks and codes take --decode host|device too: 'device' decodes a batch's files in the same way and then resizes and normalises them
      there in one call, ch_ingest_images / ch_ingest_labels (ctrlhair_amd.ingest): the networks see the same tensors bit for bit)
     (under torch.distributed.run for several GPUs; RANK / WORLD_SIZE / LOCAL_RANK are read from the environment)
@@ -72,6 +77,8 @@ import pickle
 from typing import Dict, Iterable, List, Sequence
 
 import numpy as np
+
+from .photometa import turns as photometa_turns      # (host code: no torch, no library)
 
 IMG_EXT = ('.png', '.jpg', '.jpeg', '.bmp')
 
@@ -111,9 +118,23 @@ def merge_pickle_dir_to_dict(dir_name: str, target_path: str) -> Dict[str, np.nd
     return res
 
 
-def read_rgb(path: str) -> np.ndarray:
+def read_rgb(path: str, orient: bool = False, metadata: bool = False):
+    """The file's pixels as uint8 [H,W,3].  orient: made upright by ImageOps.exif_transpose (EXIF orientation 2..8; anything else leaves
+    them alone).  metadata: -> (pixels, (orientation, exif bytes or None, icc profile or None)), photometa.image_metadata's triple: the
+    EXIF block is the one that belongs to the returned pixels, without the orientation tag when they were made upright, with it else."""
     from PIL import Image
-    return np.asarray(Image.open(path).convert('RGB'))
+    im = Image.open(path)
+    if not orient and not metadata:
+        return np.asarray(im.convert('RGB'))
+    from PIL import ImageOps
+    from . import photometa
+    from .orient import turns
+    try:
+        meta = photometa.image_metadata(im, strip=orient)
+    except Exception:                                       # as read_metadata: EXIF that Pillow cannot read is no metadata, and no turn
+        meta = photometa.NONE
+    pixels = np.asarray((ImageOps.exif_transpose(im) if orient and turns(meta[0]) else im).convert('RGB'))
+    return (pixels, meta) if metadata else pixels
 
 
 def read_gray(path: str) -> np.ndarray:
@@ -156,30 +177,60 @@ def _png_decoder(decode: str, owner):
 class _PhotoReader:
     """read_rgb for the crop jobs with decode='device': .jpg / .jpeg files through jpegdec.JpegDecoder, .png files through
     pngdec.PngDecoder, on `owner`'s handle and device; anything else, and every file a decoder hands back, is Pillow's.  The pixels are
-    device tensors and the same as read_rgb's; fallbacks counts the files Pillow decoded."""
+    device tensors and the same as read_rgb's; fallbacks counts the files Pillow decoded.
+    orient: read_rgb / read_rgb_many make the pixels upright as dataset.read_rgb(orient=True) does: the files are decoded as stored, by
+    the device or by Pillow, and those whose EXIF orientation is 2..8 are then turned by ONE orient.Orienter.apply call per batch.  The
+    orientation, like the rest of the metadata, is photometa.read_metadata's, from Pillow's lazy open of the file (headers only)."""
 
-    def __init__(self, owner):
+    def __init__(self, owner, orient: bool = False):
         from .jpegdec import JpegDecoder
         from .pngdec import PngDecoder
         self.jpeg, self.png, self.other = JpegDecoder(owner.handle, owner.device), PngDecoder(owner.handle, owner.device), 0
         self.device = owner.device
+        self.orient = bool(orient)
+        self._owner, self._orienter = owner, None
 
     @property
     def fallbacks(self) -> int:
         return self.jpeg.fallbacks + self.png.fallbacks + self.other
 
-    def read_rgb(self, path: str):
-        import torch
-        if _is_jpeg(path):
-            return self.jpeg.read_rgb([path])[0]
-        if _is_png(path):
-            return self.png.read_rgb([path])[0]
-        self.other += 1
-        return torch.from_numpy(np.array(read_rgb(path))).to(self.device)
+    @property
+    def orienter(self):
+        """orient.Orienter on the owner's handle and device, made when the first photo is to be turned."""
+        if self._orienter is None:
+            from .orient import Orienter
+            self._orienter = Orienter(self._owner.handle, self._owner.device)
+        return self._orienter
 
-    def _read_many(self, paths, gray: bool) -> List:
+    def _metadata(self, paths, orient: bool) -> List:
+        """photometa.read_metadata per path: Pillow's lazy open of the file, which reads its headers and not the scan a decoder read."""
+        from . import photometa
+        return [photometa.read_metadata(p, strip=orient) for p in paths]
+
+    def read_rgb(self, path: str, orient: bool = None, metadata: bool = False):
+        """dataset.read_rgb(path, orient, metadata) with the pixels on the device; orient: default the reader's own."""
+        import torch
+        orient = self.orient if orient is None else bool(orient)
+        if _is_jpeg(path):
+            t = self.jpeg.read_rgb([path])[0]
+        elif _is_png(path):
+            t = self.png.read_rgb([path])[0]
+        else:
+            self.other += 1
+            t = torch.from_numpy(np.array(read_rgb(path))).to(self.device)
+        if not orient and not metadata:
+            return t
+        meta = self._metadata([path], orient)[0]
+        if orient and photometa_turns(meta[0]):
+            t = self.orienter.apply([t], [meta[0]])[0]
+        return (t, meta) if metadata else t
+
+    def _read_many(self, paths, gray: bool, orient: bool = False) -> List:
         import torch
         paths = list(paths)
+        if orient:
+            stored, orientations = self._read_many(paths, gray), [m[0] for m in self._metadata(paths, True)]
+            return self.orienter.apply(stored, orientations) if any(photometa_turns(o) for o in orientations) else stored
         out = [None] * len(paths)
         for decoder, takes in ((self.jpeg, _is_jpeg), (self.png, _is_png)):
             idx = [i for i, p in enumerate(paths) if takes(p)]
@@ -194,18 +245,60 @@ class _PhotoReader:
 
     def read_rgb_many(self, paths) -> List:
         """read_rgb of a batch, in the order of `paths`: one JpegDecoder call for its .jpg / .jpeg files and one PngDecoder call for its
-        .png files (each groups equal sizes into one launch); uint8 device tensors [H,W,3]."""
-        return self._read_many(paths, gray=False)
+        .png files (each groups equal sizes into one launch); uint8 device tensors [H,W,3].  A reader made with orient=True turns the
+        whole batch's tagged files in one further launch."""
+        return self._read_many(paths, gray=False, orient=self.orient)
 
     def read_gray_many(self, paths) -> List:
         """dataset.read_gray of a batch in the same way: uint8 device tensors [H,W]; only grey files are decoded on the device."""
         return self._read_many(paths, gray=True)
 
 
-def _photo_reader(decode: str, owner):
+def _photo_reader(decode: str, owner, orient: bool = False):
     """None for decode='host' (dataset.read_rgb reads the photos); for 'device' a _PhotoReader on `owner`'s handle and device."""
     from .pngdec import check_decode_mode
-    return _PhotoReader(owner) if check_decode_mode(decode) == 'device' else None
+    return _PhotoReader(owner, orient) if check_decode_mode(decode) == 'device' else None
+
+
+LANDMARK_FRAMES = ('upright', 'stored')
+METADATA_MODES = ('drop', 'keep')
+
+
+def _check_photo_options(orient, landmark_frame: str, metadata: str) -> None:
+    if landmark_frame not in LANDMARK_FRAMES:
+        raise ValueError(f"landmark_frame must be 'upright' or 'stored', got {landmark_frame!r}")
+    if metadata not in METADATA_MODES:
+        raise ValueError(f"metadata must be 'drop' or 'keep', got {metadata!r}")
+
+
+def _read_photo(reader, path: str, orient: bool, keep: bool):
+    """(pixels, (orientation, exif, icc)) of a photo of the crop jobs: read_rgb of the host or of the device reader; with neither option
+    the plain read of before and no metadata."""
+    from . import photometa
+    read = read_rgb if reader is None else reader.read_rgb
+    if not orient and not keep:
+        return read(path), photometa.NONE
+    return read(path, orient=orient, metadata=True)
+
+
+def _photo_landmarks(lm, meta, photo_shape, orient: bool, landmark_frame: str):
+    """The landmarks in the frame of the pixels the job works on: with orient those are upright, and landmarks given for the stored
+    pixels (landmark_frame='stored') move with them (orient.orient_points)."""
+    from .orient import orient_points, turns, upright_shape
+    if not orient or landmark_frame != 'stored' or not turns(meta[0]):
+        return lm
+    Hs, Ws = upright_shape(int(photo_shape[0]), int(photo_shape[1]), meta[0])      # the stored size: the turn's shape rule is its own inverse
+    return orient_points(np.asarray(lm, np.float64), meta[0], Hs, Ws)
+
+
+def _kept_metadata(meta, keep: bool, name: str) -> dict:
+    """save() / encoder keywords of metadata='keep': the photo's ICC profile and the EXIF block that belongs to the job's pixels.  An
+    EXIF block too long for a .jpg name's APP1 segment is dropped with a warning, whoever writes the file."""
+    from . import photometa
+    if not keep:
+        return {}
+    exif = photometa.droppable(meta[1], name) if _is_jpeg(name) else meta[1]
+    return {k: v for k, v in (('exif', exif), ('icc_profile', meta[2])) if v}
 
 
 def _is_png(name: str) -> bool:
@@ -386,20 +479,26 @@ def find_landmarks(landmarks: Dict[str, np.ndarray], dataset: str, file_name: st
 
 def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = 256, rank: int = 0,
                world: int = 1, png: str = 'host', jpeg: str = 'host', jpeg_quality: int = 75, jpeg_subsampling=2, decode: str = 'host',
-               stats: dict = None):
+               stats: dict = None, orient: bool = False, landmark_frame: str = 'upright', metadata: str = 'drop'):
     """dataset_scripts/script_crop.py:36-54 for this rank's shard of `src_dir`: align every photo that has landmarks
     (`aligner`: alignment.FaceAligner) and write it to `out_dir/<name>`.  Returns (done, skipped): the file names written and the
     ones without a landmark entry, which are reported and left out.  png='device': .png names are encoded on the device.  jpeg='device':
     .jpg / .jpeg names are encoded on the device, to the bytes Pillow writes at jpeg_quality and jpeg_subsampling (0 / '444' or
     2 / '420'); jpeg='host' passes those two to Pillow when they are not its defaults.  decode='device': the photos are decoded on the
     device (.jpg / .jpeg: jpegdec.JpegDecoder, .png: pngdec.PngDecoder; the same pixels, so the same files); what a decoder does not take
-    is Pillow's, file by file, and counted in stats['fallbacks'] when a dict is passed."""
+    is Pillow's, file by file, and counted in stats['fallbacks'] when a dict is passed.
+    orient: every photo is made upright by its EXIF orientation before it is aligned, as a viewer (and a landmark detector that opens
+    the file like one) sees it: ImageOps.exif_transpose on the host, orient.Orienter on the device, the same pixels.  The landmarks are
+    then pixels of the upright photo; landmark_frame='stored': they are pixels of the stored photo and are moved along.
+    metadata='keep': the photo's ICC profile and its EXIF block (with orient without the orientation tag) are written into the crop,
+    by Pillow's save(exif=, icc_profile=) or by the device encoders, to the same bytes; 'drop': neither, as before."""
     from PIL import Image
+    _check_photo_options(orient, landmark_frame, metadata)
     os.makedirs(out_dir, exist_ok=True)
     encoder = _png_encoder(png, aligner)
     jpeg_encoder, jpeg_options = _jpeg_writer(jpeg, jpeg_quality, jpeg_subsampling, aligner)
     reader = _photo_reader(decode, aligner)
-    read = read_rgb if reader is None else reader.read_rgb
+    keep = metadata == 'keep'
     done, skipped = [], []
     for n in shard(list_images(src_dir), rank, world):
         lm = find_landmarks(landmarks, dataset, n)
@@ -407,17 +506,21 @@ def crop_faces(aligner, src_dir: str, out_dir: str, dataset: str, landmarks: Dic
             print(f'crop: no landmarks for {n}, skipped')
             skipped.append(n)
             continue
-        crop, _ = aligner.align(read(os.path.join(src_dir, n)), lm[:68], size)
+        photo, meta = _read_photo(reader, os.path.join(src_dir, n), orient, keep)
+        lm = _photo_landmarks(lm, meta, photo.shape, orient, landmark_frame)
+        crop, _ = aligner.align(photo, lm[:68], size)
+        kept = _kept_metadata(meta, keep, n)
+        lists = {k: [v] for k, v in kept.items()}
         if encoder is not None and _is_png(n):
-            encoder.write([os.path.join(out_dir, n)], crop[None])
+            encoder.write([os.path.join(out_dir, n)], crop[None], **lists)
             done.append(n)
             continue
         if jpeg_encoder is not None and _is_jpeg(n):
-            jpeg_encoder.write([os.path.join(out_dir, n)], crop[None], **jpeg_options)
+            jpeg_encoder.write([os.path.join(out_dir, n)], crop[None], **jpeg_options, **lists)
             done.append(n)
             continue
         crop = crop.cpu().numpy() if hasattr(crop, 'cpu') else np.asarray(crop)
-        Image.fromarray(crop).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}))
+        Image.fromarray(crop).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}), **kept)
         done.append(n)
     if stats is not None:
         stats['fallbacks'] = 0 if reader is None else reader.fallbacks
@@ -439,7 +542,8 @@ def label_weight(label_path: str, S: int) -> np.ndarray:
 
 def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: str, landmarks: Dict[str, np.ndarray], size: int = None,
                  rank: int = 0, world: int = 1, label_dir: str = None, matte=None, png: str = 'host', jpeg: str = 'host',
-                 jpeg_quality: int = 75, jpeg_subsampling=2, decode: str = 'host', stats: dict = None):
+                 jpeg_quality: int = 75, jpeg_subsampling=2, decode: str = 'host', stats: dict = None, orient: bool = False,
+                 landmark_frame: str = 'upright', metadata: str = 'drop'):
     """The inverse of crop_faces for this rank's shard of `photo_dir`: paste the edited crop `edit_dir/<name>` back into the photo
     `photo_dir/<name>` it was aligned from (same landmarks, same file names) and write the photo-sized result to `out_dir/<name>`.
     size: the crops' side (default: each edit's own).  label_dir: per-image weight from `label_dir/<stem>.png` (hair = 255); matte
@@ -447,12 +551,18 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
     (done, skipped); a photo without landmarks, without an edit or (with label_dir) without a label map is reported and left out.
     png='device': .png names are encoded on the device (the photo-sized result is never downloaded).  jpeg='device': the same for
     .jpg / .jpeg names, to the bytes Pillow writes at jpeg_quality and jpeg_subsampling (0 / '444' or 2 / '420'); jpeg='host' passes
-    those two to Pillow when they are not its defaults.  Neither path carries the photo's EXIF or ICC data over.  decode='device': the
-    photos and the edits are decoded on the device, as in crop_faces (stats['fallbacks']: the files Pillow decoded after all)."""
+    those two to Pillow when they are not its defaults.  decode='device': the photos and the edits are decoded on the device, as in
+    crop_faces (stats['fallbacks']: the files Pillow decoded after all).
+    orient, landmark_frame: as in crop_faces -- the PHOTO is made upright before the plan is made and the result is the upright,
+    photo-sized picture; edits and label maps are the crop job's own outputs and are taken as they are.  metadata='keep': the result
+    carries the photo's ICC profile and its EXIF block, with orient without the orientation tag (the pixels are upright now), without
+    orient with it (they are still the stored ones); 'drop' (default): neither path carries EXIF or ICC data over, as before."""
     from PIL import Image
     from .alignment import align_plan
     if matte is not None and label_dir is None:
         raise ValueError('matte refines a weight map: it needs label_dir')
+    _check_photo_options(orient, landmark_frame, metadata)
+    keep = metadata == 'keep'
     os.makedirs(out_dir, exist_ok=True)
     encoder = _png_encoder(png, aligner)
     jpeg_encoder, jpeg_options = _jpeg_writer(jpeg, jpeg_quality, jpeg_subsampling, aligner)
@@ -470,7 +580,10 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
             print(f'uncrop: no label map for {n}, skipped')
             skipped.append(n)
             continue
-        photo, edit = read(os.path.join(photo_dir, n)), read(os.path.join(edit_dir, n))
+        (photo, meta), edit = _read_photo(reader, os.path.join(photo_dir, n), orient, keep), read(os.path.join(edit_dir, n))
+        lm = _photo_landmarks(lm, meta, photo.shape, orient, landmark_frame)
+        kept = _kept_metadata(meta, keep, n)
+        lists = {k: [v] for k, v in kept.items()}
         S = int(edit.shape[0]) if size is None else int(size)
         if edit.shape[:2] != (S, S):
             raise ValueError(f'{os.path.join(edit_dir, n)}: expected a {S} x {S} crop, got {edit.shape[1]} x {edit.shape[0]}')
@@ -480,11 +593,11 @@ def uncrop_faces(aligner, photo_dir: str, edit_dir: str, out_dir: str, dataset: 
         else:
             out = aligner.paste_back(photo, edit, plan, weight=label_weight(label, S), matte=matte)[0]
         if encoder is not None and _is_png(n):
-            encoder.write([os.path.join(out_dir, n)], out[None])
+            encoder.write([os.path.join(out_dir, n)], out[None], **lists)
         elif jpeg_encoder is not None and _is_jpeg(n):
-            jpeg_encoder.write([os.path.join(out_dir, n)], out[None], **jpeg_options)
+            jpeg_encoder.write([os.path.join(out_dir, n)], out[None], **jpeg_options, **lists)
         else:
-            Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}))
+            Image.fromarray(out.cpu().numpy()).save(os.path.join(out_dir, n), **(jpeg_options if _is_jpeg(n) else {}), **kept)
         done.append(n)
     if stats is not None:
         stats['fallbacks'] = 0 if reader is None else reader.fallbacks
@@ -770,6 +883,9 @@ def _main_crop(argv):
     ap.add_argument('--jpeg-quality', type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's own default)")
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help="JPEG chroma subsampling (default 420, Pillow's own default)")
     ap.add_argument('--decode', choices=('host', 'device'), default='host', help='who decodes the files read: Pillow on the host (default), or the device: ch_jpeg_decode for .jpg / .jpeg, ch_png_decode for .png (the same pixels, so the same results; whatever the device does not take is Pillow\'s, file by file)')
+    ap.add_argument('--orient', action='store_true', help='make every photo upright by its EXIF orientation before it is used, as a viewer shows it (ch_orient_u8 with --decode device, Pillow\'s exif_transpose else; the same pixels)')
+    ap.add_argument('--landmark-frame', choices=('upright', 'stored'), default='upright', help='with --orient: the landmarks are pixels of the upright photo (default) or of the stored one')
+    ap.add_argument('--metadata', choices=('drop', 'keep'), default='drop', help="keep: write the photo's ICC profile and EXIF block (with --orient without its orientation tag) into the output; drop (default): neither")
     args = ap.parse_args(argv)
     if not 1 <= args.jpeg_quality <= 100:
         ap.error('--jpeg-quality must be in 1..100')
@@ -781,7 +897,8 @@ def _main_crop(argv):
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = crop_faces(aligner, args.src_dir, os.path.join(args.root, args.dataset, 'images_256'), args.dataset,
                                load_landmarks(args.landmarks), args.size, rank, world, png=args.png, jpeg=args.jpeg,
-                               jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, decode=args.decode)
+                               jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, decode=args.decode,
+                               orient=args.orient, landmark_frame=args.landmark_frame, metadata=args.metadata)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} without landmarks')
 
 
@@ -803,6 +920,9 @@ def _main_uncrop(argv):
     ap.add_argument('--jpeg-quality', type=int, default=75, help="JPEG quality 1..100 (default 75, Pillow's own default)")
     ap.add_argument('--jpeg-subsampling', choices=('420', '444'), default='420', help="JPEG chroma subsampling (default 420, Pillow's own default)")
     ap.add_argument('--decode', choices=('host', 'device'), default='host', help='who decodes the files read: Pillow on the host (default), or the device: ch_jpeg_decode for .jpg / .jpeg, ch_png_decode for .png (the same pixels, so the same results; whatever the device does not take is Pillow\'s, file by file)')
+    ap.add_argument('--orient', action='store_true', help='make every photo upright by its EXIF orientation before it is used, as a viewer shows it (ch_orient_u8 with --decode device, Pillow\'s exif_transpose else; the same pixels)')
+    ap.add_argument('--landmark-frame', choices=('upright', 'stored'), default='upright', help='with --orient: the landmarks are pixels of the upright photo (default) or of the stored one')
+    ap.add_argument('--metadata', choices=('drop', 'keep'), default='drop', help="keep: write the photo's ICC profile and EXIF block (with --orient without its orientation tag) into the output; drop (default): neither")
     args = ap.parse_args(argv)
     if not 1 <= args.jpeg_quality <= 100:
         ap.error('--jpeg-quality must be in 1..100')
@@ -824,7 +944,8 @@ def _main_uncrop(argv):
     aligner = FaceAligner(lib.Handle(local), torch.device('cuda', local))
     done, skipped = uncrop_faces(aligner, args.photos, args.edits, args.out, args.dataset, load_landmarks(args.landmarks), args.size,
                                  rank, world, label_dir=args.labels, matte=matte, png=args.png, jpeg=args.jpeg,
-                                 jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, decode=args.decode)
+                                 jpeg_quality=args.jpeg_quality, jpeg_subsampling=args.jpeg_subsampling, decode=args.decode,
+                                 orient=args.orient, landmark_frame=args.landmark_frame, metadata=args.metadata)
     print(f'rank {rank}/{world}: {len(done)} files, {len(skipped)} skipped')
 
 

@@ -17,6 +17,7 @@ from typing import List, Sequence
 import numpy as np
 
 from .devop import DeviceOp
+from .photometa import EXIF_MAX, per_image      # (shared with pngenc and the jobs; re-exported here)
 
 JPEG_MODES = ('host', 'device')
 SUBSAMPLINGS = (0, 2)                     # Pillow's numbering: 0 = 4:4:4, 2 = 4:2:0
@@ -79,16 +80,37 @@ def _segment(marker: int, payload: bytes) -> bytes:
     return struct.pack('>BBH', 0xFF, marker, len(payload) + 2) + payload
 
 
-def wrap_jpeg(scan: bytes, H: int, W: int, C: int, quality: int = 75, subsampling: int = 2) -> bytes:
+ICC_CHUNK = 65519                         # profile bytes per APP2 segment: 65533 - len('ICC_PROFILE\0', index, count)
+
+
+def metadata_segments(exif: bytes = None, icc_profile: bytes = None) -> bytes:
+    """The segments Pillow's save(exif=, icc_profile=) puts between APP0 and the first DQT: APP1 with the EXIF block as given (it starts
+    with 'Exif\\0\\0'), then the profile cut into APP2 'ICC_PROFILE\\0' segments of at most 65519 profile bytes, numbered from 1."""
+    out = []
+    if exif:
+        if len(exif) > EXIF_MAX:
+            raise ValueError('EXIF data is too long')             # Pillow's own refusal, in its words
+        out.append(_segment(0xE1, bytes(exif)))
+    if icc_profile:
+        chunks = [bytes(icc_profile[a:a + ICC_CHUNK]) for a in range(0, len(icc_profile), ICC_CHUNK)]
+        if len(chunks) > 255:
+            raise ValueError(f'ICC profile of {len(icc_profile)} bytes needs more than 255 APP2 segments')
+        out += [_segment(0xE2, b'ICC_PROFILE\x00' + bytes([i + 1, len(chunks)]) + c) for i, c in enumerate(chunks)]
+    return b''.join(out)
+
+
+def wrap_jpeg(scan: bytes, H: int, W: int, C: int, quality: int = 75, subsampling: int = 2, exif: bytes = None,
+              icc_profile: bytes = None) -> bytes:
     """A JPEG file around the entropy-coded scan, marker for marker what Pillow writes: SOI, APP0 (JFIF 1.01, no units, density 1 x 1),
-    one DQT per table in zigzag order, SOF0, one DHT per table, SOS, the scan, EOI.  C = 1: one table of each kind.  The luma sampling
-    factor is 2 x 2 for subsampling 2 and 1 x 1 for 0 -- for grey as well, where it changes nothing but that byte."""
+    with exif / icc_profile the segments of metadata_segments, one DQT per table in zigzag order, SOF0, one DHT per table, SOS, the
+    scan, EOI.  C = 1: one table of each kind.  The luma sampling factor is 2 x 2 for subsampling 2 and 1 x 1 for 0 -- for grey as
+    well, where it changes nothing but that byte."""
     if C not in (1, 3):
         raise ValueError(f'wrap_jpeg: C must be 1 or 3, got {C}')
     if not (1 <= H <= 65535 and 1 <= W <= 65535):
         raise ValueError('wrap_jpeg: H and W must be in 1..65535')
     quality, subsampling = check_jpeg_params(quality, subsampling)
-    parts = [b'\xff\xd8', _segment(0xE0, b'JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00')]
+    parts = [b'\xff\xd8', _segment(0xE0, b'JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00'), metadata_segments(exif, icc_profile)]
     for k, q in enumerate(quant_tables(quality)[:1 if C == 1 else 2]):
         parts.append(_segment(0xDB, bytes([k]) + bytes(int(q[i]) for i in ZIGZAG)))
     comps = [(1, 0x22 if subsampling == 2 else 0x11, 0)] + ([(2, 0x11, 1), (3, 0x11, 1)] if C == 3 else [])
@@ -134,17 +156,20 @@ class JpegEncoder(DeviceOp):
                          ws.numel(), self._stream())
         return self._fetch_ragged(out, bound, sizes, 1, 'ch_jpeg_encode returned scan lengths')
 
-    def encode(self, images, quality: int = 75, subsampling: int = 2) -> List[bytes]:
-        """uint8 device tensor [N,H,W,C] or [N,H,W] -> N whole JPEG files (bytes)."""
-        _, H, W, C = self._shape(images)
+    def encode(self, images, quality: int = 75, subsampling: int = 2, exif: Sequence = None, icc_profile: Sequence = None) -> List[bytes]:
+        """uint8 device tensor [N,H,W,C] or [N,H,W] -> N whole JPEG files (bytes).  exif / icc_profile: per image a bytes object or None
+        (lists of N), written as Pillow's save(exif=, icc_profile=) writes them."""
+        N, H, W, C = self._shape(images)
         quality, subsampling = check_jpeg_params(quality, subsampling)
-        return [wrap_jpeg(s, H, W, C, quality, subsampling) for s in self.scans(images, quality, subsampling)]
+        exif, icc_profile = per_image(exif, N, 'exif'), per_image(icc_profile, N, 'icc_profile')
+        return [wrap_jpeg(s, H, W, C, quality, subsampling, e, p) for s, e, p in zip(self.scans(images, quality, subsampling), exif, icc_profile)]
 
-    def write(self, paths: Sequence[str], images, quality: int = 75, subsampling: int = 2) -> None:
+    def write(self, paths: Sequence[str], images, quality: int = 75, subsampling: int = 2, exif: Sequence = None,
+              icc_profile: Sequence = None) -> None:
         """Encode images [N,...] and write file n to paths[n]."""
         paths = list(paths)
         if len(paths) != int(images.shape[0]):
             raise ValueError(f'JpegEncoder.write: {len(paths)} paths for {int(images.shape[0])} images')
-        for path, jpg in zip(paths, self.encode(images, quality, subsampling)):
+        for path, jpg in zip(paths, self.encode(images, quality, subsampling, exif, icc_profile)):
             with open(path, 'wb') as f:
                 f.write(jpg)

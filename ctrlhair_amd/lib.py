@@ -45,6 +45,8 @@ SYMBOLS = {
     'ch_ingest_workspace_bytes': (C.c_size_t, [_VP, C.c_size_t, _I, _I, _I]),
     'ch_ingest_images': (_I, [_VP, _VP, C.c_size_t, _I, _I, _I, _VP, _VP, _VP, C.c_size_t, _VP]),
     'ch_ingest_labels': (_I, [_VP, _VP, C.c_size_t, _I, _I, _VP, _VP, C.c_size_t, _VP]),
+    'ch_orient_workspace_bytes': (C.c_size_t, [_VP, C.c_size_t, _I, C.c_size_t]),
+    'ch_orient_u8': (_I, [_VP, _VP, C.c_size_t, _I, _VP, C.c_size_t, _VP, C.c_size_t, _VP]),
     'ch_sheet_compose': (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     'ch_sweep_stats': (_I, [_VP, _VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
     'ch_png_chunk_bytes': (_I, []),

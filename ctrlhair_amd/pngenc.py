@@ -70,14 +70,21 @@ def _chunk(kind: bytes, data: bytes) -> bytes:
     return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(data, zlib.crc32(kind)) & 0xFFFFFFFF)
 
 
-def wrap_png(zlib_stream: bytes, H: int, W: int, C: int) -> bytes:
-    """A PNG file around the zlib stream of its filtered rows: 8-bit, colour type 0 / 2 / 6 for C = 1 / 3 / 4, not interlaced."""
+def wrap_png(zlib_stream: bytes, H: int, W: int, C: int, exif: bytes = None, icc_profile: bytes = None) -> bytes:
+    """A PNG file around the zlib stream of its filtered rows: 8-bit, colour type 0 / 2 / 6 for C = 1 / 3 / 4, not interlaced.
+    icc_profile: an iCCP chunk (profile name 'ICC Profile', as Pillow names it, deflated); exif: an eXIf chunk, whose payload is the
+    EXIF block without the 'Exif\\0\\0' prefix JPEG's APP1 carries; both before the first IDAT.  Pillow reads both back as given."""
     if C not in COLOUR_TYPE:
         raise ValueError(f'wrap_png: C must be 1, 3 or 4, got {C}')
     if H < 1 or W < 1:
         raise ValueError('wrap_png: H and W must be positive')
     z = bytes(zlib_stream)
     parts = [PNG_SIGNATURE, _chunk(b'IHDR', struct.pack('>IIBBBBB', W, H, 8, COLOUR_TYPE[C], 0, 0, 0))]
+    if icc_profile:
+        parts.append(_chunk(b'iCCP', b'ICC Profile\x00\x00' + zlib.compress(bytes(icc_profile))))
+    if exif:
+        exif = bytes(exif)
+        parts.append(_chunk(b'eXIf', exif[6:] if exif.startswith(b'Exif\x00\x00') else exif))
     for a in range(0, max(len(z), 1), IDAT_MAX):
         parts.append(_chunk(b'IDAT', z[a:a + IDAT_MAX]))
     parts.append(_chunk(b'IEND', b''))
@@ -122,17 +129,21 @@ class PngEncoder(DeviceOp):
                              ws.numel(), self._stream())
         return self._fetch_ragged(out, bound, sizes, 8, 'ch_png_encode returned stream lengths')
 
-    def encode(self, images, filter: int = -1, distances: Sequence[int] = ()) -> List[bytes]:
-        """uint8 device tensor [N,H,W,C] or [N,H,W] -> N whole PNG files (bytes)."""
-        H, W = int(images.shape[1]), int(images.shape[2])
+    def encode(self, images, filter: int = -1, distances: Sequence[int] = (), exif: Sequence = None, icc_profile: Sequence = None) -> List[bytes]:
+        """uint8 device tensor [N,H,W,C] or [N,H,W] -> N whole PNG files (bytes).  exif / icc_profile: per image a bytes object or None
+        (lists of N): the eXIf and iCCP chunks of wrap_png."""
+        from .photometa import per_image
+        N, H, W = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
         C = int(images.shape[3]) if images.dim() == 4 else 1
-        return [wrap_png(z, H, W, C) for z in self.streams(images, filter, distances)]
+        exif, icc_profile = per_image(exif, N, 'exif'), per_image(icc_profile, N, 'icc_profile')
+        return [wrap_png(z, H, W, C, e, p) for z, e, p in zip(self.streams(images, filter, distances), exif, icc_profile)]
 
-    def write(self, paths: Sequence[str], images, filter: int = -1, distances: Sequence[int] = ()) -> None:
+    def write(self, paths: Sequence[str], images, filter: int = -1, distances: Sequence[int] = (), exif: Sequence = None,
+              icc_profile: Sequence = None) -> None:
         """Encode images [N,...] and write file n to paths[n]."""
         paths = list(paths)
         if len(paths) != int(images.shape[0]):
             raise ValueError(f'PngEncoder.write: {len(paths)} paths for {int(images.shape[0])} images')
-        for path, png in zip(paths, self.encode(images, filter, distances)):
+        for path, png in zip(paths, self.encode(images, filter, distances, exif, icc_profile)):
             with open(path, 'wb') as f:
                 f.write(png)

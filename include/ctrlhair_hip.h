@@ -358,6 +358,28 @@ int  ch_ingest_images(ch_handle* h, const void* batch, size_t batch_bytes, int N
 int  ch_ingest_labels(ch_handle* h, const void* batch, size_t batch_bytes, int N, int S, uint8_t* out, void* workspace,
                       size_t workspace_bytes, ch_stream_t stream);
 
+/* ---- EXIF orientation: N decoded images of ANY sizes -> the upright images, in one launch -------------------------------------------
+ * ch_orient_u8 turns uint8 images [H,W,C] (C = 1, 3 or 4) by their EXIF orientation (tag 0x0112) 1..8, as Pillow's
+ * ImageOps.exif_transpose does.  With a = the stored image and t = a transposed ([W,H,C]), the upright image is
+ *   1: a   2: a[:, ::-1]   3: a[::-1, ::-1]   4: a[::-1]   5: t   6: t[:, ::-1]   7: t[::-1, ::-1]   8: t[::-1]
+ * so orientations 5..8 give [W,H,C].  A pure permutation of bytes: exact.
+ * batch: HOST bytes (8-byte aligned; may be freed on return): N descriptors of CH_ORIENT_DESC_BYTES bytes {uint64 device address of
+ *   the stored pixels, int64 byte offset of the upright pixels in dst, int32 H, int32 W, int32 C, int32 orientation}; H, W, C are the
+ *   STORED image's.  1 <= N <= 65535, sides 1..CH_ORIENT_MAX_SIDE.  The destination offsets ascend and the images do not overlap;
+ *   neither the offsets nor the source addresses need any alignment.
+ * dst: ONE device buffer of dst_bytes bytes that receives every image at its offset.  Everything the batch says is checked on the
+ *   host before the launch -- offsets and extents inside dst, C, orientation, H * W * C, no source inside dst -- and a refusal names
+ *   the image; the extent of a source is the caller's word.
+ * workspace: caller-owned device buffer (256-byte aligned) of ch_orient_workspace_bytes(batch, batch_bytes, N, dst_bytes) bytes (0 = a
+ *   batch the entry would refuse): the descriptors' device copy.  Contents undefined.
+ * One copy and one launch on `stream` whatever N is: no synchronisation, no allocation, no atomics, no waiting between workgroups;
+ *   image n of a batch is bit-identical to an N = 1 call. */
+#define CH_ORIENT_DESC_BYTES 32
+#define CH_ORIENT_MAX_SIDE 32768
+size_t ch_orient_workspace_bytes(const void* batch, size_t batch_bytes, int N, size_t dst_bytes);
+int  ch_orient_u8(ch_handle* h, const void* batch, size_t batch_bytes, int N, uint8_t* dst, size_t dst_bytes, void* workspace,
+                  size_t workspace_bytes, ch_stream_t stream);
+
 /* ---- Direction search: contact sheets and per-render measurements (shape_branch/script_find_direction.py:55-76,
  *      color_texture_branch/script_find_direction.py:55-74, util/canvas_grid.py:15-31) ------------------------------------------
  * ch_sheet_compose replaces Canvas.process_draw_image for n sources at once: source s goes to cell (cells[2s], cells[2s+1]) =

@@ -27,9 +27,10 @@ NO_MESSAGE = ('ch_sean_set_tap', 'ch_profile_enable')      # with a handle these
 # Entry points added after the table was recorded.  The table is a snapshot that guards the messages of the entry points it holds; a
 # later entry point's refusals and messages are asserted where it is tested (ch_jpeg_decode: tests/test_hip_jpegdec.py::test_abi_refusals,
 # ch_jpeg_decode_rst: tests/test_hip_jpegdec_rst.py::test_abi_refusals, ch_ingest_*: tests/test_hip_ingest.py::test_abi_refusals,
-# ch_sean_code_memo_stats: a query, its counters are asserted call by call in tests/test_hip_code_memo.py)
+# ch_sean_code_memo_stats: a query, its counters are asserted call by call in tests/test_hip_code_memo.py,
+# ch_orient_*: tests/test_hip_orient.py::test_abi_refusals)
 AFTER_THE_TABLE = ('ch_jpeg_decode', 'ch_jpeg_decode_rst', 'ch_ingest_workspace_bytes', 'ch_ingest_images', 'ch_ingest_labels',
-                   'ch_sean_code_memo_stats')
+                   'ch_sean_code_memo_stats', 'ch_orient_workspace_bytes', 'ch_orient_u8')
 
 
 def handle_entries(symbols):
